@@ -9,8 +9,20 @@ forward, then ONE fused libctdd launch (softmax -> S x S ratio contraction -> fo
 -> Poisson jump draw -> state update).  Inputs (state x, per-step q_{t|0} tables, random-init
 weights) are resident in HBM before the timed region.  Sampling shards over GPUs with no
 data-path collective: weak scaling, value = all ranks' sample-steps / max-rank time.
+Step i runs grid step i mod 1000 of the config's grid (W warm-up steps, then the K timed ones): more steps than the grid
+has go round it again from t = 1, the state carrying on.  The --full kernel roofline times the 20 grid steps after the
+timed ones the same way, on the state the timed steps reached (sub-batches joined into one batch).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, config).
+--dump-outputs DIR (bench_out/ is git-ignored) also writes what the last timed step handed back, as DIR/<name>.npy:
+  x                 float32 (batch, D): every sample's state after the last timed step (rank 0's samples);
+  changed_fraction  float64 (1000,): the fraction of dimensions each grid step changed, as TauL.finish reports it
+                    (steps run more than once add up);
+  with --train: loss (float64 (1,), the last step's loss) and params (float32: the updated parameters, flattened, or a fixed
+  seeded sample of 2^22 of them when there are more).
+The inputs (random-init weights, initial state, Philox keys) are seeded: the same arguments give the same inputs.
+
+With --full the JSON line also carries (each --no-* option drops one block)
   roofline          the fused tau-leap kernel (k_tauleap_s256_b16 in the bf16 mode the headline runs: one bf16 product,
                     bf16 logits straight from the output convolution; k_tauleap_s256 in the fp32 parity mode):
                     algorithmic bytes per sample-step (407 680 B with bf16 logits, 809 088 B with fp32
@@ -20,7 +32,8 @@ The JSON line also carries
   roofline_network  the score-network forward (the larger share of the step): 2 M N K matrix FLOPs of its convolutions /
                     the forward's wall time as it runs in the loop (graph replay, two sub-batches on parallel streams, GroupNorm
                     etc. included) vs the dense bf16 MFMA peak; the convolution launches replayed one by one are reported too;
-  cpu_baseline      the CPU oracle (checker, never the product) running the same step on host cores.
+  cpu_baseline      the CPU oracle (checker, never the product) running the same step on host cores;
+  train_step, train_step_hollow, configs   training steps and the BASELINE configs 3-5 (see their functions).
 """
 import argparse
 import json
@@ -50,11 +63,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="samples per GPU (SURVEY 8d: 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the rooflines, the fp32 parity mode, the training steps, the BASELINE configs 3-5 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--cpu-batch", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-mode", action="store_true", help="skip the fp32 parity-mode timing")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the training-step timing")
-    ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE configs 3-5 block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fp32-mode", action="store_true", help="with --full: skip the fp32 parity-mode timing")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: skip the training-step timing")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the BASELINE configs 3-5 block")
     ap.add_argument("--train", action="store_true",
                     help="time the data-parallel TRAINING step instead (MNIST tauLDR CT-ELBO, 64 samples per GPU, DDP over RCCL)")
     ap.add_argument("--engine-streams", type=int, default=None, help="sub-batches of the U-Net engine on parallel streams")
@@ -420,6 +436,13 @@ def cpu_baseline(model_gpu, cfg, batch, budget_s=12.0):
             "sample": f"{done} tau-leaping steps of {batch} samples (oracle U-Net fwd + rates + torch.poisson + update), {el:.1f} s"}
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64, a few MB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def ddp_train_bench(a, world, rank, dev, dist):
     """`bench.py --gpus N --train`: K data-parallel training steps of the MNIST tauLDR U-Net (CT-ELBO, per-rank batch 64 =
     config_tauUnet_mnist's batch, global batch 64 N; cfg.distributed wraps the network in DistributedDataParallel: one gradient
@@ -454,7 +477,7 @@ def ddp_train_bench(a, world, rank, dev, dist):
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(K):
-        step.step(state, loss, mb)
+        last = step.step(state, loss, mb)
         state["n_iter"] += 1
     torch.cuda.synchronize()
     if dist:
@@ -465,6 +488,12 @@ def ddp_train_bench(a, world, rank, dev, dist):
         tt = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if rank == 0 and a.dump_outputs:
+        flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]).cpu()
+        cap = 1 << 22
+        if flat.numel() > cap:
+            flat = flat[torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values]
+        dump_outputs(a.dump_outputs, {"loss": np.array([float(last)], dtype=np.float64), "params": flat.numpy()})
     if rank == 0:
         nparam = sum(p.numel() for p in model.parameters())
         print(json.dumps({
@@ -517,18 +546,18 @@ def main():
     sampler.seed = 42
     sampler.rank_stream = rank              # distinct Philox key per rank; no data-path collective
     K, W = a.steps, a.warmup
-    assert W + K + 1 <= sampler.num_steps
+    grid = sampler.num_steps                    # step i runs grid step i mod grid
     with torch.no_grad():
         st = sampler.begin(model, a.batch)
         for i in range(W):
-            sampler.advance(st, i)
+            sampler.advance(st, i % grid)
         torch.cuda.synchronize()
         if dist:
             dist.barrier()
             torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(W, W + K):
-            sampler.advance(st, i)
+            sampler.advance(st, i % grid)
         torch.cuda.synchronize()
         if dist:
             dist.barrier()
@@ -538,40 +567,50 @@ def main():
             tt = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
-        if rank == 0 and getattr(st, "parts", 1) > 1:
-            # the roofline launches are timed one by one on the whole batch: a joined state advanced to the same step
-            st = sampler.begin(model, a.batch, pipeline=False)
-            for i in range(W + K):
-                sampler.advance(st, i)
-            torch.cuda.synchronize()
-        roof = kernel_roofline(sampler, st, range(W + K, min(W + K + 20, sampler.num_steps - 1)), a.batch) if rank == 0 else None
-        # the same kernel mid-trajectory (t ~ 0.5: fewer dimensions jump than next to t = 1, where the timed steps run)
-        mid = sampler.num_steps // 2
-        roof_mid = kernel_roofline(sampler, st, range(mid, mid + 20), a.batch, restore_state=True) if rank == 0 else None
-        roof_net = network_roofline(model, a.batch, sampler) if rank == 0 else None
-        fp32_mode = fp32_parity_mode(cfg, model, sampler, a.batch) if (rank == 0 and world == 1 and not a.no_fp32_mode) else None
+        if rank == 0 and a.dump_outputs:
+            changed = st.changed if st.parts == 1 else st.changed_p.sum(0)
+            dump_outputs(a.dump_outputs, {"x": sampler.state_x(st).float().cpu().numpy(),
+                                          "changed_fraction": changed.cpu().numpy().astype(np.float64) / a.batch})
+        roof = roof_mid = roof_net = fp32_mode = None
+        if rank == 0 and a.full:
+            if getattr(st, "parts", 1) > 1:
+                # the roofline launches are timed one by one on the whole batch: the timed steps' sub-batches joined
+                x = sampler.state_x(st)
+                st = sampler.begin(model, a.batch, pipeline=False)
+                st.x = x
+                torch.cuda.synchronize()
+            # the 20 grid steps after the timed ones (round the grid, as the timed loop goes)
+            roof = kernel_roofline(sampler, st, [(W + K + j) % grid for j in range(20)], a.batch)
+            # the same kernel mid-trajectory (t ~ 0.5: fewer dimensions jump than next to t = 1, where the timed steps run)
+            mid = sampler.num_steps // 2
+            roof_mid = kernel_roofline(sampler, st, range(mid, mid + 20), a.batch, restore_state=True)
+            roof_net = network_roofline(model, a.batch, sampler)
+            fp32_mode = fp32_parity_mode(cfg, model, sampler, a.batch) if (world == 1 and not a.no_fp32_mode) else None
     if rank == 0:
         value = a.batch * K * world / el
         line = {
             "metric": "tau-leaping sample-steps/s", "value": round(value, 2), "unit": "sample-steps/s",
             "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(el / K * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "dtype_detail": "bf16 score network (fp32 accumulate, bf16 logits) + tau-leap step with f32 softmax / rates and ONE bf16 MFMA product for the S x S ratio contraction (relative rate error <= 3 * 2^-8; the three-product f32-parity step is timed in fp32_parity_mode)", "data": "synthetic (random-init weights, Gaussian initial state, resident in HBM)",
+            "dtype": "bf16", "dtype_detail": "bf16 score network (fp32 accumulate, bf16 logits) + tau-leap step with f32 softmax / rates and ONE bf16 MFMA product for the S x S ratio contraction (relative rate error <= 3 * 2^-8; the three-product f32-parity step is timed in fp32_parity_mode with --full)", "data": "synthetic (random-init weights, Gaussian initial state, resident in HBM)",
             "config": {"workload": "MNIST tauLDR U-Net TauL step (config_tauUnet_mnist: D=784, S=256, 1000-step grid)",
                        "batch_per_gpu": a.batch, "global_batch": a.batch * world, "D": D, "S": S,
                        "parallelism": f"sample-sharded x{world}, no collective in the loop"},
             "dims_per_s": round(value * D, 1),
-            "roofline": roof,
-            "roofline_network": roof_net,
-            "roofline_mid_trajectory": None if roof_mid is None else {k_: roof_mid[k_] for k_ in ("bound", "achieved", "peak", "unit", "frac", "avg_launch_us", "fp32_logit_equivalent_frac", "mfma_view")},
-            "fp32_parity_mode": fp32_mode,
         }
-        if world == 1 and not a.no_train_step:
+        if a.full:
+            line.update({
+                "roofline": roof,
+                "roofline_network": roof_net,
+                "roofline_mid_trajectory": None if roof_mid is None else {k_: roof_mid[k_] for k_ in ("bound", "achieved", "peak", "unit", "frac", "avg_launch_us", "fp32_logit_equivalent_frac", "mfma_view")},
+                "fp32_parity_mode": fp32_mode,
+            })
+        if a.full and world == 1 and not a.no_train_step:
             line["train_step"] = train_step_timing()
             line["train_step_hollow"] = hollow_train_step_timing()
-        if world == 1 and not a.no_configs:
+        if a.full and world == 1 and not a.no_configs:
             line["configs"] = baseline_configs()
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(model, cfg, a.cpu_batch)
         print(json.dumps(line), flush=True)
     if dist:

@@ -1,9 +1,9 @@
 """HBM traffic per launch of a kernel from two rocprofv3 counter passes (MI355X_MICROARCH.md, HBM section: FETCH_SIZE and WRITE_SIZE
 cannot share a pass; on gfx950 FETCH_SIZE reports half the bytes of wide coalesced streaming reads -> doubled; both count KiB).
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o f -- python3 bench.py --no-cpu-baseline --no-train-step --no-fp32-mode --no-configs --steps 4 --warmup 1
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -o w -- python3 bench.py ...   (same command)
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch/f_counter_collection.csv gpurun_out/pmc_write/w_counter_collection.csv \\
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d prof_out/pmc_fetch -o f -- python3 bench.py --full --no-cpu-baseline --no-train-step --no-fp32-mode --no-configs --steps 4 --warmup 1
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d prof_out/pmc_write -o w -- python3 bench.py ...   (same command)
+    python tools/pmc_traffic.py prof_out/pmc_fetch/f_counter_collection.csv prof_out/pmc_write/w_counter_collection.csv \\
            k_tauleap_s256_b16 401408 profiles/r03_pmc_traffic_tauleap_s256_b16.json [algorithmic bytes per launch]
 
 Only dispatches of the named kernel with the given grid size (threads; 401408 = the 1568 workgroups of a 256-sample launch) count.

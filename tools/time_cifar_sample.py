@@ -1,4 +1,4 @@
-"""CIFAR-10 tauLDR U-Net TauL sampling (BASELINE config 5's sampler), timed like bench.py's `configs` block, three repeats."""
+"""CIFAR-10 tauLDR U-Net TauL sampling (BASELINE config 5's sampler), timed like the `configs` block of bench.py --full, three repeats."""
 import os, sys, time
 _R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [_R, os.path.join(_R, "continuous-time-diffusion-models-for-discrete-data_amd")]
