@@ -34,6 +34,10 @@ struct StepArgs {
   float* out_b;          // ratio | ll_xt
   int32_t* out_x;
   int32_t* out_changed;
+  // row-list launches (ctdd_tauleap_step_rows): launch row v < n_rows works on row rows[v] of the N*D row space -- loads,
+  // stores and the Philox counter all take rows[v]; the full launches leave both fields zero and use the identity
+  const int32_t* rows;
+  int64_t n_rows;
 };
 
 // ---- reductions / scans over the G lanes of a row on DPP (data-parallel primitives: one VALU op per stage) instead of
@@ -123,20 +127,25 @@ __device__ inline float grp_scan(float v, int G, int li) {
 }
 
 constexpr int ROWS_PER_WAVE = 4;
-template <int EPT>
+// ROWS: the row-list variant (MODE_TAULEAP only): R counts the listed rows, a row group's loads, stores and Philox counter go
+// through a.rows (dead lanes clamp to the last listed row); false is the full launch, unchanged.
+template <int EPT, bool ROWS = false>
 __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int G = a.G, S = a.S;
   const int li = lane & (G - 1), gi = lane / G, gbase = lane - li;
-  const int64_t R = (int64_t)a.N * a.D;
+  const int64_t R = ROWS ? a.n_rows : (int64_t)a.N * a.D;
   // A wave walks ROWS_PER_WAVE consecutive row groups; the state and the logits of the NEXT group are requested before the
   // current one is worked on (one row per wave and kernel lifetime left every load latency of the x -> table -> logits
   // chain exposed: 7 us per row at S = 256).
   const int64_t first = ((int64_t)blockIdx.x * 4 + wave) * ROWS_PER_WAVE * (WAVE / G) + gi;
   int nx_x = 0, nx_xb = 0;
+  int64_t nx_p = 0;                                           // (ROWS: the listed row the prefetched group works on)
   float nx_l[EPT];
   auto prefetch = [&](int64_t r) {
-    const int64_t rc = r < R ? r : R - 1;
+    const int64_t rl = r < R ? r : R - 1;
+    const int64_t rc = ROWS ? (int64_t)a.rows[rl] : rl;
+    if constexpr (ROWS) nx_p = rc;
     nx_x = a.x[rc];
     nx_xb = a.x_base ? a.x_base[rc] : 0;
     const float* lr = a.logits + (size_t)rc * S;
@@ -152,12 +161,14 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
   if (row - gi >= R) break;                                   // (uniform over the wave: the whole group is past the end)
   const bool live = row < R;
   const int64_t rowc = live ? row : R - 1;
+  const int64_t prow = ROWS ? nx_p : rowc;                    // row of the N*D space: loads, tables, Philox counter
+  const int64_t orow = ROWS ? nx_p : row;                     // ... and stores (live rows only)
   const int cur_x = nx_x, cur_xb = nx_xb;
   float raw[EPT];
 #pragma unroll
   for (int k = 0; k < EPT; ++k) raw[k] = nx_l[k];
   if (it + 1 < ROWS_PER_WAVE) prefetch(row + (WAVE / G));
-  const int n = (int)(rowc / a.D);
+  const int n = (int)(prow / a.D);
   const int tbl = a.tidx ? a.tidx[n] : 0;
   const float* qt0 = a.qt0 ? a.qt0 + (size_t)tbl * S * S : nullptr;
   const float* rate = a.rate ? a.rate + (size_t)tbl * S * S : nullptr;
@@ -231,17 +242,17 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
         const int s = li + k * G;
         if (s < S) {
           const float pr = acc[k] / tot;
-          if (live && a.out_a) a.out_a[(size_t)row * S + s] = pr;
+          if (live && a.out_a) a.out_a[(size_t)orow * S + s] = pr;
           float Ev;
-          if (a.E) Ev = a.E[(size_t)rowc * S + s];
-          else Ev = -logf(u01(philox_row(a.seed, a.offset, (uint64_t)rowc, (uint32_t)s).x));
+          if (a.E) Ev = a.E[(size_t)prow * S + s];
+          else Ev = -logf(u01(philox_row(a.seed, a.offset, (uint64_t)prow, (uint32_t)s).x));
           const float v = pr / Ev;
           if (v > best || (v == best && s < bi)) { best = v; bi = s; }
         }
       }
       grp_argmax(best, bi, G);
       if (live && li == 0) {
-        a.out_x[row] = bi;
+        a.out_x[orow] = bi;
         if (a.out_changed && bi != xcur) atomicAdd(a.out_changed, 1);
       }
       continue;
@@ -340,9 +351,9 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
 #pragma unroll
           for (int k = 0; k < EPT; ++k) {
             const int s = li + k * G;
-            if (s < S) a.out_a[(size_t)row * S + s] = ll[k];
+            if (s < S) a.out_a[(size_t)orow * S + s] = ll[k];
           }
-          if (li == 0) a.out_b[row] = ll_xt;
+          if (li == 0) a.out_b[orow] = ll_xt;
         }
         continue;
       }
@@ -362,8 +373,8 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
       for (int k = 0; k < EPT; ++k) {
         const int s = li + k * G;
         if (s < S) {
-          a.out_a[(size_t)row * S + s] = rr[k];
-          if (a.out_b) a.out_b[(size_t)row * S + s] = ratio[k];
+          a.out_a[(size_t)orow * S + s] = rr[k];
+          if (a.out_b) a.out_b[(size_t)orow * S + s] = ratio[k];
         }
       }
     }
@@ -385,7 +396,7 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
     for (int k = 0; k < EPT; ++k) acc += rr[k] * (float)(li + k * G - xv);
     acc = grp_sum(acc, G);
     const int change = (int)rintf(a.h * acc);   // a.h carries float(0.5*h)
-    if (live && li == 0) a.out_x[row] = min(max(xv + change, 0), S - 1);
+    if (live && li == 0) a.out_x[orow] = min(max(xv + change, 0), S - 1);
     continue;
   }
 
@@ -433,17 +444,17 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
       const int s = li + k * G;
       if (s < S) {
         pr[k] /= se2;
-        if (live && a.out_a) a.out_a[(size_t)row * S + s] = pr[k];
+        if (live && a.out_a) a.out_a[(size_t)orow * S + s] = pr[k];
         float Ev;
-        if (a.E) Ev = a.E[(size_t)rowc * S + s];
-        else Ev = -logf(u01(philox_row(a.seed, a.offset, (uint64_t)rowc, (uint32_t)s).x));
+        if (a.E) Ev = a.E[(size_t)prow * S + s];
+        else Ev = -logf(u01(philox_row(a.seed, a.offset, (uint64_t)prow, (uint32_t)s).x));
         const float v = pr[k] / Ev;
         if (v > best || (v == best && s < bi)) { best = v; bi = s; }
       }
     }
     grp_argmax(best, bi, G);
     if (live && li == 0) {
-      a.out_x[row] = bi;
+      a.out_x[orow] = bi;
       if (a.out_changed && bi != xv) atomicAdd(a.out_changed, 1);
     }
     continue;
@@ -458,7 +469,7 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
   const bool ordinal = a.flags & CTDD_STEP_ORDINAL;
   int jump = 0, njumps = 0;                                   // njumps: jump events drawn for this dimension (sum_s k_s)
   if (Lam > 0.0f && Lam <= SUPERPOSE_MAX_LAMBDA) {
-    PhiloxStream rng(a.seed, a.offset, (uint64_t)rowc, 0u);   // identical in every lane of the row
+    PhiloxStream rng(a.seed, a.offset, (uint64_t)prow, 0u);   // identical in every lane of the row
     const int K = poisson_row(Lam, rng);
     njumps = K;
     if (K > 0 && (ordinal || K == 1)) {
@@ -502,9 +513,9 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
         if (s + 2 >= S) r2 = 0.0f;
         if (s + 3 >= S) r3 = 0.0f;
         const int b = s >> 2;
-        const u4 blk = philox_row(a.seed, a.offset, (uint64_t)rowc, DENSE_DRAW0 + (uint32_t)(b >> 2));
+        const u4 blk = philox_row(a.seed, a.offset, (uint64_t)prow, DENSE_DRAW0 + (uint32_t)(b >> 2));
         const uint32_t w = (b & 3) == 0 ? blk.x : (b & 3) == 1 ? blk.y : (b & 3) == 2 ? blk.z : blk.w;
-        cnt += min(subblock_draw(rr[k], r1, r2, r3, a.h, u01(w), a.seed, a.offset, (uint64_t)rowc, b, base,
+        cnt += min(subblock_draw(rr[k], r1, r2, r3, a.h, u01(w), a.seed, a.offset, (uint64_t)prow, b, base,
                                  min(4, S - s), &jl), 1 << 20);
       }
     }
@@ -516,7 +527,7 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
   }
   if (live && li == 0) {
     const int xn = min(max(xcur + jump, 0), S - 1);
-    a.out_x[row] = xn;
+    a.out_x[orow] = xn;
     const bool moved = (a.flags & CTDD_STEP_COUNT_RAW) ? (jump != 0) : (xn != xcur);
     if (a.out_changed && moved) atomicAdd(a.out_changed, 1);
     if (a.out_changed && (a.flags & CTDD_STEP_COUNT_JUMPS)) {  // sampling.py:489-495: dimensions with >= 1 and with > 1 jump events
@@ -535,7 +546,8 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
 // states one int4 each way), both tables sit in LDS, and every row loop is unrolled straight-line code in the operation order
 // of k_rows with G = 1 (sequential sums in s order -- for S <= 4 bit-identical to it, for 5 <= S <= 8 the oracle's own order
 // where k_rows uses a lane tree).  Same Philox streams, same draw rules (draw.hpp).
-template <int S, int MODE>
+// ROWS (MODE_TAULEAP only): the thread's four rows are launch rows of the list a.rows, gathered one by one; false: unchanged.
+template <int S, int MODE, bool ROWS = false>
 __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
   __shared__ float Tq[S * S], Tr[S * S];
   for (int i = threadIdx.x; i < S * S; i += 256) {
@@ -543,13 +555,14 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
     Tr[i] = a.rate ? a.rate[i] : 0.0f;
   }
   __syncthreads();
-  const int64_t R = (int64_t)a.N * a.D;
+  const int64_t R = ROWS ? a.n_rows : (int64_t)a.N * a.D;
   const int64_t row0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   int n_changed = 0, n_j1 = 0, n_j2 = 0;
   if (row0 < R) {
     float L[4 * S], RB[MODE == MODE_RATES ? 4 * S : 1];
     int X[4], XB[4], XO[4];
-    const bool full = row0 + 3 < R;
+    int64_t P[4];                                        // (ROWS: the listed rows of the N*D space)
+    const bool full = !ROWS && row0 + 3 < R;
     if (full) {
 #pragma unroll
       for (int i = 0; i < S; ++i) {
@@ -562,7 +575,9 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
     } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t rc = row0 + r < R ? row0 + r : R - 1;
+        const int64_t rl = row0 + r < R ? row0 + r : R - 1;
+        const int64_t rc = ROWS ? (int64_t)a.rows[rl] : rl;
+        P[r] = rc;
 #pragma unroll
         for (int s_ = 0; s_ < S; ++s_) L[r * S + s_] = a.logits[(size_t)rc * S + s_];
         X[r] = a.x[rc];
@@ -574,6 +589,7 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
       const int64_t row = row0 + r;
       const bool live = row < R;
       const int64_t rowc = live ? row : R - 1;
+      const int64_t prow = ROWS ? P[r] : rowc, orow = ROWS ? P[r] : row;
       const int xcur = min(max(X[r], 0), S - 1);
       const int xv = a.x_base ? min(max(XB[r], 0), S - 1) : xcur;
       XO[r] = xcur;
@@ -685,10 +701,10 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
 #pragma unroll
         for (int k = 0; k < S; ++k) {
           pr[k] /= se2;
-          if (live && a.out_a) a.out_a[(size_t)row * S + k] = pr[k];
+          if (live && a.out_a) a.out_a[(size_t)orow * S + k] = pr[k];
           float Ev;
-          if (a.E) Ev = a.E[(size_t)rowc * S + k];
-          else Ev = -logf(u01(philox_row(a.seed, a.offset, (uint64_t)rowc, (uint32_t)k).x));
+          if (a.E) Ev = a.E[(size_t)prow * S + k];
+          else Ev = -logf(u01(philox_row(a.seed, a.offset, (uint64_t)prow, (uint32_t)k).x));
           const float v = pr[k] / Ev;
           if (v > best || (v == best && k < bi)) { best = v; bi = k; }
         }
@@ -704,7 +720,7 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
       const bool ordinal = a.flags & CTDD_STEP_ORDINAL;
       int jump = 0, njumps = 0;
       if (Lam > 0.0f && Lam <= SUPERPOSE_MAX_LAMBDA) {
-        PhiloxStream rng(a.seed, a.offset, (uint64_t)rowc, 0u);
+        PhiloxStream rng(a.seed, a.offset, (uint64_t)prow, 0u);
         const int K = poisson_row(Lam, rng);
         njumps = K;
         if (K > 0 && (ordinal || K == 1)) {
@@ -726,9 +742,9 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
         for (int k = 0; k < S; k += 4) {
           const float r1 = k + 1 < S ? rr[k + 1] : 0.0f, r2 = k + 2 < S ? rr[k + 2] : 0.0f, r3 = k + 3 < S ? rr[k + 3] : 0.0f;
           const int b = k >> 2;
-          const u4 blk = philox_row(a.seed, a.offset, (uint64_t)rowc, DENSE_DRAW0 + (uint32_t)(b >> 2));
+          const u4 blk = philox_row(a.seed, a.offset, (uint64_t)prow, DENSE_DRAW0 + (uint32_t)(b >> 2));
           const uint32_t w = (b & 3) == 0 ? blk.x : (b & 3) == 1 ? blk.y : (b & 3) == 2 ? blk.z : blk.w;
-          cnt += min(subblock_draw(rr[k], r1, r2, r3, a.h, u01(w), a.seed, a.offset, (uint64_t)rowc, b, base, min(4, S - k), &jl), 1 << 20);
+          cnt += min(subblock_draw(rr[k], r1, r2, r3, a.h, u01(w), a.seed, a.offset, (uint64_t)prow, b, base, min(4, S - k), &jl), 1 << 20);
         }
         jl = jl > S ? S : (jl < -S ? -S : jl);
         jump = (ordinal || cnt <= 1) ? (int)jl : 0;
@@ -765,7 +781,7 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
       else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (row0 + r < R) a.out_x[row0 + r] = XO[r];
+          if (row0 + r < R) a.out_x[ROWS ? P[r] : row0 + r] = XO[r];
       }
     }
   }
@@ -781,6 +797,7 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
 
 template <int S>
 static void launch_small_mode(const StepArgs& a, dim3 g, hipStream_t st) {
+  if (a.rows) { hipLaunchKernelGGL((k_rows_small<S, MODE_TAULEAP, true>), g, dim3(256), 0, st, a); return; }   // (tau-leap only)
   switch (a.mode) {
     case MODE_RATES: hipLaunchKernelGGL((k_rows_small<S, MODE_RATES>), g, dim3(256), 0, st, a); break;
     case MODE_TAULEAP: hipLaunchKernelGGL((k_rows_small<S, MODE_TAULEAP>), g, dim3(256), 0, st, a); break;
@@ -796,7 +813,7 @@ static bool small_rows_ok(const StepArgs& a) {
   return al16(a.logits) && al16(a.x) && al16(a.x_base) && al16(a.out_x) && (a.mode != MODE_RATES || (al16(a.out_a) && al16(a.out_b)));
 }
 static int launch_rows_small(const StepArgs& a, void* stream) {
-  const int64_t R = (int64_t)a.N * a.D;
+  const int64_t R = a.rows ? a.n_rows : (int64_t)a.N * a.D;
   const int64_t grid = (R + 1023) / 1024;
   CTDD_REQUIRE(grid > 0 && grid < (1ll << 31), CTDD_ERANGE, "rows out of range: %lld", (long long)R);
   hipStream_t st = (hipStream_t)stream;
@@ -821,12 +838,20 @@ static int launch_rows(const StepArgs& a0, void* stream) {
   if (a.S <= 4) G = 1;          // maze (S = 3), synthetic (S = 2): a row per LANE -- 64 rows share a wave's instruction stream
   a.G = G;
   const int ept_need = (a.S + G - 1) / G;
-  const int64_t R = (int64_t)a.N * a.D;
+  const int64_t R = a.rows ? a.n_rows : (int64_t)a.N * a.D;
   const int rows_per_wg = 4 * ROWS_PER_WAVE * (64 / G);
   const int64_t grid = (R + rows_per_wg - 1) / rows_per_wg;
   CTDD_REQUIRE(grid > 0 && grid < (1ll << 31), CTDD_ERANGE, "rows out of range: %lld", (long long)R);
   hipStream_t st = (hipStream_t)stream;
   dim3 g((unsigned)grid), b(256);
+  if (a.rows) {                 // row-list launch (tau-leap only): the same kernels with the ROWS indirection
+    if (ept_need <= 1) hipLaunchKernelGGL((k_rows<1, true>), g, b, 0, st, a);
+    else if (ept_need <= 2) hipLaunchKernelGGL((k_rows<2, true>), g, b, 0, st, a);
+    else if (ept_need <= 4) hipLaunchKernelGGL((k_rows<4, true>), g, b, 0, st, a);
+    else if (ept_need <= 8) hipLaunchKernelGGL((k_rows<8, true>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((k_rows<16, true>), g, b, 0, st, a);
+    return finish_launch("k_rows (row list)");
+  }
   if (ept_need <= 1) hipLaunchKernelGGL(k_rows<1>, g, b, 0, st, a);
   else if (ept_need <= 2) hipLaunchKernelGGL(k_rows<2>, g, b, 0, st, a);
   else if (ept_need <= 4) hipLaunchKernelGGL(k_rows<4>, g, b, 0, st, a);
@@ -914,6 +939,28 @@ extern "C" int ctdd_tauleap_step(int branch, int logit_type, const float* logits
   a.out_x = out_x; a.out_changed = out_changed;
   int st;
   if (try_s256(a, stream, &st)) return st;
+  return launch_rows(a, stream);
+}
+
+/* The tau-leap step on the listed rows only (include/ctdd.h): same kernels and draws as ctdd_tauleap_step, row v of the
+ * launch is row rows[v]; unlisted rows of out_x are not written, so out_x must not alias x. */
+extern "C" int ctdd_tauleap_step_rows(int branch, int logit_type, const float* logits, const int32_t* x,
+                                      const int32_t* x_base, const float* qt0, const float* base_rate,
+                                      float beta, float eps, float h, uint32_t flags, uint64_t seed,
+                                      uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
+                                      int32_t* out_x, int32_t* out_changed, void* stream) {
+  if (int rc = check_common(logits, x, N, D, S)) return rc;
+  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
+  CTDD_REQUIRE(out_x, CTDD_EINVAL, "null output");
+  CTDD_REQUIRE(out_x != x, CTDD_EINVAL, "out_x must not alias x (unlisted rows are not written)");
+  CTDD_REQUIRE(n_rows >= 0 && (int64_t)n_rows <= (int64_t)N * D, CTDD_ERANGE, "n_rows=%d outside [0, N*D]", n_rows);
+  if (n_rows == 0) return CTDD_OK;
+  CTDD_REQUIRE(rows, CTDD_EINVAL, "null row list");
+  StepArgs a{};
+  a.logits = logits; a.x = x; a.x_base = x_base; a.qt0 = qt0; a.rate = base_rate; a.beta = beta;
+  a.eps = eps; a.h = h; a.flags = flags; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
+  a.branch = branch; a.logit_type = logit_type; a.mode = MODE_TAULEAP;
+  a.out_x = out_x; a.out_changed = out_changed; a.rows = rows; a.n_rows = n_rows;
   return launch_rows(a, stream);
 }
 

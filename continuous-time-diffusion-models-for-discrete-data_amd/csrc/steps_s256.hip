@@ -139,6 +139,9 @@ __host__ __device__ constexpr int mid_wait(int kk) {
 }
 template <int N> __device__ inline void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// ROWS: the row-list launch -- tile row v is row a.rows[v] for the logits / state loads, the stores and the Philox counter (dead
+// lanes clamp to the last listed row); false: the full launch, unchanged.
+template <bool ROWS>
 __global__ __launch_bounds__(256, 1) void k_tauleap_s256(const S256Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #ifdef CTDD_S256_STAMPS
@@ -172,9 +175,12 @@ __global__ __launch_bounds__(256, 1) void k_tauleap_s256(const S256Args a) {
   unsigned char* wl_lo = wl_hi + 16384;
   float zv = 1.0f;                     // lane l keeps Z of row (l & 31)
   int xj, xcur;                        // rate-state / current state of row (l & 31)
+  int prj = 0;                         // (ROWS: the listed row of tile row (l & 31))
   {
     const int64_t rj = wrow0 + j;
-    const int64_t rjc = rj < a.R ? rj : a.R - 1;
+    const int64_t rjl = rj < a.R ? rj : a.R - 1;
+    if constexpr (ROWS) prj = a.rows[rjl];
+    const int64_t rjc = ROWS ? (int64_t)prj : rjl;
     xcur = min(max(a.x[rjc], 0), S256 - 1);
     xj = a.x_base ? min(max(a.x_base[rjc], 0), S256 - 1) : xcur;
   }
@@ -184,7 +190,7 @@ __global__ __launch_bounds__(256, 1) void k_tauleap_s256(const S256Args a) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       const int64_t row = wrow0 + b * 8 + r;
-      const int64_t rowc = row < a.R ? row : a.R - 1;
+      const int64_t rowc = ROWS ? (int64_t)__builtin_amdgcn_readlane(prj, b * 8 + r) : (row < a.R ? row : a.R - 1);
       const int xr = __builtin_amdgcn_readlane(xj, b * 8 + r);
       L[r] = *(const float4*)(a.logits + (size_t)rowc * S256 + lane * 4);
       Q[r] = *(const float4*)(invq + (size_t)xr * S256 + lane * 4);
@@ -334,6 +340,7 @@ __global__ __launch_bounds__(256, 1) void k_tauleap_s256(const S256Args a) {
   const float scale = a.beta * invz;                            // true rate = scale * r
   const int64_t myrow = wrow0 + j;
   const bool live = myrow < a.R;
+  const int64_t orow = ROWS ? (int64_t)prj : myrow;             // row of the outputs (live lanes)
   const float* crow = a.R0 + (size_t)xj * S256 + 4 * g;
   // the masked rates r (units of beta/Z) go to the wave's own LDS region as [block 32][lane 64]
   // float4 (block = 8 consecutive destinations shared by the lane pair), so that the draw code
@@ -355,7 +362,7 @@ __global__ __launch_bounds__(256, 1) void k_tauleap_s256(const S256Args a) {
       T += (v0 + v1) + (v2 + v3);
       rl4[(4 * m + q) * 64] = make_float4(v0, v1, v2, v3);
       if (a.out_rates && live)
-        *(float4*)(a.out_rates + (size_t)myrow * S256 + 32 * m + 8 * q + 4 * g) =
+        *(float4*)(a.out_rates + (size_t)orow * S256 + 32 * m + 8 * q + 4 * g) =
             make_float4(scale * v0, scale * v1, scale * v2, scale * v3);
     }
     __builtin_amdgcn_sched_barrier(0);                          // keep the loads' live ranges per m-tile
@@ -366,7 +373,7 @@ __global__ __launch_bounds__(256, 1) void k_tauleap_s256(const S256Args a) {
 
   const float Lam = scale * T * a.h;
   const bool ordinal = a.flags & CTDD_STEP_ORDINAL;
-  const uint64_t rngrow = (uint64_t)(live ? myrow : a.R - 1);
+  const uint64_t rngrow = ROWS ? (uint64_t)prj : (uint64_t)(live ? myrow : a.R - 1);
   int jump = 0, njumps = 0;               // njumps: jump events drawn for this dimension (sum_s k_s)
   if (Lam > 0.0f && Lam <= SUPERPOSE_MAX_LAMBDA) {
     PhiloxStream rng(a.seed, a.offset, rngrow, 0u);             // both lanes of the pair: same stream
@@ -457,7 +464,7 @@ __global__ __launch_bounds__(256, 1) void k_tauleap_s256(const S256Args a) {
   bool moved = false;
   if (live && g == 0) {
     const int xn = min(max(xcur + jump, 0), S256 - 1);
-    a.out_x[myrow] = xn;
+    a.out_x[orow] = xn;
     moved = (a.flags & CTDD_STEP_COUNT_RAW) ? (jump != 0) : (xn != xcur);
   }
   if (a.out_changed) {                       // one atomic per wave instead of one per row on a single address
@@ -503,10 +510,9 @@ static int s256_prepare(const float* qt0, const float* base_rate, float eps, int
   return CTDD_OK;
 }
 
-extern "C" int ctdd_tauleap_step_s256(const void* logits, const int32_t* x, const int32_t* x_base,
-                                      const void* step_tables, const float* RT0, const float* R0, float beta,
-                                      float h, uint32_t flags, uint64_t seed, uint64_t offset, int N, int D,
-                                      float* out_rates, int32_t* out_x, int32_t* out_changed, void* stream) {
+static int tauleap_s256(const void* logits, const int32_t* x, const int32_t* x_base, const void* step_tables, const float* RT0,
+                        const float* R0, float beta, float h, uint32_t flags, uint64_t seed, uint64_t offset, int N, int D,
+                        const int32_t* rows, int n_rows, float* out_rates, int32_t* out_x, int32_t* out_changed, void* stream) {
   CTDD_REQUIRE(logits && x && step_tables && RT0 && R0, CTDD_EINVAL, "null input");
   CTDD_REQUIRE(out_x || out_rates, CTDD_EINVAL, "no output requested");
   CTDD_REQUIRE(N > 0 && D > 0, CTDD_EINVAL, "N=%d D=%d must be positive", N, D);
@@ -515,14 +521,42 @@ extern "C" int ctdd_tauleap_step_s256(const void* logits, const int32_t* x, cons
   a.logits = (const float*)logits; a.x = x; a.x_base = x_base; a.tables = (const unsigned char*)step_tables;
   a.RT0 = (flags & CTDD_STEP_CRM) ? R0 : RT0;      // CRM branch: forward rate out of x, R[x][s]
   a.R0 = R0; a.beta = beta; a.h = h; a.flags = flags; a.seed = seed; a.offset = offset;
-  a.R = (int64_t)N * D; a.out_rates = out_rates; a.out_x = out_x; a.out_changed = out_changed;
+  a.R = rows ? (int64_t)n_rows : (int64_t)N * D; a.out_rates = out_rates; a.out_x = out_x; a.out_changed = out_changed;
+  a.rows = rows;
   if (flags & CTDD_STEP_BF16) return launch_tauleap_s256_b16(a, (hipStream_t)stream);
   const int64_t grid = (a.R + TILE_ROWS - 1) / TILE_ROWS;
   CTDD_REQUIRE(grid < (1ll << 31), CTDD_ERANGE, "too many rows");
-  static bool attr_done[16] = {};
-  ensure_lds_ceiling((const void*)k_tauleap_s256, attr_done);
-  hipLaunchKernelGGL(k_tauleap_s256, dim3((unsigned)grid), dim3(256), 163840, (hipStream_t)stream, a);
+  static bool attr_done[2][16] = {};
+  auto go = [&](auto kernel, int slot) {
+    ensure_lds_ceiling((const void*)kernel, attr_done[slot]);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 163840, (hipStream_t)stream, a);
+  };
+  if (rows) go(k_tauleap_s256<true>, 1);
+  else go(k_tauleap_s256<false>, 0);
   return finish_launch("k_tauleap_s256");
+}
+
+extern "C" int ctdd_tauleap_step_s256(const void* logits, const int32_t* x, const int32_t* x_base,
+                                      const void* step_tables, const float* RT0, const float* R0, float beta,
+                                      float h, uint32_t flags, uint64_t seed, uint64_t offset, int N, int D,
+                                      float* out_rates, int32_t* out_x, int32_t* out_changed, void* stream) {
+  return tauleap_s256(logits, x, x_base, step_tables, RT0, R0, beta, h, flags, seed, offset, N, D, nullptr, 0, out_rates, out_x,
+                      out_changed, stream);
+}
+
+/* The S = 256 step on the listed rows only (include/ctdd.h): listed rows bit-identical to ctdd_tauleap_step_s256, unlisted rows
+ * of out_x / out_rates not written (out_x must not alias x). */
+extern "C" int ctdd_tauleap_step_s256_rows(const void* logits, const int32_t* x, const int32_t* x_base,
+                                           const void* step_tables, const float* RT0, const float* R0, float beta,
+                                           float h, uint32_t flags, uint64_t seed, uint64_t offset, int N, int D,
+                                           const int32_t* rows, int n_rows, float* out_rates, int32_t* out_x,
+                                           int32_t* out_changed, void* stream) {
+  CTDD_REQUIRE(n_rows >= 0 && (int64_t)n_rows <= (int64_t)N * D, CTDD_ERANGE, "n_rows=%d outside [0, N*D]", n_rows);
+  CTDD_REQUIRE(!out_x || out_x != x, CTDD_EINVAL, "out_x must not alias x (unlisted rows are not written)");
+  if (n_rows == 0) return CTDD_OK;
+  CTDD_REQUIRE(rows, CTDD_EINVAL, "null row list");
+  return tauleap_s256(logits, x, x_base, step_tables, RT0, R0, beta, h, flags, seed, offset, N, D, rows, n_rows, out_rates, out_x,
+                      out_changed, stream);
 }
 
 namespace ctdd {

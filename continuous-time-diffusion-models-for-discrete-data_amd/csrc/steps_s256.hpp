@@ -24,6 +24,8 @@ struct S256Args {
   float* out_rates;              // optional (R,256): masked reverse rates (validation / unfused use)
   int32_t* out_x;
   int32_t* out_changed;
+  const int32_t* rows;           // row-list launch (ctdd_tauleap_step_s256_rows): tile row v is row rows[v] of the N*D space and
+                                 // R counts the listed rows; null for the full launch
 };
 
 // steps_s256_b16.hip: the CTDD_STEP_BF16 variant of the launch (same arguments, same tables)

@@ -100,7 +100,9 @@ __host__ __device__ constexpr int mid_wait(int c) { return c == 0 ? 12 : c <= 4 
 // code with those uniform branches compiled out, so the epilogue is straight-line.
 // L16 = true: the logits are bf16 (the bf16 network's output convolution writes them that way: half the bytes of the
 // step's one large read); both passes then fit the staging buffer and come in by LDS-DMA.
-template <bool GENERAL, bool L16>
+// ROWS = true: the row-list launch -- tile row v is row a.rows[v] for the LDS-DMA / register loads of the logits, the state
+// loads, the stores and the Philox counter (dead lanes clamp to the last listed row); false: the full launch, unchanged.
+template <bool GENERAL, bool L16, bool ROWS = false>
 __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #ifdef CTDD_S256_STAMPS
@@ -127,9 +129,12 @@ __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
     }
   };
   int xj, xcur;                        // rate-state / current state of row (lane & 31): first, the invq gathers hang on them
+  int prj = 0;                         // (ROWS: the listed row of tile row (lane & 31))
   {
     const int64_t rj = wrow0 + j;
-    const int64_t rjc = rj < a.R ? rj : a.R - 1;
+    const int64_t rjl = rj < a.R ? rj : a.R - 1;
+    if constexpr (ROWS) prj = a.rows[rjl];
+    const int64_t rjc = ROWS ? (int64_t)prj : rjl;
     xcur = a.x[rjc];
     xj = (GENERAL && a.x_base) ? a.x_base[rjc] : xcur;
   }
@@ -152,7 +157,11 @@ __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
     for (int i = 0; i < 16; ++i) {
       const int r = 2 * i + (lane >> 5);
       const int64_t row = wrow0 + r;
-      const int64_t rowc = row < a.R ? row : a.R - 1;
+      int64_t rowc = row < a.R ? row : a.R - 1;
+      if constexpr (ROWS) {
+        const int p0 = __builtin_amdgcn_readlane(prj, 2 * i), p1 = __builtin_amdgcn_readlane(prj, 2 * i + 1);
+        rowc = (lane >> 5) ? p1 : p0;
+      }
       const unsigned char* src = (const unsigned char*)(lg + (size_t)rowc * S256) + (((lane & 31) ^ (r & 15)) << 4);
       __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
                                        (void __attribute__((address_space(3)))*)(stg + i * 1024), 16, 0, 0);
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t row = wrow0 + r;
-    const int64_t rowc = row < a.R ? row : a.R - 1;
+    const int64_t rowc = ROWS ? (int64_t)__builtin_amdgcn_readlane(prj, r) : (row < a.R ? row : a.R - 1);
     // LDS position `lane` of row r receives global 16-byte piece lane ^ r
     const unsigned char* src = (const unsigned char*)(a.logits + (size_t)rowc * S256) + ((lane ^ r) << 4);
     __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
@@ -228,7 +237,7 @@ __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t row = wrow0 + 16 + r;
-    const int64_t rowc = row < a.R ? row : a.R - 1;
+    const int64_t rowc = ROWS ? (int64_t)__builtin_amdgcn_readlane(prj, 16 + r) : (row < a.R ? row : a.R - 1);
     st1[r] = *(const f32x4*)(a.logits + (size_t)rowc * S256 + ((lane ^ r) << 2));
   }
   xcur = min(max(xcur, 0), S256 - 1);
@@ -387,6 +396,7 @@ __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
   const float scale = a.beta * invz;                            // true rate = scale * r
   const int64_t myrow = wrow0 + j;
   const bool live = myrow < a.R;
+  const int64_t orow = ROWS ? (int64_t)prj : myrow;             // row of the outputs (live lanes)
   const float* crow = a.R0 + (size_t)xj * S256 + 4 * g;
   __builtin_amdgcn_s_barrier();                                 // every wave has left the A ring
   float T0 = 0.0f, T1 = 0.0f, T2 = 0.0f, T3 = 0.0f;     // (four running sums: a per-block sum here would be kept alive for the
@@ -410,7 +420,7 @@ __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
       T0 += v0; T1 += v1; T2 += v2; T3 += v3;
       acc[m][4 * q + 0] = v0; acc[m][4 * q + 1] = v1; acc[m][4 * q + 2] = v2; acc[m][4 * q + 3] = v3;
       if (GENERAL && a.out_rates && live)
-        *(float4*)(a.out_rates + (size_t)myrow * S256 + 32 * m + 8 * q + 4 * g) =
+        *(float4*)(a.out_rates + (size_t)orow * S256 + 32 * m + 8 * q + 4 * g) =
             make_float4(scale * v0, scale * v1, scale * v2, scale * v3);
     }
   };
@@ -436,7 +446,7 @@ __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
 
   const float Lam = scale * T * a.h;
   const bool ordinal = a.flags & CTDD_STEP_ORDINAL;
-  const uint64_t rngrow = (uint64_t)(live ? myrow : a.R - 1);
+  const uint64_t rngrow = ROWS ? (uint64_t)prj : (uint64_t)(live ? myrow : a.R - 1);
   int jump = 0, njumps = 0;               // njumps: jump events drawn for this dimension (sum_s k_s)
   const bool dense = Lam > SUPERPOSE_MAX_LAMBDA;
   const bool superp = Lam > 0.0f && Lam <= SUPERPOSE_MAX_LAMBDA;
@@ -592,7 +602,7 @@ __global__ __launch_bounds__(256, 2) void k_tauleap_s256_b16(const S256Args a) {
   bool moved = false;
   if (live && g == 0) {
     const int xn = min(max(xcur + jump, 0), S256 - 1);
-    a.out_x[myrow] = xn;
+    a.out_x[orow] = xn;
     moved = (a.flags & CTDD_STEP_COUNT_RAW) ? (jump != 0) : (xn != xcur);
   }
   if (a.out_changed) {
@@ -623,11 +633,18 @@ int launch_tauleap_s256_b16(const S256Args& a, hipStream_t stream) {
   CTDD_REQUIRE(grid < (1ll << 31), CTDD_ERANGE, "too many rows");
   const bool general = a.x_base || a.out_rates || (a.flags & (CTDD_STEP_CORRECTOR | CTDD_STEP_CRM));
   const bool l16 = a.flags & CTDD_STEP_LOGITS_BF16;
-  static bool attr_done4[4][16] = {};
+  static bool attr_done4[8][16] = {};
   auto go = [&](auto kernel, int slot) {
     ensure_lds_ceiling((const void*)kernel, attr_done4[slot]);
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), b16::LDS_BYTES, stream, a);
   };
+  if (a.rows) {                                // row-list launch (ctdd_tauleap_step_s256_rows)
+    if (general && l16) go(b16::k_tauleap_s256_b16<true, true, true>, 4);
+    else if (general) go(b16::k_tauleap_s256_b16<true, false, true>, 5);
+    else if (l16) go(b16::k_tauleap_s256_b16<false, true, true>, 6);
+    else go(b16::k_tauleap_s256_b16<false, false, true>, 7);
+    return finish_launch("k_tauleap_s256_b16 (row list)");
+  }
   if (general && l16) go(b16::k_tauleap_s256_b16<true, true>, 0);
   else if (general) go(b16::k_tauleap_s256_b16<true, false>, 1);
   else if (l16) go(b16::k_tauleap_s256_b16<false, true>, 2);

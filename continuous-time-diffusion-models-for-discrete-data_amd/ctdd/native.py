@@ -40,6 +40,7 @@ _SIGS = {
     "ctdd_tauleap_apply": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P], _I),
     "ctdd_tauleap_draw": ([_P, _P, _P, _F, _U32, _U64, _U64, _I, _I, _I, _P, _P, _P], _I),
     "ctdd_tauleap_step": ([_I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _U32, _U64, _U64, _I, _I, _I, _P, _P, _P], _I),
+    "ctdd_tauleap_step_rows": ([_I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _U32, _U64, _U64, _I, _I, _I, _P, _I, _P, _P, _P], _I),
     "ctdd_lbjf_step": ([_I, _I, _P, _P, _P, _P, _F, _F, _F, _U32, _P, _U64, _U64, _I, _I, _I, _P, _P, _P, _P], _I),
     "ctdd_logprob_rp_mfma": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
     "ctdd_logprob_rp_bwd_mfma": ([_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P], _I),
@@ -54,6 +55,7 @@ _SIGS = {
     "ctdd_s256_prepare": ([_P, _P, _F, _I, _P, _P, _P, _P], _I),
     "ctdd_s256_prepare_crm": ([_P, _P, _I, _P, _P, _P, _P], _I),
     "ctdd_tauleap_step_s256": ([_P, _P, _P, _P, _P, _P, _F, _F, _U32, _U64, _U64, _I, _I, _P, _P, _P, _P], _I),
+    "ctdd_tauleap_step_s256_rows": ([_P, _P, _P, _P, _P, _P, _F, _F, _U32, _U64, _U64, _I, _I, _P, _I, _P, _P, _P, _P], _I),
     "ctdd_crm_loss": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_ctelbo_scratch_bytes": ([_I, _I, _I], _I64),
     "ctdd_ctelbo_loss": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P], _I),
@@ -224,6 +226,41 @@ def tauleap_step(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, fl
                                   float(beta), float(eps), float(h), int(flags), seed, offset, N, D, S,
                                   _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream())
     _check(rc, "ctdd_tauleap_step")
+    return out
+
+
+def _row_list(rows, N, D):
+    if rows.dim() != 1:
+        raise CtddError(f"rows: expected a 1-D int32 tensor, got shape {tuple(rows.shape)}")
+    if rows.numel() > N * D:
+        raise CtddError(f"rows: {rows.numel()} entries for {N * D} rows")
+    return _ptr(rows, i32, "rows"), int(rows.numel())
+
+
+def _prefilled(out, x, N, D):
+    """The output state of a row-list step: unlisted rows are not written, so it starts as one device copy of x."""
+    if out is None:
+        return x.clone()
+    if out.data_ptr() == x.data_ptr():
+        raise CtddError("out must not alias x: the row-list step leaves unlisted rows of out untouched")
+    if tuple(out.shape) != (N, D):
+        raise CtddError(f"out: expected shape {(N, D)}, got {tuple(out.shape)}")
+    return out
+
+
+def tauleap_step_rows(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, seed, offset, rows,
+                      x_base=None, out=None, changed=None):
+    """tauleap_step on the rows listed in `rows` (ascending, distinct int32 indices into the N*D rows, on the device): listed
+    rows of the result are bit-identical to the full step's, the others are `out` as given (default: a copy of x)."""
+    N, D, S = logits.shape
+    rp, nr = _row_list(rows, N, D)
+    out = _prefilled(out, x, N, D)
+    rc = load().ctdd_tauleap_step_rows(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
+                                       _ptr(x_base, i32, "x_base"), _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"),
+                                       float(beta), float(eps), float(h), int(flags), seed, offset, N, D, S, rp, nr,
+                                       _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream())
+    _check(rc, "ctdd_tauleap_step_rows")
+    _count("ctdd_tauleap_step_rows")
     return out
 
 
@@ -473,4 +510,31 @@ def tauleap_step_s256(logits, x, tables, i, beta, h, flags, seed, offset, x_base
                                        int(flags) | (STEP_CRM if tables.crm else 0) | (STEP_BF16 if tables.bf16 else 0) | lflag, seed, offset, N, D, _ptr(rates), _ptr(out, i32, "out") if want_x else None,
                                        _ptr(changed, i32, "changed"), _stream())
     _check(rc, "ctdd_tauleap_step_s256")
+    return (out, rates) if want_rates else out
+
+
+def tauleap_step_s256_rows(logits, x, tables, i, beta, h, flags, seed, offset, rows, x_base=None, out=None, changed=None,
+                           want_rates=False, rates=None):
+    """tauleap_step_s256 on the rows listed in `rows` (see tauleap_step_rows).  want_rates: also the masked reverse rates of the
+    listed rows, into `rates` (N, D, 256) f32 when given (unlisted rows untouched), else into a fresh uninitialised tensor."""
+    N, D, S = logits.shape
+    if S != 256:
+        raise CtddError("tauleap_step_s256_rows needs S == 256")
+    rp, nr = _row_list(rows, N, D)
+    out = _prefilled(out, x, N, D)
+    if want_rates and rates is None:
+        rates = torch.empty(logits.shape, dtype=f32, device=logits.device)
+    lflag = 0
+    if logits.dtype == torch.bfloat16:
+        if not tables.bf16:
+            raise CtddError("tauleap_step_s256_rows: bf16 logits need S256Tables(..., bf16=True)")
+        lflag = STEP_LOGITS_BF16
+    rc = load().ctdd_tauleap_step_s256_rows(_ptr(logits, torch.bfloat16 if lflag else f32, "logits"), _ptr(x, i32, "x"),
+                                            _ptr(x_base, i32, "x_base"), tables.step_ptr(i), _ptr(tables.RT0), _ptr(tables.R0),
+                                            float(beta), float(h),
+                                            int(flags) | (STEP_CRM if tables.crm else 0) | (STEP_BF16 if tables.bf16 else 0) | lflag,
+                                            seed, offset, N, D, rp, nr, _ptr(rates, f32, "rates") if want_rates else None,
+                                            _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream())
+    _check(rc, "ctdd_tauleap_step_s256_rows")
+    _count("ctdd_tauleap_step_s256_rows")
     return (out, rates) if want_rates else out

@@ -1,5 +1,6 @@
 """Samplers behind the reference's registry names (lib/sampling/sampling.py): TauL 82-234,
-LBJF 238-356, MidPointTauL 360-526, PCTauL 530-646.
+LBJF 238-356, MidPointTauL 360-526, PCTauL 530-646, ConditionalTauLeaping 649-758,
+ConditionalPCTauLeaping 761-905.
 
 Same constructor `(cfg)`, same `sample(model, N)` return shapes; the per-step work is one fused
 libctdd launch (reverse rates -> jump draw -> state update) on int32 device state.  Differences
@@ -149,6 +150,14 @@ class _GridSampler:
         return native.tauleap_step(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta,
                                    self.eps_ratio, h, flags, key, offset, x_base=x_base, changed=changed)
 
+    def _leap_rows(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, rows, changed=None):
+        """_leap on the listed rows only (int32 device tensor of row indices into the N*D rows); the other rows of the returned
+        state are those of x."""
+        if fast is not None:
+            return native.tauleap_step_s256_rows(logits, x, fast, i, beta, h, flags, key, offset, rows, changed=changed)
+        return native.tauleap_step_rows(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta,
+                                        self.eps_ratio, h, flags, key, offset, rows, changed=changed)
+
     def _lbjf(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, changed=None):
         """One Euler / LBJF step; at S = 256 the reverse rates come from the matrix-core kernel, the posterior and the
         categorical draw run on them."""
@@ -242,13 +251,14 @@ class TauL(_GridSampler):
                     with torch.cuda.stream(st.streams[j]):
                         model._engine_slot = j
                         # a Philox key per sub-batch (the rows of a launch are numbered from 0)
-                        st.xs[j] = self._advance_one(st, i, st.xs[j], st.N // st.parts, st.key + 7919 * j, st.changed_p[j, i:i + 1])
+                        st.xs[j] = self._advance_one(st, i, st.xs[j], st.N // st.parts, st.key + 7919 * j, st.changed_p[j, i:i + 1],
+                                                     part=j)
             finally:
                 model._engine_slot = None
                 if st.temb is not None:
                     model._engine_time_row = None
 
-    def _advance_one(self, st, i, x, N, key, changed):
+    def _advance_one(self, st, i, x, N, key, changed, part=0):
         model = st.model
         t = st.ts[i]
         h = float(np.float32(st.ts[i] - st.ts[i + 1]))
@@ -419,6 +429,166 @@ class PCTauL(_GridSampler):
                                        native.STEP_ORDINAL | native.STEP_CORRECTOR, key, i * sub + 1 + c)
             x = self._final_argmax(model, x, N)
             return x.cpu().numpy().astype(int)
+
+
+class _Conditioned:
+    """Shared part of the conditional samplers: argument checks (all before any device work) and the held / free split.
+
+    `inpaint(model, x_known, mask)`: x_known (N, D) integer states, mask (D,) or (N, D) bool, True = held at x_known.  The
+    state is always the full (N, D): held entries are scattered in once after the initial draw, so the network sees them at
+    every step, and every step launch moves only the free rows (the `_rows` step entry points: a held row costs no softmax,
+    no S x S contraction and no draw).  The final argmax is taken at min_t and the held entries are restored in the result.
+    `sample(model, N, conditioner)` (the reference's call) is `inpaint` with the first cfg.sampler.condition_dim columns
+    held.  D is cfg.model.concat_dim (the reference reads cfg.data.shape[0], which is D only for 1-D data); for image data
+    the flattened order is the row-major (C, H, W) one, so a prefix of the dimensions is the top rows of the image."""
+
+    def _prefix(self, N, conditioner):
+        cd = getattr(self.cfg.sampler, "condition_dim", None)
+        if cd is None or not 0 < int(cd) < self.D:
+            raise ValueError(f"cfg.sampler.condition_dim must satisfy 0 < condition_dim < D = {self.D}, got {cd!r}")
+        cd, N = int(cd), int(N)
+        cond = torch.as_tensor(conditioner)
+        if tuple(cond.shape) != (N, cd):
+            raise ValueError(f"conditioner: expected shape {(N, cd)}, got {tuple(cond.shape)}")
+        x_known = torch.zeros((N, self.D), dtype=torch.int64)
+        x_known[:, :cd] = cond.cpu().to(torch.int64)
+        mask = torch.zeros(self.D, dtype=torch.bool)
+        mask[:cd] = True
+        return x_known, mask
+
+    def _held(self, x_known, mask):
+        """-> (N, x_known int32 (N, D), mask bool (N, D)) on the host, after the shape / dtype / value checks."""
+        xk = torch.as_tensor(x_known)
+        if xk.dim() != 2 or xk.shape[1] != self.D:
+            raise ValueError(f"x_known: expected shape (N, {self.D}), got {tuple(xk.shape)}")
+        if xk.dtype.is_floating_point or xk.dtype.is_complex or xk.dtype == torch.bool:
+            raise ValueError(f"x_known: expected an integer tensor, got {xk.dtype}")
+        N = int(xk.shape[0])
+        m = torch.as_tensor(mask)
+        if m.dtype != torch.bool:
+            raise ValueError(f"mask: expected a bool tensor, got {m.dtype}")
+        if tuple(m.shape) == (self.D,):
+            m = m.view(1, self.D).expand(N, self.D)
+        elif tuple(m.shape) != (N, self.D):
+            raise ValueError(f"mask: expected shape ({self.D},) or {(N, self.D)}, got {tuple(m.shape)}")
+        if N < 1:
+            raise ValueError("x_known: no samples")
+        xk, m = xk.cpu().to(torch.int32), m.cpu().contiguous()         # (the call's one host round trip, before the loop)
+        held = xk[m]
+        if held.numel() and (int(held.min()) < 0 or int(held.max()) >= self.S):
+            raise ValueError(f"x_known: held values must lie in [0, {self.S})")
+        return N, xk, m
+
+    @staticmethod
+    def _free_rows(m, parts, dev):
+        """Free-row lists (int32, ascending, on the device), one per sub-batch and relative to it."""
+        N = m.shape[0]
+        n = N // parts
+        return [(~m[j * n:(j + 1) * n]).reshape(-1).nonzero().view(-1).to(torch.int32).to(dev) for j in range(parts)]
+
+
+@sampling_utils.register_sampler
+class ConditionalTauLeaping(_Conditioned, TauL):
+    """Conditional tau-leaping (sampling.py:649-758), see _Conditioned: CT-ELBO rates with direct logits whatever cfg.loss is,
+    ordinal sum-and-clamp update (the reference overwrites its reject_multiple_jumps branch, line 744), initial std
+    cfg.model.Q_sigma, grid linspace(1.0, min_t, num_steps) + [0], no corrector, argmax at min_t.  The loop is TauL's
+    begin / advance / finish, so on the U-Net engine it runs as two pipelined sub-batch chains, each with its own row list."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        self.branch, self.logit_type = native.BRANCH_CTELBO, "direct"
+        self.max_t = 1.0
+        self.num_corrector_steps = 0
+        self.is_ordinal = True
+        self._held_now = None
+
+    def sample(self, model, N, conditioner):
+        x_known, mask = self._prefix(N, conditioner)
+        return self.inpaint(model, x_known, mask)
+
+    def inpaint(self, model, x_known, mask):
+        N, xk, m = self._held(x_known, mask)
+        if bool(m.all()):
+            return xk.numpy().astype(int)
+        dev = torch.device(model.device)
+        parts = self._pipeline_parts(model, N)
+        rows = self._free_rows(m, parts, dev)
+        self._held_now = (xk.to(dev), m.to(dev))
+        try:
+            with torch.no_grad(), self._borrow(model):
+                st = self.begin(model, N, pipeline=parts)
+                st.rows = rows
+                for i in range(self.num_steps):
+                    self.advance(st, i)
+                x = self._final_argmax(model, self.state_x(st), N)
+                return torch.where(self._held_now[1], self._held_now[0], x).cpu().numpy().astype(int)
+        finally:
+            self._held_now = None
+
+    def _initial(self, model, N, key, std):
+        x = super()._initial(model, N, key, std)
+        return x if self._held_now is None else torch.where(self._held_now[1], self._held_now[0], x)
+
+    def _advance_one(self, st, i, x, N, key, changed, part=0):
+        model = st.model
+        h = float(np.float32(st.ts[i] - st.ts[i + 1]))
+        t_ones = st.t_dev[i].expand(N) if st.temb is not None else self._t_ones(st.t32, i, N, st.dev)
+        q_i = st.qt0[i] if st.qt0 is not None else None
+        logits = self._net_logits(model, x, t_ones, st.fast)
+        return self._leap_rows(model, logits, x, q_i, st.fast, i, st.betas[i], h, st.flags, key, i * st.sub, st.rows[part],
+                               changed=changed)
+
+
+@sampling_utils.register_sampler
+class ConditionalPCTauLeaping(_Conditioned, _GridSampler):
+    """Conditional predictor-corrector tau-leaping (sampling.py:761-905), see _Conditioned: CT-ELBO rates with direct logits,
+    initial std cfg.model.Q_sigma, h = 1 / num_steps, grid linspace(1.0, min_t + h, num_steps) walked over ts[:-1];
+    correctors at t - h with step corrector_step_size_multiplier * h when t <= corrector_entry_time; sum-and-clamp update
+    (cfg.sampler.reject_multiple_jumps, default False, keeps only single-event dimensions, as the reference's
+    take_poisson_step does); argmax at min_t."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        self.branch, self.logit_type = native.BRANCH_CTELBO, "direct"
+
+    def sample(self, model, N, conditioner):
+        x_known, mask = self._prefix(N, conditioner)
+        return self.inpaint(model, x_known, mask)
+
+    def inpaint(self, model, x_known, mask):
+        N, xk, m = self._held(x_known, mask)
+        if bool(m.all()):
+            return xk.numpy().astype(int)
+        s = self.cfg.sampler
+        dev = torch.device(model.device)
+        rows = self._free_rows(m, 1, dev)[0]
+        xk, m = xk.to(dev), m.to(dev)
+        flags = 0 if bool(getattr(s, "reject_multiple_jumps", False)) else native.STEP_ORDINAL
+        key = self._key()
+        with torch.no_grad(), self._borrow(model):
+            x = torch.where(m, xk, self._initial(model, N, key, self.cfg.model.Q_sigma))
+            h0 = 1.0 / s.num_steps
+            ts = np.linspace(1.0, s.min_t + h0, s.num_steps)
+            pr = model.process
+            t32, qt0, betas = self._tables(model, ts)
+            fast = self._fast_tables(model, qt0)
+            sub = 1 + max(int(s.num_corrector_steps), 0)
+            for i, t in enumerate(ts[:-1]):
+                h = ts[i] - ts[i + 1]
+                logits = self._net_logits(model, x, self._t_ones(t32, i, N, dev), fast)
+                x = self._leap_rows(model, logits, x, qt0[i], fast, i, betas[i], float(np.float32(h)), flags, key, i * sub, rows)
+                if t <= s.corrector_entry_time:
+                    tc = torch.tensor([t - h], dtype=torch.float64).to(torch.float32)
+                    qc = pr.tables(tc, want_qt0=True)[0][0]
+                    bc = float(pr.beta(tc)[0])
+                    t_c = torch.full((N,), float(tc[0]), device=dev)
+                    fast_c = self._fast_tables(model, qc.unsqueeze(0)) if fast is not None else None
+                    for c in range(s.num_corrector_steps):
+                        logits = self._net_logits(model, x, t_c, fast_c)
+                        x = self._leap_rows(model, logits, x, qc, fast_c, 0, bc, float(np.float32(s.corrector_step_size_multiplier * h)),
+                                            flags | native.STEP_CORRECTOR, key, i * sub + 1 + c, rows)
+            x = self._final_argmax(model, x, N)
+            return torch.where(m, xk, x).cpu().numpy().astype(int)
 
 
 @sampling_utils.register_sampler

@@ -128,6 +128,17 @@ int ctdd_tauleap_step(int branch, int logit_type, const float* logits, const int
                       float eps, float h, uint32_t flags, uint64_t seed, uint64_t offset,
                       int N, int D, int S, int32_t* out_x, int32_t* out_changed, void* stream);
 
+/* Tau-leap step on the rows listed in `rows` only: n_rows ascending, distinct int32 indices into the N*D row space.
+ * For a listed row r, out_x[r] is bit-identical to what ctdd_tauleap_step writes for r with the same seed/offset/flags:
+ * the Philox counter is keyed by r, not by r's position in the list.  Unlisted rows of out_x are not written (out_x must
+ * not alias x).  out_changed counts listed rows only.  n_rows == 0 is a no-op.  (The conditional samplers: frozen
+ * dimensions need no softmax, no S x S contraction and no draw.) */
+int ctdd_tauleap_step_rows(int branch, int logit_type, const float* logits, const int32_t* x,
+                           const int32_t* x_base, const float* qt0, const float* base_rate, float beta,
+                           float eps, float h, uint32_t flags, uint64_t seed, uint64_t offset,
+                           int N, int D, int S, const int32_t* rows, int n_rows,
+                           int32_t* out_x, int32_t* out_changed, void* stream);
+
 /* K7  Euler / LBJF step (lib/sampling/sampling.py:278-293, corrector 296-341): posterior row
  * P = h*R^*(1-onehot) + clip(1-h*sum,0)*onehot, normalised, then x_new ~ Categorical(log(P+1e-35))
  * by exponential race.  E (N*D,S) explicit or NULL for Philox.  out_probs (N,D,S) may be NULL. */
@@ -189,6 +200,13 @@ int ctdd_tauleap_step_s256(const void* logits /* f32; bf16 with CTDD_STEP_LOGITS
                            const void* step_tables, const float* RT0, const float* R0, float beta,
                            float h, uint32_t flags, uint64_t seed, uint64_t offset, int N, int D,
                            float* out_rates, int32_t* out_x, int32_t* out_changed, void* stream);
+/* ctdd_tauleap_step_s256 on the listed rows only: the contract of ctdd_tauleap_step_rows (listed rows of out_x and out_rates
+ * bit-identical to the full launch, unlisted rows not written, counters over listed rows, n_rows == 0 a no-op). */
+int ctdd_tauleap_step_s256_rows(const void* logits /* f32; bf16 with CTDD_STEP_LOGITS_BF16 */, const int32_t* x,
+                                const int32_t* x_base, const void* step_tables, const float* RT0, const float* R0,
+                                float beta, float h, uint32_t flags, uint64_t seed, uint64_t offset, int N, int D,
+                                const int32_t* rows, int n_rows, float* out_rates, int32_t* out_x,
+                                int32_t* out_changed, void* stream);
 
 /* test hook: the raw uniforms a kernel would see: out[row*4*nblk + 4*j + i]. */
 int ctdd_philox_uniform(uint64_t seed, uint64_t offset, int64_t nrows, int nblk, float* out,
