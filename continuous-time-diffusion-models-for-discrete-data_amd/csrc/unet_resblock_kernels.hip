@@ -1,0 +1,385 @@
+// unet_resblock_kernels.hip -- a whole ResBlock of a small-resolution U-Net level in ONE launch (bf16 inference).
+//
+// At a fixed resolution a ResBlock (reference lib/networks/unet.py:100-140) is sample-local: the 3x3 convolutions never read
+// across samples, GroupNorm statistics are per (sample, group), the time bias is per (sample, channel), the residual / 1x1
+// skip is per pixel.  A workgroup that owns ONE whole sample (H*W <= 64 pixels) and ALL N = 192 output channels runs
+//   GN1 + Swish -> conv1 + bias + time bias -> GN2 + Swish -> conv2 (+ 1x1 skip segments on the raw input | + residual)
+// with nobody else involved: one launch instead of four, h1 and both activated tensors never leave LDS, every element is
+// normalised once, the statistics are a reduction inside the workgroup.  The rounding points are those of the four launches
+// it replaces (k_gn_onepass, k_conv_patch): a1, h1 (before GN2's statistics), a2 and the output are rounded to bf16, sums
+// are fp32 per thread / fp64 across threads, accumulation is fp32 on the matrix cores.
+//
+// Matrix mapping (v_mfma_f32_16x16x32_bf16, weights as the A operand, pixels as the B operand, so that a lane's four result
+// registers are four CONSECUTIVE channels of one pixel = one 8-byte bf16 store): wave w of four owns output channels
+// [48 w, 48 w + 48) (three 16-row weight tiles) x all pixel tiles (NPT = 4 of 16 pixels, 1 for H*W <= 16).  No two waves
+// read the same weight element, so the weights are streamed global -> registers by the wave that uses them, from a copy of
+// the [N][K] matrix packed in fragment order (every wave-instruction reads 1 KiB of consecutive bytes), PD chunks ahead; there is no
+// weight image in LDS, no ring and no barrier inside a K loop.  The pixel operand is read from a zero-bordered LDS slab in
+// which the nine taps are row offsets: per 64-channel chunk and wave 2 NPT ds_read_b128 and 6 global_load_dwordx4 feed
+// 6 NPT matrix instructions.
+//
+// LDS: raw input [HW][C] (kept for the skip segments / the residual), slab [(H+2)(W+2)][C] for a1, reused as the
+// [(H+2)(W+2)][N] slab of h1 / a2 and as the output image; rows are padded by 16 bytes (row stride = 4 banks mod 64:
+// conflict-free 16-byte reads of 16 consecutive rows).  7x7, C = 384: 38 + 62 + 29 (reduction scratch) = 129 KB.
+#include <type_traits>
+
+#include "common.hpp"
+#include "../../include/ctdd_unet.h"
+
+namespace ctdd {
+namespace {
+
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using bf16x2v = __attribute__((ext_vector_type(2))) __bf16;
+using f32x2v = __attribute__((ext_vector_type(2))) float;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+
+__device__ inline unsigned rb_pack2(float a, float b) {
+  f32x2v v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
+}
+
+constexpr int RB_THREADS = 256, RB_N = 192, RB_PST = 20, RB_MAXC = 384;
+
+struct RbLds {                       // byte offsets into the dynamic LDS block
+  int raw, slab, part, red, scale, total;
+  int rsA, rs2, prows;               // row strides (bytes) of the C- and N-channel images, rows of the padded grid
+};
+__host__ __device__ inline RbLds rb_layout(int H, int W, int C) {
+  RbLds L;
+  L.rsA = C * 2 + 16;
+  L.rs2 = RB_N * 2 + 16;
+  L.prows = (H + 2) * (W + 2);
+  const int slabA = L.prows * L.rsA, slab2 = L.prows * L.rs2;
+  L.raw = 0;
+  L.slab = H * W * L.rsA;
+  L.part = L.slab + (slabA > slab2 ? slabA : slab2);
+  L.red = L.part + RB_THREADS * RB_PST * 4;
+  L.scale = L.red + 2 * RB_MAXC * 8;
+  L.total = L.scale + 2 * RB_MAXC * 4;
+  return L;
+}
+
+__device__ inline int rb_prow(int p, int W) {
+  const int y = p / W;
+  return (y + 1) * (W + 2) + (p - y * W) + 1;
+}
+
+// GroupNorm + Swish of an [HW][C] bf16 image in LDS (`src`, rows p or padded rows): statistics as k_gn_onepass takes them
+// (fp32 per thread over its pixels, fp64 across threads and group members), then bf16(swish(x * scale + shift)) into the padded
+// rows of `dst` (which may be `src` itself: every element is read and written by the same thread).  Ends with a barrier.
+__device__ __attribute__((always_inline)) inline void rb_groupnorm(unsigned char* sm, const RbLds& L, int src, int src_rs, bool src_padded, int dst, int dst_rs,
+                                                      int HW, int W, int C, int G, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float eps) {
+  const int t = threadIdx.x, noct = C >> 3;
+  const int npl = RB_THREADS / noct < HW ? RB_THREADS / noct : HW, T = noct * npl;
+  const bool act = t < T;
+  const int oct = act ? t % noct : 0, pl = act ? t / noct : 0;
+  float* part = (float*)(sm + L.part);
+  double* red = (double*)(sm + L.red);
+  float* scale = (float*)(sm + L.scale);
+  float* shift = scale + RB_MAXC;
+  float sx[8], sq[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { sx[j] = 0.0f; sq[j] = 0.0f; }
+  if (act) {
+    for (int p = pl; p < HW; p += npl) {
+      const int row = src_padded ? rb_prow(p, W) : p;
+      const uint4 u = *(const uint4*)(sm + src + row * src_rs + oct * 16);
+      const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float x0 = __uint_as_float(w[j] << 16), x1 = __uint_as_float(w[j] & 0xFFFF0000u);
+        sx[2 * j] += x0; sq[2 * j] = fmaf(x0, x0, sq[2 * j]);
+        sx[2 * j + 1] += x1; sq[2 * j + 1] = fmaf(x1, x1, sq[2 * j + 1]);
+      }
+    }
+    float4* pt = (float4*)(part + t * RB_PST);
+    pt[0] = make_float4(sx[0], sx[1], sx[2], sx[3]); pt[1] = make_float4(sx[4], sx[5], sx[6], sx[7]);
+    pt[2] = make_float4(sq[0], sq[1], sq[2], sq[3]); pt[3] = make_float4(sq[4], sq[5], sq[6], sq[7]);
+  }
+  __syncthreads();
+  for (int r = t; r < 2 * C; r += RB_THREADS) {                 // (moment m, channel c): over the pixel lanes, in fp64
+    const int m = r >= C ? 1 : 0, c = r - m * C;
+    const float* pp = part + (c >> 3) * RB_PST + m * 8 + (c & 7);
+    double acc = 0.0;
+    for (int q = 0; q < npl; ++q) acc += (double)pp[q * noct * RB_PST];
+    red[r] = acc;
+  }
+  __syncthreads();
+  const int cg = C / G;
+  for (int c = t; c < C; c += RB_THREADS) {
+    const int g0 = (c / cg) * cg;
+    double s = 0.0, q = 0.0;
+    for (int j = g0; j < g0 + cg; ++j) { s += red[j]; q += red[C + j]; }
+    const double n = (double)cg * (double)HW;
+    const double mean = s / n;
+    const double var = fmax(q / n - mean * mean, 0.0);
+    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    scale[c] = rstd * gamma[c];
+    shift[c] = beta[c] - (float)mean * rstd * gamma[c];
+  }
+  __syncthreads();
+  if (act) {
+    const float4 sc0 = *(const float4*)(scale + oct * 8), sc1 = *(const float4*)(scale + oct * 8 + 4);
+    const float4 sh0 = *(const float4*)(shift + oct * 8), sh1 = *(const float4*)(shift + oct * 8 + 4);
+    const f32x2v scv[4] = {{sc0.x, sc0.y}, {sc0.z, sc0.w}, {sc1.x, sc1.y}, {sc1.z, sc1.w}};
+    const f32x2v shv[4] = {{sh0.x, sh0.y}, {sh0.z, sh0.w}, {sh1.x, sh1.y}, {sh1.z, sh1.w}};
+    for (int p = pl; p < HW; p += npl) {
+      const int prow = rb_prow(p, W);
+      const uint4 u = *(const uint4*)(sm + src + (src_padded ? prow : p) * src_rs + oct * 16);
+      const unsigned w[4] = {u.x, u.y, u.z, u.w};
+      unsigned ow[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {                              // as k_gn_onepass / k_gn_apply: packed fma, hardware exp2 / rcp
+        const f32x2v x = {__uint_as_float(w[j] << 16), __uint_as_float(w[j] & 0xFFFF0000u)};
+        f32x2v y = __builtin_elementwise_fma(x, scv[j], shv[j]);
+        const f32x2v z = y * (f32x2v){-1.4426950408889634f, -1.4426950408889634f};
+        const f32x2v d = (f32x2v){__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)} + (f32x2v){1.0f, 1.0f};
+        y = y * (f32x2v){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+        ow[j] = rb_pack2(y.x, y.y);
+      }
+      *(uint4*)(sm + dst + prow * dst_rs + oct * 16) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    }
+  }
+  __syncthreads();
+}
+
+// One K loop: acc[t][pt] += W[48 w + 16 t .. +16][k] * X[k][16 pt .. +16] over `n3` 64-channel chunks of a 3x3 segment on the
+// padded image at b3 (row stride rs3, `cpt` chunks per tap) followed by nchunks - n3 chunks of 1x1 segments on the image at b1.
+// wrow: this wave's weight stream + 8 lane elements.  The weights are packed in the order the fragments are consumed
+// (ctdd_unet.h: [wave][chunk][tile][k half][lane][8]), so a wave-instruction reads 1 KiB of consecutive bytes and a wave's
+// whole stream is sequential: with the plain [N][K] matrix the 16 lanes of a quarter wave sit in 16 different rows, every lane's
+// 16 bytes are a request of their own at the L1, and the stream ran at 31 GB/s per CU (0.78 us per chunk against 0.29 us of
+// matrix work).  The weights of chunk ci + PD are requested when chunk ci has been consumed; the compiler's counted vmcnt waits
+// let PD - 1 chunks stay in flight.  wr: the ring, holding chunks 0 .. PD - 1 (rb_wprologue).
+__device__ __attribute__((always_inline)) inline void rb_wload(u32x4 (&dst)[3][2], const unsigned short* __restrict__ wrow, int ci) {
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) dst[t][s] = *(const u32x4*)(wrow + (size_t)ci * 3072 + (t * 2 + s) * 512);
+}
+// the first PD chunks of a weight stream (nchunks >= 9 > PD: a 3x3 segment of >= 64 channels): issued by the kernel BEFORE the
+// GroupNorm phase that precedes the K loop, so that the stream's first latency hides behind it
+template <int PD>
+__device__ __attribute__((always_inline)) inline void rb_wprologue(u32x4 (&wr)[PD][3][2], const unsigned short* __restrict__ wrow) {
+#pragma unroll
+  for (int u = 0; u < PD; ++u) rb_wload(wr[u], wrow, u);
+}
+
+template <int NPT, int PD>
+__device__ __attribute__((always_inline)) inline void rb_gemm(f32x4 (&acc)[3][NPT], u32x4 (&wr)[PD][3][2], const unsigned short* __restrict__ wrow, int nchunks, int n3,
+                                                             int cpt, const unsigned char* sm, const int (&b3)[NPT], int rs3, int Wp,
+                                                             const int (&b1)[NPT]) {
+  auto wload = [&](u32x4 (&dst)[3][2], int ci) { rb_wload(dst, wrow, ci); };
+  // the pixel fragments of chunk `cn` (requested in sequence, one chunk ahead of their use, so that the LDS latency hides behind
+  // the previous chunk's matrix instructions; the request past the last chunk repeats a valid address)
+  int tap = 0, cc = 0;
+  auto xload = [&](bf16x8 (&xf)[NPT][2], int cn) {
+    // (selects, not branches: a join inside the group would make the counted waits conservative)
+    const int c = cn < nchunks ? cn : nchunks - 1;
+    const bool three = c < n3;
+    const int tp = tap < 8 ? tap : 8;
+    const int dy = tp / 3 - 1, dx = tp - (tp / 3) * 3 - 1;
+    const int koff = three ? (dy * Wp + dx) * rs3 + cc * 128 : (c - n3) * 128;
+    const bool wrap = cc + 1 == cpt;
+    cc = wrap ? 0 : cc + 1;
+    tap += wrap ? 1 : 0;
+#pragma unroll
+    for (int pt = 0; pt < NPT; ++pt) {
+      const int xb = (three ? b3[pt] : b1[pt]) + koff;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) xf[pt][s] = *(const bf16x8*)(sm + xb + s * 64);
+    }
+  };
+  // one chunk from ring slot `slot`; GUARD: the uniform tests of the last groups (the steady-state groups carry none, so that
+  // the counted waits see one straight line of PD loads and PD uses)
+  auto step = [&](u32x4 (&slot)[3][2], bf16x8 (&xf)[NPT][2], bf16x8 (&xnext)[NPT][2], int ci, auto guard) {
+    constexpr bool GUARD = decltype(guard)::value;
+    if (GUARD && ci >= nchunks) return;
+    xload(xnext, ci + 1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int pt = 0; pt < NPT; ++pt)
+          acc[t][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t][s]), xf[pt][s], acc[t][pt], 0, 0, 0);
+    if (!GUARD || ci + PD < nchunks) wload(slot, ci + PD);
+  };
+  static_assert(PD % 2 == 0, "the two pixel-fragment buffers alternate inside a group");
+  bf16x8 xq[2][NPT][2];
+  xload(xq[0], 0);
+  int ci0 = 0;
+  for (; ci0 + 2 * PD <= nchunks; ci0 += PD) {
+#pragma unroll
+    for (int u = 0; u < PD; ++u) step(wr[u], xq[u & 1], xq[(u + 1) & 1], ci0 + u, std::false_type{});
+  }
+  for (; ci0 < nchunks; ci0 += PD) {
+#pragma unroll
+    for (int u = 0; u < PD; ++u) step(wr[u], xq[u & 1], xq[(u + 1) & 1], ci0 + u, std::true_type{});
+  }
+}
+
+template <int NPT>
+__global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_resblock_args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+  constexpr int PD = 6;
+  const int t = threadIdx.x, b = blockIdx.x;
+  const int H = a.H, W = a.W, HW = H * W, C = a.C1 + a.C2, Wp = W + 2;
+  const RbLds L = rb_layout(H, W, C);
+  const int lane = t & 63, wv = t >> 6, lj = lane & 15, lq = lane >> 4;
+
+  const int K1 = 9 * C, K2 = 9 * RB_N + (a.skip ? C : 0);
+  const unsigned short* w1p = (const unsigned short*)a.w1 + (size_t)wv * (K1 / 64) * 3072 + lane * 8;
+  const unsigned short* w2p = (const unsigned short*)a.w2 + (size_t)wv * (K2 / 64) * 3072 + lane * 8;
+  u32x4 wr[PD][3][2];                                         // the weight ring (rb_gemm)
+
+  // ---- phase A: raw sample -> LDS, zero the slab, GroupNorm 1 + Swish into the slab
+  {
+    const int noct = C >> 3, nvec = HW * noct;
+    const unsigned short* s1 = (const unsigned short*)a.s1_bf16 + (size_t)b * HW * a.C1;
+    const unsigned short* s2 = (const unsigned short*)a.s2_bf16 + (size_t)b * HW * a.C2;
+    constexpr int MAXV = 12;                                  // 64 pixels x 48 vectors over 256 threads; all requested before the first store
+    u32x4 u[MAXV];
+#pragma unroll
+    for (int k = 0; k < MAXV; ++k) {
+      const int v = t + k * RB_THREADS, p = v / noct, c0 = (v - p * noct) * 8;
+      const unsigned short* src = c0 < a.C1 ? s1 + (size_t)p * a.C1 + c0 : s2 + (size_t)p * a.C2 + (c0 - a.C1);
+      u[k] = v < nvec ? *(const u32x4*)src : (u32x4){0u, 0u, 0u, 0u};
+    }
+    rb_wprologue<PD>(wr, w1p);
+#pragma unroll
+    for (int k = 0; k < MAXV; ++k) {
+      const int v = t + k * RB_THREADS, p = v / noct, c0 = (v - p * noct) * 8;
+      if (v < nvec) *(u32x4*)(sm + L.raw + p * L.rsA + c0 * 2) = u[k];
+    }
+    const int nz = (L.part - L.slab) >> 4;
+    for (int v = t; v < nz; v += RB_THREADS) *(uint4*)(sm + L.slab + v * 16) = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    rb_groupnorm(sm, L, L.raw, L.rsA, false, L.slab, L.rsA, HW, W, C, a.G1, a.gamma1, a.beta1, a.eps1);
+  }
+
+  // this lane's pixel of each pixel tile (pixels past the sample repeat the last one: computed, never stored)
+  int pix[NPT], b3[NPT], b1[NPT];
+#pragma unroll
+  for (int pt = 0; pt < NPT; ++pt) {
+    const int p = pt * 16 + lj;
+    pix[pt] = p;
+    const int pe = p < HW ? p : HW - 1;
+    b3[pt] = L.slab + rb_prow(pe, W) * L.rsA + lq * 16;
+    b1[pt] = L.raw + pe * L.rsA + lq * 16;
+  }
+  const int n0 = wv * 48;                                     // this wave's first output channel
+  f32x4 acc[3][NPT];
+#pragma unroll
+  for (int tt = 0; tt < 3; ++tt)
+#pragma unroll
+    for (int pt = 0; pt < NPT; ++pt) acc[tt][pt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+
+  // ---- phase B: conv1 on the slab
+  rb_gemm<NPT, PD>(acc, wr, w1p, K1 / 64, K1 / 64, C / 64, sm, b3, L.rsA, Wp, b1);
+  __syncthreads();                                            // every wave has read its last a1 fragment: the slab becomes h1's
+  rb_wprologue<PD>(wr, w2p);                                  // conv2's first chunks travel during the epilogue and GroupNorm 2
+  {
+    // borders of the N-channel image (its interior is written below by the lanes that own it)
+    const int npc = L.rs2 >> 4, nv = L.prows * npc;
+    for (int v = t; v < nv; v += RB_THREADS) {
+      const int row = v / npc, y = row / Wp, x = row - y * Wp;
+      if (y == 0 || y == H + 1 || x == 0 || x == W + 1) *(uint4*)(sm + L.slab + v * 16) = make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int tt = 0; tt < 3; ++tt) {
+      const int n = n0 + tt * 16 + lq * 4;
+      const float4 bv = *(const float4*)(a.bias1 + n);
+      const float4 tb = a.tbias ? *(const float4*)(a.tbias + (size_t)b * a.tb_stride + n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      const float add[4] = {bv.x + tb.x, bv.y + tb.y, bv.z + tb.z, bv.w + tb.w};
+#pragma unroll
+      for (int pt = 0; pt < NPT; ++pt) {
+        if (pix[pt] < HW) {
+          const f32x4 v = acc[tt][pt];
+          *(uint2*)(sm + L.slab + rb_prow(pix[pt], W) * L.rs2 + n * 2) =
+              make_uint2(rb_pack2(v[0] + add[0], v[1] + add[1]), rb_pack2(v[2] + add[2], v[3] + add[3]));
+        }
+        acc[tt][pt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase C: GroupNorm 2 + Swish of the bf16 h1, in place
+  rb_groupnorm(sm, L, L.slab, L.rs2, true, L.slab, L.rs2, HW, W, RB_N, a.G2, a.gamma2, a.beta2, a.eps2);
+
+  // ---- phase D: conv2 on a2, then the 1x1 skip segments on the raw input
+#pragma unroll
+  for (int pt = 0; pt < NPT; ++pt) {
+    const int pe = pix[pt] < HW ? pix[pt] : HW - 1;
+    b3[pt] = L.slab + rb_prow(pe, W) * L.rs2 + lq * 16;
+  }
+  rb_gemm<NPT, PD>(acc, wr, w2p, K2 / 64, 9 * RB_N / 64, RB_N / 64, sm, b3, L.rs2, Wp, b1);
+  __syncthreads();                                            // a2 is dead: the slab becomes the [HW][N] output image
+#pragma unroll
+  for (int tt = 0; tt < 3; ++tt) {
+    const int n = n0 + tt * 16 + lq * 4;
+    const float4 bv = *(const float4*)(a.bias2 + n);
+#pragma unroll
+    for (int pt = 0; pt < NPT; ++pt) {
+      if (pix[pt] < HW) {
+        const f32x4 v = acc[tt][pt];
+        float o[4] = {v[0] + bv.x, v[1] + bv.y, v[2] + bv.z, v[3] + bv.w};
+        if (!a.skip) {                                        // residual: the raw input (C1 == N)
+          const uint2 r = *(const uint2*)(sm + L.raw + pix[pt] * L.rsA + n * 2);
+          o[0] += __uint_as_float(r.x << 16); o[1] += __uint_as_float(r.x & 0xFFFF0000u);
+          o[2] += __uint_as_float(r.y << 16); o[3] += __uint_as_float(r.y & 0xFFFF0000u);
+        }
+        *(uint2*)(sm + L.slab + pix[pt] * L.rs2 + n * 2) = make_uint2(rb_pack2(o[0], o[1]), rb_pack2(o[2], o[3]));
+      }
+    }
+  }
+  __syncthreads();
+  {
+    constexpr int npc = RB_N / 8;
+    unsigned short* out = (unsigned short*)a.out_bf16 + (size_t)b * HW * RB_N;
+    for (int v = t; v < HW * npc; v += RB_THREADS) {
+      const int p = v / npc, c0 = (v - p * npc) * 8;
+      *(uint4*)(out + (size_t)p * RB_N + c0) = *(const uint4*)(sm + L.slab + p * L.rs2 + c0 * 2);
+    }
+  }
+}
+
+}  // namespace
+}  // namespace ctdd
+
+using namespace ctdd;
+
+// Refuses (non-zero, ctdd_last_error set, nothing launched) what the kernel cannot hold: fp32 mode, H*W > 64 or W > 8, N != 192,
+// source channel counts that are not multiples of 64 or exceed 384 in all, groups that do not divide the channels, an LDS
+// image over the CU's 160 KiB.
+extern "C" int ctdd_unet_resblock_small(const void* args_, int f32, void* stream) {
+  CTDD_REQUIRE(args_, CTDD_EINVAL, "ctdd_unet_resblock_small: null arguments");
+  const ctdd_resblock_args& a = *(const ctdd_resblock_args*)args_;
+  CTDD_REQUIRE(f32 == 0, CTDD_ERANGE, "ctdd_unet_resblock_small: bf16 inference only (the fp32 mode keeps the four launches)");
+  CTDD_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.W <= 8 && a.H * a.W <= 64, CTDD_ERANGE,
+               "ctdd_unet_resblock_small: a sample of %dx%d pixels does not fit the workgroup tile (H*W <= 64, W <= 8)", a.H, a.W);
+  const int C = a.C1 + a.C2;
+  CTDD_REQUIRE(a.N == RB_N && a.C1 > 0 && a.C1 % 64 == 0 && a.C2 >= 0 && a.C2 % 64 == 0 && C <= RB_MAXC, CTDD_ERANGE,
+               "ctdd_unet_resblock_small: channel counts off the tile (N=%d, C1=%d, C2=%d; N = 192, sources in multiples of 64, <= 384)", a.N,
+               a.C1, a.C2);
+  CTDD_REQUIRE(a.G1 > 0 && C % a.G1 == 0 && a.G2 > 0 && RB_N % a.G2 == 0, CTDD_EINVAL, "ctdd_unet_resblock_small: groups do not divide the channels");
+  CTDD_REQUIRE(a.skip || (a.C2 == 0 && a.C1 == RB_N), CTDD_EINVAL, "ctdd_unet_resblock_small: a residual block needs C1 == N and one source");
+  CTDD_REQUIRE(a.s1_bf16 && (a.C2 == 0 || a.s2_bf16) && a.w1 && a.w2 && a.bias1 && a.bias2 && a.gamma1 && a.beta1 && a.gamma2 && a.beta2 &&
+                   a.out_bf16, CTDD_EINVAL, "ctdd_unet_resblock_small: null pointer");
+  const RbLds L = rb_layout(a.H, a.W, C);
+  CTDD_REQUIRE(L.total <= 160 * 1024, CTDD_ERANGE, "ctdd_unet_resblock_small: LDS image of %d bytes over the 160 KiB budget", L.total);
+  hipStream_t st = (hipStream_t)stream;
+  static bool attr_done[2][16] = {};
+  if (a.H * a.W <= 16) {
+    ensure_lds_ceiling((const void*)k_resblock_small<1>, attr_done[0]);
+    hipLaunchKernelGGL(k_resblock_small<1>, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, st, a);
+  } else {
+    ensure_lds_ceiling((const void*)k_resblock_small<4>, attr_done[1]);
+    hipLaunchKernelGGL(k_resblock_small<4>, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, st, a);
+  }
+  return finish_launch("k_resblock_small");
+}

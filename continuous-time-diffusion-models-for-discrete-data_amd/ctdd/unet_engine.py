@@ -46,6 +46,12 @@ class _GnArgs(C.Structure):
                 ("out_hi", _P), ("out_f32", _P)]
 
 
+class _ResblockArgs(C.Structure):
+    _fields_ = [("s1_bf16", _P), ("s2_bf16", _P), ("C1", _I), ("C2", _I), ("gamma1", _P), ("beta1", _P), ("gamma2", _P), ("beta2", _P),
+                ("G1", _I), ("G2", _I), ("eps1", _F), ("eps2", _F), ("w1", _P), ("bias1", _P), ("tbias", _P), ("tb_stride", _I),
+                ("w2", _P), ("bias2", _P), ("skip", _I), ("B", _I), ("H", _I), ("W", _I), ("N", _I), ("out_bf16", _P)]
+
+
 class _TimeArgs(C.Structure):
     _fields_ = [("t", _P), ("B", _I), ("ch", _I), ("tdim", _I), ("w1", _P), ("b1", _P), ("w2", _P), ("b2", _P),
                 ("hid", _P), ("act", _P)]
@@ -70,7 +76,7 @@ def _lib():
                            ("ctdd_unet_upsample2x", [_P, _I, _I, _I, _I, _P, _P]), ("ctdd_unet_first_conv", [_P, _P]),
                            ("ctdd_unet_gn_apply", [_P, _P]), ("ctdd_unet_gn_onepass", [_P, _I, _I, _P]), ("ctdd_unet_channel_stats", [_P, _I, _I, _I, _P, _P]),
                            ("ctdd_unet_time", [_P, _P, _P, _I, _P, _P]), ("ctdd_unet_time_uniform", [_P, _P, _P, _I, _P, _P]),
-                           ("ctdd_unet_attention", [_P, _P]),
+                           ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_resblock_small", [_P, _I, _P]),
                            ("ctdd_unet_logistic_head", [_P, _P])):
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argt, _I
@@ -101,6 +107,24 @@ def training_supported(model):
 
 class _GnUncovered(Exception):
     """A GroupNorm shape outside k_gn_onepass (UNetEngine._build falls back to statistics epilogues + k_gn_apply)."""
+
+
+def resblock_small_covers(H, W, cs, cout, G1, G2):
+    """Shapes ctdd_unet_resblock_small holds (csrc/unet_resblock_kernels.hip): a sample of <= 64 pixels in rows of <= 8, 192 output
+    channels, one or two sources in multiples of 64 channels (<= 384 in all), and its LDS image within the CU's 160 KiB."""
+    Ct = sum(cs)
+    if H * W > 64 or W > 8 or cout != 192 or len(cs) > 2 or any(c % 64 for c in cs) or Ct > 384 or Ct % G1 or cout % G2:
+        return False
+    rs_a, rs_2, prows = Ct * 2 + 16, cout * 2 + 16, (H + 2) * (W + 2)
+    return H * W * rs_a + prows * max(rs_a, rs_2) + 256 * 80 + 2 * 384 * 8 + 2 * 384 * 4 <= 160 * 1024
+
+
+def pack_resblock_weights(w2d):
+    """[192][K] (K % 64 == 0) -> the fragment order ctdd_unet_resblock_small streams (include/ctdd_unet.h): [wave][chunk][tile][k half]
+    [q][i][8], so that every wave-instruction of the weight stream reads 1 KiB of consecutive bytes."""
+    N, K = w2d.shape
+    assert N == 192 and K % 64 == 0
+    return w2d.reshape(4, 3, 16, K // 64, 2, 4, 8).permute(0, 3, 1, 4, 5, 2, 6).contiguous().reshape(N, K)
 
 
 def _onepass_slab(B, HW, Cn, G, max_threads=1024):
@@ -470,11 +494,51 @@ class UNetEngine:
         if tc is not None:
             tc.record_first(c0, fa, cur)
 
+        def resblock_fused(rb, srcs):
+            """The block as ONE ctdd_unet_resblock_small launch: the same [N][K] matrices in the kernel's fragment order, the same summed
+            conv2 + skip bias."""
+            Hc, Wc = srcs[0].H, srcs[0].W
+            cs = [s.C for s in srcs]
+            Ct, cout = sum(cs), rb.conv1.weight.shape[0]
+            y = _Tensor(self, B, Hc, Wc, cout)
+            a = _ResblockArgs()
+            a.s1_bf16, a.C1 = ptr(srcs[0].hi), cs[0]
+            if len(srcs) == 2:
+                a.s2_bf16, a.C2 = ptr(srcs[1].hi), cs[1]
+            par = [p_.detach().float().contiguous() for p_ in (rb.norm1.weight, rb.norm1.bias, rb.norm2.weight, rb.norm2.bias, rb.conv1.bias)]
+            a.gamma1, a.beta1, a.gamma2, a.beta2, a.bias1 = (ptr(p_) for p_ in par)
+            a.G1, a.G2, a.eps1, a.eps2 = rb.norm1.num_groups, rb.norm2.num_groups, rb.norm1.eps, rb.norm2.eps
+            a.tbias, a.tb_stride = st.tproj.data_ptr() + 4 * toff[id(rb)], tb_stride
+            w1, _ = self._pack(pack_resblock_weights(self._w2d([(rb.conv1.weight, 0)], [(None, Ct, SEG_3x3)])))
+            segs, wsrc, bias2 = [(None, cout, SEG_3x3)], [(rb.conv2.weight, 0)], rb.conv2.bias.detach().float()
+            if rb.skip is not None:
+                c_ = 0
+                for cs_ in cs:
+                    segs.append((None, cs_, SEG_1x1))
+                    wsrc.append((rb.skip.weight, c_))
+                    c_ += cs_
+                bias2 = bias2 + rb.skip.bias.detach().float()
+            bias2 = bias2.contiguous()
+            w2, _ = self._pack(pack_resblock_weights(self._w2d(wsrc, segs)))
+            a.w1, a.w2, a.bias2, a.skip = ptr(w1), ptr(w2), ptr(bias2), int(rb.skip is not None)
+            a.B, a.H, a.W, a.N, a.out_bf16 = B, Hc, Wc, cout, ptr(y.hi)
+            keep.extend(par + [w1, w2, bias2, a])
+            K1, K2 = w1.shape[1], w2.shape[1]
+            launch(lib.ctdd_unet_resblock_small, C.byref(a), 0, label=f"{Hc}x{Wc} resblock C={cs} N={cout} K={K1}+{K2}",
+                   flops=2 * B * Hc * Wc * cout * (K1 + K2))
+            return y
+
         def resblock(rb, srcs):
             """srcs: list of 1-2 tensors forming the (virtual) channel concatenation."""
             Hc, Wc = srcs[0].H, srcs[0].W
             cs = [s.C for s in srcs]
             cout = rb.conv1.weight.shape[0]
+            # a small level's whole block in one launch (csrc/unet_resblock_kernels.hip: one workgroup per sample, both activated
+            # tensors and h1 stay in LDS); cfg.model.resblock_fused = 0 keeps the four launches below
+            if (onepass_gn and tc is None and not self.precise and int(getattr(m, "resblock_fused", 1))
+                    and Hc * Wc <= self._plan_no_stats_hw and all(s_.stats is None for s_ in srcs)
+                    and resblock_small_covers(Hc, Wc, cs, cout, rb.norm1.num_groups, rb.norm2.num_groups)):
+                return resblock_fused(rb, srcs)
             a1 = gn_apply(srcs, rb.norm1, True, rb.norm1.eps, Hc * Wc)
             h = _Tensor(self, B, Hc, Wc, cout)
             b1 = rb.conv1.bias.detach().float().contiguous()

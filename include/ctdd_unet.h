@@ -73,6 +73,23 @@ int ctdd_unet_gn_onepass(const void* gn_args, int slab_channels, int max_threads
 int ctdd_unet_channel_stats(const float* x, int B, int HW, int C, double* stats, void* stream);
 
 typedef struct {
+  const void* s1_bf16; const void* s2_bf16; int C1, C2;   /* raw input [B][H][W][C1] (+ [B][H][W][C2]: their channel concatenation) */
+  const float* gamma1; const float* beta1; const float* gamma2; const float* beta2; int G1, G2; float eps1, eps2;
+  const void* w1; const float* bias1; const float* tbias; int tb_stride;   /* conv1: the [N][9 (C1 + C2)] bf16 matrix, K = tap -> channel, in fragment order (below) */
+  const void* w2; const float* bias2;   /* conv2: [N][9 N (+ C1 + C2)], the 3x3 segment on a2, then the 1x1 skip segments on the raw input; fragment order */
+  int skip;                             /* 1: 1x1 skip segments (their bias summed into bias2); 0: residual = the raw input (C1 == N, C2 == 0) */
+  int B, H, W, N; void* out_bf16;       /* [B][H][W][N] bf16 */
+} ctdd_resblock_args;
+/* A whole ResBlock (unet.py:100-140, eval mode) of a small level in one launch, bf16: GroupNorm + Swish -> conv3x3 + bias + time bias
+ * -> GroupNorm + Swish -> conv3x3 (+ 1x1 skip | + residual), one workgroup per sample, intermediates in LDS, the rounding points of
+ * the four launches it replaces (ctdd_unet_gn_onepass, ctdd_unet_conv_patch, twice).  H * W <= 64, W <= 8, N = 192, C1 and C2
+ * multiples of 64 with C1 + C2 <= 384; f32 must be 0.  Anything else: CTDD_ERANGE / CTDD_EINVAL, nothing launched.
+ * Weights in fragment order: element (n, k) of the [N][K] matrix, n = 48 wave + 16 tile + i, k = 64 chunk + 32 half + 8 q + e, is at
+ * ((((wave * K / 64 + chunk) * 3 + tile) * 2 + half) * 64 + 16 q + i) * 8 + e (ctdd/unet_engine.py: pack_resblock_weights): each
+ * wave-instruction of the kernel's weight stream reads 1 KiB of consecutive bytes. */
+int ctdd_unet_resblock_small(const void* resblock_args, int f32, void* stream);
+
+typedef struct {
   const float* t; int B, ch, tdim;
   const float* w1; const float* b1; const float* w2; const float* b2;   /* Linear weights transposed to [in][out] */
   float* hid; float* act;                                                /* [B][tdim] scratch, [B][tdim] = swish(temb) */
