@@ -43,3 +43,13 @@ def hollow(c, embed_dim, num_layers, mlp_dim, concat_dim, S):
                    transformer_norm_type="prenorm", mlp_dim=mlp_dim, out_dim=None, readout_dim=S,
                    num_output_ffresiduals=2, qkv_dim=embed_dim, ema_decay=0.9999, time_scale_factor=1000,
                    log_prob="cat", fix_logistic=False)
+
+
+def encoder(c, name, embed_dim, num_layers, mlp_dim, concat_dim, S, num_output_ffresiduals=2):
+    """Single-stream transformer score models (x0-prediction "BERT" and masked): hollow_networks.BertEnumTransformer /
+    EnumerativeTransformer.  Training runs the autograd module (engine_train = "torch")."""
+    c.model.update(name=name, is_ebm=False, use_cat=False, use_one_hot_input=False, embed_dim=embed_dim, readout="resnet",
+                   dropout_rate=0.1, concat_dim=concat_dim, num_layers=num_layers, num_heads=8, attention_dropout_rate=0.1,
+                   transformer_norm_type="prenorm", mlp_dim=mlp_dim, out_dim=S, readout_dim=S,
+                   num_output_ffresiduals=num_output_ffresiduals, qkv_dim=embed_dim, ema_decay=0.9999, time_scale_factor=1000,
+                   log_prob="cat", Q_sigma=20.0, engine_train="torch")

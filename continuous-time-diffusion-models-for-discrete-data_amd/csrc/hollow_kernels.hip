@@ -11,6 +11,10 @@
 //   k_hollow_attention      fp32 masked multi-head attention with an online softmax: causal (j <= i), anti-causal
 //                           (j >= i) and the readout mask [temb | l2r j <= i | r2l j >= i]
 //   k_hollow_attention_mfma the same on the bf16 matrix cores (single or hi + lo operands), fp32 softmax
+// and what the single-stream transformers built from the same blocks add (BertEnumTransformer, EnumerativeTransformer; ctdd_bert.h):
+//   k_bert_embed            state -> [temb | x_0..x_{D-1}] + pe, per sample or per (sample, masked position) sequence
+//   k_bert_attention_short  unmasked attention for Tq, Tk <= 64: one wave per (sequence, head), K / V resident in LDS
+//   k_bert_gather           encoder rows 1..D of every sequence, or row p of sequence (b, p) -> the readout input
 #include "common.hpp"
 
 namespace ctdd {
@@ -246,7 +250,10 @@ __global__ __launch_bounds__(256) void k_hollow_put_rows(const float* __restrict
 
 // ------------------------------------------------------------------ masked attention, online softmax
 // q rows (b, i): q + b*q_bs + i*q_rs + h*hd ; k / v likewise; out (b, i): out + (b*Tq + i)*E_out + h*hd.
-// mode 0: key j allowed iff j <= i ; 1: j >= i ; 2 (readout, Tk = 2 Tq + 1): j == 0 | 1 <= j <= Tq: j-1 <= i | j > Tq: j-Tq-1 >= i.
+// mode 0: key j allowed iff j <= i ; 1: j >= i ; 2 (readout, Tk = 2 Tq + 1): j == 0 | 1 <= j <= Tq: j-1 <= i | j > Tq: j-Tq-1 >= i ;
+// 3: unmasked (every j < Tk, Tq and Tk independent) -- the encoder of the single-stream transformers (bert_kernels.hip).  Mode 3 is
+// the compile-time switch FULL of both kernels: no chunk is skipped and only the ragged last chunk is masked; the FULL = false
+// instantiations are the masked kernels as they were.
 struct HollowAttnArgs {
   const float* q; const float* k; const float* v;
   int64_t q_bs, k_bs, v_bs; int q_rs, k_rs, v_rs;
@@ -263,7 +270,7 @@ struct HollowAttnArgs {
 constexpr int AQ = 128, AK = 32;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 __device__ inline f32x2 pk_fma(f32x2 x, f32x2 y, f32x2 z) { return __builtin_elementwise_fma(x, y, z); }   // v_pk_fma_f32
-template <int HD>
+template <int HD, bool FULL>
 __global__ __launch_bounds__(AQ) void k_hollow_attention(const HollowAttnArgs a) {
   __shared__ __attribute__((aligned(16))) float Ks[AK * HD];
   __shared__ __attribute__((aligned(16))) float Vs[AK * HD];
@@ -285,6 +292,7 @@ __global__ __launch_bounds__(AQ) void k_hollow_attention(const HollowAttnArgs a)
   float m = -INFINITY, l = 0.0f;
   const int ilo = i0, ihi = min(i0 + AQ, a.Tq) - 1;           // query range of the workgroup
   auto allowed = [&](int j) {
+    if (FULL) return true;
     if (a.mode == 0) return j <= i;
     if (a.mode == 1) return j >= i;
     return j == 0 || (j <= a.Tq ? j - 1 <= i : j - a.Tq - 1 >= i);
@@ -292,7 +300,8 @@ __global__ __launch_bounds__(AQ) void k_hollow_attention(const HollowAttnArgs a)
   for (int j0 = 0; j0 < a.Tk; j0 += AK) {
     const int j1 = min(j0 + AK, a.Tk) - 1;
     bool any;                                                  // does any query of the workgroup see this chunk? (uniform)
-    if (a.mode == 0) any = j0 <= ihi;
+    if (FULL) any = true;
+    else if (a.mode == 0) any = j0 <= ihi;
     else if (a.mode == 1) any = j1 >= ilo;
     else any = j0 == 0 || (j0 <= a.Tq && j0 - 1 <= ihi) || (j1 > a.Tq && j1 - a.Tq - 1 >= ilo);
     if (!any) continue;
@@ -394,11 +403,11 @@ __device__ inline void hk_mask_tile(f32x16& s, int Tq, int Tk, int i, bool qok, 
     bool ok = qok & (j < Tk);
     if (MODE == 0) ok &= j <= i;
     else if (MODE == 1) ok &= j >= i;
-    else ok &= (j == 0) | ((j <= Tq) & (j - 1 <= i)) | ((j > Tq) & (j - Tq - 1 >= i));
+    else if (MODE == 2) ok &= (j == 0) | ((j <= Tq) & (j - 1 <= i)) | ((j > Tq) & (j - Tq - 1 >= i));
     s[r] = ok ? s[r] : -INFINITY;
   }
 }
-template <int HD, bool SPLIT>
+template <int HD, bool SPLIT, bool FULL>
 __global__ __launch_bounds__(256) void k_hollow_attention_mfma(const HollowAttnArgs a) {
   constexpr int KS = HD / 16;                       // k-steps of the score product
   constexpr int KLD = HD + 8, VLD = 32 + 4;         // LDS row lengths (bf16 elements): K rows 16-byte padded; V^T rows of 72 bytes, so that
@@ -411,7 +420,7 @@ __global__ __launch_bounds__(256) void k_hollow_attention_mfma(const HollowAttnA
   const int col = lane & 31, kh = lane >> 5;
   // causal tiles: the LAST query tile has the longest key range -- dispatch the heavy tiles first (a launch that ends on its
   // longest workgroups idles most of the chip through its tail: 111 vs 92 us for the mirrored anti-causal layer)
-  const int qtile = a.mode == 0 ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
+  const int qtile = (!FULL && a.mode == 0) ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
   const int q0 = qtile * 128 + wave * 32;           // first query of this wave
   const int i = q0 + col;                           // this lane's query
   const bool qok = i < a.Tq;
@@ -446,6 +455,7 @@ __global__ __launch_bounds__(256) void k_hollow_attention_mfma(const HollowAttnA
   auto range_any = [&](int jc, int lo, int hi) {
     const int jl = min(jc + 32, a.Tk) - 1;
     if (hi < lo) return false;
+    if (FULL) return true;
     if (a.mode == 0) return jc <= hi;
     if (a.mode == 1) return jl >= lo;
     return jc == 0 || (jc <= a.Tq && jc - 1 <= hi) || (jl > a.Tq && jl - a.Tq - 1 >= lo);
@@ -511,8 +521,9 @@ __global__ __launch_bounds__(256) void k_hollow_attention_mfma(const HollowAttnA
     // ---- mask + online softmax for the lane's query over its 16 keys (+ the partner lane's 16)
     float mx = -INFINITY;
     // chunks every query of the wave sees in full need no per-element mask (most of a causal triangle); wave-uniform
-    bool full = q0 + 31 < a.Tq && j0 + 31 < a.Tk;
-    if (a.mode == 0) full = full && j0 + 31 <= q0;
+    bool full = FULL ? j0 + 31 < a.Tk : q0 + 31 < a.Tq && j0 + 31 < a.Tk;
+    if (FULL) {}
+    else if (a.mode == 0) full = full && j0 + 31 <= q0;
     else if (a.mode == 1) full = full && j0 >= q0 + 31;
     else full = full && ((j0 >= 1 && j0 + 31 <= a.Tq && j0 + 30 <= q0) || (j0 > a.Tq && j0 - a.Tq - 1 >= q0 + 31));
     if (full) {
@@ -521,7 +532,8 @@ __global__ __launch_bounds__(256) void k_hollow_attention_mfma(const HollowAttnA
     } else {
       // (branch-free, the launch-uniform mode hoisted: a per-register `if` chain on it compiles to scalar lane-mask and / or /
       //  branch sequences an order of magnitude longer than the softmax arithmetic)
-      if (a.mode == 0) hk_mask_tile<0>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);
+      if (FULL) hk_mask_tile<3>(sacc, a.Tq, a.Tk, i, true, j0 + 4 * kh);      // (rows of queries past Tq are never stored)
+      else if (a.mode == 0) hk_mask_tile<0>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);
       else if (a.mode == 1) hk_mask_tile<1>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);
       else hk_mask_tile<2>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);
 #pragma unroll
@@ -585,6 +597,168 @@ __global__ __launch_bounds__(256) void k_hollow_attention_mfma(const HollowAttnA
   }
 }
 
+// ------------------------------------------------------------------ single-stream embedding (hollow_networks.py:450-493, 859-1031)
+// One token sequence [temb, x_0 .. x_{D-1}] + pe per row of `out` (rows, D + 1, E).  Plain: row r is sample r.  Enumerate (the
+// masked model): row r is sequence g = *r0 + r of the (B D') enumeration, D' = D - cond -- sample b = g / D' with token
+// p = cond + g % D' replaced by the mask value S; the masked batch exists only as these indices.  r0 lives in device memory so
+// that one captured launch serves every chunk; rows past the last sequence (ragged final chunk) repeat the last sequence.
+struct BertEmbedArgs {
+  const int64_t* x64; const int32_t* x32;       // (B, D) states
+  const float* t;                                 // (B)
+  const float* w_in; const float* b_in;           // Linear(1 -> E): weight[:, 0], bias
+  const float* pe;                                // (>= D + 1, E)
+  int B, D, E, S; float temb_scale;
+  float* out;                                     // (rows, D + 1, E)
+  float* temb;                                    // (B, E), optional
+  int enumerate, cond, rows;
+  const int32_t* r0;                              // device scalar, enumerate mode (null: 0)
+};
+__global__ __launch_bounds__(256) void k_bert_embed(const BertEmbedArgs a) {
+  const int r = blockIdx.y, E = a.E, D = a.D, T = D + 1, half = E / 2;
+  int b = r, p = -1;
+  if (a.enumerate) {
+    const int Dp = D - a.cond;
+    const int64_t total = (int64_t)a.B * Dp;
+    int64_t g = (int64_t)(a.r0 ? *a.r0 : 0) + r;
+    g = g < 0 ? 0 : (g >= total ? total - 1 : g);
+    b = (int)(g / Dp); p = a.cond + (int)(g % Dp);
+  }
+  const float tv = a.t[b] * a.temb_scale;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < T * E; i += gridDim.x * 256) {
+    const int j = i / E, e = i % E;
+    float v;
+    if (j == 0) {
+      const int fe = e < half ? e : e - half;
+      const float freq = expf((float)fe * -(logf(10000.0f) / (float)(half - 1)));
+      const float arg = tv * freq;
+      v = e < half ? sinf(arg) : cosf(arg);
+      if (a.temb && (!a.enumerate || p == a.cond)) a.temb[(size_t)b * E + e] = v;      // (once per sample)
+    } else {
+      const int d = j - 1;
+      const float xr = d == p ? (float)a.S : (a.x64 ? (float)a.x64[(size_t)b * D + d] : (float)a.x32[(size_t)b * D + d]);
+      const float xn = (xr / (float)(a.S - 1)) * 2.0f - 1.0f;
+      v = xn * a.w_in[e] + a.b_in[e];
+    }
+    a.out[((size_t)r * T + j) * E + e] = v + a.pe[(size_t)j * E + e];
+  }
+}
+
+// Readout input of the single-stream transformers from the encoder output enc (rows, D + 1, E), one wave per output row, fp32
+// and / or bf16 hi (+ lo).  enumerate = 0 (BERT): output row g = b D + d takes enc row 1 + d of sequence b (the temb row is
+// dropped).  enumerate = 1 (masked): chunk row r is sequence g = *r0 + r = (b, p) as in k_bert_embed; its row 1 + p goes to row
+// g of out (B D', E), and rows past the last sequence are dropped.
+__global__ __launch_bounds__(256) void k_bert_gather(const float* __restrict__ enc, const int32_t* __restrict__ r0, int rows, int enumerate,
+                                                    int64_t total, int D, int cond, int E, float* __restrict__ out,
+                                                    unsigned short* __restrict__ out_hi, unsigned short* __restrict__ out_lo) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const int64_t g = (int64_t)((enumerate && r0) ? *r0 : 0) + r;
+  if (g < 0 || g >= total) return;
+  const int Dp = D - cond;
+  const int64_t seq = enumerate ? r : g / Dp;
+  const float* src = enc + ((size_t)seq * (D + 1) + 1 + cond + (int)(g % Dp)) * E;
+  for (int e = lane; e < E; e += 64) {
+    const float v = src[e];
+    if (out) out[(size_t)g * E + e] = v;
+    if (out_hi) {
+      const unsigned short hv = hk_bf16(v);
+      out_hi[(size_t)g * E + e] = hv;
+      if (out_lo) out_lo[(size_t)g * E + e] = hk_lo(v, hv);
+    }
+  }
+}
+
+// Unmasked attention for short sequences (Tq, Tk <= 64: T = D + 1 = 33 in three of the four shipped encoder configurations, where
+// the generic kernels' 128-query workgroups leave three quarters of their lanes idle).  One wave owns one (sequence, head) pair:
+// lane = query, the pair's whole K and V resident in LDS (staged once, read as wave-uniform float4s), NW pairs per workgroup.
+// fp32 FMA arithmetic as k_hollow_attention, whatever the engine precision: the work is bound by reading q / k / v once.
+template <int HD, int NW>
+__global__ __launch_bounds__(64 * NW) void k_bert_attention_short(const HollowAttnArgs a) {
+  __shared__ __attribute__((aligned(16))) float Ks[NW][64 * HD];
+  __shared__ __attribute__((aligned(16))) float Vs[NW][64 * HD];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t pair = (int64_t)blockIdx.x * NW + wave;
+  const bool live = pair < (int64_t)a.B * a.H;
+  const int b = live ? (int)(pair / a.H) : 0, h = live ? (int)(pair % a.H) : 0;
+  const int Tk4 = (a.Tk + 3) & ~3;                              // keys are consumed four at a time: rows Tk .. Tk4 - 1 hold zeros
+  if (live) {
+    for (int idx = lane; idx < Tk4 * (HD / 4); idx += 64) {
+      const int j = idx / (HD / 4), c4 = idx % (HD / 4);
+      float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
+      if (j < a.Tk) {
+        kv = *(const float4*)(a.k + (size_t)b * a.k_bs + (size_t)j * a.k_rs + h * HD + c4 * 4);
+        vv = *(const float4*)(a.v + (size_t)b * a.v_bs + (size_t)j * a.v_rs + h * HD + c4 * 4);
+      }
+      *(float4*)(&Ks[wave][j * HD + c4 * 4]) = kv;
+      *(float4*)(&Vs[wave][j * HD + c4 * 4]) = vv;
+    }
+  }
+  __syncthreads();                                              // (the only barrier: nothing below is shared between waves)
+  const int i = lane;
+  if (!live || i >= a.Tq) return;
+  f32x2 qv[HD / 2], acc[HD / 2];
+  const float* qr = a.q + (size_t)b * a.q_bs + (size_t)i * a.q_rs + h * HD;
+#pragma unroll
+  for (int c = 0; c < HD; c += 4) {
+    const float4 u = *(const float4*)(qr + c);
+    qv[c / 2] = f32x2{u.x * a.scale, u.y * a.scale};
+    qv[c / 2 + 1] = f32x2{u.z * a.scale, u.w * a.scale};
+    acc[c / 2] = f32x2{0.0f, 0.0f};
+    acc[c / 2 + 1] = f32x2{0.0f, 0.0f};
+  }
+  float m = -INFINITY, l = 0.0f;
+  for (int jj = 0; jj < Tk4; jj += 4) {
+    float s[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      f32x2 d2 = {0.0f, 0.0f};
+      const float* kr = &Ks[wave][(jj + u) * HD];
+#pragma unroll
+      for (int c = 0; c < HD; c += 4) {
+        const float4 kv = *(const float4*)(kr + c);
+        d2 = pk_fma(qv[c / 2], f32x2{kv.x, kv.y}, d2);
+        d2 = pk_fma(qv[c / 2 + 1], f32x2{kv.z, kv.w}, d2);
+      }
+      s[u] = jj + u < a.Tk ? d2.x + d2.y : -INFINITY;
+    }
+    const float mn = fmaxf(fmaxf(m, fmaxf(s[0], s[1])), fmaxf(s[2], s[3]));      // (finite: key jj exists)
+    const float corr = expf(m - mn);
+    float p[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) p[u] = expf(s[u] - mn);
+    l = l * corr + ((p[0] + p[1]) + (p[2] + p[3]));
+    const f32x2 corr2 = {corr, corr};
+#pragma unroll
+    for (int c = 0; c < HD / 2; ++c) acc[c] *= corr2;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float* vr = &Vs[wave][(jj + u) * HD];
+      const f32x2 p2 = {p[u], p[u]};
+#pragma unroll
+      for (int c = 0; c < HD; c += 4) {
+        const float4 vv = *(const float4*)(vr + c);
+        acc[c / 2] = pk_fma(p2, f32x2{vv.x, vv.y}, acc[c / 2]);
+        acc[c / 2 + 1] = pk_fma(p2, f32x2{vv.z, vv.w}, acc[c / 2 + 1]);
+      }
+    }
+    m = mn;
+  }
+  const float inv = 1.0f / l;
+  const size_t oo = ((size_t)b * a.Tq + i) * a.out_rs + h * HD;
+#pragma unroll
+  for (int c = 0; c < HD; c += 4) {
+    const float4 v = make_float4(acc[c / 2].x * inv, acc[c / 2].y * inv, acc[c / 2 + 1].x * inv, acc[c / 2 + 1].y * inv);
+    if (a.out) *(float4*)(a.out + oo + c) = v;
+    if (a.out_hi) {
+      const unsigned h01 = hk_pack2(v.x, v.y), h23 = hk_pack2(v.z, v.w);
+      *(uint2*)(a.out_hi + oo + c) = make_uint2(h01, h23);
+      if (a.out_lo)
+        *(uint2*)(a.out_lo + oo + c) = make_uint2(hk_pack2(v.x - __uint_as_float(h01 << 16), v.y - __uint_as_float(h01 & 0xFFFF0000u)),
+                                                  hk_pack2(v.z - __uint_as_float(h23 << 16), v.w - __uint_as_float(h23 & 0xFFFF0000u)));
+    }
+  }
+}
+
 }  // namespace ctdd
 using namespace ctdd;
 
@@ -596,6 +770,48 @@ extern "C" int ctdd_hollow_embed(const void* args_, void* stream) {
   gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
   hipLaunchKernelGGL(k_hollow_embed, dim3(gx, a.B), dim3(256), 0, (hipStream_t)stream, a);
   return finish_launch("k_hollow_embed");
+}
+
+extern "C" int ctdd_bert_embed(const void* args_, void* stream) {
+  const BertEmbedArgs& a = *(const BertEmbedArgs*)args_;
+  CTDD_REQUIRE((a.x64 || a.x32) && a.t && a.w_in && a.b_in && a.pe && a.out, CTDD_EINVAL, "bert embed: null buffer");
+  CTDD_REQUIRE(a.E % 2 == 0 && a.E >= 4 && a.S >= 2 && a.D >= 1 && a.B >= 1 && a.rows >= 1 && a.rows <= 65535, CTDD_EINVAL,
+               "bert embed: E=%d S=%d D=%d B=%d rows=%d", a.E, a.S, a.D, a.B, a.rows);
+  CTDD_REQUIRE(a.enumerate ? (a.cond >= 0 && a.cond < a.D) : a.rows == a.B, CTDD_EINVAL, "bert embed: enumerate=%d cond=%d rows=%d B=%d",
+               a.enumerate, a.cond, a.rows, a.B);
+  int gx = ((a.D + 1) * a.E + 2047) / 2048;
+  gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
+  hipLaunchKernelGGL(k_bert_embed, dim3(gx, a.rows), dim3(256), 0, (hipStream_t)stream, a);
+  return finish_launch("k_bert_embed");
+}
+
+extern "C" int ctdd_bert_gather(const float* enc, const int32_t* r0, int rows, int enumerate, int B, int D, int cond, int E, float* out,
+                                void* out_bf16, void* out_lo, void* stream) {
+  CTDD_REQUIRE(enc && (out || out_bf16) && rows > 0 && B > 0 && E > 0 && cond >= 0 && cond < D, CTDD_EINVAL, "bert gather: bad arguments");
+  const int64_t total = (int64_t)B * (D - cond);
+  CTDD_REQUIRE(enumerate || rows == total, CTDD_EINVAL, "bert gather: plain mode takes rows == B (D - cond), got %d", rows);
+  hipLaunchKernelGGL(k_bert_gather, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, enc, r0, rows, enumerate, total, D, cond, E, out,
+                     (unsigned short*)out_bf16, (unsigned short*)out_lo);
+  return finish_launch("k_bert_gather");
+}
+
+extern "C" int ctdd_bert_attention_short(const void* args_, void* stream) {
+  const HollowAttnArgs& a = *(const HollowAttnArgs*)args_;
+  CTDD_REQUIRE(a.q && a.k && a.v && (a.out || a.out_hi), CTDD_EINVAL, "short attention: null buffer");
+  CTDD_REQUIRE(a.mode == 3 && a.Tq > 0 && a.Tk > 0 && a.Tq <= 64 && a.Tk <= 64 && a.B > 0 && a.H > 0, CTDD_EINVAL,
+               "short attention: mode %d (3) with Tq=%d Tk=%d (<= 64)", a.mode, a.Tq, a.Tk);
+  CTDD_REQUIRE(a.q_rs % 4 == 0 && a.k_rs % 4 == 0 && a.v_rs % 4 == 0 && a.out_rs % 4 == 0 && a.q_bs % 4 == 0 && a.k_bs % 4 == 0 && a.v_bs % 4 == 0,
+               CTDD_EINVAL, "short attention: strides must be multiples of 4 floats");
+  const int64_t pairs = (int64_t)a.B * a.H;
+  hipStream_t st = (hipStream_t)stream;
+  switch (a.hd) {
+    case 4: hipLaunchKernelGGL((k_bert_attention_short<4, 4>), dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, a); break;
+    case 8: hipLaunchKernelGGL((k_bert_attention_short<8, 4>), dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, a); break;
+    case 16: hipLaunchKernelGGL((k_bert_attention_short<16, 4>), dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, a); break;
+    case 32: hipLaunchKernelGGL((k_bert_attention_short<32, 2>), dim3((unsigned)((pairs + 1) / 2)), dim3(128), 0, st, a); break;
+    default: CTDD_REQUIRE(false, CTDD_ERANGE, "short attention: head dim %d (4, 8, 16 or 32)", a.hd);
+  }
+  return finish_launch("k_bert_attention_short");
 }
 
 extern "C" int ctdd_hollow_layernorm(const void* args_, void* stream) {
@@ -685,20 +901,27 @@ extern "C" int ctdd_hollow_put_rows(const float* src, float* dst, void* dst_bf16
 extern "C" int ctdd_hollow_attention_bf16(const void* args_, void* stream) {
   const HollowAttnArgs& a = *(const HollowAttnArgs*)args_;
   CTDD_REQUIRE(a.q && a.k && a.v && (a.out || a.out_hi), CTDD_EINVAL, "hollow attention: null buffer");
-  CTDD_REQUIRE(a.mode >= 0 && a.mode <= 2 && (a.mode != 2 || a.Tk == 2 * a.Tq + 1) && (a.mode == 2 || a.Tk == a.Tq), CTDD_EINVAL,
-               "hollow attention: mode %d with Tq=%d Tk=%d", a.mode, a.Tq, a.Tk);
+  CTDD_REQUIRE(a.mode >= 0 && a.mode <= 3 && a.Tq > 0 && a.Tk > 0 && (a.mode != 2 || a.Tk == 2 * a.Tq + 1) && (a.mode >= 2 || a.Tk == a.Tq),
+               CTDD_EINVAL, "hollow attention: mode %d with Tq=%d Tk=%d", a.mode, a.Tq, a.Tk);
   CTDD_REQUIRE(a.q_rs % 4 == 0 && a.k_rs % 4 == 0 && a.v_rs % 4 == 0 && a.out_rs % 4 == 0 && a.q_bs % 4 == 0 && a.k_bs % 4 == 0 && a.v_bs % 4 == 0,
                CTDD_EINVAL, "hollow attention: strides must be multiples of 4 floats");
   const dim3 g((a.Tq + 127) / 128, a.H, a.B);
   hipStream_t st = (hipStream_t)stream;
+  const bool full = a.mode == 3;
   switch (a.hd) {
     case 16:
-      if (a.split) hipLaunchKernelGGL((k_hollow_attention_mfma<16, true>), g, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((k_hollow_attention_mfma<16, false>), g, dim3(256), 0, st, a);
+      if (full) {
+        if (a.split) hipLaunchKernelGGL((k_hollow_attention_mfma<16, true, true>), g, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_hollow_attention_mfma<16, false, true>), g, dim3(256), 0, st, a);
+      } else if (a.split) hipLaunchKernelGGL((k_hollow_attention_mfma<16, true, false>), g, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((k_hollow_attention_mfma<16, false, false>), g, dim3(256), 0, st, a);
       break;
     case 32:
-      if (a.split) hipLaunchKernelGGL((k_hollow_attention_mfma<32, true>), g, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((k_hollow_attention_mfma<32, false>), g, dim3(256), 0, st, a);
+      if (full) {
+        if (a.split) hipLaunchKernelGGL((k_hollow_attention_mfma<32, true, true>), g, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_hollow_attention_mfma<32, false, true>), g, dim3(256), 0, st, a);
+      } else if (a.split) hipLaunchKernelGGL((k_hollow_attention_mfma<32, true, false>), g, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((k_hollow_attention_mfma<32, false, false>), g, dim3(256), 0, st, a);
       break;
     default: CTDD_REQUIRE(false, CTDD_ERANGE, "bf16 hollow attention: head dim %d (16 or 32)", a.hd);
   }
@@ -708,19 +931,23 @@ extern "C" int ctdd_hollow_attention_bf16(const void* args_, void* stream) {
 extern "C" int ctdd_hollow_attention(const void* args_, void* stream) {
   const HollowAttnArgs& a = *(const HollowAttnArgs*)args_;
   CTDD_REQUIRE(a.q && a.k && a.v && (a.out || a.out_hi), CTDD_EINVAL, "hollow attention: null buffer");
-  CTDD_REQUIRE(a.mode >= 0 && a.mode <= 2 && (a.mode != 2 || a.Tk == 2 * a.Tq + 1) && (a.mode == 2 || a.Tk == a.Tq), CTDD_EINVAL,
-               "hollow attention: mode %d with Tq=%d Tk=%d", a.mode, a.Tq, a.Tk);
+  CTDD_REQUIRE(a.mode >= 0 && a.mode <= 3 && a.Tq > 0 && a.Tk > 0 && (a.mode != 2 || a.Tk == 2 * a.Tq + 1) && (a.mode >= 2 || a.Tk == a.Tq),
+               CTDD_EINVAL, "hollow attention: mode %d with Tq=%d Tk=%d", a.mode, a.Tq, a.Tk);
   CTDD_REQUIRE(a.q_rs % 4 == 0 && a.k_rs % 4 == 0 && a.v_rs % 4 == 0 && a.out_rs % 4 == 0 && a.q_bs % 4 == 0 && a.k_bs % 4 == 0 && a.v_bs % 4 == 0,
                CTDD_EINVAL, "hollow attention: strides must be multiples of 4 floats");
   const dim3 g((a.Tq + AQ - 1) / AQ, a.H, a.B);
   hipStream_t st = (hipStream_t)stream;
+#define ATTN_CASE(hd_)                                                                                       \
+  if (a.mode == 3) hipLaunchKernelGGL((k_hollow_attention<hd_, true>), g, dim3(AQ), 0, st, a);   \
+  else hipLaunchKernelGGL((k_hollow_attention<hd_, false>), g, dim3(AQ), 0, st, a);
   switch (a.hd) {
-    case 4: hipLaunchKernelGGL(k_hollow_attention<4>, g, dim3(AQ), 0, st, a); break;
-    case 8: hipLaunchKernelGGL(k_hollow_attention<8>, g, dim3(AQ), 0, st, a); break;
-    case 16: hipLaunchKernelGGL(k_hollow_attention<16>, g, dim3(AQ), 0, st, a); break;
-    case 32: hipLaunchKernelGGL(k_hollow_attention<32>, g, dim3(AQ), 0, st, a); break;
-    case 64: hipLaunchKernelGGL(k_hollow_attention<64>, g, dim3(AQ), 0, st, a); break;
+    case 4: ATTN_CASE(4) break;
+    case 8: ATTN_CASE(8) break;
+    case 16: ATTN_CASE(16) break;
+    case 32: ATTN_CASE(32) break;
+    case 64: ATTN_CASE(64) break;
     default: CTDD_REQUIRE(false, CTDD_ERANGE, "hollow attention: head dim %d (4, 8, 16, 32 or 64)", a.hd);
   }
+#undef ATTN_CASE
   return finish_launch("k_hollow_attention");
 }

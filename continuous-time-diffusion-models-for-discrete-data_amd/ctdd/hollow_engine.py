@@ -3,7 +3,8 @@ reference TAUnSDDM/lib/networks/hollow_networks.py:668-755 + lib/models/models.p
 
 Walks a built `BidirectionalTransformer2` once, keeps pointers to its fp32 parameters (torch Linear layout
 [out][in] is the [N][K] layout the GEMM kernel streams), allocates every intermediate for a batch size and
-records the forward as a flat list of pre-bound libctdd launches, replayed as one HIP graph:
+records the forward as a flat list of pre-bound libctdd launches (the builders of ctdd/plan_common.py, shared with
+ctdd/bert_engine.py), replayed as one HIP graph:
 
   embed (csrc/hollow_kernels.hip) -> per direction and layer: LayerNorm -> QKV GEMM -> masked attention ->
   out-proj GEMM (+residual) -> LayerNorm -> fc1 GEMM (ReLU) -> fc2 GEMM (+residual) -> readout: two LayerNorms
@@ -17,53 +18,12 @@ precision = "bf16":  the token-level GEMMs take bf16 operands (weights and the L
                      LayerNorm, softmax and the per-sample FiLM path stay fp32.  Throughput mode, looser bar.
 """
 import ctypes as C
-import math
 
 import torch
 
 from . import native
-from .unet_engine import _ConvArgs, _lib as _unet_lib, _unwrap, SEG_1x1
-
-_P, _I, _F, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
-
-
-class _EmbedArgs(C.Structure):
-    _fields_ = [("x64", _P), ("x32", _P), ("t", _P), ("w_in", _P), ("b_in", _P), ("pe", _P), ("B", _I), ("D", _I), ("E", _I),
-                ("S", _I), ("temb_scale", _F), ("l2r", _P), ("r2l", _P), ("temb", _P)]
-
-
-class _LnArgs(C.Structure):
-    _fields_ = [("x", _P), ("y", _P), ("x_bs", _I64), ("y_bs", _I64), ("out_bs", _I64), ("gamma", _P), ("beta", _P), ("eps", _F),
-                ("film", _P), ("film_stride", _I), ("B", _I), ("T", _I), ("E", _I), ("out", _P), ("out_hi", _P), ("out_hi_bs", _I64), ("out_lo", _P)]
-
-
-class _GemmArgs(C.Structure):
-    _fields_ = [("a", _P * 3), ("nseg", _I), ("w", _P), ("bias", _P), ("res", _P), ("out_f32", _P), ("out_hi", _P), ("out_lo", _P),
-                ("M", _I), ("N", _I), ("K", _I), ("act", _I), ("drop_p", _F), ("rng", _P), ("layer", C.c_uint64), ("mask_u", _P)]
-
-
-class _AttnArgs(C.Structure):
-    _fields_ = [("q", _P), ("k", _P), ("v", _P), ("q_bs", _I64), ("k_bs", _I64), ("v_bs", _I64), ("q_rs", _I), ("k_rs", _I),
-                ("v_rs", _I), ("B", _I), ("Tq", _I), ("Tk", _I), ("H", _I), ("hd", _I), ("mode", _I), ("scale", _F), ("out", _P),
-                ("out_rs", _I), ("out_hi", _P), ("out_lo", _P), ("split", _I)]
-
-
-_sigs_done = False
-
-
-def _lib():
-    global _sigs_done
-    lib = _unet_lib()
-    if not _sigs_done:
-        for name, argt in (("ctdd_hollow_embed", [_P, _P]), ("ctdd_hollow_layernorm", [_P, _P]),
-                           ("ctdd_hollow_add", [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _I64, _P]),
-                           ("ctdd_hollow_put_rows", [_P, _P, _P, _P, _I64, _I, _I, _P]), ("ctdd_hollow_attention", [_P, _P]),
-                           ("ctdd_hollow_attention_bf16", [_P, _P]), ("ctdd_gemm_bf16", [_P, _P]),
-                           ("ctdd_hollow_small_linear", [_P, _P, _P, _I, _I, _I, _I, _P, _P])):
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argt, _I
-        _sigs_done = True
-    return lib
+from .plan_common import PlanBuilder, _AttnArgs, _EmbedArgs, _GemmArgs, _LnArgs, _lib  # noqa: F401  (part of this module's interface)
+from .unet_engine import _unwrap
 
 
 def supports(model):
@@ -107,132 +67,12 @@ class HollowEngine:
         D = int(m.concat_dim)
         hd = E // H
         st = type("Plan", (), {})()
-        plan, keep = [], []
+        pb = PlanBuilder(self, B)
+        plan, keep, fast, split = pb.plan, pb.keep, self.fast, self.split
+        f32, hi, lo, P, W, launch, linear, layernorm, attention = (pb.f32, pb.hi, pb.lo, pb.P, pb.W, pb.launch, pb.linear, pb.layernorm,
+                                                                   pb.attention)
         st.x_in = torch.zeros((B, D), dtype=x_dtype, device=dev)
         st.t_in = torch.zeros((B,), dtype=torch.float32, device=dev)
-        stream = lambda: torch.cuda.current_stream().cuda_stream
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        fast, split = self.fast, self.split
-        hi = lambda *shape: torch.empty(shape, dtype=torch.bfloat16, device=dev) if fast else None     # bf16 GEMM operands
-        lo = lambda *shape: torch.empty(shape, dtype=torch.bfloat16, device=dev) if split else None    # their second terms
-
-        def P(t):
-            return None if t is None else t.data_ptr()
-
-        def W(p):                                   # fp32 contiguous view of a parameter (kept alive)
-            t = p.detach().float().contiguous()
-            keep.append(t)
-            return t
-
-        def launch(fn, *args, label=None, flops=0):
-            def run():
-                rc = fn(*args, stream())
-                if rc != 0:
-                    raise native.CtddError(f"{fn.__name__} failed ({rc}): {lib.ctdd_last_error().decode()}")
-            run.label, run.flops = (fn.__name__, label), flops
-            plan.append(run)
-
-        def linear(x, rows, K, lin_w, lin_b, out, act=0, res=None, label="", x_hi=None, out_hi=None, x_lo=None, out_lo=None):
-            """out[rows][N] = act(x[rows][K] @ W^T + b) (+ res) on the implicit-GEMM kernel: fp32 operands, or bf16
-            operands (x_hi, bf16 weights) when x_hi is given; out (fp32) and/or out_hi (bf16) receive the result."""
-            w = W(lin_w)
-            N = w.shape[0]
-            assert w.shape[1] == K and K % 16 == 0
-            if x_hi is None and res is None and rows <= 64 and K % 64 == 0 and K <= 1024 and x is not None and out is not None:
-                # per-sample layers (time-embedding MLP, FiLM): a few MFLOP in fp32 -- one wave per output column
-                bptr = P(W(lin_b)) if lin_b is not None else None
-                launch(lib.ctdd_hollow_small_linear, P(x), P(w), bptr, rows, K, N, act, P(out), label=f"linear {label} {rows}x{K}->{N} rows",
-                       flops=2 * rows * K * N)
-                return
-            a = _ConvArgs()
-            a.nseg = 1
-            a.seg[0].C, a.seg[0].kind = K, SEG_1x1
-            use_bf16 = x_hi is not None
-            if split and use_bf16 and (N % 8 != 0 or x_lo is None):
-                assert x is not None, label                      # (a 3-column logits layer: the exact-fp32 kernel)
-                use_bf16 = False
-            if use_bf16 and split and label in self.single:
-                wh = w.to(torch.bfloat16).contiguous()
-                keep.append(wh)
-                a.seg[0].hi, a.w_hi = P(x_hi), P(wh)
-            elif use_bf16 and split:
-                wh = w.to(torch.bfloat16)
-                wl = (w - wh.float()).to(torch.bfloat16)
-                wcat = torch.cat([wh, wh, wl], dim=1).contiguous()        # [N][3K] against the segments [x_hi | x_lo | x_hi]
-                keep.append(wcat)
-                a.nseg = 3
-                for si, xs in enumerate((x_hi, x_lo, x_hi)):
-                    a.seg[si].C, a.seg[si].kind, a.seg[si].hi = K, SEG_1x1, P(xs)
-                a.w_hi = P(wcat)
-            elif use_bf16:
-                wh = w.to(torch.bfloat16).contiguous()
-                keep.append(wh)
-                a.seg[0].hi, a.w_hi = P(x_hi), P(wh)
-            else:
-                a.seg[0].f32, a.w_f32 = P(x), P(w)
-            a.B, a.H, a.W, a.Hin, a.Win, a.N, a.Ktot = 1, rows, 1, rows, 1, N, K * a.nseg
-            a.bias = P(W(lin_b)) if lin_b is not None else None
-            a.res_f32 = P(res)
-            a.out_f32, a.out_hi, a.act = P(out), P(out_hi) if use_bf16 or not split else None, act
-            a.out_lo = P(out_lo) if use_bf16 else None
-            keep.append(a)
-            if use_bf16:
-                bk = 96 if K % 96 == 0 else 64 if K % 64 == 0 else 32 if K % 32 == 0 else 16
-                bnt = 1 if bk == 16 else (3 if (N % 96 == 0 and bk in (96, 32)) else 4 if N % 128 == 0 else 2 if (N % 64 == 0 and bk == 64) else 1)
-                if (bk, bnt) not in ((96, 3), (96, 4), (96, 1), (64, 4), (64, 2), (64, 1), (32, 1), (32, 3), (32, 4), (16, 1)):
-                    bnt = 1
-            else:
-                bk = 32 if K % 32 == 0 else 16
-                bnt = 1 if bk == 16 else (3 if N % 96 == 0 else 4 if N % 128 == 0 else 1)
-            if use_bf16 and N % 8 == 0 and K % 64 == 0 and getattr(m, "engine_linear", "gemm") == "gemm":
-                # the plain GEMM kernel (csrc/gemm_kernels.hip); the hi / lo split product is three A segments against the
-                # concatenated weight.  MNIST hollow forward, batch 64: linears 9.2 ms on the slab kernel below (model.engine_linear =
-                # "patch") -> 7.7 ms; maze batch 128: forward 6.35 -> 5.52 ms
-                ga = _GemmArgs()
-                ga.nseg, ga.w, ga.bias, ga.res = a.nseg, a.w_hi, a.bias, a.res_f32
-                for si in range(a.nseg):
-                    ga.a[si] = a.seg[si].hi
-                ga.out_f32, ga.out_hi, ga.out_lo, ga.M, ga.N, ga.K, ga.act = a.out_f32, a.out_hi, a.out_lo, rows, N, K, act
-                keep.append(ga)
-                launch(lib.ctdd_gemm_bf16, C.byref(ga), label=f"linear {label} {rows}x{K}->{N} gemm", flops=2 * rows * K * N * a.nseg)
-                return
-            if use_bf16 and N % 8 == 0 and K % 16 == 0 and getattr(m, "engine_linear", "gemm") in ("gemm", "patch"):
-                # the U-Net's slab kernel run as a plain GEMM (one 1x1 segment over a rows x 1 "image"): 16-byte row-major
-                # epilogue, weights and activations staged per 128/256-row tile
-                pbk = 64 if K % 64 == 0 else 48 if K % 48 == 0 else 32 if K % 32 == 0 else 16
-                if pbk == 64:
-                    pbnt = 4 if N > 64 else 2 if N > 32 else 1
-                elif pbk == 48:
-                    pbnt = 4 if N % 128 == 0 else 3 if N > 64 else 2 if N > 32 else 1
-                elif pbk == 32:
-                    pbnt = 4 if N % 128 == 0 else 3 if N > 32 else 1
-                else:
-                    pbnt = 1
-                ext = act != 0 or a.out_lo                 # activation / hi + lo outputs: the EXT instantiations (wm = 32)
-                wm = 64 if (not ext and rows >= 256 * 256 and (pbk, pbnt) in ((48, 3), (48, 4), (64, 4), (64, 2), (48, 2))) else 32
-                launch(lib.ctdd_unet_conv_patch, C.byref(a), pbk, pbnt, wm, label=f"linear {label} {rows}x{K}->{N} patch",
-                       flops=2 * rows * K * N * a.nseg)
-                return
-            launch(lib.ctdd_unet_conv, C.byref(a), bk, bnt, 0 if use_bf16 else 1, label=f"linear {label} {rows}x{K}->{N}",
-                   flops=2 * rows * K * N)
-
-        def layernorm(x, x_bs, T, Ed, norm, out, out_bs, y=None, y_bs=0, film=None, film_stride=0, out_hi=None, out_hi_bs=0, out_lo=None):
-            a = _LnArgs()
-            a.x, a.y, a.x_bs, a.y_bs, a.out_bs = P(x), P(y), x_bs, y_bs, out_bs
-            a.gamma, a.beta, a.eps = P(W(norm.weight)), P(W(norm.bias)), float(norm.eps)
-            a.film, a.film_stride, a.B, a.T, a.E, a.out = P(film), film_stride, B, T, Ed, P(out)
-            a.out_hi, a.out_hi_bs, a.out_lo = P(out_hi), out_hi_bs, P(out_lo)
-            keep.append(a)
-            launch(lib.ctdd_hollow_layernorm, C.byref(a))
-
-        def attention(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, Tq, Tk, mode, out, out_hi=None, out_lo=None):
-            a = _AttnArgs()
-            a.q, a.k, a.v, a.q_bs, a.k_bs, a.v_bs, a.q_rs, a.k_rs, a.v_rs = q, k, v, q_bs, k_bs, v_bs, q_rs, k_rs, v_rs
-            a.B, a.Tq, a.Tk, a.H, a.hd, a.mode, a.scale, a.out, a.out_rs = B, Tq, Tk, H, hd, mode, 1.0 / math.sqrt(hd), P(out), E
-            a.out_hi, a.out_lo, a.split = P(out_hi), P(out_lo), 1 if split else 0
-            keep.append(a)
-            fn = lib.ctdd_hollow_attention_bf16 if (fast and hd in (16, 32) and getattr(m, "engine_attention", "mfma") == "mfma") else lib.ctdd_hollow_attention
-            launch(fn, C.byref(a), label=f"attention mode {mode} {Tq}x{Tk}")
 
         R = B * D
         # ---- embedding

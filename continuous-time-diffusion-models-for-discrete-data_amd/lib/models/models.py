@@ -265,6 +265,61 @@ class HollowTransformer(nn.Module):
         return "infer"
 
 
+class _EncoderModel(nn.Module):
+    """Shared wrapper of the two single-stream transformer score models (hollow_networks.py: BertEnumTransformer,
+    EnumerativeTransformer).  Inference under eval() / no_grad runs the HIP plan of ctdd/bert_engine.py; with gradients enabled
+    or in train mode the autograd module runs (there are no training kernels for these nets): one RuntimeWarning per model
+    unless cfg.model.engine_train == "torch" says that this is meant."""
+
+    _net_class = None
+    _engine_int32_states = True          # forward() takes the samplers' int32 states as they are
+
+    def __init__(self, cfg, device, rank=None):
+        super().__init__()
+        from lib.networks import hollow_networks
+        net = getattr(hollow_networks, self._net_class)(cfg).to(device)
+        self.net = _maybe_ddp(net, cfg, rank)
+        self.cfg = cfg
+        self._engine = None
+
+    def forward(self, x, times):
+        if self._use_engine(x):
+            from ctdd import bert_engine
+            if self._engine is None:
+                # cfg.model.engine_precision: "bf16x3" (default), "fp32" or "bf16", as for the hollow transformer
+                self._engine = bert_engine.BertEngine(self, precision=getattr(self.cfg.model, "engine_precision", None))
+            out = self._engine(x, times)
+            return out if getattr(self, "_borrow_engine_output", False) else out.clone()
+        return self.net(x, times)
+
+    def _use_engine(self, x):
+        if getattr(self.cfg.model, "engine", "hip") != "hip" or not x.is_cuda:
+            return False
+        from ctdd import bert_engine
+        if torch.is_grad_enabled() or self.training:
+            if getattr(self.cfg.model, "engine_train", "hip") != "torch":
+                _warn_once(self, "bert-train", "no HIP training kernels for this network; training runs on torch device ops "
+                                               "(set cfg.model.engine_train = 'torch' to say so)")
+            return False
+        if x.dtype not in (torch.int64, torch.int32):
+            _warn_once(self, "bert-dtype", f"HIP engine takes integer states, got {x.dtype}; running torch device ops")
+            return False
+        if not bert_engine.supports(self):
+            _warn_once(self, "bert", "transformer variant outside the HIP engine's coverage; running torch device ops")
+            return False
+        return True
+
+
+class BertMLPRes(_EncoderModel):
+    """x0-prediction ("BERT") transformer wrapper (models.py:639-658)."""
+    _net_class = "BertEnumTransformer"
+
+
+class MaskedModel(_EncoderModel):
+    """Masked (enumerative) transformer wrapper (models.py:617-636)."""
+    _net_class = "EnumerativeTransformer"
+
+
 class EMA:
     """Exponential moving average of the trainable parameters with train/eval weight swapping
     (models.py:730-823).  Mixed in FIRST so its state_dict/load_state_dict/train win the MRO."""
@@ -362,3 +417,8 @@ UniformRateImageX0PredEMA = _compose("UniformRateImageX0PredEMA", ImageX0PredBas
 GaussianHollowEMA = _compose("GaussianHollowEMA", HollowTransformer, GaussianTargetRate, "hollow transformer, Gaussian-target CTMC")
 UniVarHollowEMA = _compose("UniVarHollowEMA", HollowTransformer, UniformVariantRate, "hollow transformer, time-warped uniform CTMC")
 UniformHollowEMA = _compose("UniformHollowEMA", HollowTransformer, UniformRate, "hollow transformer, uniform CTMC")
+# single-stream transformer models (models.py:1034-1060, 883-900)
+UniVarBertEMA = _compose("UniVarBertEMA", BertMLPRes, UniformVariantRate, "x0-prediction transformer, time-warped uniform CTMC")
+UniformBertEMA = _compose("UniformBertEMA", BertMLPRes, UniformRate, "x0-prediction transformer, uniform CTMC")
+UniVarMaskedEMA = _compose("UniVarMaskedEMA", MaskedModel, UniformVariantRate, "masked transformer, time-warped uniform CTMC")
+UniformMaskedEMA = _compose("UniformMaskedEMA", MaskedModel, UniformRate, "masked transformer, uniform CTMC")

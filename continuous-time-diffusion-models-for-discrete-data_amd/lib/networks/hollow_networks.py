@@ -8,6 +8,12 @@ the right-to-left stack, never x_d itself ("hollow"), so logits[d] parameterises
 p(x^d | x^{\\d}).  The module tree keeps the reference's parameter names (including the two
 sub-modules its forward never uses, `embedding` and `temb_net`) so checkpoints load unchanged.
 Device ops (autograd-capable); the HIP inference plan is ctdd/hollow_engine.py, the HIP training path ctdd/hollow_train.py.
+
+The same blocks also build the two single-stream score networks of the SDDM / tauLDR comparison (reference
+hollow_networks.py: TransformerEncoder 450-493, MaskedTransformer 859-914, EnumerativeTransformer 917-960,
+BertEnumTransformer 963-1031): an unmasked encoder over [temb, x_0..x_{D-1}] read out at every position (x0 prediction,
+"BERT"), and the masked model that runs that encoder once per position p on a copy of x with x[p] = S.  Their HIP inference
+plan is ctdd/bert_engine.py; training runs these modules under autograd.
 """
 import math
 
@@ -264,3 +270,150 @@ class BidirectionalTransformer2(nn.Module):
         l2r = self.module_l2r(x_embed, temb)
         r2l = self.module_r2l(x_embed, temb)
         return self.readout_module(l2r, r2l, temb).view(B, D, self.readout_dim)
+
+
+class TransformerEncoder(nn.Module):
+    """Unmasked pre/post-norm encoder over [temb, x_0..x_{D-1}] + pe; the temb row is dropped from the result."""
+
+    def __init__(self, config):
+        super().__init__()
+        m = config.model
+        if getattr(m, "is_ebm", False):
+            raise ValueError("is_ebm=True (the energy-based variant) is not built")
+        self.config = config
+        self.dropout = nn.Dropout(m.dropout_rate)
+        self.trans_block_layers = nn.ModuleList([TransformerBlock(config) for _ in range(m.num_layers)])
+        self.pos_embed = PositionalEncoding(config.device, m.embed_dim, m.dropout_rate, m.concat_dim + 1)
+
+    def forward(self, x, temb):
+        assert x.ndim == 3 and temb.ndim == 2
+        x = torch.cat([temb.unsqueeze(1), x], dim=1)
+        x = self.dropout(self.pos_embed(x))               # (two dropouts in train mode, as the reference applies them)
+        for blk in self.trans_block_layers:
+            x = blk(x, masks=None)
+        return x[:, 1:]
+
+
+def _token_embedding(config, num_symbols):
+    m = config.model
+    if m.use_cat:
+        return nn.Linear(num_symbols, m.embed_dim) if m.use_one_hot_input else nn.Embedding(num_symbols, m.embed_dim)
+    return nn.Linear(1, m.embed_dim)
+
+
+def _embed_tokens(net, x, num_symbols):
+    """(B, D) states -> (B, D, E).  Without use_cat a state enters as the scalar 2 x / (S - 1) - 1 (the mask value S of the
+    masked net lands outside [-1, 1])."""
+    B, D = x.shape
+    if net.use_cat:
+        if net.use_one_hot_input:
+            return net.input_embedding(F.one_hot(x.long(), num_symbols).float())
+        return net.input_embedding(x.long())
+    return net.input_embedding(normalize_input(x.float(), net.S).view(B, D, 1))
+
+
+class BertEnumTransformer(nn.Module):
+    """x0-prediction transformer: one encoder pass, FiLM residual readout at every position -> (B, D, S)."""
+
+    def __init__(self, config):
+        super().__init__()
+        m = config.model
+        self.config = config
+        self.use_cat, self.use_one_hot_input = m.use_cat, m.use_one_hot_input
+        self.S, self.embed_dim = config.data.S, m.embed_dim
+        self.temb_scale = m.time_scale_factor
+        if m.readout == "mlp":
+            # (the reference's constructor fails on this setting with a TypeError: it hands a function where a module is needed)
+            raise ValueError("BertEnumTransformer: readout='mlp' cannot be built (use 'resnet')")
+        if m.readout != "resnet":
+            raise ValueError("Unknown readout type %s" % m.readout)
+        self.trans_encoder = TransformerEncoder(config)
+        self.model = ResidualReadout(config)
+        self.input_embedding = _token_embedding(config, self.S)
+
+    def forward(self, x, t):
+        temb = transformer_timestep_embedding(t * self.temb_scale, self.embed_dim)
+        x = x.view(x.shape[0], -1)
+        embed = self.trans_encoder(_embed_tokens(self, x, self.S), temb)
+        return self.model(embed, temb)
+
+
+class MaskedTransformer(nn.Module):
+    """Encoder over a masked copy of x (symbols 0..S, S = the mask) with the readout applied to chosen rows only."""
+
+    def __init__(self, config):
+        super().__init__()
+        m = config.model
+        self.config = config
+        self.use_cat, self.use_one_hot_input = m.use_cat, m.use_one_hot_input
+        self.S, self.embed_dim = config.data.S, m.embed_dim
+        self.trans_encoder = TransformerEncoder(config)
+        if m.readout == "mlp":
+            self.model = MLP([m.embed_dim, m.mlp_dim, self.S], activation=nn.GELU())
+        elif m.readout == "resnet":
+            self.model = ResidualReadout(config)
+        else:
+            raise ValueError("Unknown readout type %s" % m.readout)
+        self.input_embedding = _token_embedding(config, self.S + 1)
+
+    def encode(self, x, temb):
+        """(R, D) masked states, (R, E) time embeddings -> (R, D, E)."""
+        return self.trans_encoder(_embed_tokens(self, x, self.S + 1), temb)
+
+    def readout(self, embed, temb):
+        """(B, n, E) encoder rows -> (B, n, S) logits; temb (B, E) is per sample (FiLM)."""
+        return self.model(embed) if self.config.model.readout == "mlp" else self.model(embed, temb)
+
+    def forward(self, x, temb, pos):
+        return self.readout(self.encode(x, temb)[:, pos].unsqueeze(1), temb)
+
+
+ENUM_CHUNK_ROWS = 65536       # default size of one enumerate chunk, in token rows (sequences x (D + 1))
+
+
+def enum_chunk_size(config, total):
+    """Sequences per chunk of the masked model's (B D') enumeration: at most cfg.model.enum_chunk (default: as many as give
+    ENUM_CHUNK_ROWS token rows -- large enough to fill the GEMMs, small enough that a chunk's activations stay cache-sized),
+    evened out so that the last chunk is not a sliver."""
+    cap = getattr(config.model, "enum_chunk", None)
+    explicit = cap is not None
+    cap = max(1, int(cap) if explicit else ENUM_CHUNK_ROWS // (int(config.model.concat_dim) + 1))
+    if explicit or total <= cap:
+        return min(cap, max(total, 1))
+    n = -(-total // cap)
+    return -(-total // n)
+
+
+class EnumerativeTransformer(nn.Module):
+    """Masked model: logits[b, p] = readout(encoder(x_b with x_b[p] = S)[p]) for every p >= conditional_dim; the first
+    conditional_dim positions are never masked and get all-zero logits.  The (B D', D) masked batch runs through the encoder
+    in chunks of enum_chunk_size() sequences; there is no loop over positions."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.S, self.embed_dim = config.data.S, config.model.embed_dim
+        self.temb_scale = config.model.time_scale_factor
+        self.transformer = MaskedTransformer(config)
+
+    def forward(self, x, t):
+        temb = transformer_timestep_embedding(t * self.temb_scale, self.embed_dim)
+        shape = x.shape
+        x = x.view(x.shape[0], -1)
+        B, D = x.shape
+        c = int(getattr(self.config.model, "conditional_dim", 0) or 0)
+        Dp = D - c
+        total = B * Dp
+        seq = torch.arange(total, device=x.device)
+        b_of, p_of = seq // Dp, c + seq % Dp
+        chunk = enum_chunk_size(self.config, total)
+        rows = []
+        for r0 in range(0, total, chunk):
+            b, p = b_of[r0:r0 + chunk], p_of[r0:r0 + chunk]
+            xm = x[b].scatter(1, p[:, None], self.S)                           # (n, D): sample b with token p masked
+            enc = self.transformer.encode(xm, temb[b])                          # (n, D, E)
+            rows.append(enc[torch.arange(b.numel(), device=x.device), p])       # row p of sequence (b, p)
+        logits = self.transformer.readout(torch.cat(rows, dim=0).view(B, Dp, self.embed_dim), temb)
+        if c:
+            logits = torch.cat([torch.zeros((B, c, logits.shape[-1]), dtype=logits.dtype, device=x.device), logits], dim=1)
+        return logits.view(tuple(shape) + (self.S,))

@@ -1,0 +1,39 @@
+/* ctdd_bert.h -- C ABI of what the single-stream transformer score models add to the hollow-transformer kernels
+ * (libctdd.so, gfx950).  Reference: TAUnSDDM/lib/networks/hollow_networks.py (TransformerEncoder 450-493, MaskedTransformer
+ * 859-914, EnumerativeTransformer 917-960, BertEnumTransformer 963-1031).  The encoder blocks, the FiLM readout and the GEMMs
+ * are the entry points of ctdd_hollow.h; the encoder's attention is ctdd_hollow_attention / _bf16 with mode 3 (unmasked).
+ * Conventions as there: fp32 device buffers, caller-owned; 0 or a negative CTDD_E* code. */
+#ifndef CTDD_BERT_H
+#define CTDD_BERT_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* out[r] = [temb_b, emb(x_b0) .. emb(x_b,D-1)] + pe, (rows, D + 1, E); temb and emb(x) = w_in (2 x / (S - 1) - 1) + b_in as
+ * ctdd_hollow_embed computes them.  enumerate = 0: rows == B, b = r.  enumerate = 1 (the masked model): row r is sequence
+ * g = *r0 + r of the (B D') enumeration, D' = D - cond: b = g / D', and token p = cond + g % D' enters as the mask value S.
+ * r0 is a device scalar (null: 0), so one captured launch serves every chunk; rows with g >= B D' repeat the last sequence.
+ * temb (B, E), optional, receives the time embedding of every sample that owns a row with p == cond (plain mode: of all). */
+typedef struct {
+  const int64_t* x64; const int32_t* x32; const float* t; const float* w_in; const float* b_in; const float* pe;
+  int B, D, E, S; float temb_scale; float* out; float* temb;
+  int enumerate, cond, rows; const int32_t* r0;
+} ctdd_bert_embed_args;
+int ctdd_bert_embed(const void* embed_args, void* stream);
+
+/* ctdd_hollow_attention's contract (a ctdd_hollow_attn_args block, ctdd_hollow.h) for mode 3 with Tq <= 64 and Tk <= 64, head
+ * dimension 4, 8, 16 or 32: one wave per (sequence, head) with its keys and values resident in LDS, fp32 arithmetic; `split` is
+ * ignored.  Anything else returns CTDD_EINVAL / CTDD_ERANGE and launches nothing. */
+int ctdd_bert_attention_short(const void* attn_args, void* stream);
+
+/* readout input from the encoder output enc (rows', D + 1, E), as fp32 and / or bf16 hi (+ lo).  enumerate = 0: rows == B (D - cond),
+ * out row g = b (D - cond) + j takes row 1 + cond + j of sequence b (r0 unused).  enumerate = 1: chunk row r is sequence
+ * g = *r0 + r = (b, p) as in ctdd_bert_embed; its row 1 + p goes to row g of out (B D', E); rows with g >= B D' are dropped */
+int ctdd_bert_gather(const float* enc, const int32_t* r0, int rows, int enumerate, int B, int D, int cond, int E, float* out, void* out_bf16,
+                     void* out_lo, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* CTDD_BERT_H */

@@ -54,7 +54,9 @@ typedef struct {
 int ctdd_gemm_bf16(const void* gemm_args, void* stream);
 
 /* masked multi-head attention, softmax(scale q.k) v: mode 0 causal (j <= i, UniDirectionalTransformer l2r 534-560),
- * 1 anti-causal (j >= i, r2l), 2 readout over [temb | l2r | r2l] with Tk = 2 Tq + 1 (CrossAttention 204-280).
+ * 1 anti-causal (j >= i, r2l), 2 readout over [temb | l2r | r2l] with Tk = 2 Tq + 1 (CrossAttention 204-280),
+ * 3 unmasked: every key j < Tk for every query i < Tq, Tq and Tk independent (TransformerEncoder 450-493; modes 0 and 1 need
+ * Tk == Tq).  Any other mode returns CTDD_EINVAL and launches nothing.
  * q/k/v rows at base + b*bs + row*rs + head*hd. */
 typedef struct {
   const float* q; const float* k; const float* v; int64_t q_bs, k_bs, v_bs; int q_rs, k_rs, v_rs;
