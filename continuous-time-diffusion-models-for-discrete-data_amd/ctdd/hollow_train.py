@@ -28,6 +28,7 @@ import math
 import torch
 
 from . import native
+from .plan_launch import patch_gemm_tiles, ptr as _p
 from .unet_engine import SEG_1x1, _ConvArgs, _unwrap
 from .hollow_engine import _AttnArgs as _InfAttnArgs, _EmbedArgs, _GemmArgs, _LnArgs, _lib as _hollow_lib, supports  # noqa: F401
 from . import unet_train
@@ -85,10 +86,6 @@ def _ck(rc, what):
         raise native.CtddError(f"{what} failed ({rc}): {native.load().ctdd_last_error().decode()}")
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 # ---------------------------------------------------------------------- launch helpers (no autograd)
 def _gemm_fusable(K, N, bf16):
     """The plain GEMM kernel takes this product (its epilogue can then carry a dropout or a ReLU-backward mask)."""
@@ -125,15 +122,7 @@ def _gemm(x, w, bias, res, rows, K, N, bf16, act=0, want_hi=False, want_f32=True
     a.B, a.H, a.W, a.Hin, a.Win, a.N, a.Ktot = 1, rows, 1, rows, 1, N, K
     a.bias, a.res_f32, a.out_f32, a.out_hi, a.act = _p(bias), _p(res), _p(out), _p(out_hi), act
     if bf16 and N % 8 == 0:
-        pbk = 64 if K % 64 == 0 else 48 if K % 48 == 0 else 32 if K % 32 == 0 else 16
-        if pbk == 64:
-            pbnt = 4 if N > 64 else 2 if N > 32 else 1
-        elif pbk == 48:
-            pbnt = 4 if N % 128 == 0 else 3 if N > 64 else 2 if N > 32 else 1
-        elif pbk == 32:
-            pbnt = 4 if N % 128 == 0 else 3 if N > 32 else 1
-        else:
-            pbnt = 1
+        pbk, pbnt = patch_gemm_tiles(K, N)
         _ck(l.ctdd_unet_conv_patch(C.byref(a), pbk, pbnt, 32, _st()), "ctdd_unet_conv_patch")
     elif bf16:
         bk = 96 if K % 96 == 0 else 64 if K % 64 == 0 else 32 if K % 32 == 0 else 16

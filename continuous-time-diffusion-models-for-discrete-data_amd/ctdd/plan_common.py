@@ -6,7 +6,7 @@ import math
 
 import torch
 
-from . import native
+from .plan_launch import bound_launch, patch_gemm_tiles, ptr
 from .unet_engine import _ConvArgs, _lib as _unet_lib, SEG_1x1
 
 _P, _I, _F, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
@@ -71,9 +71,7 @@ class PlanBuilder:
     def lo(self, *shape):                           # their second terms
         return torch.empty(shape, dtype=torch.bfloat16, device=self.dev) if self.split else None
 
-    @staticmethod
-    def P(t):
-        return None if t is None else t.data_ptr()
+    P = staticmethod(ptr)
 
     def W(self, p):                                 # fp32 contiguous view of a parameter (kept alive)
         t = p.detach().float().contiguous()
@@ -81,14 +79,7 @@ class PlanBuilder:
         return t
 
     def launch(self, fn, *args, label=None, flops=0):
-        lib = self.lib
-
-        def run():
-            rc = fn(*args, torch.cuda.current_stream().cuda_stream)
-            if rc != 0:
-                raise native.CtddError(f"{fn.__name__} failed ({rc}): {lib.ctdd_last_error().decode()}")
-        run.label, run.flops = (fn.__name__, label), flops
-        self.plan.append(run)
+        self.plan.append(bound_launch(fn, *args, label=label, flops=flops))
 
     def linear(self, x, rows, K, lin_w, lin_b, out, act=0, res=None, label="", x_hi=None, out_hi=None, x_lo=None, out_lo=None):
         """out[rows][N] = act(x[rows][K] @ W^T + b) (+ res) on the implicit-GEMM kernel: fp32 operands, or bf16
@@ -158,15 +149,7 @@ class PlanBuilder:
         if use_bf16 and N % 8 == 0 and K % 16 == 0 and getattr(m, "engine_linear", "gemm") in ("gemm", "patch"):
             # the U-Net's slab kernel run as a plain GEMM (one 1x1 segment over a rows x 1 "image"): 16-byte row-major
             # epilogue, weights and activations staged per 128/256-row tile
-            pbk = 64 if K % 64 == 0 else 48 if K % 48 == 0 else 32 if K % 32 == 0 else 16
-            if pbk == 64:
-                pbnt = 4 if N > 64 else 2 if N > 32 else 1
-            elif pbk == 48:
-                pbnt = 4 if N % 128 == 0 else 3 if N > 64 else 2 if N > 32 else 1
-            elif pbk == 32:
-                pbnt = 4 if N % 128 == 0 else 3 if N > 32 else 1
-            else:
-                pbnt = 1
+            pbk, pbnt = patch_gemm_tiles(K, N)
             ext = act != 0 or a.out_lo                 # activation / hi + lo outputs: the EXT instantiations (wm = 32)
             wm = 64 if (not ext and rows >= 256 * 256 and (pbk, pbnt) in ((48, 3), (48, 4), (64, 4), (64, 2), (48, 2))) else 32
             launch(lib.ctdd_unet_conv_patch, C.byref(a), pbk, pbnt, wm, label=f"linear {label} {rows}x{K}->{N} patch",

@@ -1,0 +1,33 @@
+"""What every plan builder shares (ctdd/unet_engine.py, ctdd/plan_common.py, ctdd/hollow_train.py): the pointer helper, the
+pre-bound launch a plan is a list of, and the tile pick of the patch kernel run as a plain GEMM."""
+import torch
+
+from . import native
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def bound_launch(fn, *args, label=None, flops=0):
+    """`fn(*args, stream)` on the stream that is current when the step runs; a non-zero return raises with the library's message."""
+    def run():
+        rc = fn(*args, torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise native.CtddError(f"{fn.__name__} failed ({rc}): {native.load().ctdd_last_error().decode()}")
+    run.label, run.flops = (fn.__name__, label), flops      # flops: matrix FLOPs of the launch (bench.py's network roofline)
+    return run
+
+
+def patch_gemm_tiles(K, N):
+    """(bk, bnt) of ctdd_unet_conv_patch for one 1x1 segment of K channels over a rows x 1 "image" with N outputs."""
+    pbk = 64 if K % 64 == 0 else 48 if K % 48 == 0 else 32 if K % 32 == 0 else 16
+    if pbk == 64:
+        pbnt = 4 if N > 64 else 2 if N > 32 else 1
+    elif pbk == 48:
+        pbnt = 4 if N % 128 == 0 else 3 if N > 64 else 2 if N > 32 else 1
+    elif pbk == 32:
+        pbnt = 4 if N % 128 == 0 else 3 if N > 32 else 1
+    else:
+        pbnt = 1
+    return pbk, pbnt

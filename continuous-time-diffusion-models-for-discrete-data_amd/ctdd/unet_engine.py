@@ -13,12 +13,13 @@ precision = "bf16":  bf16 activations / weights on v_mfma_f32_32x32x16_bf16, fp3
 precision = "fp32":  fp32 activations / weights on the exact-fp32 v_mfma_f32_32x32x2_f32 -- the path
                      the 1e-4 logit parity test runs.
 """
+import contextlib
 import ctypes as C
-import math
 
 import torch
 
 from . import native
+from .plan_launch import bound_launch, ptr
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SEG_3x3, SEG_1x1, SEG_3x3_S2, SEG_3x3_UP = 0, 1, 2, 3
@@ -105,9 +106,6 @@ def training_supported(model):
     return net.channel % 16 == 0 and all((net.channel * int(m_)) % 16 == 0 for m_ in model.cfg.model.ch_mult)
 
 
-class _GnUncovered(Exception):
-    """A GroupNorm shape outside k_gn_onepass (UNetEngine._build falls back to statistics epilogues + k_gn_apply)."""
-
 
 def resblock_small_covers(H, W, cs, cout, G1, G2):
     """Shapes ctdd_unet_resblock_small holds (csrc/unet_resblock_kernels.hip): a sample of <= 64 pixels in rows of <= 8, 192 output
@@ -154,18 +152,464 @@ def _onepass_slab(B, HW, Cn, G, max_threads=1024):
 
 
 class _Tensor:
-    """NHWC activation [B*H*W][C]: bf16 (`hi`) in bf16 mode, fp32 (`f32`) in fp32 mode, plus the offset
+    """NHWC activation [B*H*W][C] of the plan `pb` builds: bf16 (`hi`) in bf16 mode, fp32 (`f32`) in fp32 mode, plus the offset
     of its per-(b, channel) statistics in the plan's pool."""
 
-    def __init__(self, eng, B, H, W, Cn, stats=True):
-        dev, M = eng.dev, B * H * W
+    def __init__(self, pb, H, W, Cn, stats=True):
+        eng, B = pb.eng, pb.B
+        M = B * H * W
         self.B, self.H, self.W, self.C = B, H, W, Cn
-        self.f32 = torch.empty((M, Cn), dtype=torch.float32, device=dev) if eng.precise else None
-        self.hi = None if eng.precise else torch.empty((M, Cn), dtype=torch.bfloat16, device=dev)
-        small = H * W <= getattr(eng, "_plan_no_stats_hw", 0)      # a one-pass GroupNorm level: no statistics from the producers
-        self.stats_by_gn = bool(stats and small and getattr(eng, "_plan_gn_writes_stats", False))   # training: k_gn_onepass leaves them for backward
-        self.stats = eng.alloc_stats(B * Cn * 2) if (stats and (not small or self.stats_by_gn)) else None
-        eng._live.append(self)           # raw pointers are baked into the plan: keep every buffer alive
+        self.f32 = torch.empty((M, Cn), dtype=torch.float32, device=eng.dev) if eng.precise else None
+        self.hi = None if eng.precise else torch.empty((M, Cn), dtype=torch.bfloat16, device=eng.dev)
+        small = H * W <= pb.no_stats_hw      # a one-pass GroupNorm level: no statistics from the producers
+        self.stats_by_gn = bool(stats and small and pb.gn_writes_stats)   # training: k_gn_onepass leaves them for backward
+        self.stats = pb.alloc_stats(B * Cn * 2) if (stats and (not small or self.stats_by_gn)) else None
+        pb.keep.append(self)             # raw pointers are baked into the plan: keep every buffer alive
+
+
+class _PlanBuilder:
+    """One build of one U-Net plan for batch B: launch list, kept-alive buffers, statistics-pool layout, split-K buffers.  `build`
+    walks the network; the training context `tc` lays out its backward plan through the same methods (unet_train.TrainCtx.finish)."""
+
+    def __init__(self, eng, B, tc, onepass_gn):
+        self.eng, self.B, self.tc, self.onepass_gn = eng, B, tc, onepass_gn
+        self.m, self.lib, self.net, self.dev, self.shape = eng.cfg.model, _lib(), eng.net, eng.dev, eng.cfg.data.shape
+        # (levels up to gn_onepass_max_hw pixels per sample: above it the one-workgroup-per-(sample, slab) kernel loses to the many
+        #  small workgroups of k_gn_apply, and those tensors keep their statistics epilogues.  MNIST net, batch 256, sampler loop:
+        #  off 85.1 k sample-steps/s, 7x7 only 85.8 k, 7x7 + 14x14 87.9 k, all levels 85.1 k)
+        self.no_stats_hw = eng._onepass_max_hw() if onepass_gn else 0
+        self.gn_writes_stats = bool(onepass_gn and tc is not None)
+        self.gn_threads = int(getattr(self.m, "gn_threads", 512))    # (measured in the two-chain sampler loop: 384-512 best, 1024 -1 %)
+        self.bks = (32, 16) if eng.precise else (96, 64, 32, 16)      # fp32 tiles: K = 32 keeps 4 workgroups per CU
+        self.plan, self.keep = [], []
+        self.stats_off = 0
+        self.stats_views = []          # (argument block, offset, field) resolved after the pool exists
+        self.zero_views = []           # split-K partial-sum buffers: (conv args, elements)
+        self._plan_to, self._zero_to = self.plan, self.zero_views     # where launch() and conv() append: see emitting_to
+        self.st = type("Plan", (), {})()
+        self.st.B = B
+
+    def alloc_stats(self, n):
+        off = self.stats_off
+        self.stats_off += n
+        return off
+
+    @contextlib.contextmanager
+    def emitting_to(self, plan, zero_views):
+        """Within the block, launches go to `plan` and split-K buffers to `zero_views` (the backward plan, the forward prologue)."""
+        saved = self._plan_to, self._zero_to
+        self._plan_to, self._zero_to = plan, zero_views
+        yield
+        self._plan_to, self._zero_to = saved           # (an exception inside abandons the whole builder)
+
+    def launch(self, fn, *args, label=None, flops=0):
+        self._plan_to.append(bound_launch(fn, *args, label=label, flops=flops))
+
+    def pick_bk(self, cs):
+        for bk in self.bks:
+            if all(c % bk == 0 for c in cs):
+                return bk
+        raise native.CtddError(f"no K tile divides channel counts {cs}")
+
+    @staticmethod
+    def pick_bnt(N, bk):
+        if bk == 16:
+            return 1
+        if N % 96 == 0 and bk in (96, 32):
+            return 3
+        if N % 128 == 0:
+            return 4
+        if N % 64 == 0 and bk == 64:
+            return 2
+        return 1
+
+    def conv(self, segs, wsrc, bias, N, Hout, Wout, Hin, Win, out, tb=None, res=None, logits_C=0, out_f32_tensor=None, bias_params=None,
+             packed=None, back=True):
+        """segs: list of (_Tensor, channels, kind); wsrc: per segment (weight parameter [N][Cin_tot][k][k], channel offset) --
+        the [N][K] matrix the kernels stream is K = segment -> tap -> channel of those slices.  bias_params: the
+        parameters whose sum `bias` is (training: each receives the bias gradient).  packed: (bf16 | None, fp32 | None)
+        ready-made weights (the data-gradient convolutions of the training plan)."""
+        eng, tc, m, lib, B = self.eng, self.tc, self.m, self.lib, self.B
+        a = _ConvArgs()
+        a.nseg = len(segs)
+        for i, (src, cs, kind) in enumerate(segs):
+            a.seg[i].hi, a.seg[i].f32, a.seg[i].C, a.seg[i].kind = ptr(src.hi), ptr(src.f32), cs, kind
+        Ktot = sum(cs * (1 if kind == SEG_1x1 else 9) for _, cs, kind in segs)
+        if packed is not None:
+            whi, wf = packed
+        elif tc is not None:
+            whi, wf = tc.packed_forward(wsrc, segs, N, Ktot)     # persistent buffers, refreshed by ONE pack launch per step
+        else:
+            w2d = eng._w2d(wsrc, segs)
+            assert w2d.shape[1] == Ktot
+            whi, wf = eng._pack(w2d)
+        self.keep.extend([whi, wf, bias])
+        a.w_hi, a.w_f32 = ptr(whi), ptr(wf)
+        a.B, a.H, a.W, a.Hin, a.Win, a.N, a.Ktot = B, Hout, Wout, Hin, Win, N, Ktot
+        a.bias = ptr(bias)
+        if tb is not None:
+            a.tbias, a.tb_stride = tb
+        if res is not None:
+            if eng.precise:
+                a.res_f32 = ptr(res.f32)
+            else:
+                a.res_bf16 = ptr(res.hi)
+        if out_f32_tensor is not None:
+            if out_f32_tensor.dtype == torch.bfloat16:      # (the bf16 logits of the sampler loops)
+                a.out_hi = ptr(out_f32_tensor)
+            else:
+                a.out_f32 = ptr(out_f32_tensor)
+        elif out is not None:
+            a.out_f32, a.out_hi = ptr(out.f32), ptr(out.hi)
+            if out.stats is not None and not out.stats_by_gn:
+                self.stats_views.append((a, out.stats, "stats"))
+        a.logits_C = logits_C
+        self.keep.append(a)
+        cs = [s[1] for s in segs]
+        patchable = (not eng.precise) and all(s[2] in (SEG_3x3, SEG_1x1) for s in segs) and Wout <= 33
+        hw_ = Hout * Wout
+        patchable = patchable and N % 8 == 0 and (hw_ >= 32 or hw_ == 16 or B == 1) and (logits_C == 0 or (N // logits_C) % 8 == 0)
+        M_ = B * Hout * Wout
+        lab = f"{Hout}x{Wout} K={Ktot} N={N} segs={[(c_, k_) for _, c_, k_ in segs]}"
+        if tc is not None and back:
+            tc.record_conv(segs, wsrc, bias_params, N, Hout, Wout, Hin, Win, out, tb, res, logits_C, out_f32_tensor)
+        which = getattr(m, "conv_kernel", "auto")
+        only3 = all(s[2] == SEG_3x3 for s in segs)
+        if which == "auto":
+            # measured at batch 256 (MNIST net): the LDS-DMA ring wins where 512-pixel tiles give >= 160
+            # workgroups and every unit has nine taps (28x28, 14x14); the patch kernel (128/256-pixel tiles, two
+            # workgroups per CU) elsewhere.  Split-K lost everywhere it was tried (fp32 atomics + finish pass).
+            ring_min = int(getattr(m, "ring_min_tiles", 80))
+            which = "ring" if (only3 and -(-M_ // 512) * -(-N // 96) >= ring_min and N % 96 == 0) else "patch"
+            # (CIFAR net, N = 256 at 16x16: 64-column ring tiles beat the 128-column patch tiles, 49 vs 54 / 69 vs 104 us at batch 128)
+            if which == "patch" and only3 and N % 64 == 0 and N % 96 != 0 and Hout * Wout <= 256 and -(-M_ // 512) * (N // 64) >= ring_min:
+                which = "ring"
+            # (MNIST net's S = 256 output convolution, 28x28 K = 864: 64-column ring tiles 88 us, the 128-column patch tiles 105 us,
+            #  128-column ring tiles 179 us at batch 128; +1.4 % on the sampler loop)
+            if which == "patch" and only3 and N % 64 == 0 and N % 96 != 0 and N >= 256 and -(-M_ // 512) * (N // 64) >= ring_min:
+                which = "ring"
+        resident = which == "res" and patchable and all(c % 32 == 0 for c in cs) and N % 32 == 0
+        ring = which == "ring" and patchable and all(c % 16 == 0 for c in cs) and N % 32 == 0
+        if resident or ring:
+            # 512-pixel tiles, all nine taps' weights in LDS: register-staged 32-channel units (k_conv_res)
+            # or an LDS-DMA ring of 16-channel units (k_conv_ring); csrc/unet_kernels.hip
+            bnt = 3 if N % 96 == 0 else 4 if (N % 128 == 0 and resident) else 2
+            ntiles = -(-M_ // 512) * -(-N // (32 * bnt))
+            units = sum(c // (32 if resident else 16) for c in cs)
+            if getattr(m, "conv_ksplit", 1) > 1 and units >= 2 and logits_C == 0:
+                a.ksplit = min(units, int(m.conv_ksplit))
+            if a.ksplit > 1:
+                self._zero_to.append((a, M_ * N))
+            fn = lib.ctdd_unet_conv_res if resident else lib.ctdd_unet_conv_ring
+            # (ring_small_tiles: 256-pixel tiles, four waves, two workgroups per CU -- the variant two concurrent chains can share a CU with)
+            sel = bnt + 10 if (ring and bnt in (2, 3) and getattr(m, "ring_small_tiles", 0)) else bnt
+            self.launch(fn, C.byref(a), sel, label=lab + f" {which} bnt={sel} ks={a.ksplit}", flops=2 * M_ * N * Ktot)
+        elif patchable:
+            # throughput kernel: slab staged once per channel chunk (csrc/unet_kernels.hip: k_conv_patch)
+            small = -(-M_ // 128) * -(-N // 96) < 256            # too few 128 x 96 tiles to fill the chip: 32-column tiles
+            if small and all(c % 64 == 0 for c in cs) and N % 32 == 0:
+                bk, bnt = 64, 1
+            elif small and all(c % 48 == 0 for c in cs) and N % 32 == 0:
+                bk, bnt = 48, 1
+            elif all(c % 48 == 0 for c in cs) and (N % 96 == 0 or N % 128 == 0):
+                bk, bnt = 48, (3 if N % 96 == 0 else 4)
+            elif all(c % 64 == 0 for c in cs) and N % 64 == 0:
+                bk, bnt = 64, (4 if N % 128 == 0 else 2)
+            elif all(c % 32 == 0 for c in cs):
+                bk, bnt = 32, (3 if N % 96 == 0 else 4 if N % 128 == 0 else 1)
+            else:
+                bk, bnt = 16, 1
+            wm = 64 if (bnt >= 2 and bk in (48, 64) and M_ >= int(getattr(m, "patch_wm64_min_rows", 196 * 128)) and (bk, bnt) != (64, 4)) else 32
+            units = sum(c // bk for c in cs)
+            nwg = -(-M_ // (4 * wm)) * -(-N // (32 * bnt))
+            if getattr(m, "conv_ksplit", 1) > 1 and units >= 2 and logits_C == 0 and out_f32_tensor is None:
+                a.ksplit = min(units, int(m.conv_ksplit))
+            elif nwg <= int(getattr(m, "ksplit_max_wgs", 96)) and units >= 4 and logits_C == 0 and out_f32_tensor is None:
+                a.ksplit = max(1, min(units // 2, 256 // nwg))       # tiny grids (4x4 levels): split K to fill the chip
+            if a.ksplit > 1:
+                self._zero_to.append((a, M_ * N))
+            self.launch(lib.ctdd_unet_conv_patch, C.byref(a), bk, bnt, wm, label=lab + f" patch bk={bk} bnt={bnt} wm={wm} ks={a.ksplit}",
+                        flops=2 * M_ * N * Ktot)
+        else:
+            bk = self.pick_bk(cs)
+            bnt = self.pick_bnt(N, bk)
+            if (not eng.precise) and -(-M_ // 128) * -(-N // (32 * bnt)) < int(getattr(m, "igemm_small_wgs", 256)) and bk in (96, 64, 32):
+                bnt = 1                                        # tiny grids: 32-column tiles, more workgroups
+            self.launch(lib.ctdd_unet_conv, C.byref(a), bk, bnt, int(eng.precise), label=lab + f" igemm bk={bk} bnt={bnt}", flops=2 * M_ * N * Ktot)
+
+    def gn_apply(self, srcs, norm, swish, eps, HW, drop_p=0.0):
+        """srcs: one or two _Tensor; returns activated planes tensor (training: dropout applied in place after it)."""
+        eng, tc, lib, B = self.eng, self.tc, self.lib, self.B
+        Ct = sum(s.C for s in srcs)
+        out = _Tensor(self, srcs[0].H, srcs[0].W, Ct, stats=False)
+        a = _GnArgs()
+        s1 = srcs[0]
+        a.s1_f32, a.s1_bf16, a.C1 = (ptr(s1.f32), None, s1.C) if eng.precise else (None, ptr(s1.hi), s1.C)
+        if s1.stats is not None:
+            self.stats_views.append((a, s1.stats, "st1"))
+        if len(srcs) == 2:
+            s2 = srcs[1]
+            a.s2_f32, a.s2_bf16, a.C2 = (ptr(s2.f32), None, s2.C) if eng.precise else (None, ptr(s2.hi), s2.C)
+            if s2.stats is not None:
+                self.stats_views.append((a, s2.stats, "st2"))
+        g, b_ = norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()
+        self.keep.extend([g, b_, a, out])
+        a.gamma, a.beta = ptr(g), ptr(b_)
+        a.B, a.HW, a.G, a.eps, a.swish = B, HW, norm.num_groups, eps, int(swish)
+        a.out_hi, a.out_f32 = ptr(out.hi), ptr(out.f32)
+        if self.onepass_gn and HW <= self.no_stats_hw:
+            if _onepass_slab(B, HW, Ct, norm.num_groups, self.gn_threads) == 0:       # (UNetEngine._build checked every shape first)
+                raise native.CtddError(f"one-pass GroupNorm does not cover HW={HW} C={Ct} G={norm.num_groups}")
+            # inference, bf16: statistics + normalisation in one pass over the tensor (k_gn_onepass); the producers' epilogues
+            # then carry no statistics at all (their tensors were created without statistics buffers)
+            self.launch(lib.ctdd_unet_gn_onepass, C.byref(a), 0, self.gn_threads, label=f"gn1 {srcs[0].H}x{srcs[0].W} C={Ct} ({len(srcs)} src)")
+        else:
+            self.launch(lib.ctdd_unet_gn_apply, C.byref(a), label=f"gn {srcs[0].H}x{srcs[0].W} C={Ct} ({len(srcs)} src)")
+        if tc is not None:
+            tc.record_gn(self, srcs, norm, swish, eps, HW, out, drop_p)
+        return out
+
+    def resblock_fused(self, rb, srcs):
+        """The block as ONE ctdd_unet_resblock_small launch: the same [N][K] matrices in the kernel's fragment order, the same summed
+        conv2 + skip bias."""
+        eng, lib, B = self.eng, self.lib, self.B
+        Hc, Wc = srcs[0].H, srcs[0].W
+        cs = [s.C for s in srcs]
+        Ct, cout = sum(cs), rb.conv1.weight.shape[0]
+        y = _Tensor(self, Hc, Wc, cout)
+        a = _ResblockArgs()
+        a.s1_bf16, a.C1 = ptr(srcs[0].hi), cs[0]
+        if len(srcs) == 2:
+            a.s2_bf16, a.C2 = ptr(srcs[1].hi), cs[1]
+        par = [p_.detach().float().contiguous() for p_ in (rb.norm1.weight, rb.norm1.bias, rb.norm2.weight, rb.norm2.bias, rb.conv1.bias)]
+        a.gamma1, a.beta1, a.gamma2, a.beta2, a.bias1 = (ptr(p_) for p_ in par)
+        a.G1, a.G2, a.eps1, a.eps2 = rb.norm1.num_groups, rb.norm2.num_groups, rb.norm1.eps, rb.norm2.eps
+        a.tbias, a.tb_stride = self.tproj.data_ptr() + 4 * self.toff[id(rb)], self.tb_stride
+        w1, _ = eng._pack(pack_resblock_weights(eng._w2d([(rb.conv1.weight, 0)], [(None, Ct, SEG_3x3)])))
+        segs, wsrc, bias2 = [(None, cout, SEG_3x3)], [(rb.conv2.weight, 0)], rb.conv2.bias.detach().float()
+        if rb.skip is not None:
+            c_ = 0
+            for cs_ in cs:
+                segs.append((None, cs_, SEG_1x1))
+                wsrc.append((rb.skip.weight, c_))
+                c_ += cs_
+            bias2 = bias2 + rb.skip.bias.detach().float()
+        bias2 = bias2.contiguous()
+        w2, _ = eng._pack(pack_resblock_weights(eng._w2d(wsrc, segs)))
+        a.w1, a.w2, a.bias2, a.skip = ptr(w1), ptr(w2), ptr(bias2), int(rb.skip is not None)
+        a.B, a.H, a.W, a.N, a.out_bf16 = B, Hc, Wc, cout, ptr(y.hi)
+        self.keep.extend(par + [w1, w2, bias2, a])
+        K1, K2 = w1.shape[1], w2.shape[1]
+        self.launch(lib.ctdd_unet_resblock_small, C.byref(a), 0, label=f"{Hc}x{Wc} resblock C={cs} N={cout} K={K1}+{K2}",
+                    flops=2 * B * Hc * Wc * cout * (K1 + K2))
+        return y
+
+    def resblock(self, rb, srcs):
+        """srcs: list of 1-2 tensors forming the (virtual) channel concatenation."""
+        eng, tc = self.eng, self.tc
+        Hc, Wc = srcs[0].H, srcs[0].W
+        cs = [s.C for s in srcs]
+        cout = rb.conv1.weight.shape[0]
+        # a small level's whole block in one launch (csrc/unet_resblock_kernels.hip: one workgroup per sample, both activated
+        # tensors and h1 stay in LDS); cfg.model.resblock_fused = 0 keeps the four launches below
+        if self.onepass_gn and eng._fuses_resblock(rb, Hc, Wc, cs, tc is not None) and all(s_.stats is None for s_ in srcs):
+            return self.resblock_fused(rb, srcs)
+        a1 = self.gn_apply(srcs, rb.norm1, True, rb.norm1.eps, Hc * Wc)
+        h = _Tensor(self, Hc, Wc, cout)
+        b1 = rb.conv1.bias.detach().float().contiguous()
+        self.conv([(a1, a1.C, SEG_3x3)], [(rb.conv1.weight, 0)], b1, cout, Hc, Wc,
+                  Hc, Wc, h, tb=(self.tproj.data_ptr() + 4 * self.toff[id(rb)], self.tb_stride), bias_params=[rb.conv1.bias])
+        drop = float(rb.dropout.p) if (tc is not None and tc.dropout) else 0.0
+        a2 = self.gn_apply([h], rb.norm2, True, rb.norm2.eps, Hc * Wc, drop_p=drop)
+        y = _Tensor(self, Hc, Wc, cout)
+        wsrc = [(rb.conv2.weight, 0)]
+        bias2, bias_params = rb.conv2.bias.detach().float(), [rb.conv2.bias]
+        segs = [(a2, cout, SEG_3x3)]
+        res = None
+        if rb.skip is not None:
+            c_ = 0
+            for s_ in srcs:                       # linear skip folded in as 1x1 K-segments on the raw input
+                segs.append((s_, s_.C, SEG_1x1))
+                wsrc.append((rb.skip.weight, c_))
+                c_ += s_.C
+            bias_params.append(rb.skip.bias)
+            bias2 = tc.summed_bias(bias_params) if tc is not None else bias2 + rb.skip.bias.detach().float()
+        else:
+            res = srcs[0]
+        self.conv(segs, wsrc, bias2.contiguous(), cout, Hc, Wc, Hc, Wc, y, res=res, bias_params=bias_params)
+        return y
+
+    def block(self, layer, srcs):
+        """One ResBlock (+ attention) module of net.down / net.mid / net.up."""
+        cur = self.resblock(layer.resblocks, srcs)
+        return cur if layer.attention is None else self.attention(layer.attention, cur)
+
+    def attention(self, att, x):
+        tc, lib, B = self.tc, self.lib, self.B
+        T = x.H * x.W
+        an = self.gn_apply([x], att.norm, False, att.norm.eps, T)
+        Cx = x.C
+        qkv = torch.empty((B * T, 3 * Cx), dtype=torch.float32, device=self.dev)
+        self.keep.append(qkv)
+        self.conv([(an, Cx, SEG_1x1)], [(att.qkv.weight, 0)],
+                  att.qkv.bias.detach().float().contiguous(), 3 * Cx, x.H, x.W, x.H, x.W, None, out_f32_tensor=qkv,
+                  bias_params=[att.qkv.bias])
+        ao = _Tensor(self, x.H, x.W, Cx, stats=False)
+        aa = _AttnArgs()
+        aa.qkv, aa.B, aa.T, aa.C, aa.heads, aa.out_hi, aa.out_f32 = ptr(qkv), B, T, Cx, att.num_heads, ptr(ao.hi), ptr(ao.f32)
+        self.keep.extend([aa, ao])
+        self.launch(lib.ctdd_unet_attention, C.byref(aa))
+        if tc is not None:
+            tc.record_attention(att, qkv, ao, B, T, Cx)
+        y = _Tensor(self, x.H, x.W, Cx)
+        self.conv([(ao, Cx, SEG_1x1)], [(att.proj_out.weight, 0)],
+                  att.proj_out.bias.detach().float().contiguous(), Cx, x.H, x.W, x.H, x.W, y, res=x, bias_params=[att.proj_out.bias])
+        return y
+
+    def time(self, uniform_t):
+        """Time embedding + all ResBlock projections in two launches (st.tproj; `toff`: each block's column offset in it)."""
+        tc, B, st, lib, dev, ch = self.tc, self.B, self.st, self.lib, self.dev, self.net.channel
+        resblocks, pw, pb, tw = self.eng._time_weights()
+        tdim, Ntot = ch * 4, pw.shape[1]
+        st.tact = torch.empty((B, tdim), dtype=torch.float32, device=dev)
+        time_row = uniform_t == "row" and tc is None
+        uniform_t = bool(uniform_t) and tc is None
+        # uniform_t: every sample at the same time (the samplers): ONE projection row from one fused launch, read by the
+        # convolutions with a zero batch stride (csrc/unet_kernels.hip: k_time_uniform).  "row": that row comes from the caller
+        # (a sampler's grid of times is known when it starts: time_table() computes every step's row at once) -- no time
+        # launch in the plan at all
+        st.time_row = time_row
+        self.tproj = st.tproj = torch.empty((1 if uniform_t else B, Ntot), dtype=torch.float32, device=dev)
+        self.tb_stride = 0 if uniform_t else Ntot
+        ta = _TimeArgs()
+        st.thid = torch.empty((B, tdim), dtype=torch.float32, device=dev)
+        ta.t, ta.B, ta.ch, ta.tdim = ptr(st.t_in), B, ch, tdim
+        ta.w1, ta.b1, ta.w2, ta.b2, ta.hid, ta.act = ptr(tw[0]), ptr(tw[1]), ptr(tw[2]), ptr(tw[3]), ptr(st.thid), ptr(st.tact)
+        self.keep.extend(tw + [pw, pb, ta])
+        if tc is None and not time_row:
+            self.launch(lib.ctdd_unet_time_uniform if uniform_t else lib.ctdd_unet_time, C.byref(ta), ptr(pw), ptr(pb), Ntot, ptr(st.tproj))
+        elif tc is None:
+            st.tproj.zero_()
+        else:
+            tc.tproj, tc.resblocks = st.tproj, resblocks          # filled by the caller before the plan runs
+        self.toff, o = {}, 0
+        for rb in resblocks:
+            self.toff[id(rb)] = o
+            o += rb.time[1].weight.shape[0]
+
+    def first_conv(self, c0):
+        st, B, net, ch, (Cin, H0, W0) = self.st, self.B, self.net, self.net.channel, self.shape
+        cur = _Tensor(self, H0, W0, ch)
+        fa = _FirstArgs()
+        if st.x_in.dtype == torch.int64:
+            fa.x64 = ptr(st.x_in)
+        else:
+            fa.x32 = ptr(st.x_in)
+        fa.lo, fa.hi = float(net.x_min_max[0]), float(net.x_min_max[1])
+        w0, b0 = c0.weight.detach().float().contiguous(), c0.bias.detach().float().contiguous()
+        fa.w, fa.bias, fa.B, fa.Cin, fa.H, fa.W, fa.Cout = ptr(w0), ptr(b0), B, Cin, H0, W0, ch
+        fa.out_f32, fa.out_hi = ptr(cur.f32), ptr(cur.hi)
+        if self.m.model_output == "logistic_pars":
+            st.x0 = torch.empty((B, Cin, H0, W0), dtype=torch.float32, device=self.dev)
+            fa.x0_f32 = ptr(st.x0)
+        if cur.stats is not None:
+            self.stats_views.append((fa, cur.stats, "stats"))
+        self.keep.extend([w0, b0, fa])
+        self.launch(self.lib.ctdd_unet_first_conv, C.byref(fa))
+        if self.tc is not None:
+            self.tc.record_first(c0, fa, cur)
+        return cur
+
+    def downsample(self, cv, cur):
+        """Downsample: stride-2 conv, pad right/bottom by one."""
+        Ho, Wo = (cur.H + 1 - 3) // 2 + 1, (cur.W + 1 - 3) // 2 + 1
+        y = _Tensor(self, Ho, Wo, cur.C)
+        self.conv([(cur, cur.C, SEG_3x3_S2)], [(cv.weight, 0)],
+                  cv.bias.detach().float().contiguous(), cur.C, Ho, Wo, cur.H, cur.W, y, bias_params=[cv.bias])
+        return y
+
+    def upsample(self, cv, cur):
+        """Upsample: nearest x2 folded into the conv's addressing (fp32 inference), or materialised before a stride-1 convolution."""
+        eng, tc, B, lib = self.eng, self.tc, self.B, self.lib
+        y = _Tensor(self, cur.H * 2, cur.W * 2, cur.C)
+        if eng.precise and tc is None:
+            self.conv([(cur, cur.C, SEG_3x3_UP)], [(cv.weight, 0)],
+                      cv.bias.detach().float().contiguous(), cur.C, cur.H * 2, cur.W * 2, cur.H, cur.W, y)
+        else:                                  # materialise the 2x grid (cheap), then a stride-1 convolution (training: both modes)
+            up = _Tensor(self, cur.H * 2, cur.W * 2, cur.C, stats=False)
+            if eng.precise:
+                self.launch(lib.ctdd_unet_upsample2x_f32, ptr(cur.f32), B, cur.H, cur.W, cur.C, ptr(up.f32))
+            else:
+                self.launch(lib.ctdd_unet_upsample2x, ptr(cur.hi), B, cur.H, cur.W, cur.C, ptr(up.hi))
+            if tc is not None:
+                tc.record_upsample(cur, up)
+            self.conv([(up, cur.C, SEG_3x3)], [(cv.weight, 0)],
+                      cv.bias.detach().float().contiguous(), cur.C, up.H, up.W, up.H, up.W, y, bias_params=[cv.bias])
+        return y
+
+    def head(self, cur, logits_out, logits_bf16):
+        """Output GroupNorm + convolution into st.logits (logistic_pars: into st.net_out, then the logistic head)."""
+        eng, tc, B, st, m, net, dev, (Cin, H0, W0) = self.eng, self.tc, self.B, self.st, self.m, self.net, self.dev, self.shape
+        S = net.S
+        ao = self.gn_apply([cur], net.out[0], True, net.out[0].eps, cur.H * cur.W)
+        oc = net.out[2]
+        n_out = oc.weight.shape[0]
+        D = Cin * H0 * W0
+        logistic = m.model_output == "logistic_pars"
+        # (bf16 logits: the output convolution's epilogue; the logistic head writes them in the bf16 inference engine when S % 4 == 0)
+        ldt = torch.bfloat16 if logits_bf16 and not (logistic and (tc is not None or eng.precise or S % 4)) else torch.float32
+        st.logits = logits_out if logits_out is not None else torch.empty((B, D, S), dtype=ldt, device=dev)
+        assert st.logits.dtype == ldt
+        if logistic:
+            st.net_out = torch.empty((B * H0 * W0, n_out), dtype=torch.float32, device=dev)
+            self.conv([(ao, ao.C, SEG_3x3)], [(oc.weight, 0)],
+                      oc.bias.detach().float().contiguous(), n_out, H0, W0, H0, W0, None, out_f32_tensor=st.net_out, bias_params=[oc.bias])
+            la = _LogisticArgs()
+            la.net, la.x0, la.B, la.C, la.HW, la.S, la.fix = ptr(st.net_out), ptr(st.x0), B, Cin, H0 * W0, S, int(bool(m.fix_logistic))
+            if ldt == torch.bfloat16:                  # (the sampler loops of the bf16 engine: the head writes what the bf16 step kernel reads)
+                la.out_bf16 = ptr(st.logits)
+            else:
+                la.out = ptr(st.logits)
+            la.fast = 0 if eng.precise else 1
+            self.keep.append(la)
+            if tc is None:                             # (training: the head runs as differentiable device ops on net_out)
+                self.launch(self.lib.ctdd_unet_logistic_head, C.byref(la))
+        else:
+            self.conv([(ao, ao.C, SEG_3x3)], [(oc.weight, 0)],
+                      oc.bias.detach().float().contiguous(), n_out, H0, W0, H0, W0, None, out_f32_tensor=st.logits,
+                      logits_C=Cin, bias_params=[oc.bias])
+
+    def build(self, x_dtype, logits_out, logits_bf16, uniform_t):
+        st, B, net, dev = self.st, self.B, self.net, self.dev
+        st.x_in = torch.zeros((B, *self.shape), dtype=x_dtype, device=dev)
+        st.t_in = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self.time(uniform_t)
+        cur = self.first_conv(net.down[0])
+        feats = [cur]
+        for layer in list(net.down)[1:]:
+            cur = self.block(layer, [cur]) if hasattr(layer, "resblocks") else self.downsample(layer.downsample[0], cur)
+            feats.append(cur)
+        for layer in net.mid:
+            cur = self.block(layer, [cur])
+        for layer in net.up:
+            cur = self.block(layer, [cur, feats.pop()]) if hasattr(layer, "resblocks") else self.upsample(layer[1], cur)
+        self.head(cur, logits_out, logits_bf16)
+        if self.tc is not None:                        # backward plan: built before the pools are laid out
+            self.tc.finish(self)
+        # ---- the per-(b, channel) statistics pool (one buffer, zeroed once per forward) and the split-K pool: the argument blocks
+        # recorded against offsets get their addresses
+        st.stats = torch.zeros((max(self.stats_off, 1),), dtype=torch.float64, device=dev)
+        base = st.stats.data_ptr()
+        for a_, off, field in self.stats_views:
+            setattr(a_, field, base + 8 * off)
+        nz = sum(n for _, n in self.zero_views)
+        st.zpool = torch.zeros((max(nz, 1),), dtype=torch.float32, device=dev)
+        zo = 0
+        for a_, n in self.zero_views:
+            a_.acc_buf = st.zpool.data_ptr() + 4 * zo
+            zo += n
+        st.plan, st.keep, st.graph = self.plan, self.keep, None
+        return st
 
 
 class UNetEngine:
@@ -182,7 +626,7 @@ class UNetEngine:
         self.precise = self.precision == "fp32"
         self._plans = {}
         self._wver = None
-        self._packed = None
+        self._time_w = None
 
     # ------------------------------------------------------------------ weights
     def _weights_version(self):
@@ -206,476 +650,62 @@ class UNetEngine:
                 parts.append(w[:, c_off:c_off + cs].permute(0, 2, 3, 1).reshape(N, 9 * cs))
         return torch.cat(parts, dim=1).contiguous()
 
-    @staticmethod
-    def _conv_w(weight, splits):
-        """torch conv weight [N][Cin][3][3] -> [N][K], K = segment -> tap -> channel."""
-        parts, c0 = [], 0
-        for cs in splits:
-            parts.append(weight[:, c0:c0 + cs].permute(0, 2, 3, 1).reshape(weight.shape[0], 9 * cs))
-            c0 += cs
-        return torch.cat(parts, dim=1)
 
     # ------------------------------------------------------------------ plan construction
-    def alloc_stats(self, n):
-        off = self._stats_off
-        self._stats_off += n
-        return off
+    def _time_weights(self):
+        """(resblocks, pw [tdim][Ntot], pb [Ntot], [w1, b1, w2, b2] as [in][out]): every ResBlock in plan order, their time
+        projections concatenated, and the time-embedding MLP, as fp32 copies; rebuilt when the weights change."""
+        ver = self._weights_version()
+        if self._time_w is None or self._time_w[0] != ver:
+            net = self.net
+            resblocks = [mod.resblocks for mod in list(net.down) + list(net.mid) + list(net.up) if hasattr(mod, "resblocks")]
+            pw = torch.cat([rb.time[1].weight.detach().float() for rb in resblocks], 0).t().contiguous()   # [tdim][Ntot]
+            pb = torch.cat([rb.time[1].bias.detach().float() for rb in resblocks], 0).contiguous()
+            tw = [net.time[1].weight.t(), net.time[1].bias, net.time[3].weight.t(), net.time[3].bias]      # weights as [in][out]
+            tw = [w.detach().float().contiguous() for w in tw]
+            self._time_w = (ver, resblocks, pw, pb, tw)
+        return self._time_w[1:]
+
+    def _onepass_max_hw(self):
+        return int(getattr(self.cfg.model, "gn_onepass_max_hw", 256))
+
+    def _fuses_resblock(self, rb, Hc, Wc, cs, training):
+        """Whether a plan with one-pass GroupNorm runs this block as ONE ctdd_unet_resblock_small launch (bf16 inference only)."""
+        return bool(not training and not self.precise and int(getattr(self.cfg.model, "resblock_fused", 1))
+                    and Hc * Wc <= self._onepass_max_hw()
+                    and resblock_small_covers(Hc, Wc, cs, rb.conv1.weight.shape[0], rb.norm1.num_groups, rb.norm2.num_groups))
+
+    def _onepass_gn_covers(self, B, training):
+        """Whether ctdd_unet_gn_onepass has a slab for every GroupNorm launch a one-pass plan would hold at its small levels (the
+        fused blocks carry theirs inside): _PlanBuilder.build's walk over shapes alone, so that nothing is built to find out."""
+        net, (_, H, W) = self.net, self.cfg.data.shape
+        max_hw, threads = self._onepass_max_hw(), int(getattr(self.cfg.model, "gn_threads", 512))
+        norms, c = [], net.channel                     # (pixels, GroupNorm) of every launch; channels of the running tensor
+        for layer in [*list(net.down)[1:], *net.mid, *net.up]:
+            if hasattr(layer, "downsample"):
+                H, W = (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1
+            elif not hasattr(layer, "resblocks"):      # Upsample
+                H, W = 2 * H, 2 * W
+            else:
+                rb, c1 = layer.resblocks, layer.resblocks.norm1.num_channels
+                if not self._fuses_resblock(rb, H, W, [c] if c1 == c else [c, c1 - c], training):     # (c1 > c: the skip concatenation)
+                    norms += [(H * W, rb.norm1), (H * W, rb.norm2)]
+                c = rb.norm2.num_channels
+                if layer.attention is not None:
+                    norms.append((H * W, layer.attention.norm))
+        norms.append((H * W, net.out[0]))
+        return all(hw > max_hw or _onepass_slab(B, hw, n.num_channels, n.num_groups, threads) > 0 for hw, n in norms)
 
     def _build(self, B, x_dtype, logits_out=None, tc=None, logits_bf16=False, uniform_t=False):
         # bf16 inference plans: GroupNorm as one pass per tensor with the statistics inside (k_gn_onepass), no statistics in
         # the convolution epilogues (cfg.model.gn_onepass, default on); a net with a GroupNorm the kernel does not cover is
-        # rebuilt the old way (statistics by the producers, k_gn_apply)
+        # built the old way (statistics by the producers, k_gn_apply)
         # (training plans too, cfg.model.gn_onepass_train: the kernel then also writes each source's per-channel sums into the
         #  tensors' statistics buffers, which the GroupNorm backward reads)
-        if (not self.precise) and int(getattr(self.cfg.model, "gn_onepass", 1)) and (tc is None or int(getattr(self.cfg.model, "gn_onepass_train", 1))):
-            try:
-                return self._build_impl(B, x_dtype, logits_out, tc, logits_bf16, uniform_t, onepass_gn=True)
-            except _GnUncovered:
-                pass
-        return self._build_impl(B, x_dtype, logits_out, tc, logits_bf16, uniform_t, onepass_gn=False)
-
-    def _build_impl(self, B, x_dtype, logits_out=None, tc=None, logits_bf16=False, uniform_t=False, onepass_gn=False):
-        net, m = self.net, self.cfg.model
-        # (levels up to gn_onepass_max_hw pixels per sample: above it the one-workgroup-per-(sample, slab) kernel loses to the many
-        #  small workgroups of k_gn_apply, and those tensors keep their statistics epilogues.  MNIST net, batch 256, sampler loop:
-        #  off 85.1 k sample-steps/s, 7x7 only 85.8 k, 7x7 + 14x14 87.9 k, all levels 85.1 k)
-        self._plan_no_stats_hw = int(getattr(m, "gn_onepass_max_hw", 256)) if onepass_gn else 0
-        self._plan_gn_writes_stats = bool(onepass_gn and tc is not None)
-        gn_threads = int(getattr(m, "gn_threads", 512))    # (measured in the two-chain sampler loop: 384-512 best, 1024 -1 %)
-        lib = _lib()
-        dev = self.dev
-        Cin, H0, W0 = self.cfg.data.shape
-        ch, S = net.channel, net.S
-        plan, keep = [], []
-        self._stats_off = 0
-        self._live = keep
-        st = type("Plan", (), {})()
-        st.B = B
-        st.x_in = torch.zeros((B, Cin, H0, W0), dtype=x_dtype, device=dev)
-        st.t_in = torch.zeros((B,), dtype=torch.float32, device=dev)
-        stream = lambda: torch.cuda.current_stream().cuda_stream
-
-        def ptr(t):
-            return None if t is None else t.data_ptr()
-
-        def launch(fn, *args, label=None, flops=0):
-            def run():
-                rc = fn(*args, stream())
-                if rc != 0:
-                    raise native.CtddError(f"{fn.__name__} failed ({rc}): {lib.ctdd_last_error().decode()}")
-            run.label = (fn.__name__, label)
-            run.flops = flops                      # matrix FLOPs of the launch (bench.py's network roofline)
-            cur_lists["plan"].append(run)
-
-        bks = (32, 16) if self.precise else (96, 64, 32, 16)      # fp32 tiles: K = 32 keeps 4 workgroups per CU
-
-        def pick_bk(cs):
-            for bk in bks:
-                if all(c % bk == 0 for c in cs):
-                    return bk
-            raise native.CtddError(f"no K tile divides channel counts {cs}")
-
-        def pick_bnt(N, bk):
-            if bk == 16:
-                return 1
-            if N % 96 == 0 and bk in (96, 32):
-                return 3
-            if N % 128 == 0:
-                return 4
-            if N % 64 == 0 and bk == 64:
-                return 2
-            return 1
-
-        stats_views = []          # (tensor, offset) resolved after the pool exists
-        zero_views = []           # split-K partial-sum buffers: (conv args, elements)
-        cur_lists = {"plan": plan, "zero": zero_views}     # the training context points these at the backward plan
-
-        def conv(segs, wsrc, bias, N, Hout, Wout, Hin, Win, out, tb=None, res=None, logits_C=0, out_f32_tensor=None, bias_params=None,
-                 packed=None, back=True):
-            """segs: list of (_Tensor, channels, kind); wsrc: per segment (weight parameter [N][Cin_tot][k][k], channel offset) --
-            the [N][K] matrix the kernels stream is K = segment -> tap -> channel of those slices.  bias_params: the
-            parameters whose sum `bias` is (training: each receives the bias gradient).  packed: (bf16 | None, fp32 | None)
-            ready-made weights (the data-gradient convolutions of the training plan)."""
-            a = _ConvArgs()
-            a.nseg = len(segs)
-            for i, (src, cs, kind) in enumerate(segs):
-                a.seg[i].hi, a.seg[i].f32, a.seg[i].C, a.seg[i].kind = ptr(src.hi), ptr(src.f32), cs, kind
-            Ktot = sum(cs * (1 if kind == SEG_1x1 else 9) for _, cs, kind in segs)
-            if packed is not None:
-                whi, wf = packed
-            elif tc is not None:
-                whi, wf = tc.packed_forward(wsrc, segs, N, Ktot)     # persistent buffers, refreshed by ONE pack launch per step
-            else:
-                w2d = self._w2d(wsrc, segs)
-                assert w2d.shape[1] == Ktot
-                whi, wf = self._pack(w2d)
-            keep.extend([whi, wf, bias])
-            a.w_hi, a.w_f32 = ptr(whi), ptr(wf)
-            a.B, a.H, a.W, a.Hin, a.Win, a.N, a.Ktot = B, Hout, Wout, Hin, Win, N, Ktot
-            a.bias = ptr(bias)
-            if tb is not None:
-                a.tbias, a.tb_stride = tb
-            if res is not None:
-                if self.precise:
-                    a.res_f32 = ptr(res.f32)
-                else:
-                    a.res_bf16 = ptr(res.hi)
-            if out_f32_tensor is not None:
-                if out_f32_tensor.dtype == torch.bfloat16:      # (the bf16 logits of the sampler loops)
-                    a.out_hi = ptr(out_f32_tensor)
-                else:
-                    a.out_f32 = ptr(out_f32_tensor)
-            elif out is not None:
-                a.out_f32, a.out_hi = ptr(out.f32), ptr(out.hi)
-                if out.stats is not None and not out.stats_by_gn:
-                    stats_views.append((a, out.stats))
-            a.logits_C = logits_C
-            keep.append(a)
-            cs = [s[1] for s in segs]
-            patchable = (not self.precise) and all(s[2] in (SEG_3x3, SEG_1x1) for s in segs) and Wout <= 33
-            hw_ = Hout * Wout
-            patchable = patchable and N % 8 == 0 and (hw_ >= 32 or hw_ == 16 or B == 1) and (logits_C == 0 or (N // logits_C) % 8 == 0)
-            M_ = B * Hout * Wout
-            lab = f"{Hout}x{Wout} K={Ktot} N={N} segs={[(c_, k_) for _, c_, k_ in segs]}"
-            if tc is not None and back:
-                tc.record_conv(conv, segs, wsrc, bias_params, N, Hout, Wout, Hin, Win, out, tb, res, logits_C, out_f32_tensor)
-            which = getattr(m, "conv_kernel", "auto")
-            only3 = all(s[2] == SEG_3x3 for s in segs)
-            if which == "auto":
-                # measured at batch 256 (MNIST net): the LDS-DMA ring wins where 512-pixel tiles give >= 160
-                # workgroups and every unit has nine taps (28x28, 14x14); the patch kernel (128/256-pixel tiles, two
-                # workgroups per CU) elsewhere.  Split-K lost everywhere it was tried (fp32 atomics + finish pass).
-                ring_min = int(getattr(m, "ring_min_tiles", 80))
-                which = "ring" if (only3 and -(-M_ // 512) * -(-N // 96) >= ring_min and N % 96 == 0) else "patch"
-                # (CIFAR net, N = 256 at 16x16: 64-column ring tiles beat the 128-column patch tiles, 49 vs 54 / 69 vs 104 us at batch 128)
-                if which == "patch" and only3 and N % 64 == 0 and N % 96 != 0 and Hout * Wout <= 256 and -(-M_ // 512) * (N // 64) >= ring_min:
-                    which = "ring"
-                # (MNIST net's S = 256 output convolution, 28x28 K = 864: 64-column ring tiles 88 us, the 128-column patch tiles 105 us,
-                #  128-column ring tiles 179 us at batch 128; +1.4 % on the sampler loop)
-                if which == "patch" and only3 and N % 64 == 0 and N % 96 != 0 and N >= 256 and -(-M_ // 512) * (N // 64) >= ring_min:
-                    which = "ring"
-            resident = which == "res" and patchable and all(c % 32 == 0 for c in cs) and N % 32 == 0
-            ring = which == "ring" and patchable and all(c % 16 == 0 for c in cs) and N % 32 == 0
-            if resident or ring:
-                # 512-pixel tiles, all nine taps' weights in LDS: register-staged 32-channel units (k_conv_res)
-                # or an LDS-DMA ring of 16-channel units (k_conv_ring); csrc/unet_kernels.hip
-                bnt = 3 if N % 96 == 0 else 4 if (N % 128 == 0 and resident) else 2
-                ntiles = -(-M_ // 512) * -(-N // (32 * bnt))
-                units = sum(c // (32 if resident else 16) for c in cs)
-                if getattr(m, "conv_ksplit", 1) > 1 and units >= 2 and logits_C == 0:
-                    a.ksplit = min(units, int(m.conv_ksplit))
-                if a.ksplit > 1:
-                    cur_lists["zero"].append((a, M_ * N))
-                fn = lib.ctdd_unet_conv_res if resident else lib.ctdd_unet_conv_ring
-                # (ring_small_tiles: 256-pixel tiles, four waves, two workgroups per CU -- the variant two concurrent chains can share a CU with)
-                sel = bnt + 10 if (ring and bnt in (2, 3) and getattr(m, "ring_small_tiles", 0)) else bnt
-                launch(fn, C.byref(a), sel, label=lab + f" {which} bnt={sel} ks={a.ksplit}", flops=2 * M_ * N * Ktot)
-            elif patchable:
-                # throughput kernel: slab staged once per channel chunk (csrc/unet_kernels.hip: k_conv_patch)
-                small = -(-M_ // 128) * -(-N // 96) < 256            # too few 128 x 96 tiles to fill the chip: 32-column tiles
-                if small and all(c % 64 == 0 for c in cs) and N % 32 == 0:
-                    bk, bnt = 64, 1
-                elif small and all(c % 48 == 0 for c in cs) and N % 32 == 0:
-                    bk, bnt = 48, 1
-                elif all(c % 48 == 0 for c in cs) and (N % 96 == 0 or N % 128 == 0):
-                    bk, bnt = 48, (3 if N % 96 == 0 else 4)
-                elif all(c % 64 == 0 for c in cs) and N % 64 == 0:
-                    bk, bnt = 64, (4 if N % 128 == 0 else 2)
-                elif all(c % 32 == 0 for c in cs):
-                    bk, bnt = 32, (3 if N % 96 == 0 else 4 if N % 128 == 0 else 1)
-                else:
-                    bk, bnt = 16, 1
-                wm = 64 if (bnt >= 2 and bk in (48, 64) and M_ >= int(getattr(m, "patch_wm64_min_rows", 196 * 128)) and (bk, bnt) != (64, 4)) else 32
-                units = sum(c // bk for c in cs)
-                nwg = -(-M_ // (4 * wm)) * -(-N // (32 * bnt))
-                if getattr(m, "conv_ksplit", 1) > 1 and units >= 2 and logits_C == 0 and out_f32_tensor is None:
-                    a.ksplit = min(units, int(m.conv_ksplit))
-                elif nwg <= int(getattr(m, "ksplit_max_wgs", 96)) and units >= 4 and logits_C == 0 and out_f32_tensor is None:
-                    a.ksplit = max(1, min(units // 2, 256 // nwg))       # tiny grids (4x4 levels): split K to fill the chip
-                if a.ksplit > 1:
-                    cur_lists["zero"].append((a, M_ * N))
-                launch(lib.ctdd_unet_conv_patch, C.byref(a), bk, bnt, wm, label=lab + f" patch bk={bk} bnt={bnt} wm={wm} ks={a.ksplit}",
-                       flops=2 * M_ * N * Ktot)
-            else:
-                bk = pick_bk(cs)
-                bnt = pick_bnt(N, bk)
-                if (not self.precise) and -(-M_ // 128) * -(-N // (32 * bnt)) < int(getattr(m, "igemm_small_wgs", 256)) and bk in (96, 64, 32):
-                    bnt = 1                                        # tiny grids: 32-column tiles, more workgroups
-                launch(lib.ctdd_unet_conv, C.byref(a), bk, bnt, int(self.precise), label=lab + f" igemm bk={bk} bnt={bnt}", flops=2 * M_ * N * Ktot)
-
-        def gn_apply(srcs, norm, swish, eps, HW, drop_p=0.0):
-            """srcs: one or two _Tensor; returns activated planes tensor (training: dropout applied in place after it)."""
-            Ct = sum(s.C for s in srcs)
-            out = _Tensor(self, B, srcs[0].H, srcs[0].W, Ct, stats=False)
-            a = _GnArgs()
-            s1 = srcs[0]
-            a.s1_f32, a.s1_bf16, a.C1 = (ptr(s1.f32), None, s1.C) if self.precise else (None, ptr(s1.hi), s1.C)
-            if s1.stats is not None:
-                stats_views.append((a, s1.stats, "st1"))
-            if len(srcs) == 2:
-                s2 = srcs[1]
-                a.s2_f32, a.s2_bf16, a.C2 = (ptr(s2.f32), None, s2.C) if self.precise else (None, ptr(s2.hi), s2.C)
-                if s2.stats is not None:
-                    stats_views.append((a, s2.stats, "st2"))
-            g, b_ = norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()
-            keep.extend([g, b_, a, out])
-            a.gamma, a.beta = ptr(g), ptr(b_)
-            a.B, a.HW, a.G, a.eps, a.swish = B, HW, norm.num_groups, eps, int(swish)
-            a.out_hi, a.out_f32 = ptr(out.hi), ptr(out.f32)
-            if onepass_gn and HW > self._plan_no_stats_hw:
-                launch(lib.ctdd_unet_gn_apply, C.byref(a), label=f"gn {srcs[0].H}x{srcs[0].W} C={Ct} ({len(srcs)} src)")
-            elif onepass_gn and _onepass_slab(B, HW, Ct, norm.num_groups, gn_threads) > 0:
-                # inference, bf16: statistics + normalisation in one pass over the tensor (k_gn_onepass); the producers' epilogues
-                # then carry no statistics at all (their tensors were created without statistics buffers)
-                launch(lib.ctdd_unet_gn_onepass, C.byref(a), 0, gn_threads, label=f"gn1 {srcs[0].H}x{srcs[0].W} C={Ct} ({len(srcs)} src)")
-            else:
-                if onepass_gn:
-                    raise _GnUncovered(f"one-pass GroupNorm does not cover HW={HW} C={Ct} G={norm.num_groups}")
-                launch(lib.ctdd_unet_gn_apply, C.byref(a), label=f"gn {srcs[0].H}x{srcs[0].W} C={Ct} ({len(srcs)} src)")
-            if tc is not None:
-                tc.record_gn(srcs, norm, swish, eps, HW, out, drop_p, launch, stats_views)
-            return out
-
-        # ---- time embedding + all ResBlock projections in two launches
-        resblocks = [mod.resblocks for mod in list(net.down) + list(net.mid) + list(net.up) if hasattr(mod, "resblocks")]
-        tdim = ch * 4
-        pw = torch.cat([rb.time[1].weight.detach().float() for rb in resblocks], 0).t().contiguous()   # [tdim][Ntot]
-        pb = torch.cat([rb.time[1].bias.detach().float() for rb in resblocks], 0).contiguous()
-        Ntot = pw.shape[1]
-        st.tact = torch.empty((B, tdim), dtype=torch.float32, device=dev)
-        time_row = uniform_t == "row" and tc is None
-        uniform_t = bool(uniform_t) and tc is None
-        # uniform_t: every sample at the same time (the samplers): ONE projection row from one fused launch, read by the
-        # convolutions with a zero batch stride (csrc/unet_kernels.hip: k_time_uniform).  "row": that row comes from the caller
-        # (a sampler's grid of times is known when it starts: time_table() computes every step's row at once) -- no time
-        # launch in the plan at all
-        st.time_row = time_row
-        st.tproj = torch.empty((1 if uniform_t else B, Ntot), dtype=torch.float32, device=dev)
-        tb_stride = 0 if uniform_t else Ntot
-        ta = _TimeArgs()
-        tw = [net.time[1].weight.t(), net.time[1].bias, net.time[3].weight.t(), net.time[3].bias]      # weights as [in][out]
-        tw = [w.detach().float().contiguous() for w in tw]
-        st.thid = torch.empty((B, tdim), dtype=torch.float32, device=dev)
-        ta.t, ta.B, ta.ch, ta.tdim = ptr(st.t_in), B, ch, tdim
-        ta.w1, ta.b1, ta.w2, ta.b2, ta.hid, ta.act = ptr(tw[0]), ptr(tw[1]), ptr(tw[2]), ptr(tw[3]), ptr(st.thid), ptr(st.tact)
-        keep.extend(tw + [pw, pb, ta])
-        if tc is None and not time_row:
-            launch(lib.ctdd_unet_time_uniform if uniform_t else lib.ctdd_unet_time, C.byref(ta), ptr(pw), ptr(pb), Ntot, ptr(st.tproj))
-        elif tc is None:
-            st.tproj.zero_()
-        else:
-            tc.tproj, tc.resblocks = st.tproj, resblocks          # filled by the caller before the plan runs
-        toff = {}
-        o = 0
-        for rb in resblocks:
-            toff[id(rb)] = o
-            o += rb.time[1].weight.shape[0]
-
-        # ---- first conv
-        c0 = net.down[0]
-        cur = _Tensor(self, B, H0, W0, ch)
-        fa = _FirstArgs()
-        if x_dtype == torch.int64:
-            fa.x64 = ptr(st.x_in)
-        else:
-            fa.x32 = ptr(st.x_in)
-        fa.lo, fa.hi = float(net.x_min_max[0]), float(net.x_min_max[1])
-        w0, b0 = c0.weight.detach().float().contiguous(), c0.bias.detach().float().contiguous()
-        fa.w, fa.bias, fa.B, fa.Cin, fa.H, fa.W, fa.Cout = ptr(w0), ptr(b0), B, Cin, H0, W0, ch
-        fa.out_f32, fa.out_hi = ptr(cur.f32), ptr(cur.hi)
-        logistic = m.model_output == "logistic_pars"
-        if logistic:
-            st.x0 = torch.empty((B, Cin, H0, W0), dtype=torch.float32, device=dev)
-            fa.x0_f32 = ptr(st.x0)
-        if cur.stats is not None:
-            stats_views.append((fa, cur.stats))
-        keep.extend([w0, b0, fa])
-        launch(lib.ctdd_unet_first_conv, C.byref(fa))
-        if tc is not None:
-            tc.record_first(c0, fa, cur)
-
-        def resblock_fused(rb, srcs):
-            """The block as ONE ctdd_unet_resblock_small launch: the same [N][K] matrices in the kernel's fragment order, the same summed
-            conv2 + skip bias."""
-            Hc, Wc = srcs[0].H, srcs[0].W
-            cs = [s.C for s in srcs]
-            Ct, cout = sum(cs), rb.conv1.weight.shape[0]
-            y = _Tensor(self, B, Hc, Wc, cout)
-            a = _ResblockArgs()
-            a.s1_bf16, a.C1 = ptr(srcs[0].hi), cs[0]
-            if len(srcs) == 2:
-                a.s2_bf16, a.C2 = ptr(srcs[1].hi), cs[1]
-            par = [p_.detach().float().contiguous() for p_ in (rb.norm1.weight, rb.norm1.bias, rb.norm2.weight, rb.norm2.bias, rb.conv1.bias)]
-            a.gamma1, a.beta1, a.gamma2, a.beta2, a.bias1 = (ptr(p_) for p_ in par)
-            a.G1, a.G2, a.eps1, a.eps2 = rb.norm1.num_groups, rb.norm2.num_groups, rb.norm1.eps, rb.norm2.eps
-            a.tbias, a.tb_stride = st.tproj.data_ptr() + 4 * toff[id(rb)], tb_stride
-            w1, _ = self._pack(pack_resblock_weights(self._w2d([(rb.conv1.weight, 0)], [(None, Ct, SEG_3x3)])))
-            segs, wsrc, bias2 = [(None, cout, SEG_3x3)], [(rb.conv2.weight, 0)], rb.conv2.bias.detach().float()
-            if rb.skip is not None:
-                c_ = 0
-                for cs_ in cs:
-                    segs.append((None, cs_, SEG_1x1))
-                    wsrc.append((rb.skip.weight, c_))
-                    c_ += cs_
-                bias2 = bias2 + rb.skip.bias.detach().float()
-            bias2 = bias2.contiguous()
-            w2, _ = self._pack(pack_resblock_weights(self._w2d(wsrc, segs)))
-            a.w1, a.w2, a.bias2, a.skip = ptr(w1), ptr(w2), ptr(bias2), int(rb.skip is not None)
-            a.B, a.H, a.W, a.N, a.out_bf16 = B, Hc, Wc, cout, ptr(y.hi)
-            keep.extend(par + [w1, w2, bias2, a])
-            K1, K2 = w1.shape[1], w2.shape[1]
-            launch(lib.ctdd_unet_resblock_small, C.byref(a), 0, label=f"{Hc}x{Wc} resblock C={cs} N={cout} K={K1}+{K2}",
-                   flops=2 * B * Hc * Wc * cout * (K1 + K2))
-            return y
-
-        def resblock(rb, srcs):
-            """srcs: list of 1-2 tensors forming the (virtual) channel concatenation."""
-            Hc, Wc = srcs[0].H, srcs[0].W
-            cs = [s.C for s in srcs]
-            cout = rb.conv1.weight.shape[0]
-            # a small level's whole block in one launch (csrc/unet_resblock_kernels.hip: one workgroup per sample, both activated
-            # tensors and h1 stay in LDS); cfg.model.resblock_fused = 0 keeps the four launches below
-            if (onepass_gn and tc is None and not self.precise and int(getattr(m, "resblock_fused", 1))
-                    and Hc * Wc <= self._plan_no_stats_hw and all(s_.stats is None for s_ in srcs)
-                    and resblock_small_covers(Hc, Wc, cs, cout, rb.norm1.num_groups, rb.norm2.num_groups)):
-                return resblock_fused(rb, srcs)
-            a1 = gn_apply(srcs, rb.norm1, True, rb.norm1.eps, Hc * Wc)
-            h = _Tensor(self, B, Hc, Wc, cout)
-            b1 = rb.conv1.bias.detach().float().contiguous()
-            conv([(a1, a1.C, SEG_3x3)], [(rb.conv1.weight, 0)], b1, cout, Hc, Wc,
-                 Hc, Wc, h, tb=(st.tproj.data_ptr() + 4 * toff[id(rb)], tb_stride), bias_params=[rb.conv1.bias])
-            drop = float(rb.dropout.p) if (tc is not None and tc.dropout) else 0.0
-            a2 = gn_apply([h], rb.norm2, True, rb.norm2.eps, Hc * Wc, drop_p=drop)
-            y = _Tensor(self, B, Hc, Wc, cout)
-            wsrc = [(rb.conv2.weight, 0)]
-            bias2, bias_params = rb.conv2.bias.detach().float(), [rb.conv2.bias]
-            segs = [(a2, cout, SEG_3x3)]
-            res = None
-            if rb.skip is not None:
-                c_ = 0
-                for s_ in srcs:                       # linear skip folded in as 1x1 K-segments on the raw input
-                    segs.append((s_, s_.C, SEG_1x1))
-                    wsrc.append((rb.skip.weight, c_))
-                    c_ += s_.C
-                bias_params.append(rb.skip.bias)
-                bias2 = tc.summed_bias(bias_params) if tc is not None else bias2 + rb.skip.bias.detach().float()
-            else:
-                res = srcs[0]
-            conv(segs, wsrc, bias2.contiguous(), cout, Hc, Wc, Hc, Wc, y, res=res, bias_params=bias_params)
-            return y
-
-        def attention(att, x):
-            T = x.H * x.W
-            an = gn_apply([x], att.norm, False, att.norm.eps, T)
-            Cx = x.C
-            qkv = torch.empty((B * T, 3 * Cx), dtype=torch.float32, device=dev)
-            keep.append(qkv)
-            if tc is not None:
-                tc.begin_attention(att, x, qkv)
-            conv([(an, Cx, SEG_1x1)], [(att.qkv.weight, 0)],
-                 att.qkv.bias.detach().float().contiguous(), 3 * Cx, x.H, x.W, x.H, x.W, None, out_f32_tensor=qkv,
-                 bias_params=[att.qkv.bias])
-            ao = _Tensor(self, B, x.H, x.W, Cx, stats=False)
-            aa = _AttnArgs()
-            aa.qkv, aa.B, aa.T, aa.C, aa.heads, aa.out_hi, aa.out_f32 = ptr(qkv), B, T, Cx, att.num_heads, ptr(ao.hi), ptr(ao.f32)
-            keep.extend([aa, ao])
-            launch(lib.ctdd_unet_attention, C.byref(aa))
-            if tc is not None:
-                tc.record_attention(att, qkv, ao, B, T, Cx)
-            y = _Tensor(self, B, x.H, x.W, Cx)
-            conv([(ao, Cx, SEG_1x1)], [(att.proj_out.weight, 0)],
-                 att.proj_out.bias.detach().float().contiguous(), Cx, x.H, x.W, x.H, x.W, y, res=x, bias_params=[att.proj_out.bias])
-            return y
-
-        feats = [cur]
-        for layer in list(net.down)[1:]:
-            if hasattr(layer, "resblocks"):
-                cur = resblock(layer.resblocks, [cur])
-                if layer.attention is not None:
-                    cur = attention(layer.attention, cur)
-            else:                                      # Downsample: stride-2 conv, pad right/bottom by one
-                cv = layer.downsample[0]
-                Ho, Wo = (cur.H + 1 - 3) // 2 + 1, (cur.W + 1 - 3) // 2 + 1
-                y = _Tensor(self, B, Ho, Wo, cur.C)
-                conv([(cur, cur.C, SEG_3x3_S2)], [(cv.weight, 0)],
-                     cv.bias.detach().float().contiguous(), cur.C, Ho, Wo, cur.H, cur.W, y, bias_params=[cv.bias])
-                cur = y
-            feats.append(cur)
-        for layer in net.mid:
-            cur = resblock(layer.resblocks, [cur])
-            if layer.attention is not None:
-                cur = attention(layer.attention, cur)
-        for layer in net.up:
-            if hasattr(layer, "resblocks"):
-                cur = resblock(layer.resblocks, [cur, feats.pop()])
-                if layer.attention is not None:
-                    cur = attention(layer.attention, cur)
-            else:                                      # Upsample: nearest x2 folded into the conv's addressing
-                cv = layer[1]
-                y = _Tensor(self, B, cur.H * 2, cur.W * 2, cur.C)
-                if self.precise and tc is None:
-                    conv([(cur, cur.C, SEG_3x3_UP)], [(cv.weight, 0)],
-                         cv.bias.detach().float().contiguous(), cur.C, cur.H * 2, cur.W * 2, cur.H, cur.W, y)
-                else:                                  # materialise the 2x grid (cheap), then a stride-1 convolution (training: both modes)
-                    up = _Tensor(self, B, cur.H * 2, cur.W * 2, cur.C, stats=False)
-                    if self.precise:
-                        launch(lib.ctdd_unet_upsample2x_f32, ptr(cur.f32), B, cur.H, cur.W, cur.C, ptr(up.f32))
-                    else:
-                        launch(lib.ctdd_unet_upsample2x, ptr(cur.hi), B, cur.H, cur.W, cur.C, ptr(up.hi))
-                    if tc is not None:
-                        tc.record_upsample(cur, up)
-                    conv([(up, cur.C, SEG_3x3)], [(cv.weight, 0)],
-                         cv.bias.detach().float().contiguous(), cur.C, up.H, up.W, up.H, up.W, y, bias_params=[cv.bias])
-                cur = y
-        ao = gn_apply([cur], net.out[0], True, net.out[0].eps, cur.H * cur.W)
-        oc = net.out[2]
-        n_out = oc.weight.shape[0]
-        D = Cin * H0 * W0
-        if logistic:
-            st.net_out = torch.empty((B * H0 * W0, n_out), dtype=torch.float32, device=dev)
-            conv([(ao, ao.C, SEG_3x3)], [(oc.weight, 0)],
-                 oc.bias.detach().float().contiguous(), n_out, H0, W0, H0, W0, None, out_f32_tensor=st.net_out, bias_params=[oc.bias])
-            ldt = torch.bfloat16 if (logits_bf16 and tc is None and not self.precise and S % 4 == 0) else torch.float32
-            st.logits = logits_out if logits_out is not None else torch.empty((B, D, S), dtype=ldt, device=dev)
-            assert st.logits.dtype == ldt
-            la = _LogisticArgs()
-            la.net, la.x0, la.B, la.C, la.HW, la.S, la.fix = ptr(st.net_out), ptr(st.x0), B, Cin, H0 * W0, S, int(bool(m.fix_logistic))
-            if ldt == torch.bfloat16:                  # (the sampler loops of the bf16 engine: the head writes what the bf16 step kernel reads)
-                la.out_bf16 = ptr(st.logits)
-            else:
-                la.out = ptr(st.logits)
-            la.fast = 0 if self.precise else 1
-            keep.append(la)
-            if tc is None:                             # (training: the head runs as differentiable device ops on net_out)
-                launch(lib.ctdd_unet_logistic_head, C.byref(la))
-        else:
-            ldt = torch.bfloat16 if logits_bf16 else torch.float32
-            st.logits = logits_out if logits_out is not None else torch.empty((B, D, S), dtype=ldt, device=dev)
-            assert st.logits.dtype == ldt
-            conv([(ao, ao.C, SEG_3x3)], [(oc.weight, 0)],
-                 oc.bias.detach().float().contiguous(), n_out, H0, W0, H0, W0, None, out_f32_tensor=st.logits,
-                 logits_C=Cin, bias_params=[oc.bias])
-
-        if tc is not None:                             # backward plan: built before the pools are laid out
-            st.launch, st.conv, st.stats_views, st.ptr, st.cur_lists, st.keep = launch, conv, stats_views, ptr, cur_lists, keep
-            st.zero_views_fwd = zero_views
-            tc.finish(st, self)
-        # ---- the per-(b, channel) statistics pool: one buffer, zeroed once per forward
-        st.stats = torch.zeros((max(self._stats_off, 1),), dtype=torch.float64, device=dev)
-        base = st.stats.data_ptr()
-        for item in stats_views:
-            if len(item) == 2:
-                item[0].stats = base + 8 * item[1]
-            else:
-                setattr(item[0], item[2], base + 8 * item[1])
-        nz = sum(n for _, n in zero_views)
-        st.zpool = torch.zeros((max(nz, 1),), dtype=torch.float32, device=dev)
-        zo = 0
-        for a_, n in zero_views:
-            a_.acc_buf = st.zpool.data_ptr() + 4 * zo
-            zo += n
-        st.plan, st.keep, st.graph = plan, keep, None
-        return st
+        m = self.cfg.model
+        onepass_gn = bool((not self.precise) and int(getattr(m, "gn_onepass", 1)) and (tc is None or int(getattr(m, "gn_onepass_train", 1)))
+                          and self._onepass_gn_covers(B, tc is not None))
+        return _PlanBuilder(self, B, tc, onepass_gn).build(x_dtype, logits_out, logits_bf16, uniform_t)
 
     # ------------------------------------------------------------------ execution
     def _run_plan(self, st):
@@ -691,20 +721,26 @@ class UNetEngine:
         self._set_time(st, times, time_row)
         self._run_plan(st)                    # eager warm-up (also sets the LDS attributes)
         torch.cuda.synchronize()
+        (st.graph,) = self._capture([lambda: self._run_plan(st)], "", "the plan runs as eager launches")
+        return st
+
+    def _capture(self, runs, what, then):
+        """One HIP graph per callable of `runs`, or None for each: cfg.model.engine_graph off, or stream capture refused (a warning)."""
         if getattr(self.cfg.model, "engine_graph", True):
             try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._run_plan(st)
-                st.graph = g
+                graphs = []
+                for run in runs:
+                    graphs.append(torch.cuda.CUDAGraph())
+                    with torch.cuda.graph(graphs[-1]):
+                        run()
+                return graphs
             except native.CtddError:          # a kernel refused its arguments: never hide that
                 raise
             except RuntimeError as e:         # stream capture refused (a HIP error, not a kernel-argument error): eager launches
                 import warnings
-                warnings.warn(f"[ctdd] UNetEngine: HIP-graph capture failed ({e}); the plan runs as eager launches", RuntimeWarning)
-                st.graph = None
+                warnings.warn(f"[ctdd] UNetEngine: HIP-graph capture{what} failed ({e}); {then}", RuntimeWarning)
                 torch.cuda.synchronize()
-        return st
+        return [None] * len(runs)
 
     @staticmethod
     def _set_time(st, times, time_row):
@@ -721,9 +757,7 @@ class UNetEngine:
         UNetEngine._set_time(st, times, time_row)
         if st.graph is not None:
             st.graph.replay()
-        else:
-            for step in st.plan:              # (stats / split-K pools are zeroed inside _run_plan for the eager path)
-                pass
+        else:                                 # (stats / split-K pools are zeroed inside _run_plan for the eager path)
             raise native.CtddError("eager replay goes through _run_plan")
 
     def time_table(self, times):
@@ -731,18 +765,8 @@ class UNetEngine:
         (`ctdd_unet_time`, the per-sample path with the T values as its rows).  A sampler computes it for its whole grid when it
         starts and hands row i to step i (`time_row=`): the plans then run without the two time launches at their head."""
         lib = _lib()
-        net, dev = self.net, self.dev
-        ver = self._weights_version()
-        tw_ = self.__dict__.get("_time_w")
-        if tw_ is None or tw_[0] != ver:
-            ch = self.cfg.model.ch
-            resblocks = [mod.resblocks for mod in list(net.down) + list(net.mid) + list(net.up) if hasattr(mod, "resblocks")]
-            pw = torch.cat([rb.time[1].weight.detach().float() for rb in resblocks], 0).t().contiguous()   # [tdim][Ntot]
-            pb = torch.cat([rb.time[1].bias.detach().float() for rb in resblocks], 0).contiguous()
-            tw = [net.time[1].weight.t(), net.time[1].bias, net.time[3].weight.t(), net.time[3].bias]
-            tw = [w.detach().float().contiguous() for w in tw]
-            tw_ = self._time_w = (ver, ch, pw, pb, tw)
-        _, ch, pw, pb, tw = tw_
+        dev, ch = self.dev, self.net.channel
+        _, pw, pb, tw = self._time_weights()
         t = times.to(dev).float().contiguous().reshape(-1)
         T, tdim, Ntot = t.numel(), ch * 4, pw.shape[1]
         hid = torch.empty((T, tdim), dtype=torch.float32, device=dev)
@@ -751,9 +775,7 @@ class UNetEngine:
         ta = _TimeArgs()
         ta.t, ta.B, ta.ch, ta.tdim = t.data_ptr(), T, ch, tdim
         ta.w1, ta.b1, ta.w2, ta.b2, ta.hid, ta.act = tw[0].data_ptr(), tw[1].data_ptr(), tw[2].data_ptr(), tw[3].data_ptr(), hid.data_ptr(), act.data_ptr()
-        rc = lib.ctdd_unet_time(C.byref(ta), pw.data_ptr(), pb.data_ptr(), Ntot, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise native.CtddError(f"ctdd_unet_time failed ({rc}): {lib.ctdd_last_error().decode()}")
+        bound_launch(lib.ctdd_unet_time, C.byref(ta), pw.data_ptr(), pb.data_ptr(), Ntot, out.data_ptr())()
         return out
 
     def __call__(self, x, times, logits_bf16=False, uniform_time=False, slot=None, time_row=None):
@@ -876,22 +898,8 @@ class UNetEngine:
             self._run_plan(st)
             self._run_bwd_plan(st)                  # (zero seed: only exercises the launches)
             torch.cuda.synchronize()
-            if getattr(self.cfg.model, "engine_graph", True):
-                try:
-                    gf = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gf):
-                        self._run_plan(st)
-                    gb = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gb):
-                        self._run_bwd_plan(st)
-                    st.fgraph, st.bgraph = gf, gb
-                except native.CtddError:
-                    raise
-                except RuntimeError as e:
-                    import warnings
-                    warnings.warn(f"[ctdd] UNetEngine: HIP-graph capture of the training plans failed ({e}); eager launches", RuntimeWarning)
-                    st.fgraph = st.bgraph = None
-                    torch.cuda.synchronize()
+            st.fgraph, st.bgraph = self._capture([lambda: self._run_plan(st), lambda: self._run_bwd_plan(st)], " of the training plans",
+                                                 "eager launches")
 
     def _train_run_forward(self, st, x, times, tproj):
         st.gen = self.__dict__["_train_gen"] = self.__dict__.get("_train_gen", 0) + 1

@@ -21,6 +21,7 @@ import ctypes as C
 import torch
 
 from . import native
+from .plan_launch import ptr
 from .unet_engine import SEG_1x1, SEG_3x3, SEG_3x3_S2, _lib
 
 SEG_3x3_S2T = 4
@@ -142,26 +143,22 @@ class TrainCtx:
         self.bias_jobs.append((buf, list(params)))
         return buf
 
-    def record_conv(self, conv, segs, wsrc, bias_params, N, Hout, Wout, Hin, Win, out, tb, res, logits_C, out_f32_tensor):
+    def record_conv(self, segs, wsrc, bias_params, N, Hout, Wout, Hin, Win, out, tb, res, logits_C, out_f32_tensor):
         fwd, gw, per_seg = self._last_pack
         self.records.append(("conv", dict(segs=list(segs), per_seg=per_seg, gw=gw, bias_params=bias_params or [], N=N, Hout=Hout, Wout=Wout,
                                           Hin=Hin, Win=Win, out=out, tb=tb, res=res, logits_C=logits_C, out_f32=out_f32_tensor)))
 
-    def record_gn(self, srcs, norm, swish, eps, HW, out, drop_p, launch, stats_views):
+    def record_gn(self, pb, srcs, norm, swish, eps, HW, out, drop_p):
         layer = self.layer_id
         self.layer_id += 1
         if drop_p > 0.0:                                                  # forward side of the dropout: in place on the activated tensor
             l = lib()
-            launch(l.ctdd_unet_dropout, None if out.f32 is None else out.f32.data_ptr(), None if out.hi is None else out.hi.data_ptr(),
-                   out.B * out.H * out.W * out.C, float(drop_p), self.rng.data_ptr(), layer, label="dropout")
-        self.records.append(("gn", dict(srcs=list(srcs), norm=norm, swish=swish, eps=eps, HW=HW, out=out, drop_p=drop_p, layer=layer,
-                                        stats_views=stats_views)))
+            pb.launch(l.ctdd_unet_dropout, ptr(out.f32), ptr(out.hi),
+                      out.B * out.H * out.W * out.C, float(drop_p), self.rng.data_ptr(), layer, label="dropout")
+        self.records.append(("gn", dict(srcs=list(srcs), norm=norm, swish=swish, eps=eps, HW=HW, out=out, drop_p=drop_p, layer=layer)))
 
     def record_first(self, conv0, fa, cur):
         self.records.append(("first", dict(conv=conv0, fa=fa, out=cur)))
-
-    def begin_attention(self, att, x, qkv):
-        self._attn = dict(att=att, x=x, qkv=qkv)
 
     def record_attention(self, att, qkv, ao, B, T, Cx):
         self.records.append(("attn", dict(att=att, qkv=qkv, ao=ao, T=T, Cx=Cx)))
@@ -236,7 +233,6 @@ class TrainCtx:
         """One ctdd_unet_wgrad launch for every queued entry.  M-split per entry: every workgroup gets about the same number
         of (16-pixel step x tap) units, ~`wgrad_wgs_per_cu` workgroups per CU over the whole table -- few enough that the
         float atomics the M-split workgroups meet in stay far below the matrix time."""
-        eng, l = self.eng, lib()
         self.wgrad_tabs = []
         for nine in (True, False):                     # nine-tap (stride-1 3x3) entries and one-tap entries: one launch each
             ents = [a for a in self.wgrad_entries if (a.kind == WG_3x3) == nine]
@@ -265,14 +261,15 @@ class TrainCtx:
         launch(l.ctdd_unet_wgrad, dev_tab.data_ptr(), C.addressof(tab), len(ents), int(eng.precise),
                label=f"wgrad table: {len(ents)} entries ({'3x3' if ents[0].kind == WG_3x3 else '1x1 / stride-2 taps / bias'}), {nwg} workgroups", flops=flops)
 
-    def finish(self, st, eng):
-        """Lay out the backward plan (called by UNetEngine._build before its pools are resolved)."""
+    def finish(self, pb):
+        """Lay out the backward plan and the forward prologue through the forward's builder `pb` (called by _PlanBuilder.build
+        before its pools are resolved)."""
         l = lib()
         B, dev = self.B, self.dev
-        self._grads, self.keep = {}, st.keep
+        eng, st = pb.eng, pb.st
+        self._grads, self.keep = {}, pb.keep
         net = eng.net
-        launch, conv, ptr = st.launch, st.conv, st.ptr
-        fwd_plan = st.cur_lists["plan"]
+        launch, conv = pb.launch, pb.conv
         # ---- gradient arena: one flat fp32 buffer, a view per engine-owned parameter (torch layout)
         time_params = {id(p) for p in net.time.parameters()}
         for rb in self.resblocks:
@@ -311,175 +308,174 @@ class TrainCtx:
         # ---- backward plan
         bwd, bzero = [], []
         self.wgrad_entries, sum_jobs = [], []
-        st.cur_lists["plan"], st.cur_lists["zero"] = bwd, bzero
-        # seed: gradient of the network output (logits (B, D, S) fp32 or net_out [B*HW][2C] fp32) -> the mode's operand type
-        last = self.records[-1][1]
-        assert self.records[-1][0] == "conv" and last["out_f32"] is not None
-        Nout, HW0 = last["N"], last["Hout"] * last["Wout"]
-        ld0 = -(-Nout // 16) * 16
-        self.seed_in = torch.zeros((B * HW0, Nout), dtype=torch.float32, device=dev)       # copy target of autograd's grad_output
-        seed = _Grad(eng, B * HW0, Nout, dev, ld=ld0)
-        seed.has = True
-        launch(l.ctdd_unet_cast_rows, self.seed_in.data_ptr(), B * HW0, Nout, Nout, ld0, ptr(seed.hi), ptr(seed.f32), label="seed cast")
-        out_grads = {id(last["out_f32"]): seed}
-        self.keep.append(seed)
+        with pb.emitting_to(bwd, bzero):
+            # seed: gradient of the network output (logits (B, D, S) fp32 or net_out [B*HW][2C] fp32) -> the mode's operand type
+            last = self.records[-1][1]
+            assert self.records[-1][0] == "conv" and last["out_f32"] is not None
+            Nout, HW0 = last["N"], last["Hout"] * last["Wout"]
+            ld0 = -(-Nout // 16) * 16
+            self.seed_in = torch.zeros((B * HW0, Nout), dtype=torch.float32, device=dev)       # copy target of autograd's grad_output
+            seed = _Grad(eng, B * HW0, Nout, dev, ld=ld0)
+            seed.has = True
+            launch(l.ctdd_unet_cast_rows, self.seed_in.data_ptr(), B * HW0, Nout, Nout, ld0, ptr(seed.hi), ptr(seed.f32), label="seed cast")
+            out_grads = {id(last["out_f32"]): seed}
+            self.keep.append(seed)
 
-        def as_seg(g_, Cn):
-            t = type("GradSeg", (), {})()
-            t.hi, t.f32, t.C, t.stats = g_.hi, g_.f32, Cn, None
-            return t
+            def as_seg(g_, Cn):
+                t = type("GradSeg", (), {})()
+                t.hi, t.f32, t.C, t.stats = g_.hi, g_.f32, Cn, None
+                return t
 
-        tb_conv_of = {id(r["out"]): r for kind, r in self.records if kind == "conv" and r["tb"] is not None and r["out"] is not None}
-        for kind, r in reversed(self.records):
-            if kind == "conv":
-                gy = self.g(r["out"]) if r["out"] is not None else out_grads[id(r["out_f32"])]
-                N, Ho, Wo, Hi, Wi = r["N"], r["Hout"], r["Wout"], r["Hin"], r["Win"]
-                ldy = gy.ld
-                if any(e["ldd"] != ldy for e in r["per_seg"]):
-                    raise native.CtddError(f"training plan: output gradient rows of {ldy} channels vs weights packed for {r['per_seg'][0]['ldd']} "
-                                           "(channel counts must be multiples of 16)")
-                gyT = as_seg(gy, ldy)
-                # bias gradients (+ the per-sample time-projection gradient): per-(sample, channel) sums of the output gradient
-                bps = r["bias_params"]
-                bias_scr = None
-                if (bps or r["tb"] is not None) and not r.get("sums_done"):
-                    out_bn, stride = None, 0
-                    if r["tb"] is not None:
-                        out_bn, stride = dtproj_ptr + (r["tb"][0] - self.tproj.data_ptr()), r["tb"][1]
-                    if out_bn is not None:            # (a time-projection gradient the GroupNorm backward could not give)
-                        launch(l.ctdd_unet_colsum, ptr(gy.f32), ptr(gy.hi), B, Ho * Wo, -(-N // 8) * 8, ldy, out_bn, stride, None,
-                               label="time-projection gradient")
-                    if bps:
-                        # sum over all pixels of gy: rides on the staging of the convolution's first weight-gradient entry
-                        # (ctdd_wgrad_args.gb), copied to the parameters' gradients by the sums launch
-                        bias_scr = zalloc(N)
-                        for bp in bps:
-                            sum_jobs.append((bias_scr, 1, 0, 1, N, gptr(bp), 0))
-                # identity skip / residual
-                if r["res"] is not None:
-                    gr = self.g(r["res"])
-                    launch(l.ctdd_unet_accumulate, ptr(gy.f32), ptr(gy.hi), ptr(gr.f32), ptr(gr.hi), gr.C * B * Ho * Wo, int(gr.has),
-                           label="residual gradient")
-                    gr.has = True
-                for (src, cs, skind), e in zip(r["segs"], r["per_seg"]):
-                    one = skind == SEG_1x1
-                    self._wgrad_entry(src, gy, N, ldy, cs, e, skind, B, Ho, Wo, Ho if one else Hi, Wo if one else Wi, gb=bias_scr)
+            tb_conv_of = {id(r["out"]): r for kind, r in self.records if kind == "conv" and r["tb"] is not None and r["out"] is not None}
+            for kind, r in reversed(self.records):
+                if kind == "conv":
+                    gy = self.g(r["out"]) if r["out"] is not None else out_grads[id(r["out_f32"])]
+                    N, Ho, Wo, Hi, Wi = r["N"], r["Hout"], r["Wout"], r["Hin"], r["Win"]
+                    ldy = gy.ld
+                    if any(e["ldd"] != ldy for e in r["per_seg"]):
+                        raise native.CtddError(f"training plan: output gradient rows of {ldy} channels vs weights packed for {r['per_seg'][0]['ldd']} "
+                                               "(channel counts must be multiples of 16)")
+                    gyT = as_seg(gy, ldy)
+                    # bias gradients (+ the per-sample time-projection gradient): per-(sample, channel) sums of the output gradient
+                    bps = r["bias_params"]
                     bias_scr = None
-                    # data gradient of the segment: a convolution of gy with the flipped / transposed weights
-                    gs = self.g(src)
-                    packed = (None, e["dgrad"]) if eng.precise else (e["dgrad"], None)
-                    gsT = as_seg(gs, cs)
-                    resT = gsT if gs.has else None
-                    if skind == SEG_3x3_S2:
-                        conv([(gyT, ldy, SEG_3x3_S2T)], None, None, cs, Hi, Wi, Ho, Wo, gsT, res=resT, packed=packed, back=False)
-                    else:
-                        conv([(gyT, ldy, skind)], None, None, cs, Ho, Wo, Ho, Wo, gsT, res=resT, packed=packed, back=False)
-                    gs.has = True
-            elif kind == "gn":
-                srcs, norm, out = r["srcs"], r["norm"], r["out"]
-                ga = self.g(out)
-                a = _GnBwdArgs()
-                s1 = srcs[0]
-                a.s1_f32, a.s1_bf16, a.C1 = ptr(s1.f32), ptr(s1.hi), s1.C
-                r["stats_views"].append((a, s1.stats, "st1"))
-                g1 = self.g(s1)
-                a.d1_f32, a.d1_bf16, a.acc1 = ptr(g1.f32), ptr(g1.hi), int(g1.has)
-                g1.has = True
-                Ct = s1.C
-                if len(srcs) == 2:
-                    s2 = srcs[1]
-                    a.s2_f32, a.s2_bf16, a.C2 = ptr(s2.f32), ptr(s2.hi), s2.C
-                    r["stats_views"].append((a, s2.stats, "st2"))
-                    g2 = self.g(s2)
-                    a.d2_f32, a.d2_bf16, a.acc2 = ptr(g2.f32), ptr(g2.hi), int(g2.has)
-                    g2.has = True
-                    Ct += s2.C
-                a.gamma, a.beta = norm.weight.data_ptr(), norm.bias.data_ptr()
-                a.B, a.HW, a.G, a.eps, a.swish = B, r["HW"], norm.num_groups, r["eps"], int(r["swish"])
-                a.da_f32, a.da_bf16 = ptr(ga.f32), ptr(ga.hi)
-                a.drop_p, a.rng, a.layer = float(r["drop_p"]), self.rng.data_ptr(), r["layer"]
-                sums = zalloc(B * Ct * 2)
-                a.sums = sums
-                cr = tb_conv_of.get(id(s1)) if len(srcs) == 1 else None
-                if cr is not None and len(cr["bias_params"]) == 1:
-                    # the GroupNorm input is conv1's output + bias + time projection and has no other consumer: sum_p dX per
-                    # (sample, channel) IS the time-projection gradient, its sum over samples the bias gradient (closed form
-                    # from the sums: no pass over the gradient tensor)
-                    a.dsum_bn, a.dsum_stride = dtproj_ptr + (cr["tb"][0] - self.tproj.data_ptr()), cr["tb"][1]
-                    a.dsum_n = gptr(cr["bias_params"][0])
-                    cr["sums_done"] = True
-                self.keep.append(a)
-                launch(l.ctdd_unet_gn_bwd, C.byref(a), label=f"gn bwd C={Ct}")
-                sum_jobs.append((sums, B, 2 * Ct, 2, Ct, gptr(norm.bias), 0))
-                sum_jobs.append((sums + 4, B, 2 * Ct, 2, Ct, gptr(norm.weight), 0))
-            elif kind == "attn":
-                gao = self.g(r["ao"])
-                T, Cx = r["T"], r["Cx"]
-                dq = _Grad(eng, B * T, 3 * Cx, dev)
-                dq.has = True
-                a = _AttnBwdArgs()
-                a.qkv, a.d_out_f32, a.d_out_bf16 = r["qkv"].data_ptr(), ptr(gao.f32), ptr(gao.hi)
-                a.B, a.T, a.C, a.heads = B, T, Cx, r["att"].num_heads
-                a.d_qkv, a.d_qkv_bf16 = ptr(dq.f32), ptr(dq.hi)
-                self.keep.extend([a, dq])
-                launch(l.ctdd_unet_attention_bwd, C.byref(a), label="attention bwd")
-                out_grads[id(r["qkv"])] = dq
-            elif kind == "up":
-                cur, up = r["cur"], r["up"]
-                gu, gc = self.g(up), self.g(cur)
-                launch(l.ctdd_unet_downsum2x, ptr(gu.f32), ptr(gu.hi), B, cur.H, cur.W, cur.C, ptr(gc.f32), ptr(gc.hi), int(gc.has),
-                       label="upsample bwd")
-                gc.has = True
-            elif kind == "first":
-                c0, fa, out = r["conv"], r["fa"], r["out"]
-                go = self.g(out)
-                a = _FirstWgradArgs()
-                a.x64, a.x32, a.lo, a.hi = fa.x64, fa.x32, fa.lo, fa.hi
-                a.dy_f32, a.dy_bf16 = ptr(go.f32), ptr(go.hi)
-                a.B, a.Cin, a.H, a.W, a.Cout = fa.B, fa.Cin, fa.H, fa.W, fa.Cout
-                a.gw, a.gbias = gptr(c0.weight), gptr(c0.bias)
-                scratch = torch.zeros(int(l.ctdd_unet_first_conv_wgrad_scratch(fa.B, fa.H, fa.Cin, fa.Cout)), dtype=torch.float32, device=dev)
-                a.partial = scratch.data_ptr()
-                self.keep.extend([a, scratch])
-                launch(l.ctdd_unet_first_conv_wgrad, C.byref(a), label="first conv wgrad")
+                    if (bps or r["tb"] is not None) and not r.get("sums_done"):
+                        out_bn, stride = None, 0
+                        if r["tb"] is not None:
+                            out_bn, stride = dtproj_ptr + (r["tb"][0] - self.tproj.data_ptr()), r["tb"][1]
+                        if out_bn is not None:            # (a time-projection gradient the GroupNorm backward could not give)
+                            launch(l.ctdd_unet_colsum, ptr(gy.f32), ptr(gy.hi), B, Ho * Wo, -(-N // 8) * 8, ldy, out_bn, stride, None,
+                                   label="time-projection gradient")
+                        if bps:
+                            # sum over all pixels of gy: rides on the staging of the convolution's first weight-gradient entry
+                            # (ctdd_wgrad_args.gb), copied to the parameters' gradients by the sums launch
+                            bias_scr = zalloc(N)
+                            for bp in bps:
+                                sum_jobs.append((bias_scr, 1, 0, 1, N, gptr(bp), 0))
+                    # identity skip / residual
+                    if r["res"] is not None:
+                        gr = self.g(r["res"])
+                        launch(l.ctdd_unet_accumulate, ptr(gy.f32), ptr(gy.hi), ptr(gr.f32), ptr(gr.hi), gr.C * B * Ho * Wo, int(gr.has),
+                               label="residual gradient")
+                        gr.has = True
+                    for (src, cs, skind), e in zip(r["segs"], r["per_seg"]):
+                        one = skind == SEG_1x1
+                        self._wgrad_entry(src, gy, N, ldy, cs, e, skind, B, Ho, Wo, Ho if one else Hi, Wo if one else Wi, gb=bias_scr)
+                        bias_scr = None
+                        # data gradient of the segment: a convolution of gy with the flipped / transposed weights
+                        gs = self.g(src)
+                        packed = (None, e["dgrad"]) if eng.precise else (e["dgrad"], None)
+                        gsT = as_seg(gs, cs)
+                        resT = gsT if gs.has else None
+                        if skind == SEG_3x3_S2:
+                            conv([(gyT, ldy, SEG_3x3_S2T)], None, None, cs, Hi, Wi, Ho, Wo, gsT, res=resT, packed=packed, back=False)
+                        else:
+                            conv([(gyT, ldy, skind)], None, None, cs, Ho, Wo, Ho, Wo, gsT, res=resT, packed=packed, back=False)
+                        gs.has = True
+                elif kind == "gn":
+                    srcs, norm, out = r["srcs"], r["norm"], r["out"]
+                    ga = self.g(out)
+                    a = _GnBwdArgs()
+                    s1 = srcs[0]
+                    a.s1_f32, a.s1_bf16, a.C1 = ptr(s1.f32), ptr(s1.hi), s1.C
+                    pb.stats_views.append((a, s1.stats, "st1"))
+                    g1 = self.g(s1)
+                    a.d1_f32, a.d1_bf16, a.acc1 = ptr(g1.f32), ptr(g1.hi), int(g1.has)
+                    g1.has = True
+                    Ct = s1.C
+                    if len(srcs) == 2:
+                        s2 = srcs[1]
+                        a.s2_f32, a.s2_bf16, a.C2 = ptr(s2.f32), ptr(s2.hi), s2.C
+                        pb.stats_views.append((a, s2.stats, "st2"))
+                        g2 = self.g(s2)
+                        a.d2_f32, a.d2_bf16, a.acc2 = ptr(g2.f32), ptr(g2.hi), int(g2.has)
+                        g2.has = True
+                        Ct += s2.C
+                    a.gamma, a.beta = norm.weight.data_ptr(), norm.bias.data_ptr()
+                    a.B, a.HW, a.G, a.eps, a.swish = B, r["HW"], norm.num_groups, r["eps"], int(r["swish"])
+                    a.da_f32, a.da_bf16 = ptr(ga.f32), ptr(ga.hi)
+                    a.drop_p, a.rng, a.layer = float(r["drop_p"]), self.rng.data_ptr(), r["layer"]
+                    sums = zalloc(B * Ct * 2)
+                    a.sums = sums
+                    cr = tb_conv_of.get(id(s1)) if len(srcs) == 1 else None
+                    if cr is not None and len(cr["bias_params"]) == 1:
+                        # the GroupNorm input is conv1's output + bias + time projection and has no other consumer: sum_p dX per
+                        # (sample, channel) IS the time-projection gradient, its sum over samples the bias gradient (closed form
+                        # from the sums: no pass over the gradient tensor)
+                        a.dsum_bn, a.dsum_stride = dtproj_ptr + (cr["tb"][0] - self.tproj.data_ptr()), cr["tb"][1]
+                        a.dsum_n = gptr(cr["bias_params"][0])
+                        cr["sums_done"] = True
+                    self.keep.append(a)
+                    launch(l.ctdd_unet_gn_bwd, C.byref(a), label=f"gn bwd C={Ct}")
+                    sum_jobs.append((sums, B, 2 * Ct, 2, Ct, gptr(norm.bias), 0))
+                    sum_jobs.append((sums + 4, B, 2 * Ct, 2, Ct, gptr(norm.weight), 0))
+                elif kind == "attn":
+                    gao = self.g(r["ao"])
+                    T, Cx = r["T"], r["Cx"]
+                    dq = _Grad(eng, B * T, 3 * Cx, dev)
+                    dq.has = True
+                    a = _AttnBwdArgs()
+                    a.qkv, a.d_out_f32, a.d_out_bf16 = r["qkv"].data_ptr(), ptr(gao.f32), ptr(gao.hi)
+                    a.B, a.T, a.C, a.heads = B, T, Cx, r["att"].num_heads
+                    a.d_qkv, a.d_qkv_bf16 = ptr(dq.f32), ptr(dq.hi)
+                    self.keep.extend([a, dq])
+                    launch(l.ctdd_unet_attention_bwd, C.byref(a), label="attention bwd")
+                    out_grads[id(r["qkv"])] = dq
+                elif kind == "up":
+                    cur, up = r["cur"], r["up"]
+                    gu, gc = self.g(up), self.g(cur)
+                    launch(l.ctdd_unet_downsum2x, ptr(gu.f32), ptr(gu.hi), B, cur.H, cur.W, cur.C, ptr(gc.f32), ptr(gc.hi), int(gc.has),
+                           label="upsample bwd")
+                    gc.has = True
+                elif kind == "first":
+                    c0, fa, out = r["conv"], r["fa"], r["out"]
+                    go = self.g(out)
+                    a = _FirstWgradArgs()
+                    a.x64, a.x32, a.lo, a.hi = fa.x64, fa.x32, fa.lo, fa.hi
+                    a.dy_f32, a.dy_bf16 = ptr(go.f32), ptr(go.hi)
+                    a.B, a.Cin, a.H, a.W, a.Cout = fa.B, fa.Cin, fa.H, fa.W, fa.Cout
+                    a.gw, a.gbias = gptr(c0.weight), gptr(c0.bias)
+                    scratch = torch.zeros(int(l.ctdd_unet_first_conv_wgrad_scratch(fa.B, fa.H, fa.Cin, fa.Cout)), dtype=torch.float32, device=dev)
+                    a.partial = scratch.data_ptr()
+                    self.keep.extend([a, scratch])
+                    launch(l.ctdd_unet_first_conv_wgrad, C.byref(a), label="first conv wgrad")
 
-        # ---- split-K partial-sum buffers of the backward convolutions: their own pool, zeroed with the arena
-        nz = sum(n for _, n in bzero)
-        self.bzpool = torch.zeros(max(nz, 1), dtype=torch.float32, device=dev)
-        zo = 0
-        for a_, n in bzero:
-            a_.acc_buf = self.bzpool.data_ptr() + 4 * zo
-            zo += n
-        # ---- pack table: one entry per (convolution, K-segment)
-        tab = (_PackEntry * len(self.entries))()
-        first = 0
-        for i, e in enumerate(self.entries):
-            t = tab[i]
-            t.w, t.fwd, t.dgrad, t.gw, t.grad = e["w"].data_ptr(), e["fwd"].data_ptr(), e["dgrad"].data_ptr(), e["gw_ptr"], gptr(e["w"])
-            t.N, t.Cin_tot, t.c_off, t.C, t.ntap, t.Ktot, t.koff, t.flip, t.ldd = (e["N"], e["Cin_tot"], e["c_off"], e["C"], e["ntap"],
-                                                                                      e["Ktot"], e["koff"], e["flip"], e["ldd"])
-            t.first = first
-            first += e["N"] * e["C"] * e["ntap"]
-        self.pack_total = first
-        self.pack_tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
-        self._wgrad_table_launch(launch)               # every convolution's weight (and bias) gradient: one launch
-        self.bwd_sum_tab, nj = self._sum_jobs_table(sum_jobs, dev)
-        launch(l.ctdd_unet_sum_jobs, self.bwd_sum_tab.data_ptr(), nj, label=f"small sums: {len(sum_jobs)} reductions")
-        launch(l.ctdd_unet_unpack_grads, self.pack_tab.data_ptr(), len(self.entries), self.pack_total, label="unpack gradients")
+            # ---- split-K partial-sum buffers of the backward convolutions: their own pool, zeroed with the arena
+            nz = sum(n for _, n in bzero)
+            self.bzpool = torch.zeros(max(nz, 1), dtype=torch.float32, device=dev)
+            zo = 0
+            for a_, n in bzero:
+                a_.acc_buf = self.bzpool.data_ptr() + 4 * zo
+                zo += n
+            # ---- pack table: one entry per (convolution, K-segment)
+            tab = (_PackEntry * len(self.entries))()
+            first = 0
+            for i, e in enumerate(self.entries):
+                t = tab[i]
+                t.w, t.fwd, t.dgrad, t.gw, t.grad = e["w"].data_ptr(), e["fwd"].data_ptr(), e["dgrad"].data_ptr(), e["gw_ptr"], gptr(e["w"])
+                t.N, t.Cin_tot, t.c_off, t.C, t.ntap, t.Ktot, t.koff, t.flip, t.ldd = (e["N"], e["Cin_tot"], e["c_off"], e["C"], e["ntap"],
+                                                                                          e["Ktot"], e["koff"], e["flip"], e["ldd"])
+                t.first = first
+                first += e["N"] * e["C"] * e["ntap"]
+            self.pack_total = first
+            self.pack_tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+            self._wgrad_table_launch(launch)               # every convolution's weight (and bias) gradient: one launch
+            self.bwd_sum_tab, nj = self._sum_jobs_table(sum_jobs, dev)
+            launch(l.ctdd_unet_sum_jobs, self.bwd_sum_tab.data_ptr(), nj, label=f"small sums: {len(sum_jobs)} reductions")
+            launch(l.ctdd_unet_unpack_grads, self.pack_tab.data_ptr(), len(self.entries), self.pack_total, label="unpack gradients")
         # ---- forward prologue: ONE pack launch for every convolution weight (+ dropout step bump), folded biases
         pro = []
-        st.cur_lists["plan"] = pro
-        launch(l.ctdd_unet_pack_weights, self.pack_tab.data_ptr(), len(self.entries), self.pack_total, int(eng.precise),
-               self.rng.data_ptr() if self.dropout else None, label="pack weights")
-        if self.bias_jobs:                             # folded biases b = sum of parameters: the "batch" walks the parameters
-            jobs = []
-            for buf, ps in self.bias_jobs:
-                assert len(ps) == 2 and (ps[1].data_ptr() - ps[0].data_ptr()) % 4 == 0
-                jobs.append((ps[0].data_ptr(), 2, (ps[1].data_ptr() - ps[0].data_ptr()) // 4, 1, ps[0].numel(), buf.data_ptr(), 0))
-            self.fwd_sum_tab, nj = self._sum_jobs_table(jobs, dev)
-            launch(l.ctdd_unet_sum_jobs, self.fwd_sum_tab.data_ptr(), nj, label="folded biases")
-        fwd_plan[:0] = pro
-        st.cur_lists["plan"], st.cur_lists["zero"] = fwd_plan, st.zero_views_fwd
+        with pb.emitting_to(pro, None):            # (no convolutions here: nothing that could take a split-K buffer)
+            launch(l.ctdd_unet_pack_weights, self.pack_tab.data_ptr(), len(self.entries), self.pack_total, int(eng.precise),
+                   self.rng.data_ptr() if self.dropout else None, label="pack weights")
+            if self.bias_jobs:                             # folded biases b = sum of parameters: the "batch" walks the parameters
+                jobs = []
+                for buf, ps in self.bias_jobs:
+                    assert len(ps) == 2 and (ps[1].data_ptr() - ps[0].data_ptr()) % 4 == 0
+                    jobs.append((ps[0].data_ptr(), 2, (ps[1].data_ptr() - ps[0].data_ptr()) // 4, 1, ps[0].numel(), buf.data_ptr(), 0))
+                self.fwd_sum_tab, nj = self._sum_jobs_table(jobs, dev)
+                launch(l.ctdd_unet_sum_jobs, self.fwd_sum_tab.data_ptr(), nj, label="folded biases")
+        pb.plan[:0] = pro
         st.bwd_plan, st.tc = bwd, self
 
 

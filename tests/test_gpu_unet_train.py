@@ -302,6 +302,43 @@ def test_parameter_gradients_tiny_golden_net(golden, tag, precision, tol):
     _compare(ga, gr, tol, (tag, precision))
 
 
+@pytest.mark.parametrize("gn_threads", [8, 4])
+def test_training_plan_without_onepass_groupnorm_cover(golden, gn_threads):
+    """cfg.model.gn_threads small enough that ctdd_unet_gn_onepass has no slab for a level of the golden tiny U-Net: the plan is
+    then built with statistics epilogues + ctdd_unet_gn_apply, from ONE training context that no abandoned attempt has filled --
+    no one-pass launch in either plan, as many records as the same net built with gn_onepass = 0, and every parameter gradient
+    within the bf16 bar of autograd.
+    (8 threads still cover every level of this net: a slab of 8 channels, 64 pixels in 8 passes of 8, under the kernel's 12; its
+    plans keep the one-pass launches and must give the same gradients.  4 threads need 16 passes at 8x8 and have no slab.)"""
+    from ctdd import unet_engine as ue, unet_train as ut
+    cfg, model, x, t = _tiny_model(golden, "logits")
+    cfg.model.engine_precision = "bf16"
+    cfg.model.gn_threads = gn_threads
+    B = x.shape[0]
+    uncovered = any(ue._onepass_slab(B, 64, c, min(c // 4, 32), gn_threads) == 0 for c in (16, 32))     # the 8x8 level's tensors
+    assert uncovered == (gn_threads == 4)
+    g = torch.Generator(device="cuda").manual_seed(4)
+    weight = torch.randn((B, cfg.model.concat_dim, cfg.data.S), generator=g, device="cuda")
+    with torch.no_grad():                       # (as above: every gradient live)
+        gg = torch.Generator(device="cuda").manual_seed(5)
+        for n_, p in model.named_parameters():
+            if p.dim() > 1 and p.abs().max().item() < 1e-6:
+                p.copy_(torch.randn(p.shape, generator=gg, device="cuda") / (p[0].numel() ** 0.5))
+    lr, gr = _grads(model, cfg, x, t, weight, "torch")
+    la, ga = _grads(model, cfg, x, t, weight, "hip")
+    eng = model._engine
+    (pool,) = eng._train_plans.values()
+    (st,) = pool
+    fns = [step.label[0] for step in list(st.plan) + list(st.bwd_plan)]
+    assert ("ctdd_unet_gn_onepass" in fns) == (not uncovered)
+    assert "ctdd_unet_gn_bwd" in fns and "ctdd_unet_wgrad" in fns
+    _compare(ga, gr, 6e-2, ("logits", "bf16", gn_threads))
+    cfg.model.gn_onepass = 0
+    tc0 = ut.TrainCtx(eng, B, False)
+    eng._build(B, torch.int64, tc=tc0)
+    assert len(st.tc.records) == len(tc0.records)
+
+
 @pytest.mark.parametrize("precision,tol", [("fp32", 1e-4), ("bf16", 6e-2)])
 def test_parameter_gradients_mnist_size(precision, tol):
     """config_tauUnet_mnist (14.0 M parameters, 28x28, ch 96 / 192), batch 4: all parameter gradients vs autograd."""
