@@ -187,6 +187,8 @@ struct ElboArgs {
   const float* logits; const int32_t* x0; const int32_t* xt;     // xt = x~ (= reg_x)
   const float* q; const float* qT; const float* R;               // (B,S,S) each
   int B, D, S; float eps, elbo_scale, nll_scale;
+  int Dl, doff;       // `logits` / `grad` are (B,Dl,S) and the objective's D rows are rows doff .. doff + D - 1 of every sample (K11's row
+                      // passes only; Dl = D, doff = 0: the dense tensor).  Everything else -- x0, xt, u, rows, base_sum, cb -- is compact (B,D,..)
   float reg_scale;    // weight of the regulariser term (= elbo_scale in the one-forward-pass objective; the two-pass objective runs
                       // the kernel once per network output with one of the two term weights at zero)
   float* RT;          // (B,S,S) or null: RT[b][x][s] = R[b][s][x], written by k_elbo_atab (all column blocks) so that a row's forward
@@ -201,6 +203,9 @@ struct ElboArgs {
   float* out_loss;    // (1)
   int ll_in;          // ScoreElbo only: `logits` holds ll_all (reverse logit types); grad = d loss / d ll_all
 };
+
+// row of the (B,Dl,S) logits / gradient that holds the objective's row (b, d)
+__device__ inline size_t elbo_lrow(const ElboArgs& a, int b, int d) { return (size_t)b * a.Dl + a.doff + d; }
 
 // block reduction of LRB values per thread; result broadcast through red[]
 __device__ inline void block_sum8(float (&v)[LRB], float* red /* [4][LRB] */, float (&out)[LRB]) {
@@ -288,13 +293,14 @@ __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
   bool ok[LRB];
   float l[LRB], mx[LRB], tmp[LRB], p[LRB];
   auto row_of = [&](int r) { return (size_t)b * D + d0 + r; };
+  auto lrow_of = [&](int r) { return elbo_lrow(a, b, d0 + r); };
 #pragma unroll
   for (int r = 0; r < LRB; ++r) {
     ok[r] = d0 + r < D;
     const size_t row = (size_t)b * D + (ok[r] ? d0 + r : D - 1);
     x[r] = min(max(a.xt[row], 0), S - 1);
     x0[r] = min(max(a.x0[row], 0), S - 1);
-    l[r] = act ? a.logits[row * S + t] : -INFINITY;
+    l[r] = act ? a.logits[elbo_lrow(a, b, ok[r] ? d0 + r : D - 1) * S + t] : -INFINITY;
     tmp[r] = l[r];
   }
   block_max8(tmp, red, mx);
@@ -308,7 +314,7 @@ __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
     const float L = mx[r] + logf(zs[r]);
     p[r] = act ? expf(l[r] - L) : 0.0f;
     const float den = act ? qT[(size_t)x[r] * S + t] + a.eps : 1.0f;
-    if (PHASE == 1) { if (act && ok[r]) a.grad[row_of(r) * S + t] = p[r] / den; }
+    if (PHASE == 1) { if (act && ok[r]) a.grad[lrow_of(r) * S + t] = p[r] / den; }
     else rvec[r][t] = p[r] / den;
     regp[r] = act ? p[r] * a.Atab[((size_t)b * S + x[r]) * S + t] : 0.0f;
     nllp[r] = (act && t == x0[r]) ? -(l[r] - L) : 0.0f;
@@ -379,13 +385,14 @@ __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
 // g contracts k = 8 g .. 8 g + 7 of the chunk: each 16-byte read feeds four instructions.
 constexpr int GK = 16, GLD = GK + 4;
 template <int NT>
-__global__ __launch_bounds__(256) void k_bgemm_f32(const float* __restrict__ A, const float* __restrict__ W, float* __restrict__ Cm, int M) {
+__global__ __launch_bounds__(256) void k_bgemm_f32(const float* __restrict__ A, const float* __restrict__ W, float* __restrict__ Cm, int M, size_t sA, size_t sC) {
   constexpr int N = 32 * NT, K = N, WV = (NT + 1) / 2;              // WV: float4 of W per thread and chunk (N * 16 / 4 / 256, rounded up)
   __shared__ __attribute__((aligned(16))) float As[2][128 * GLD];
   __shared__ __attribute__((aligned(16))) float Ws[2][N * GLD];
   using f32x16l = __attribute__((ext_vector_type(16))) float;
   const int b = blockIdx.y, m0 = blockIdx.x * 128, t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, g = lane >> 5;
-  const float* Ab = A + (size_t)b * M * K;
+  const float* Ab = A + (size_t)b * sA;          // sA / sC: batch strides of A / C in floats (M K / M N when dense; a window of rows of a
+                                                 // taller tensor has the taller one's).  Rows >= M are never read (zero operand) nor written.
   const float* Wb = W + (size_t)b * N * K;
   float4 pa[2], pw[WV];
   auto fetch = [&](int k0) {
@@ -441,7 +448,7 @@ __global__ __launch_bounds__(256) void k_bgemm_f32(const float* __restrict__ A, 
     __syncthreads();
   }
   // accumulator tile i: column 32 i + li, rows (r & 3) + 8 (r >> 2) + 4 g of the wave's 32
-  float* Cb = Cm + (size_t)b * M * N;
+  float* Cb = Cm + (size_t)b * sC;
 #pragma unroll
   for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -512,7 +519,7 @@ __global__ __launch_bounds__(256) void k_elbo_bwd(const ElboArgs a) {
     const size_t row = (size_t)b * D + (ok[r] ? d0 + r : D - 1);
     x[r] = min(max(a.xt[row], 0), S - 1);
     x0[r] = min(max(a.x0[row], 0), S - 1);
-    l[r] = act ? a.logits[row * S + t] : -INFINITY;
+    l[r] = act ? a.logits[elbo_lrow(a, b, ok[r] ? d0 + r : D - 1) * S + t] : -INFINITY;
     tmp[r] = l[r];
     // G[s] = c_b Wt[s] / (u[s] + eps)
     float G = 0.0f;
@@ -522,7 +529,7 @@ __global__ __launch_bounds__(256) void k_elbo_bwd(const ElboArgs a) {
       const float qx0xt = q[(size_t)x0[r] * S + x[r]] + a.eps;
       G = cb * orate * (qx0 / qx0xt) / (a.u[row * S + t] + a.eps);
     }
-    if (PHASE == 1) { if (act && ok[r]) a.grad[row * S + t] = G; }
+    if (PHASE == 1) { if (act && ok[r]) a.grad[elbo_lrow(a, b, d0 + r) * S + t] = G; }
     else if (PHASE == 0) gvec[r][t] = G;
   }
   if (PHASE == 1) return;
@@ -555,7 +562,7 @@ __global__ __launch_bounds__(256) void k_elbo_bwd(const ElboArgs a) {
 #pragma unroll
   for (int r = 0; r < LRB; ++r)
     if (act && ok[r])
-      a.grad[((size_t)b * D + d0 + r) * S + t] = p[r] * (dp[r] - pdot[r]) + a.nll_scale * (p[r] - (t == x0[r] ? 1.0f : 0.0f));
+      a.grad[elbo_lrow(a, b, d0 + r) * S + t] = p[r] * (dp[r] - pdot[r]) + a.nll_scale * (p[r] - (t == x0[r] ? 1.0f : 0.0f));
 }
 
 // ---- the regulariser table on the matrix cores (S % 32 == 0): A[b][x][s0] = sum_{s != x} q[s0][s] R[s][x] / (q[s0][x] + eps)
@@ -628,15 +635,16 @@ __global__ __launch_bounds__(256) void k_elbo_rowsv(const ElboArgs a) {
     float4 lg[2], t1[2], t2[2], t3[2];
     int x[2], x0[2];
     bool ok[2];
-    size_t row[2];
+    size_t row[2], lrow[2];                                      // compact (x0, x~, u, rows) / in the (B,Dl,S) logits and gradient
 #pragma unroll
     for (int e = 0; e < 2; ++e) {                                // everything the two rows need, requested together
       const int d = d0 + r2 + e;
       ok[e] = d < D;
       row[e] = (size_t)b * D + (ok[e] ? d : D - 1);
+      lrow[e] = elbo_lrow(a, b, ok[e] ? d : D - 1);
       x[e] = min(max(a.xt[row[e]], 0), S - 1);
       x0[e] = min(max(a.x0[row[e]], 0), S - 1);
-      if (MODE == 0 || MODE == 3) lg[e] = *(const float4*)(a.logits + row[e] * S + s0);
+      if (MODE == 0 || MODE == 3) lg[e] = *(const float4*)(a.logits + lrow[e] * S + s0);
       if (MODE == 0 || MODE == 3) { t1[e] = *(const float4*)(qT + (size_t)x[e] * S + s0); t2[e] = *(const float4*)(At + (size_t)x[e] * S + s0); }
       if (MODE == 1 || MODE == 2) { t1[e] = *(const float4*)(RT + (size_t)x[e] * S + s0); t2[e] = *(const float4*)(q + (size_t)x0[e] * S + s0); }
       if (MODE != 0) t3[e] = *(const float4*)(a.u + row[e] * S + s0);
@@ -659,7 +667,7 @@ __global__ __launch_bounds__(256) void k_elbo_rowsv(const ElboArgs a) {
           float reg = 0.0f, nll = 0.0f;
 #pragma unroll
           for (int c = 0; c < 4; ++c) { reg = fmaf(p[c], at[c], reg); nll += (s0 + c == x0[e]) ? -(l4[c] - L) : 0.0f; }
-          if (ok[e]) *(float4*)(a.grad + row[e] * S + s0) = make_float4(p[0] / den[0], p[1] / den[1], p[2] / den[2], p[3] / den[3]);
+          if (ok[e]) *(float4*)(a.grad + lrow[e] * S + s0) = make_float4(p[0] / den[0], p[1] / den[1], p[2] / den[2], p[3] / den[3]);
           reg = lwave_sum(reg); nll = lwave_sum(nll);
           if (lane == 0 && ok[e]) { double* dst = a.rows + row[e] * 4; dst[2] = reg; dst[3] = nll; }
         } else {
@@ -671,7 +679,7 @@ __global__ __launch_bounds__(256) void k_elbo_rowsv(const ElboArgs a) {
           float o[4];
 #pragma unroll
           for (int c = 0; c < 4; ++c) o[c] = p[c] * (dp[c] - pd) + a.nll_scale * (p[c] - (s0 + c == x0[e] ? 1.0f : 0.0f));
-          if (ok[e]) *(float4*)(a.grad + row[e] * S + s0) = make_float4(o[0], o[1], o[2], o[3]);
+          if (ok[e]) *(float4*)(a.grad + lrow[e] * S + s0) = make_float4(o[0], o[1], o[2], o[3]);
         }
       } else {
         const float rt[4] = {t1[e].x, t1[e].y, t1[e].z, t1[e].w}, qx[4] = {t2[e].x, t2[e].y, t2[e].z, t2[e].w};
@@ -696,10 +704,28 @@ __global__ __launch_bounds__(256) void k_elbo_rowsv(const ElboArgs a) {
             const float orate = (s0 + c == x[e]) ? 0.0f : rt[c];
             G[c] = cb * orate * (qx[c] / qx0xt) / (uu[c] + a.eps);
           }
-          if (ok[e]) *(float4*)(a.grad + row[e] * S + s0) = make_float4(G[0], G[1], G[2], G[3]);
+          if (ok[e]) *(float4*)(a.grad + lrow[e] * S + s0) = make_float4(G[0], G[1], G[2], G[3]);
         }
       }
     }
+  }
+}
+
+// ---- K11 on a window of rows: d/dlogits of the rows outside the window is zero.  Per sample the Dl - D held rows are the two
+// contiguous runs [0, doff) and [doff + D, Dl); only they are written (grid (blocks, B), 16-byte stores where S % 4 == 0).
+__global__ __launch_bounds__(256) void k_elbo_zero_held(const ElboArgs a) {
+  const int S = a.S, b = blockIdx.y;
+  float* g = a.grad + (size_t)b * a.Dl * S;
+  const size_t head = (size_t)a.doff * S, tail0 = (size_t)(a.doff + a.D) * S, n = (size_t)(a.Dl - a.D) * S;
+  const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
+  if (S % 4 == 0) {                                     // (every run then starts and ends on a 16-byte boundary)
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (size_t i = i0; i < n / 4; i += step) {
+      const size_t e = 4 * i;
+      *(float4*)(g + (e < head ? e : tail0 + (e - head))) = z;
+    }
+  } else {
+    for (size_t e = i0; e < n; e += step) g[e < head ? e : tail0 + (e - head)] = 0.0f;
   }
 }
 
@@ -711,18 +737,31 @@ extern "C" int64_t ctdd_ctelbo_scratch_bytes(int B, int D, int S) {
   return 2 * al((int64_t)B * S * S * 4) + al((int64_t)B * D * S * 4) + al((int64_t)B * D * 32) + 2 * al((int64_t)B * 4) + al((int64_t)B * 32);
 }
 
-extern "C" int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
-                                      const float* rate, int B, int D, int S, float eps, float sig_scale, float reg_scale, float nll_scale,
-                                      void* scratch, float* grad_logits, float* out_loss, void* stream);
+static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
+                       const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
+                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream);
 extern "C" int ctdd_ctelbo_loss(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
                                 const float* rate, int B, int D, int S, float eps, float elbo_scale, float nll_scale,
                                 void* scratch, float* grad_logits, float* out_loss, void* stream) {
-  return ctdd_ctelbo_loss_terms(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, eps, elbo_scale, elbo_scale, nll_scale, scratch, grad_logits,
-                                out_loss, stream);
+  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, elbo_scale, elbo_scale, nll_scale, scratch, grad_logits, out_loss,
+                     stream);
 }
 extern "C" int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
                                       const float* rate, int B, int D, int S, float eps, float sig_scale, float reg_scale, float nll_scale,
                                       void* scratch, float* grad_logits, float* out_loss, void* stream) {
+  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss, stream);
+}
+// K11 on rows [d_off, d_off + D) of (B, Dl, S) logits, read in place; the full-shape gradient is written in place, zeros outside the window
+extern "C" int ctdd_ctelbo_loss_window(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
+                                       const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
+                                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream) {
+  CTDD_REQUIRE(d_off >= 0 && D >= 1 && Dl >= D && d_off <= Dl - D, CTDD_ERANGE, "ct-elbo window: rows [%d, %d + %d) of Dl=%d", d_off, d_off, D, Dl);
+  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, Dl, d_off, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss,
+                     stream);
+}
+static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
+                       const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
+                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream) {
   const float elbo_scale = sig_scale;
   CTDD_REQUIRE(logits && x0 && x_tilde && qt0 && qt0T && rate && scratch && grad_logits && out_loss, CTDD_EINVAL, "ct-elbo: null buffer");
   CTDD_REQUIRE(B > 0 && D > 0 && S >= 2 && S <= 256, CTDD_ERANGE, "ct-elbo: B=%d D=%d S=%d (S <= 256)", B, D, S);
@@ -731,6 +770,7 @@ extern "C" int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, co
   ElboArgs a;
   a.logits = logits; a.x0 = x0; a.xt = x_tilde; a.q = qt0; a.qT = qt0T; a.R = rate;
   a.B = B; a.D = D; a.S = S; a.eps = eps; a.elbo_scale = elbo_scale; a.nll_scale = nll_scale; a.reg_scale = reg_scale;
+  a.Dl = Dl; a.doff = d_off;
   a.Atab = (float*)sp; sp += al((int64_t)B * S * S * 4);
   a.u = (float*)sp; sp += al((int64_t)B * D * S * 4);
   a.rows = (double*)sp; sp += al((int64_t)B * D * 32);
@@ -742,27 +782,34 @@ extern "C" int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, co
   hipStream_t st = (hipStream_t)stream;
   const dim3 rg((D + LRB - 1) / LRB, B), gg((D + 127) / 128, B);
   const bool mfma = S % 32 == 0;                     // the S x S contractions on the exact-fp32 matrix instruction
-  auto gemm_m = [&](const float* Am, const float* Wm, float* Cm, int Mrows) {
+  auto gemm_m = [&](const float* Am, const float* Wm, float* Cm, int Mrows, size_t sA, size_t sC) {
     const dim3 g2((Mrows + 127) / 128, B);
     switch (S / 32) {
-      case 1: hipLaunchKernelGGL(k_bgemm_f32<1>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows); break;
-      case 2: hipLaunchKernelGGL(k_bgemm_f32<2>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows); break;
-      case 3: hipLaunchKernelGGL(k_bgemm_f32<3>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows); break;
-      case 4: hipLaunchKernelGGL(k_bgemm_f32<4>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows); break;
-      case 5: hipLaunchKernelGGL(k_bgemm_f32<5>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows); break;
-      case 6: hipLaunchKernelGGL(k_bgemm_f32<6>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows); break;
-      case 7: hipLaunchKernelGGL(k_bgemm_f32<7>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows); break;
-      default: hipLaunchKernelGGL(k_bgemm_f32<8>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows); break;
+      case 1: hipLaunchKernelGGL(k_bgemm_f32<1>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
+      case 2: hipLaunchKernelGGL(k_bgemm_f32<2>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
+      case 3: hipLaunchKernelGGL(k_bgemm_f32<3>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
+      case 4: hipLaunchKernelGGL(k_bgemm_f32<4>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
+      case 5: hipLaunchKernelGGL(k_bgemm_f32<5>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
+      case 6: hipLaunchKernelGGL(k_bgemm_f32<6>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
+      case 7: hipLaunchKernelGGL(k_bgemm_f32<7>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
+      default: hipLaunchKernelGGL(k_bgemm_f32<8>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
     }
     return finish_launch("k_bgemm_f32");
   };
-  auto gemm = [&](const float* Am, const float* Wm, float* Cm) { return gemm_m(Am, Wm, Cm, D); };
+  // the row GEMMs: left operand = the D window rows of the gradient buffer (batch stride Dl S), result = the compact u
+  float* gwin = a.grad + (size_t)d_off * S;
+  auto gemm = [&](const float* Wm) { return gemm_m(gwin, Wm, a.u, D, (size_t)Dl * S, (size_t)D * S); };
+  if (Dl > D) {                                      // held rows: zeros, written once (the row passes never touch them)
+    const size_t n = (size_t)(Dl - D) * S / (S % 4 == 0 ? 4 : 1);
+    hipLaunchKernelGGL(k_elbo_zero_held, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), B), dim3(256), 0, st, a);
+    if (int rc = finish_launch("k_elbo_zero_held")) return rc;
+  }
   (void)gg;
   static const bool atab_fma = [] { const char* e = getenv("CTDD_ELBO_ATAB_FMA"); return e && e[0] == '1'; }();   // (A/B: the FMA-chain table kernel)
   if (mfma && !atab_fma) {
     hipLaunchKernelGGL(k_elbo_rt, dim3(S / 32, S / 32, B), dim3(256), 0, st, a);
     if (int rc = finish_launch("k_elbo_rt")) return rc;
-    if (int rc = gemm_m(a.RT, a.q, a.Atab, S)) return rc;
+    if (int rc = gemm_m(a.RT, a.q, a.Atab, S, (size_t)S * S, (size_t)S * S)) return rc;
     hipLaunchKernelGGL(k_elbo_afix, dim3(1024), dim3(256), 0, st, a);
     if (int rc = finish_launch("k_elbo_afix")) return rc;
   } else {
@@ -775,13 +822,13 @@ extern "C" int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, co
   if (wave_rows) {
     hipLaunchKernelGGL(k_elbo_rowsv<0>, wg, dim3(256), 0, st, a);               // rvec -> grad buffer; reg / nll row sums
     if (int rc = finish_launch("k_elbo_rowsv<0>")) return rc;
-    if (int rc = gemm(a.grad, a.qT, a.u)) return rc;
+    if (int rc = gemm(a.qT)) return rc;
     hipLaunchKernelGGL(k_elbo_rowsv<1>, wg, dim3(256), 0, st, a);
     if (int rc = finish_launch("k_elbo_rowsv<1>")) return rc;
   } else if (mfma) {
     hipLaunchKernelGGL(k_elbo_fwd<1>, rg, dim3(256), 0, st, a);                 // rvec -> grad buffer; reg / nll row sums
     if (int rc = finish_launch("k_elbo_fwd<1>")) return rc;
-    if (int rc = gemm(a.grad, a.qT, a.u)) return rc;                            // u[row][s] = sum_s0 rvec[row][s0] qT[s][s0]
+    if (int rc = gemm(a.qT)) return rc;                                         // u[row][s] = sum_s0 rvec[row][s0] qT[s][s0]
     hipLaunchKernelGGL(k_elbo_fwd<2>, rg, dim3(256), 0, st, a);
     if (int rc = finish_launch("k_elbo_fwd<2>")) return rc;
   } else {
@@ -795,14 +842,14 @@ extern "C" int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, co
   if (wave_rows) {
     hipLaunchKernelGGL(k_elbo_rowsv<2>, wg, dim3(256), 0, st, a);               // G -> grad buffer
     if (int rc = finish_launch("k_elbo_rowsv<2>")) return rc;
-    if (int rc = gemm(a.grad, a.q, a.u)) return rc;                             // dr = G q^T (over u)
+    if (int rc = gemm(a.q)) return rc;                                          // dr = G q^T (over u)
     hipLaunchKernelGGL(k_elbo_rowsv<3>, wg, dim3(256), 0, st, a);
     return finish_launch("k_elbo_rowsv<3>");
   }
   if (mfma) {
     hipLaunchKernelGGL(k_elbo_bwd<1>, rg, dim3(256), 0, st, a);                 // G -> grad buffer
     if (int rc = finish_launch("k_elbo_bwd<1>")) return rc;
-    if (int rc = gemm(a.grad, a.q, a.u)) return rc;                             // dr[row][s0] = sum_s G[row][s] q[s0][s]   (over u)
+    if (int rc = gemm(a.q)) return rc;                                          // dr[row][s0] = sum_s G[row][s] q[s0][s]   (over u)
     hipLaunchKernelGGL(k_elbo_bwd<2>, rg, dim3(256), 0, st, a);
     return finish_launch("k_elbo_bwd<2>");
   }
@@ -925,6 +972,7 @@ static int score_elbo_impl(const float* logits, const int32_t* x0, const int32_t
   ElboArgs a;
   a.logits = logits; a.x0 = x0; a.xt = x_tilde; a.q = qt0; a.qT = qt0; a.R = rate;
   a.B = B; a.D = D; a.S = S; a.eps = eps; a.elbo_scale = 1.0f; a.nll_scale = nll_scale; a.reg_scale = 1.0f;
+  a.Dl = D; a.doff = 0;
   a.Atab = (float*)sp; sp += al((int64_t)B * S * S * 4);
   a.u = (float*)sp; sp += al((int64_t)B * D * S * 4);
   a.rows = (double*)sp; sp += al((int64_t)B * D * 32);
@@ -1122,14 +1170,14 @@ __global__ __launch_bounds__(256) void k_lp_final(const float* __restrict__ logi
 template <typename F>
 static int launch_bgemm(int S, dim3 gg, hipStream_t st, const float* Am, const float* Wm, float* Cm, int M) {
   switch (S / 32) {
-    case 1: hipLaunchKernelGGL(k_bgemm_f32<1>, gg, dim3(256), 0, st, Am, Wm, Cm, M); break;
-    case 2: hipLaunchKernelGGL(k_bgemm_f32<2>, gg, dim3(256), 0, st, Am, Wm, Cm, M); break;
-    case 3: hipLaunchKernelGGL(k_bgemm_f32<3>, gg, dim3(256), 0, st, Am, Wm, Cm, M); break;
-    case 4: hipLaunchKernelGGL(k_bgemm_f32<4>, gg, dim3(256), 0, st, Am, Wm, Cm, M); break;
-    case 5: hipLaunchKernelGGL(k_bgemm_f32<5>, gg, dim3(256), 0, st, Am, Wm, Cm, M); break;
-    case 6: hipLaunchKernelGGL(k_bgemm_f32<6>, gg, dim3(256), 0, st, Am, Wm, Cm, M); break;
-    case 7: hipLaunchKernelGGL(k_bgemm_f32<7>, gg, dim3(256), 0, st, Am, Wm, Cm, M); break;
-    default: hipLaunchKernelGGL(k_bgemm_f32<8>, gg, dim3(256), 0, st, Am, Wm, Cm, M); break;
+    case 1: hipLaunchKernelGGL(k_bgemm_f32<1>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
+    case 2: hipLaunchKernelGGL(k_bgemm_f32<2>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
+    case 3: hipLaunchKernelGGL(k_bgemm_f32<3>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
+    case 4: hipLaunchKernelGGL(k_bgemm_f32<4>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
+    case 5: hipLaunchKernelGGL(k_bgemm_f32<5>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
+    case 6: hipLaunchKernelGGL(k_bgemm_f32<6>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
+    case 7: hipLaunchKernelGGL(k_bgemm_f32<7>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
+    default: hipLaunchKernelGGL(k_bgemm_f32<8>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
   }
   return finish_launch("k_bgemm_f32");
 }

@@ -60,6 +60,7 @@ _SIGS = {
     "ctdd_ctelbo_scratch_bytes": ([_I, _I, _I], _I64),
     "ctdd_ctelbo_loss": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_ctelbo_loss_terms": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P], _I),
+    "ctdd_ctelbo_loss_window": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_score_elbo_loss": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_crm_loss_ll": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P], _I),
     "ctdd_score_elbo_loss_ll": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
@@ -459,6 +460,31 @@ def ctelbo_loss(logits, x0, x_tilde, qt0, qt0T, rate, eps, elbo_scale, nll_scale
         _check(lib.ctdd_ctelbo_loss(*head, float(elbo_scale), *tail), "ctdd_ctelbo_loss")
     else:
         _check(lib.ctdd_ctelbo_loss_terms(*head, float(elbo_scale), float(reg_scale), *tail), "ctdd_ctelbo_loss_terms")
+    return out[0], grad
+
+
+def ctelbo_loss_window(logits_full, x0, x_tilde, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale, d_off, grad_out=None):
+    """K11 on rows [d_off, d_off + D) of the (B, Dl, S) logits, read in place; x0 / x_tilde are the compact (B, D) window.
+    Returns (loss scalar tensor, d loss / d logits_full): full shape, zeros on the rows outside the window, every element
+    written by the call (`grad_out`: write into this (B, Dl, S) buffer instead of a fresh one).  Terms and weights as
+    ctelbo_loss with `reg_scale` given."""
+    B, Dl, S = logits_full.shape
+    D = x0.shape[1]
+    if x0.shape != (B, D) or x_tilde.shape != (B, D):
+        raise CtddError(f"ctelbo_loss_window: x0 {tuple(x0.shape)} / x_tilde {tuple(x_tilde.shape)} against {B} samples")
+    if not (0 <= int(d_off) and D >= 1 and int(d_off) + D <= Dl):
+        raise CtddError(f"ctelbo_loss_window: rows [{d_off}, {d_off} + {D}) of {Dl}")
+    lib = load()
+    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits_full.device)
+    grad = torch.empty_like(logits_full) if grad_out is None else grad_out
+    if grad.shape != logits_full.shape:
+        raise CtddError(f"ctelbo_loss_window: grad_out {tuple(grad.shape)} against logits {tuple(logits_full.shape)}")
+    out = torch.empty((1,), dtype=torch.float32, device=logits_full.device)
+    _count("ctdd_ctelbo_loss_window")
+    _check(lib.ctdd_ctelbo_loss_window(_ptr(logits_full, torch.float32, "logits"), _ptr(x0, torch.int32, "x0"), _ptr(x_tilde, torch.int32, "x_tilde"),
+                                       _ptr(qt0, torch.float32, "qt0"), _ptr(qt0T, torch.float32, "qt0T"), _ptr(rate, torch.float32, "rate"),
+                                       B, D, S, Dl, int(d_off), float(eps), float(sig_scale), float(reg_scale), float(nll_scale),
+                                       _ptr(scratch), _ptr(grad, torch.float32, "grad_out"), _ptr(out), _stream()), "ctdd_ctelbo_loss_window")
     return out[0], grad
 
 

@@ -1,6 +1,6 @@
 """Training losses behind the reference's registry names (lib/losses/losses.py): CTElbo 12-287,
-NLL 1504-1778, CTElboLambda 1783-2058, CatRM 786-890, CatRMNLL 1135-1242, NLLOriginal 1049-1103,
-ScoreElbo 1246-1500.
+NLL 1504-1778, CTElboLambda 1783-2058, CondCTElbo 547-781, CatRM 786-890, CatRMNLL 1135-1242,
+NLLOriginal 1049-1103, ScoreElbo 1246-1500.
 
 Every loss = forward noising x0 -> x_t (and, for the ELBO family, the one-jump neighbour x~) followed
 by an objective on the network's logits.  Noising runs in the HIP kernels K1/K2/K3 (per-sample
@@ -178,6 +178,77 @@ class CTElboLambda(_CTElboBase):
         state, minibatch = _unpack(state, minibatch)
         w = state["n_iter"] / self.max_iter
         return self._total(state, minibatch, w, 1 - w)
+
+
+class _CtElboWindowFn(torch.autograd.Function):
+    """K11 on a window of rows (ctdd_ctelbo_loss_window): the network's full (B, Dl, S) logits are read in place, the gradient
+    comes back full-shape with zeros on the rows before `d_off`; x0 / x_tilde are the compact (B, Dl - d_off) free rows."""
+
+    @staticmethod
+    def forward(ctx, logits_full, x0, x_tilde, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale, d_off):
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        val, grad = native.ctelbo_loss_window(logits_full.detach().float().contiguous(), i32(x0), i32(x_tilde), qt0.contiguous(),
+                                              qt0T.contiguous(), rate.contiguous(), eps, sig_scale, reg_scale, nll_scale, d_off)
+        ctx.save_for_backward(grad)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 10
+
+
+@losses_utils.register_loss
+class CondCTElbo:
+    """CT-ELBO of the free rows given a held prefix (losses.py:547-781): the first `condition_dim` entries of every sample are the
+    conditioner, passed to the network unnoised; rows condition_dim .. D-1 are noised and carry the objective.  What the
+    conditional samplers (ConditionalTauLeaping / ConditionalPCTauLeaping) assume the model was trained with.
+
+    Unlike CTElbo, t ~ U(min_time, 1) (567, no max_t), the single forward of one_forward_pass is at x~ (615-620), and with two
+    passes the cross entropy is on the second (x~) forward's logits (665, 777-779)."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.ratio_eps = cfg.loss.eps_ratio
+        self.nll_weight = cfg.loss.nll_weight
+        self.min_time = cfg.loss.min_time
+        self.one_forward_pass = cfg.loss.one_forward_pass
+        self.condition_dim = cfg.loss.condition_dim
+        self.cross_ent = nn.CrossEntropyLoss()
+
+    def calc_loss(self, minibatch, state=None, label=None):
+        state, minibatch = _unpack(minibatch, state)
+        minibatch = _flatten(minibatch)
+        D, k = self.cfg.model.concat_dim, self.condition_dim
+        if not (isinstance(k, int) and 0 < k < D):
+            raise ValueError(f"CondCTElbo: loss.condition_dim must be an integer in (0, {D}), got {k!r}")
+        if minibatch.dim() != 2 or minibatch.shape[1] != D:
+            raise ValueError(f"CondCTElbo: minibatch of shape {tuple(minibatch.shape)}, model.concat_dim = {D}")
+        model = state["model"]
+        x0_full = minibatch.long()
+        B, d = x0_full.shape[0], D - k
+        conditioner, data = x0_full[:, :k], x0_full[:, k:].contiguous()
+        ts = _draw_ts(B, model.device, self.min_time, 1.0)
+        qt0, rate, x_t, x_tilde, qT = _noise(model, data, ts, True, want_T=True)          # (B, d): only the free rows are noised
+        eps, nll_coef = float(self.ratio_eps), float(self.nll_weight)
+        if self.one_forward_pass:
+            logits_sig = logits_reg = model(torch.cat((conditioner, x_tilde), dim=1), ts)   # (B, D, S)
+            reg_x = x_tilde
+        else:
+            logits_reg = model(torch.cat((conditioner, x_t), dim=1), ts)
+            logits_sig = model(torch.cat((conditioner, x_tilde), dim=1), ts)
+            reg_x = x_t
+        fused = logits_sig.is_cuda and logits_sig.shape[-1] <= 256 and getattr(self.cfg.loss, "fused", True)
+        if fused and self.one_forward_pass:
+            return _CtElboWindowFn.apply(logits_sig, data, x_tilde, qt0, qT, rate, eps, 1.0, 1.0, nll_coef / (B * d), k)
+        if fused:
+            reg = _CtElboWindowFn.apply(logits_reg, data, x_t, qt0, qT, rate, eps, 0.0, 1.0, 0.0, k)
+            sig = _CtElboWindowFn.apply(logits_sig, data, x_tilde, qt0, qT, rate, eps, 1.0, 0.0, nll_coef / (B * d), k)
+            return reg + sig
+        l_reg = logits_reg[:, k:, :]                                                       # (S > 256, cfg.loss.fused = False)
+        l_sig = l_reg if self.one_forward_pass else logits_sig[:, k:, :]
+        neg_elbo = _ct_elbo_terms(l_reg, l_sig, data, reg_x, x_tilde, qt0, rate, self.ratio_eps)
+        return neg_elbo + self.nll_weight * self.cross_ent(l_sig.permute(0, 2, 1), data)
 
 
 def _crm_loss(cfg, model, xt, t, ll_all, ll_xt):

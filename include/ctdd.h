@@ -238,6 +238,17 @@ int ctdd_ctelbo_loss(const float* logits, const int32_t* x0, const int32_t* x_ti
 int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
                            const float* rate, int B, int D, int S, float eps, float sig_scale, float reg_scale, float nll_scale,
                            void* scratch, float* grad_logits, float* out_loss, void* stream);
+/* K11 on a window of rows: the objective of prefix-conditioned training (lib/losses/losses.py:547-781, CondCTElbo: the network sees
+ * and returns logits for the full state, x_logits_full[:, condition_dim:, :] at 618 / 624 / 665 enters the CT-ELBO and the cross
+ * entropy at 777-779).  logits / grad_logits: (B, Dl, S).  Rows [d_off, d_off + D) of every sample are the objective's D rows;
+ * x0, x_tilde: (B, D) compact.  Terms and weights exactly as ctdd_ctelbo_loss_terms (base_sum / Z / the per-sample normaliser
+ * run over the D window rows only).  The logits are read in place and grad_logits is written in place: no contiguous copy of the
+ * window, no scatter into a zero-filled tensor; grad rows outside the window are written as zeros by this call (those rows only:
+ * there is no pass over the whole tensor).  With Dl = D, d_off = 0 the result is bit-identical to ctdd_ctelbo_loss_terms.
+ * scratch: ctdd_ctelbo_scratch_bytes(B, D, S)  (the window's D, not Dl).  Requires 0 <= d_off, D >= 1, d_off + D <= Dl. */
+int ctdd_ctelbo_loss_window(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
+                            const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
+                            float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream);
 
 /* ---- ScoreElbo with direct logits (lib/losses/losses.py:1255-1500), value and d/dlogits:
  * out_loss = mean_b(-sig_b / norm_b) + mean_b(reg_b) + nll_scale * sum_{b,d} -log_softmax(logits)[x~]   (nll_scale = nll_weight / B).
