@@ -19,6 +19,7 @@
 // optionally straight in the (B, D, S) logits layout, and accumulates per-(b, channel) sum /
 // sum-of-squares for the next GroupNorm with one atomic per lane.
 #include "common.hpp"
+#include <type_traits>
 
 namespace ctdd {
 
@@ -1469,6 +1470,163 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_conv_ring(const Co
 #endif
 }
 
+// ------------------------------------------------------------------ stride-2 ring convolution (Downsample, bf16)
+// The ring design for the 3x3 stride-2 convolution with the reference's (0,1,0,1) padding, even input grids
+// (Hin = 2 H, Win = 2 W).  Output pixels are taken in flattened (b, y, x) order; tap (0,0) of output pixel o sits at
+// input pixel 4 o - 2 x and tap (dy, dx) adds dy * Win + dx, so the inputs of a tile of BMP = 128 consecutive output
+// pixels under all nine taps are ONE contiguous run of at most 4 * 127 + 6 W + 1 input pixels starting at the even pixel
+// q0 = 4 p0 - 2 x(p0).  Per 16-channel unit that run and the weights of all nine taps go global -> LDS by LDS-DMA into
+// a ring of NBUF unit buffers, as in k_conv_ring.
+//
+// A lane's pixels under one tap are two input pixels apart, which read naively puts 16 lanes of a ds_read_b128 on four
+// bank quads.  The DMA's source address is per lane, so the run is split on the way in: the even pixels (run index
+// s = 2 i) fill slab rows [0, PLR), the odd ones rows [PLR, 2 PLR).  The parity of s is the parity of dx (q0 and Win
+// are even), so tap (dy, dx) of output pixel p0 + d reads plane dx & 1 at row 2 d - (x - x0) + dy W + (dx >> 1):
+// consecutive lanes read consecutive 32-byte rows (a step of W + 1 where the output row wraps), and the half-swap
+// swizzle of k_conv_ring keeps them on distinct bank quads.
+//
+// 4 waves x 32 rows x (32 BNT) columns.  Validity (input row 2y + dy = Hin or column 2x + dx = Win is the zero pad;
+// rows >= M) is a per-lane bit per tap that zeroes the A fragment; DMA source addresses are clamped into the tensor
+// and the weight matrix, what they fetch there is only consumed under a cleared bit or never written back.
+template <int BNT, int NBUF>
+__global__ __launch_bounds__(256) void k_conv_ring_s2(const ConvArgs a) {
+  constexpr int BK = 16, NW = 4, WM = 32, MT = 1;
+  constexpr int BN = 32 * BNT, BMP = NW * WM;
+  constexpr int PP = 10, PLR = PP * 32, SP = 2 * PP;             // pieces per parity plane: 4*127 + 6*16 + 1 = 605 pixels <= 2 * 320 (W <= 16)
+  constexpr int SLABB = SP * 1024, BUFB = SLABB + 9 * BN * 32;
+  constexpr int OPS = (SP + 9 * BNT + NW - 1) / NW;              // DMA ops per wave and unit
+  constexpr int DEPTH = NBUF - 1;
+  static_assert(DEPTH == 1 || DEPTH == 2, "ring of two or three unit buffers");
+  static_assert(OPS <= 18, "at most two DMA ops per tap");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, g = lane >> 5;
+  const int HW = a.H * a.W, Wd = a.W;
+  const int64_t M = (int64_t)a.B * HW;
+  const int64_t Min = 4 * M;                                     // input pixels (the host checks 4 M < 2^31)
+  const int64_t p0 = (int64_t)blockIdx.x * BMP;
+  const int n0 = blockIdx.y * BN;
+  const int x0 = (int)((unsigned)p0 % (unsigned)Wd);
+  const int64_t q0 = 4 * p0 - 2 * x0;                            // first input pixel of the run
+  const int Ntot = a.N, Ktot = a.Ktot, Cin = a.seg[0].C;
+  const int nunits = Cin / BK;
+  const unsigned char* const x_base = (const unsigned char*)a.seg[0].hi;
+  const unsigned char* const w_base = (const unsigned char*)a.w_hi;
+
+  // DMA op j of this wave for unit u into ring buffer `buf`: piece = wave + 4 j (clamped: the last pieces may be issued
+  // twice, same bytes to the same place).  Lane l fills LDS bytes [16 l, 16 l + 16) of the piece = row l/2, stored half l&1.
+  // Slab piece p: plane p / PP, rows 32 (p % PP) .. + 31 of it = input pixels q0 + plane + 2 (32 (p % PP) + l/2).
+  const int rl = lane >> 1;
+  const unsigned swz16 = (unsigned)(((lane & 1) ^ ((rl >> 3) & 1)) << 4);   // byte offset of the lane's half
+  const unsigned wlane = (unsigned)rl * (unsigned)Ktot * 2u + swz16;
+  // The source of op j differs from unit to unit by the unit's channel offset (32 bytes) only, for slab and weight pieces
+  // alike: the per-lane source pointers of unit 0 are computed once, and an op in the loop is one 64-bit add, M0 and the
+  // DMA instruction (computed per op, with its branches on the piece's kind, the address arithmetic was ~30 of the ~40
+  // instructions a wave issues per tap next to three matrix instructions).
+  const unsigned char* opsrc[OPS];
+#pragma unroll
+  for (int j = 0; j < OPS; ++j) {
+    constexpr int total = SP + 9 * BNT;
+    int p = wave + NW * j;
+    p = p < total ? p : total - 1;
+    if (p < SP) {
+      const int plane = p >= PP ? 1 : 0;
+      const int64_t qf = q0 + plane + 64 * (p - plane * PP);     // wave-uniform first pixel of the piece
+      int64_t q = qf + 2 * rl;
+      q = q < Min ? q : Min - 1;
+      opsrc[j] = x_base + (size_t)q * Cin * 2 + swz16;
+    } else {
+      const int wp = p - SP;                                     // = tap * BNT + t
+      const int tap = wp / BNT;
+      int nb = n0 + (wp - tap * BNT) * 32;
+      nb = nb + 32 <= Ntot ? nb : Ntot - 32;
+      opsrc[j] = w_base + ((size_t)nb * Ktot + (size_t)tap * Cin) * 2 + wlane;
+    }
+  }
+  auto issue_op = [&](int u, int buf, int j) {
+    constexpr int total = SP + 9 * BNT;
+    int p = wave + NW * j;
+    p = p < total ? p : total - 1;
+    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(opsrc[j] + (size_t)u * (BK * 2)),
+                                     (void __attribute__((address_space(3)))*)(smem + (size_t)buf * BUFB + (size_t)p * 1024), 16, 0, 0);
+  };
+
+  f32x16 acc[MT][BNT];
+#pragma unroll
+  for (int t = 0; t < BNT; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[0][t][i] = 0.0f;
+
+  // ---- prologue: the first DEPTH units, all ops at once
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d)
+    if (d < nunits)
+      for (int j = 0; j < OPS; ++j) issue_op(d, d, j);
+
+  // per-lane slab byte offset (swizzled) of the A fragment under every tap, and validity bits (bit = tap); 32-bit arithmetic
+  const int64_t po = p0 + wave * WM + li;
+  const unsigned ro = (unsigned)po % (unsigned)HW;
+  const int oy = (int)(ro / (unsigned)Wd), ox = (int)(ro % (unsigned)Wd);
+  const int rbase = 2 * (wave * WM + li) - ((int)((unsigned)po % (unsigned)Wd) - x0);   // (x of a row >= M is still po % W: the offset stays in the slab)
+  unsigned aoff[9], vmask = 0;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    const int dy = tap / 3, dx = tap % 3;
+    const int r = (dx & 1) * PLR + rbase + dy * Wd + (dx >> 1);
+    aoff[tap] = (unsigned)(r * 32 + ((g ^ ((r >> 3) & 1)) << 4));
+    const bool ok = po < M && 2 * oy + dy < a.Hin && 2 * ox + dx < a.Win;
+    vmask |= (ok ? 1u : 0u) << tap;
+  }
+  const unsigned boff = (unsigned)(SLABB + li * 32 + ((g ^ ((li >> 3) & 1)) << 4));
+
+  auto read_frags = [&](unsigned ao, unsigned bo, u32x4& af, u32x4 (&bf)[BNT]) {     // B first, A last: the wait for A covers the set
+#pragma unroll
+    for (int t = 0; t < BNT; ++t) bf[t] = *(const u32x4*)(smem + bo + t * 1024);
+    af = *(const u32x4*)(smem + ao);
+  };
+
+  int buf = 0, k = 0;
+  // one unit; FETCH (a compile-time flag: the tap sequence has no branch): unit k + DEPTH is requested between the taps
+  auto run_unit = [&](auto fetch_c) {
+    constexpr bool FETCH = decltype(fetch_c)::value;
+    // unit k has landed once at most the ops of the younger unit in flight remain
+    if (DEPTH == 2 && k + 1 < nunits) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();          // everyone's pieces of unit k are in LDS; unit k-1's buffer is out of use
+    const int kn = k + DEPTH;              // the unit to start fetching now, into the buffer unit k-1 used
+    const int nbuf = buf == 0 ? NBUF - 1 : buf - 1;
+    const unsigned sb = (unsigned)buf * BUFB;
+    u32x4 fa[2], fb[2][BNT];
+    read_frags(sb + aoff[0], sb + boff, fa[0], fb[0]);
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      fa[tap & 1] &= (unsigned)__builtin_amdgcn_sbfe(vmask, tap, 1);      // 0 or ~0
+      __builtin_amdgcn_sched_barrier(0);
+      if (tap + 1 < 9) read_frags(sb + aoff[tap + 1], sb + boff + (tap + 1) * BN * 32, fa[(tap + 1) & 1], fb[(tap + 1) & 1]);
+      if (FETCH && tap < OPS) issue_op(kn, nbuf, tap);
+      if (FETCH && tap + 9 < OPS) issue_op(kn, nbuf, tap + 9);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < BNT; ++t)
+        acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[tap & 1]), __builtin_bit_cast(bf16x8, fb[tap & 1][t]),
+                                                            acc[0][t], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    buf = buf + 1 == NBUF ? 0 : buf + 1;
+    ++k;
+  };
+  while (k + DEPTH < nunits) run_unit(std::true_type{});
+  while (k < nunits) run_unit(std::false_type{});
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+  const TileStats ts = tile_stats_begin(a, smem, p0, BMP, n0, BN, M, HW);     // (barrier: the LDS tiles are out of use)
+  if (!ts.lds) __syncthreads();
+  float* xt = (float*)(smem + (size_t)tile_stats_samples(BMP, HW) * BN * 16) + (size_t)wave * 32 * (BN + 4);
+  conv_epilogue_rows<BNT, MT>(a, acc, xt, p0 + wave * WM, n0, M, HW, ts);
+  tile_stats_flush(a, ts);
+}
+
 // split-K finish: acc_buf (+ bias, time bias, residual) -> outputs and GroupNorm statistics
 __global__ __launch_bounds__(256) void k_conv_finish(const ConvArgs a) {
   const int HW = a.H * a.W;
@@ -2242,6 +2400,37 @@ static int launch_conv(const ConvArgs& a, hipStream_t st) {
   return finish_launch("k_conv_igemm");
 }
 
+template <int BNT>
+static int launch_ring_s2(const ConvArgs& a, hipStream_t st) {
+  constexpr int NBUF = 3, BMP = 128;
+  const int64_t M = (int64_t)a.B * a.H * a.W;
+  dim3 g((unsigned)((M + BMP - 1) / BMP), (unsigned)((a.N + 32 * BNT - 1) / (32 * BNT)));
+  size_t lds = (size_t)NBUF * (20 * 1024 + 9 * 32 * BNT * 32);
+  const size_t epi_lds = epilogue_rows_lds(4, BNT, BMP, a.H * a.W);
+  if (lds < epi_lds) lds = epi_lds;
+  static bool attr_done[16] = {};
+  ensure_lds_ceiling((const void*)k_conv_ring_s2<BNT, NBUF>, attr_done);
+  hipLaunchKernelGGL((k_conv_ring_s2<BNT, NBUF>), g, dim3(256), lds, st, a);
+  return finish_launch("k_conv_ring_s2");
+}
+
+// Does the stride-2 ring kernel take this call of ctdd_unet_conv?  Everything else stays on k_conv_igemm.
+static bool ring_s2_takes(const ConvArgs& a, int f32) {
+  static const bool s2_old = [] { const char* e = getenv("CTDD_CONV_S2_OLD"); return e && e[0] == '1'; }();
+  if (s2_old || f32 || a.nseg != 1 || a.seg[0].kind != SEG_3x3_S2) return false;
+  const int Cin = a.seg[0].C;
+  const int64_t HW = (int64_t)a.H * a.W, M = HW * a.B;
+  if (Cin < 16 || Cin % 16 != 0 || a.N < 32 || a.N % 32 != 0 || a.Ktot != 9 * Cin || a.ksplit > 1) return false;
+  if (a.Hin != 2 * a.H || a.Win != 2 * a.W || a.W < 1 || a.W > 16 || a.B < 1) return false;   // even input grids; the slab planes hold 4*127 + 6 W + 1 pixels
+  if (!(HW >= 32 || HW == 16 || a.B == 1)) return false;                          // row-major epilogue: a 32-row slice spans two samples at most
+  if (a.logits_C > 0 || a.act != 0 || a.out_lo) return false;
+  if ((int64_t)a.Ktot * 64 >= (int64_t)1 << 31 || 4 * M >= (int64_t)1 << 31) return false;   // 32-bit lane offsets and pixel arithmetic
+  const uintptr_t al = (uintptr_t)a.seg[0].hi | (uintptr_t)a.w_hi | (uintptr_t)a.out_hi | (uintptr_t)a.out_f32 | (uintptr_t)a.res_bf16 |
+                       (uintptr_t)a.res_f32;
+  if (al & 15) return false;                                                      // 16-byte DMA pieces, epilogue loads and stores
+  return true;
+}
+
 extern "C" int ctdd_unet_conv(const void* args_, int bk, int bnt, int f32, void* stream) {
   const ConvArgs& a = *(const ConvArgs*)args_;
   CTDD_REQUIRE(a.nseg >= 1 && a.nseg <= 3, CTDD_EINVAL, "nseg=%d", a.nseg);
@@ -2252,6 +2441,14 @@ extern "C" int ctdd_unet_conv(const void* args_, int bk, int bnt, int f32, void*
   }
   CTDD_REQUIRE(f32 ? a.w_f32 != nullptr : a.w_hi != nullptr, CTDD_EINVAL, "null weights");
   hipStream_t st = (hipStream_t)stream;
+  // Downsample (one 3x3 stride-2 segment, bf16): the stride-2 ring kernel, whatever (bk, bnt) the plan names.
+  // CTDD_CONV_S2_OLD=1 (read once) keeps k_conv_igemm: the A/B switch.
+  // No grid-size rule: launched alone (median of 5 x 20 launches, both kernels in alternation, two rounds that agree to
+  // 0.4 us) the ring kernel wins at every grid, down to one workgroup -- MNIST 28->14 C=96 / 14->7 C=192 at batch 128:
+  // 30.1 -> 16.0 / 38.8 -> 19.0 us (196 / 98 workgroups), batch 64: 23.3 -> 12.4 / 33.7 -> 15.5, batch 16: 19.7 -> 10.7 /
+  // 31.1 -> 14.5, batch 4: 19.3 -> 10.4 / 30.7 -> 14.3 (7 / 4 workgroups); CIFAR C=128 32->16, C=256 16->8 and 8->4 at
+  // batch 64: 28.3 -> 16.8, 38.8 -> 18.1, 37.9 -> 14.7, at batch 4: 22.7 -> 10.0, 38.1 -> 14.5, 36.7 -> 14.2 (2 workgroups).
+  if (ring_s2_takes(a, f32)) return a.N % 96 == 0 ? launch_ring_s2<3>(a, st) : launch_ring_s2<2>(a, st);
 #define CASE(BK_, BNT_) \
   if (bk == BK_ && bnt == BNT_) return f32 ? launch_conv<BK_, BNT_, true>(a, st) : launch_conv<BK_, BNT_, false>(a, st);
   CASE(96, 3) CASE(96, 4) CASE(96, 1) CASE(64, 4) CASE(64, 2) CASE(64, 1) CASE(32, 1) CASE(32, 3) CASE(32, 4)

@@ -37,7 +37,13 @@ typedef struct {
   void* out_lo;                                                /* ctdd_unet_conv_patch: optional bf16(out - out_hi), the second term of a split operand */
 } ctdd_conv_args;
 /* out = conv(segments) + bias + tbias[b] + residual; bk in {96,64,32,16}, bnt = N-tile/32,
- * f32 = 0: bf16 MFMA, 1: exact-fp32 MFMA */
+ * f32 = 0: bf16 MFMA, 1: exact-fp32 MFMA.
+ * A bf16 call (f32 = 0) with exactly one CTDD_SEG_3x3_S2 segment (the Downsample convolution) runs on the stride-2
+ * ring kernel whatever (bk, bnt) it names, when Hin = 2 H, Win = 2 W, W <= 16, C % 16 == 0, N % 32 == 0,
+ * Ktot = 9 C, ksplit <= 1, H*W >= 32 or == 16 or B == 1, no logits layout / activation / out_lo, 16-byte aligned
+ * tensors, 4*B*H*W < 2^31.  Every other call runs on the generic gather kernel as before; the results of the two
+ * differ by the order of the fp32 sums only.  CTDD_CONV_S2_OLD=1 in the environment (read once per process) keeps
+ * the generic kernel for those calls too. */
 int ctdd_unet_conv(const void* conv_args, int bk, int bnt, int f32, void* stream);
 /* bf16 throughput kernel for stride-1 3x3 / 1x1 segments: the input slab of a pixel tile is staged in
  * LDS once per channel chunk and shared by the nine taps; bk in {48,64,32,16}, wm = rows per wave */
