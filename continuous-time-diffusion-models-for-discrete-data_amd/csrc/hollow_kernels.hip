@@ -15,6 +15,7 @@
 //   k_bert_embed            state -> [temb | x_0..x_{D-1}] + pe, per sample or per (sample, masked position) sequence
 //   k_bert_attention_short  unmasked attention for Tq, Tk <= 64: one wave per (sequence, head), K / V resident in LDS
 //   k_bert_gather           encoder rows 1..D of every sequence, or row p of sequence (b, p) -> the readout input
+//   k_bert_embed_bwd, k_bert_gather_bwd   their backward in plain mode (the x0-prediction model's training path)
 #include "common.hpp"
 
 namespace ctdd {
@@ -668,6 +669,37 @@ __global__ __launch_bounds__(256) void k_bert_gather(const float* __restrict__ e
   }
 }
 
+// ------------------------------------------------------------------ backward of the two (training: ctdd/bert_train.py)
+// k_bert_embed, plain mode: row 1 + d of sequence b is w_in xn_bd + b_in + pe, so with g the gradient of the (B, D + 1, E) encoder
+// input  dw_in[e] = sum_{b,d} g[b][1 + d][e] xn_bd,  db_in[e] = sum_{b,d} g[b][1 + d][e];  row 0 (the sinusoidal time embedding)
+// has no parameters.  Thread = column e over a strided run of rows, fp32 atomics into the zeroed dw / db as k_hollow_embed_bwd.
+struct BertEmbedBwdArgs { const int64_t* x64; const int32_t* x32; const float* g; int B, D, E, S; float* dw; float* db; };
+__global__ __launch_bounds__(256) void k_bert_embed_bwd(const BertEmbedBwdArgs a) {
+  const int b = blockIdx.y, E = a.E, D = a.D;
+  for (int e = threadIdx.x; e < E; e += 256) {
+    float sw = 0.0f, sb = 0.0f;
+    for (int d = blockIdx.x; d < D; d += gridDim.x) {
+      const float xr = a.x64 ? (float)a.x64[(size_t)b * D + d] : (float)a.x32[(size_t)b * D + d];
+      const float xn = (xr / (float)(a.S - 1)) * 2.0f - 1.0f;
+      const float g = a.g[((size_t)b * (D + 1) + 1 + d) * E + e];
+      sw = fmaf(g, xn, sw); sb += g;
+    }
+    atomicAdd(a.dw + e, sw);
+    atomicAdd(a.db + e, sb);
+  }
+}
+// k_bert_gather, plain mode with cond = 0: the (B D, E) readout-input gradient goes to rows 1..D of the (B, D + 1, E) encoder-output
+// gradient, row 0 is written as zero (every element of d_enc is written).  One wave per row of d_enc.
+__global__ __launch_bounds__(256) void k_bert_gather_bwd(const float* __restrict__ d_out, int64_t rows, int D, int E, float* __restrict__ d_enc) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);            // row (b, j) of d_enc
+  if (r >= rows) return;
+  const int64_t b = r / (D + 1);
+  const int j = (int)(r % (D + 1));
+  const float* src = j ? d_out + ((size_t)b * D + j - 1) * E : nullptr;
+  for (int e = lane; e < E; e += 64) d_enc[(size_t)r * E + e] = src ? src[e] : 0.0f;
+}
+
 // Unmasked attention for short sequences (Tq, Tk <= 64: T = D + 1 = 33 in three of the four shipped encoder configurations, where
 // the generic kernels' 128-query workgroups leave three quarters of their lanes idle).  One wave owns one (sequence, head) pair:
 // lane = query, the pair's whole K and V resident in LDS (staged once, read as wave-uniform float4s), NW pairs per workgroup.
@@ -793,6 +825,22 @@ extern "C" int ctdd_bert_gather(const float* enc, const int32_t* r0, int rows, i
   hipLaunchKernelGGL(k_bert_gather, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, enc, r0, rows, enumerate, total, D, cond, E, out,
                      (unsigned short*)out_bf16, (unsigned short*)out_lo);
   return finish_launch("k_bert_gather");
+}
+
+extern "C" int ctdd_bert_embed_bwd(const void* args_, void* stream) {
+  const BertEmbedBwdArgs& a = *(const BertEmbedBwdArgs*)args_;
+  CTDD_REQUIRE((a.x64 || a.x32) && a.g && a.dw && a.db, CTDD_EINVAL, "bert embed bwd: null buffer");
+  CTDD_REQUIRE(a.E >= 1 && a.S >= 2 && a.D >= 1 && a.B >= 1 && a.B <= 65535, CTDD_EINVAL, "bert embed bwd: E=%d S=%d D=%d B=%d", a.E, a.S, a.D, a.B);
+  hipLaunchKernelGGL(k_bert_embed_bwd, dim3(16, a.B), dim3(256), 0, (hipStream_t)stream, a);
+  return finish_launch("k_bert_embed_bwd");
+}
+
+extern "C" int ctdd_bert_gather_bwd(const float* d_out, int B, int D, int cond, int E, float* d_enc, void* stream) {
+  CTDD_REQUIRE(d_out && d_enc && B > 0 && D > 0 && E > 0, CTDD_EINVAL, "bert gather bwd: bad arguments");
+  CTDD_REQUIRE(cond == 0, CTDD_EINVAL, "bert gather bwd: plain mode with cond = 0 only, got cond=%d", cond);
+  const int64_t rows = (int64_t)B * (D + 1);
+  hipLaunchKernelGGL(k_bert_gather_bwd, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_out, rows, D, E, d_enc);
+  return finish_launch("k_bert_gather_bwd");
 }
 
 extern "C" int ctdd_bert_attention_short(const void* args_, void* stream) {

@@ -323,7 +323,10 @@ __global__ __launch_bounds__(256) void k_hollow_ln_bwd_v4(const LnBwdArgs a, int
 }
 
 // ============================================================================ attention, training mode
-// rows as in hollow_kernels.hip: q (b, i) at q + b*q_bs + i*q_rs + h*hd etc.; mode 0 causal, 1 anti-causal, 2 readout.
+// rows as in hollow_kernels.hip: q (b, i) at q + b*q_bs + i*q_rs + h*hd etc.; mode 0 causal, 1 anti-causal, 2 readout,
+// 3 unmasked (every key j < Tk for every query i < Tq, Tq and Tk independent: the encoder of the single-stream transformers).
+// Mode 3 is a compile-time switch (FULL) of every kernel, as in the inference kernels: the masked instantiations are the code
+// they were, the unmasked ones carry no mask arithmetic and no chunk search -- only the range mask of the ragged last chunk.
 // dropout (nn.MultiheadAttention's attention dropout): out_i = sum_j softmax(s)_ij keep_ij / (1 - p) v_j.
 struct AttnTrainArgs {
   const float* q; const float* k; const float* v; int64_t q_bs, k_bs, v_bs; int q_rs, k_rs, v_rs;
@@ -359,7 +362,7 @@ __device__ inline bool attn_keep(const AttnTrainArgs& a, int b, int h, int i, in
   return (keep8v(a.rng[0], a.rng[1] * 4096u + a.layer, oct, attn_thr(a.drop_p)) >> (j & 7)) & 1u;
 }
 constexpr int TQ = 128, TK = 32;
-template <int HD>
+template <int HD, bool FULL>
 __global__ __launch_bounds__(TQ) void k_hollow_attn_train(const AttnTrainArgs a) {
   __shared__ __attribute__((aligned(16))) float Ks[TK * HD];
   __shared__ __attribute__((aligned(16))) float Vs[TK * HD];
@@ -387,7 +390,7 @@ __global__ __launch_bounds__(TQ) void k_hollow_attn_train(const AttnTrainArgs a)
     const int nj = min(TK, a.Tk - j0);
     for (int jj = 0; jj < nj; ++jj) {
       const int j = j0 + jj;
-      if (!attn_allowed(a.mode, a.Tq, i, j)) continue;
+      if (!FULL && !attn_allowed(a.mode, a.Tq, i, j)) continue;
       float s = 0.0f;
 #pragma unroll
       for (int c = 0; c < HD; ++c) s = fmaf(qv[c], Ks[jj * HD + c], s);
@@ -410,7 +413,7 @@ __global__ __launch_bounds__(TQ) void k_hollow_attn_train(const AttnTrainArgs a)
   }
 }
 // thread = query: D_i = dO_i . O_i, dQ_i = scale sum_j dS_ij k_j,  dS_ij = p_ij (keep_ij / (1-p) dO_i.v_j - D_i)
-template <int HD>
+template <int HD, bool FULL>
 __global__ __launch_bounds__(TQ) void k_hollow_attn_bwd_q(const AttnTrainArgs a) {
   __shared__ __attribute__((aligned(16))) float Ks[TK * HD];
   __shared__ __attribute__((aligned(16))) float Vs[TK * HD];
@@ -443,7 +446,7 @@ __global__ __launch_bounds__(TQ) void k_hollow_attn_bwd_q(const AttnTrainArgs a)
     const int nj = min(TK, a.Tk - j0);
     for (int jj = 0; jj < nj; ++jj) {
       const int j = j0 + jj;
-      if (!attn_allowed(a.mode, a.Tq, i, j)) continue;
+      if (!FULL && !attn_allowed(a.mode, a.Tq, i, j)) continue;
       float s = 0.0f, dp = 0.0f;
 #pragma unroll
       for (int c = 0; c < HD; ++c) { s = fmaf(qv[c], Ks[jj * HD + c], s); dp = fmaf(dO[c], Vs[jj * HD + c], dp); }
@@ -461,7 +464,7 @@ __global__ __launch_bounds__(TQ) void k_hollow_attn_bwd_q(const AttnTrainArgs a)
   }
 }
 // thread = key: dV_j = sum_i p_ij keep/(1-p) dO_i ; dK_j = scale sum_i dS_ij q_i  over the queries that see key j
-template <int HD>
+template <int HD, bool FULL>
 __global__ __launch_bounds__(TQ) void k_hollow_attn_bwd_kv(const AttnTrainArgs a) {
   __shared__ __attribute__((aligned(16))) float Qs[TK * HD];
   __shared__ __attribute__((aligned(16))) float Ds[TK * HD];
@@ -495,7 +498,7 @@ __global__ __launch_bounds__(TQ) void k_hollow_attn_bwd_kv(const AttnTrainArgs a
     const int ni = min(TK, a.Tq - i0);
     for (int ii = 0; ii < ni; ++ii) {
       const int i = i0 + ii;
-      if (!attn_allowed(a.mode, a.Tq, i, j)) continue;
+      if (!FULL && !attn_allowed(a.mode, a.Tq, i, j)) continue;
       float s = 0.0f, dp = 0.0f;
 #pragma unroll
       for (int c = 0; c < HD; ++c) { s = fmaf(Qs[ii * HD + c], kv[c], s); dp = fmaf(Ds[ii * HD + c], vv[c], dp); }
@@ -562,6 +565,7 @@ __device__ inline bool chunk_full(int mode, int Tq, int Tk, int j0, int q0) {   
 // sequences -- ~1700 instructions per 32 x 32 tile, an order of magnitude above the softmax arithmetic.
 template <int MODE>
 __device__ inline bool allowed_t(int Tq, int i, int j) {
+  if (MODE == 3) return true;
   if (MODE == 0) return j <= i;
   if (MODE == 1) return j >= i;
   return (j == 0) | ((j <= Tq) & (j - 1 <= i)) | ((j > Tq) & (j - Tq - 1 >= i));
@@ -635,7 +639,7 @@ __device__ inline bf16x8t tfrag(const unsigned short* T, int col, int kh, int s_
 }
 
 // MODE_BWD false: forward with dropout, writes out (+ bf16 copy) and the row statistics;  true: D_i = dO.O and dQ
-template <int HD, bool BWD, int NW>      // NW waves = 32 NW queries per workgroup
+template <int HD, bool BWD, int NW, bool FULL>      // NW waves = 32 NW queries per workgroup; FULL: mode 3
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_hollow_attn_q_mfma(const AttnTrainArgs a) {
   constexpr int KS = HD / 16, RLD = HD + RLD16;
   __shared__ __attribute__((aligned(16))) unsigned short Kr[32 * RLD];          // K rows [key][dim]
@@ -677,7 +681,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
   const float* vb = a.v + (size_t)b * a.v_bs + h * HD;
   Stage2<HD, 64 * NW> stg;
   auto next_visible = [&](int jc) {                                             // (uniform over the workgroup)
-    while (jc < a.Tk && !chunk_any(a.mode, a.Tq, a.Tk, jc, wlo, whi)) jc += 32;
+    if (!FULL) while (jc < a.Tk && !chunk_any(a.mode, a.Tq, a.Tk, jc, wlo, whi)) jc += 32;
     return jc;
   };
   int jnext = next_visible(0);
@@ -689,7 +693,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     __syncthreads();
     jnext = next_visible(j0 + 32);
     if (jnext < a.Tk) stg.fetch(kb, a.k_rs, vb, a.v_rs, jnext, a.Tk);
-    if (!chunk_any(a.mode, a.Tq, a.Tk, j0, mylo, myhi)) continue;               // (wave-uniform; no barrier below)
+    if (FULL ? myhi < mylo : !chunk_any(a.mode, a.Tq, a.Tk, j0, mylo, myhi)) continue;   // (wave-uniform; no barrier below)
     f32x16t sacc, pacc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { sacc[r] = 0.0f; pacc[r] = 0.0f; }
@@ -702,9 +706,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[s_], pacc, 0, 0, 0);
       }
     }
-    const bool full = chunk_full(a.mode, a.Tq, a.Tk, j0, q0);
+    const bool full = FULL ? (q0 + 31 < a.Tq && j0 + 31 < a.Tk) : chunk_full(a.mode, a.Tq, a.Tk, j0, q0);
     if (!full) {
-      if (a.mode == 0) mask_tile_q<0>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);
+      if (FULL) mask_tile_q<3>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);     // (the range mask of a ragged chunk)
+      else if (a.mode == 0) mask_tile_q<0>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);
       else if (a.mode == 1) mask_tile_q<1>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);
       else mask_tile_q<2>(sacc, a.Tq, a.Tk, i, qok, j0 + 4 * kh);
     }
@@ -774,7 +779,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
 // dK, dV: wave = 32 keys (lane = key), loop over chunks of 32 queries
 // (held to 128 registers = four waves per SIMD: the unconstrained build takes 156 for three waves; the few spilled dwords cost less
 //  than the lost wave -- dQ + dK/dV pair 196 -> 158 us at the maze shape, 408 -> 376 us at the MNIST hollow shape)
-template <int HD, int NW>
+template <int HD, int NW, bool FULL>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_hollow_attn_kv_mfma(const AttnTrainArgs a) {
   constexpr int KS = HD / 16, RLD = HD + RLD16;
   __shared__ __attribute__((aligned(16))) unsigned short Qr[32 * RLD], Dr[32 * RLD];     // scale Q rows, dO rows  [query][dim]
@@ -800,6 +805,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
   auto q_any = [&](int i0, int lo, int hi) {
     const int il = min(i0 + 32, a.Tq) - 1;
     if (hi < lo) return false;
+    if (FULL) return true;
     if (a.mode == 0) return lo <= il;                                          // j <= i for some pair
     if (a.mode == 1) return hi >= i0;
     if (lo == 0) return true;
@@ -866,7 +872,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         keep |= (((w >> (j & 7)) & 1u) << (2 * c)) | (((w >> (8 + (j & 7))) & 1u) << (2 * c + 1));
       }
     }
-    const unsigned okm = a.mode == 0 ? mask_bits_kv<0>(a.Tq, j, kok, i0 + 4 * kh)
+    const unsigned okm = FULL ? mask_bits_kv<3>(a.Tq, j, kok, i0 + 4 * kh) : a.mode == 0 ? mask_bits_kv<0>(a.Tq, j, kok, i0 + 4 * kh)
                        : a.mode == 1 ? mask_bits_kv<1>(a.Tq, j, kok, i0 + 4 * kh) : mask_bits_kv<2>(a.Tq, j, kok, i0 + 4 * kh);
     unsigned pw[8], dw[8];
 #pragma unroll
@@ -1077,17 +1083,20 @@ extern "C" int ctdd_hollow_layernorm_bwd(const void* args_, void* stream) {
   return finish_launch("k_hollow_ln_bwd");
 }
 
-#define HD_DISPATCH(KERNEL, GRIDX)                                                                          \
-  switch (a.hd) {                                                                                            \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(GRIDX, a.H, a.B), dim3(TQ), 0, (hipStream_t)stream, a); break;   \
-    case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(GRIDX, a.H, a.B), dim3(TQ), 0, (hipStream_t)stream, a); break;   \
-    case 16: hipLaunchKernelGGL(KERNEL<16>, dim3(GRIDX, a.H, a.B), dim3(TQ), 0, (hipStream_t)stream, a); break; \
-    case 32: hipLaunchKernelGGL(KERNEL<32>, dim3(GRIDX, a.H, a.B), dim3(TQ), 0, (hipStream_t)stream, a); break; \
+#define HD_DISPATCH_(KERNEL, FULL, GRIDX)                                                                         \
+  switch (a.hd) {                                                                                                  \
+    case 4: hipLaunchKernelGGL((KERNEL<4, FULL>), dim3(GRIDX, a.H, a.B), dim3(TQ), 0, (hipStream_t)stream, a); break;   \
+    case 8: hipLaunchKernelGGL((KERNEL<8, FULL>), dim3(GRIDX, a.H, a.B), dim3(TQ), 0, (hipStream_t)stream, a); break;   \
+    case 16: hipLaunchKernelGGL((KERNEL<16, FULL>), dim3(GRIDX, a.H, a.B), dim3(TQ), 0, (hipStream_t)stream, a); break; \
+    case 32: hipLaunchKernelGGL((KERNEL<32, FULL>), dim3(GRIDX, a.H, a.B), dim3(TQ), 0, (hipStream_t)stream, a); break; \
     default: CTDD_REQUIRE(false, CTDD_ERANGE, "attention (training): head dimension %d (4, 8, 16 or 32)", a.hd);   \
   }
+#define HD_DISPATCH(KERNEL, GRIDX)                     \
+  if (a.mode == 3) { HD_DISPATCH_(KERNEL, true, GRIDX) } \
+  else { HD_DISPATCH_(KERNEL, false, GRIDX) }
 static int attn_check(const AttnTrainArgs& a) {
   CTDD_REQUIRE(a.q && a.k && a.v && a.out && a.stats, CTDD_EINVAL, "attention (training): null buffer");
-  CTDD_REQUIRE(a.mode >= 0 && a.mode <= 2 && (a.mode != 2 || a.Tk == 2 * a.Tq + 1), CTDD_EINVAL, "attention (training): mode %d Tq=%d Tk=%d", a.mode, a.Tq, a.Tk);
+  CTDD_REQUIRE(a.mode >= 0 && a.mode <= 3 && (a.mode != 2 || a.Tk == 2 * a.Tq + 1), CTDD_EINVAL, "attention (training): mode %d Tq=%d Tk=%d", a.mode, a.Tq, a.Tk);
   CTDD_REQUIRE(a.drop_p >= 0.0f && a.drop_p < 1.0f && (a.drop_p == 0.0f || a.rng), CTDD_EINVAL, "attention (training): dropout %g", (double)a.drop_p);
   return CTDD_OK;
 }
@@ -1107,11 +1116,19 @@ extern "C" int ctdd_hollow_attention_bwd(const void* args_, void* stream) {
   return finish_launch("k_hollow_attn_bwd_kv");
 }
 #undef HD_DISPATCH
+#undef HD_DISPATCH_
 
 constexpr int ATT_NW = CTDD_ATT_NW;
-#define HD_DISPATCH_MFMA(KERNEL16, KERNEL32, GRIDX)                                                                  \
+#define HD_LAUNCH_MFMA(KERNEL16, KERNEL32, GRIDX)                                                                     \
   if (a.hd == 16) hipLaunchKernelGGL(KERNEL16, dim3(GRIDX, a.H, a.B), dim3(64 * ATT_NW), 0, (hipStream_t)stream, a); \
   else hipLaunchKernelGGL(KERNEL32, dim3(GRIDX, a.H, a.B), dim3(64 * ATT_NW), 0, (hipStream_t)stream, a);
+// KERNEL(HD, FULL): the instantiation; mode 3 takes the unmasked one
+#define HD_DISPATCH_MFMA(KERNEL, GRIDX)                                         \
+  if (a.mode == 3) { HD_LAUNCH_MFMA(KERNEL(16, true), KERNEL(32, true), GRIDX) }  \
+  else { HD_LAUNCH_MFMA(KERNEL(16, false), KERNEL(32, false), GRIDX) }
+#define K_ATT_FWD(HD, FULL) (k_hollow_attn_q_mfma<HD, false, ATT_NW, FULL>)
+#define K_ATT_DQ(HD, FULL) (k_hollow_attn_q_mfma<HD, true, ATT_NW, FULL>)
+#define K_ATT_DKV(HD, FULL) (k_hollow_attn_kv_mfma<HD, ATT_NW, FULL>)
 static int attn_check_mfma(const AttnTrainArgs& a) {
   if (int rc = attn_check(a)) return rc;
   CTDD_REQUIRE(a.hd == 16 || a.hd == 32, CTDD_ERANGE, "attention (training, matrix cores): head dimension %d (16 or 32)", a.hd);
@@ -1122,7 +1139,7 @@ static int attn_check_mfma(const AttnTrainArgs& a) {
 extern "C" int ctdd_hollow_attention_train_bf16(const void* args_, void* stream) {
   const AttnTrainArgs& a = *(const AttnTrainArgs*)args_;
   if (int rc = attn_check_mfma(a)) return rc;
-  HD_DISPATCH_MFMA((k_hollow_attn_q_mfma<16, false, ATT_NW>), (k_hollow_attn_q_mfma<32, false, ATT_NW>), (a.Tq + 32 * ATT_NW - 1) / (32 * ATT_NW))
+  HD_DISPATCH_MFMA(K_ATT_FWD, (a.Tq + 32 * ATT_NW - 1) / (32 * ATT_NW))
   return finish_launch("k_hollow_attn_q_mfma (forward)");
 }
 extern "C" int ctdd_hollow_attention_bwd_bf16(const void* args_, void* stream) {
@@ -1131,9 +1148,9 @@ extern "C" int ctdd_hollow_attention_bwd_bf16(const void* args_, void* stream) {
   CTDD_REQUIRE(a.d_out && (a.dq || a.dq_bf16) && (a.dk || a.dk_bf16) && (a.dv || a.dv_bf16), CTDD_EINVAL, "attention bwd: null gradient buffer");
   CTDD_REQUIRE(a.dq_rs % 4 == 0 && a.dk_rs % 4 == 0 && a.dv_rs % 4 == 0 && a.dq_bs % 4 == 0 && a.dk_bs % 4 == 0 && a.dv_bs % 4 == 0, CTDD_EINVAL,
                "attention bwd (matrix cores): gradient rows must be 16-byte aligned");
-  HD_DISPATCH_MFMA((k_hollow_attn_q_mfma<16, true, ATT_NW>), (k_hollow_attn_q_mfma<32, true, ATT_NW>), (a.Tq + 32 * ATT_NW - 1) / (32 * ATT_NW))
+  HD_DISPATCH_MFMA(K_ATT_DQ, (a.Tq + 32 * ATT_NW - 1) / (32 * ATT_NW))
   if (int rc = finish_launch("k_hollow_attn_q_mfma (dQ)")) return rc;
-  HD_DISPATCH_MFMA((k_hollow_attn_kv_mfma<16, ATT_NW>), (k_hollow_attn_kv_mfma<32, ATT_NW>), (a.Tk + 32 * ATT_NW - 1) / (32 * ATT_NW))
+  HD_DISPATCH_MFMA(K_ATT_DKV, (a.Tk + 32 * ATT_NW - 1) / (32 * ATT_NW))
   return finish_launch("k_hollow_attn_kv_mfma");
 }
 

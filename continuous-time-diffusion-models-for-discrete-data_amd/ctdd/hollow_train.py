@@ -653,31 +653,23 @@ def training_supported(model):
     return (m.embed_dim // m.num_heads) in (4, 8, 16, 32) and m.embed_dim <= 256 and m.embed_dim % 16 == 0 and m.mlp_dim % 16 == 0
 
 
-class HollowTrainer:
-    def __init__(self, model, precision=None):
-        self.model, self.net = model, _unwrap(model.net)
-        m = self.net.config.model
-        self.precision = precision or getattr(m, "engine_train_precision", "bf16")
-        if self.precision not in ("fp32", "bf16"):
-            raise ValueError(f"unknown training precision {self.precision}")
-        self.dev = next(self.net.parameters()).device
-        if self.dev.type != "cuda":
-            raise native.CtddError("HollowTrainer needs the model on a GPU")
-        lib()
-        self.rng = torch.zeros(2, dtype=torch.int64, device=self.dev)
-        self.rng[0] = native.dropout_seed()
-        self.pe = None
-        self._pack_key, self._packs, self._pack_tab, self._pack_total = None, {}, None, 0
+class WeightPacks:
+    """The packed GEMM operands of a network's matrix-core linears, shared by the trainers (HollowTrainer, bert_train.BertTrainer):
+    ONE launch per forward converts every weight into the forward operand [N][K] and the data-gradient operand [K][N']
+    (transposed, N' = N rounded up to 16) in the mode's operand type; it also advances the dropout stream.  The table is rebuilt
+    when a parameter's storage moves."""
 
-    def _pack_weights(self, bump):
-        """ONE launch converts every matrix-core linear's weight into the forward operand [N][K] and the data-gradient
-        operand [K][N'] (transposed, N' = N rounded up to 16) in the mode's operand type; it also advances the dropout
-        stream.  The table is rebuilt when a parameter's storage moves."""
-        net, bf = self.net, self.precision == "bf16"
+    def __init__(self, net, bf16, dev):
+        self.net, self.bf16, self.dev = net, bf16, dev
+        self._key, self._packs, self._tab, self._total, self._n = None, {}, None, 0, 0
+
+    def refresh(self, rng):
+        """Repack every weight; rng: the {seed, step} tensor whose step the launch bumps, or None."""
+        net, bf = self.net, self.bf16
         ws = [p for n, p in net.named_parameters()
               if p.dim() == 2 and p.shape[1] % 16 == 0 and not n.startswith(("embedding", "temb_net", "input_embedding"))]
         key = tuple(p.data_ptr() for p in ws)
-        if key != self._pack_key:
+        if key != self._key:
             dt = torch.bfloat16 if bf else torch.float32
             total = sum(2 * p.shape[1] * (-(-p.shape[0] // 16) * 16) for p in ws)
             arena = torch.zeros(total, dtype=dt, device=self.dev)
@@ -693,14 +685,54 @@ class HollowTrainer:
                 t.N, t.Cin_tot, t.c_off, t.C, t.ntap, t.Ktot, t.koff, t.flip, t.ldd, t.first = N, K, 0, K, 1, K, 0, 0, ld, first
                 first += N * K
                 packs[id(p)] = (fwd, dg)
-            self._pack_key, self._packs, self._pack_total, self._arena = key, packs, first, arena
-            self._pack_tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.dev)
-            self._pack_n = len(ws)
-        _ck(lib().ctdd_unet_pack_weights(self._pack_tab.data_ptr(), self._pack_n, self._pack_total, 0 if bf else 1,
-                                         self.rng.data_ptr() if bump else None, _st()), "ctdd_unet_pack_weights")
+            self._key, self._packs, self._total, self._arena = key, packs, first, arena
+            self._tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.dev)
+            self._n = len(ws)
+        _ck(lib().ctdd_unet_pack_weights(self._tab.data_ptr(), self._n, self._total, 0 if bf else 1,
+                                         None if rng is None else rng.data_ptr(), _st()), "ctdd_unet_pack_weights")
 
-    def pk(self, w):
+    def __call__(self, w):
         return self._packs[id(w)]
+
+    def linear(self, x, w, b, use_bf, res=None):
+        """LinearFn on the packed operands when the pack's type is the layer's."""
+        return linear(x, w, b, use_bf, res, self(w) if use_bf == self.bf16 else None)
+
+
+def film_readout(rr, xr, temb, B, D, bf, pk):
+    """The FiLM residual readout (hollow_networks.py: ResidualReadout) over xr (B*D, E) with the per-sample time embedding temb
+    (B, E) -> logits (B, D, out_dim): the per-sample time MLP and FiLM linears in fp32, the per-token linears in the mode's
+    operand type, LayerNorm(h + r) with FiLM in one Function.  pk: the trainer's WeightPacks."""
+    dense = pk.linear
+    R, E2 = B * D, rr.input_layer.weight.shape[0]
+    lin = [l_ for l_ in rr.mlp.layers if isinstance(l_, torch.nn.Linear)]
+    tm = dense(ActFn.apply(dense(temb, lin[0].weight, lin[0].bias, False), 2, 0.0, None, 0), lin[1].weight, lin[1].bias, False)
+    hh = dense(xr, rr.input_layer.weight, rr.input_layer.bias, bf)
+    for i in range(rr.n_res):
+        mlp_i, ln_i = rr.resid_layers[2 * i], rr.resid_layers[2 * i + 1]
+        li = [l_ for l_ in mlp_i.layers if isinstance(l_, torch.nn.Linear)]
+        r_ = dense(ActFn.apply(dense(hh, li[0].weight, li[0].bias, bf), 2, 0.0, None, 0), li[1].weight, li[1].bias, bf)
+        fl = dense(tm, rr.film_layer[i].weight, rr.film_layer[i].bias, False)
+        hh = LayerNormFn.apply(hh.view(B, D, E2), r_.view(B, D, E2), ln_i.weight, ln_i.bias, fl, ln_i.eps).view(R, E2)
+    logits = dense(hh, rr.logits_layer.weight, rr.logits_layer.bias, bf)
+    return logits.view(B, D, rr.out_dim)
+
+
+class HollowTrainer:
+    def __init__(self, model, precision=None):
+        self.model, self.net = model, _unwrap(model.net)
+        m = self.net.config.model
+        self.precision = precision or getattr(m, "engine_train_precision", "bf16")
+        if self.precision not in ("fp32", "bf16"):
+            raise ValueError(f"unknown training precision {self.precision}")
+        self.dev = next(self.net.parameters()).device
+        if self.dev.type != "cuda":
+            raise native.CtddError("HollowTrainer needs the model on a GPU")
+        lib()
+        self.rng = torch.zeros(2, dtype=torch.int64, device=self.dev)
+        self.rng[0] = native.dropout_seed()
+        self.pe = None
+        self.pk = WeightPacks(self.net, self.precision == "bf16", self.dev)
 
     def __call__(self, x, times):
         net = self.net
@@ -712,7 +744,7 @@ class HollowTrainer:
         training = bool(self.model.training)
         p_drop = float(m.dropout_rate) if training else 0.0
         p_att = float(m.attention_dropout_rate) if training else 0.0
-        self._pack_weights(bump=training)                     # (+ one dropout stream per training forward)
+        self.pk.refresh(self.rng if training else None)       # (+ one dropout stream per training forward)
         # every forward keeps its OWN {seed, step}: the Functions save this tensor and their backward kernels read the step
         # from it, so a second training forward before the first one's backward (two-forward-pass CT-ELBO, gradient
         # accumulation over micro-batches) must not move the first one's masks
@@ -743,9 +775,7 @@ class HollowTrainer:
                                      (B, D, E, p_drop, nxt(), nxt(), bf, ff.norm.eps, pk(ff.mlp.fc1.weight), pk(ff.mlp.fc2.weight)))
             streams.append(h)
         l2r, r2l = streams
-        def dense(x_, w_, b_, use_bf, res=None):                # packed operands when the pack's type is the layer's
-            return linear(x_, w_, b_, use_bf, res, pk(w_) if use_bf == bf else None)
-
+        dense = pk.linear
         # ---- attention readout (prenorm): cross attention over [temb | ln1(l2r) | ln2(r2l)] + (l2r + r2l)
         ro = net.readout_module
         ca = ro.cross_attention
@@ -760,17 +790,4 @@ class HollowTrainer:
         vb = dense(allk, ca.dense_val.weight, ca.dense_val.bias, bf)
         ctxv = AttentionFn.apply(qb, kb, vb, B, D, Tk, H, hd, 2, 0.0, None, nxt(), bf)
         xr = dense(ctxv, ca.out_linear.weight, ca.out_linear.bias, bf, res=raw)
-        # ---- FiLM residual readout
-        rr = ro.model
-        E2 = 2 * E
-        lin = [l_ for l_ in rr.mlp.layers if isinstance(l_, torch.nn.Linear)]
-        tm = dense(ActFn.apply(dense(temb, lin[0].weight, lin[0].bias, False), 2, 0.0, None, 0), lin[1].weight, lin[1].bias, False)
-        hh = dense(xr, rr.input_layer.weight, rr.input_layer.bias, bf)
-        for i in range(rr.n_res):
-            mlp_i, ln_i = rr.resid_layers[2 * i], rr.resid_layers[2 * i + 1]
-            li = [l_ for l_ in mlp_i.layers if isinstance(l_, torch.nn.Linear)]
-            r_ = dense(ActFn.apply(dense(hh, li[0].weight, li[0].bias, bf), 2, 0.0, None, 0), li[1].weight, li[1].bias, bf)
-            fl = dense(tm, rr.film_layer[i].weight, rr.film_layer[i].bias, False)
-            hh = LayerNormFn.apply(hh.view(B, D, E2), r_.view(B, D, E2), ln_i.weight, ln_i.bias, fl, ln_i.eps).view(R, E2)
-        logits = dense(hh, rr.logits_layer.weight, rr.logits_layer.bias, bf)
-        return logits.view(B, D, rr.out_dim)
+        return film_readout(ro.model, xr, temb, B, D, bf, pk)

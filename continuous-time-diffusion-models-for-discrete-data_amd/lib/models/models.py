@@ -267,9 +267,10 @@ class HollowTransformer(nn.Module):
 
 class _EncoderModel(nn.Module):
     """Shared wrapper of the two single-stream transformer score models (hollow_networks.py: BertEnumTransformer,
-    EnumerativeTransformer).  Inference under eval() / no_grad runs the HIP plan of ctdd/bert_engine.py; with gradients enabled
-    or in train mode the autograd module runs (there are no training kernels for these nets): one RuntimeWarning per model
-    unless cfg.model.engine_train == "torch" says that this is meant."""
+    EnumerativeTransformer).  Inference under eval() / no_grad runs the HIP plan of ctdd/bert_engine.py.  With gradients enabled
+    or in train mode the autograd module runs -- one RuntimeWarning per model unless cfg.model.engine_train == "torch" says that
+    this is meant -- except under cfg.model.engine_train == "hip-encoder", which trains the x0-prediction model on the HIP
+    kernels of ctdd/bert_train.py (the masked models have no training kernels: one RuntimeWarning, then the module)."""
 
     _net_class = None
     _engine_int32_states = True          # forward() takes the samplers' int32 states as they are
@@ -280,10 +281,22 @@ class _EncoderModel(nn.Module):
         net = getattr(hollow_networks, self._net_class)(cfg).to(device)
         self.net = _maybe_ddp(net, cfg, rank)
         self.cfg = cfg
-        self._engine = None
+        self._engine, self._trainer = None, None
 
     def forward(self, x, times):
-        if self._use_engine(x):
+        mode = self._use_engine(x)
+        if mode == "train":
+            from ctdd import bert_train
+            if self._trainer is None:
+                # cfg.model.engine_train_precision: "bf16" (default) or "fp32", as for the hollow transformer
+                self._trainer = bert_train.BertTrainer(self)
+            inner = unwrap(self.net)
+            inner._engine_hook = self._trainer          # through DistributedDataParallel.forward when wrapped
+            try:
+                return self.net(x, times)
+            finally:
+                inner._engine_hook = None
+        if mode:
             from ctdd import bert_engine
             if self._engine is None:
                 # cfg.model.engine_precision: "bf16x3" (default), "fp32" or "bf16", as for the hollow transformer
@@ -293,11 +306,19 @@ class _EncoderModel(nn.Module):
         return self.net(x, times)
 
     def _use_engine(self, x):
+        """False: the module; True: the inference plan; "train": the training kernels."""
         if getattr(self.cfg.model, "engine", "hip") != "hip" or not x.is_cuda:
             return False
         from ctdd import bert_engine
         if torch.is_grad_enabled() or self.training:
-            if getattr(self.cfg.model, "engine_train", "hip") != "torch":
+            engine_train = getattr(self.cfg.model, "engine_train", "hip")
+            if engine_train == "hip-encoder":
+                from ctdd import bert_train
+                if x.dtype in (torch.int64, torch.int32) and bert_train.training_supported(self):
+                    return "train"
+                _warn_once(self, "bert-train-encoder", "this network, shape or state dtype is outside the HIP encoder training kernels' "
+                                                       "coverage (x0-prediction models only); training runs on torch device ops")
+            elif engine_train != "torch":
                 _warn_once(self, "bert-train", "no HIP training kernels for this network; training runs on torch device ops "
                                                "(set cfg.model.engine_train = 'torch' to say so)")
             return False

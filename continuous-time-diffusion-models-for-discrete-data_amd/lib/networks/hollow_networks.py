@@ -332,6 +332,9 @@ class BertEnumTransformer(nn.Module):
         self.input_embedding = _token_embedding(config, self.S)
 
     def forward(self, x, t):
+        hook = getattr(self, "_engine_hook", None)       # the HIP training path (ctdd/bert_train.py), entered through
+        if hook is not None:                             # this forward so a DistributedDataParallel wrapper sees the call
+            return hook(x, t)
         temb = transformer_timestep_embedding(t * self.temb_scale, self.embed_dim)
         x = x.view(x.shape[0], -1)
         embed = self.trans_encoder(_embed_tokens(self, x, self.S), temb)

@@ -33,6 +33,18 @@ int ctdd_bert_attention_short(const void* attn_args, void* stream);
 int ctdd_bert_gather(const float* enc, const int32_t* r0, int rows, int enumerate, int B, int D, int cond, int E, float* out, void* out_bf16,
                      void* out_lo, void* stream);
 
+/* backward of ctdd_bert_embed in plain mode: g (B, D + 1, E) is the gradient of `out`; dw_in[e] += sum_{b,d} g[b][1 + d][e]
+ * (2 x_bd / (S - 1) - 1), db_in[e] += sum_{b,d} g[b][1 + d][e] (fp32 atomics: the caller zeroes dw and db).  Row 0, the time
+ * embedding, has no parameters. */
+typedef struct {
+  const int64_t* x64; const int32_t* x32; const float* g; int B, D, E, S; float* dw; float* db;
+} ctdd_bert_embed_bwd_args;
+int ctdd_bert_embed_bwd(const void* embed_bwd_args, void* stream);
+
+/* backward of ctdd_bert_gather in plain mode with cond = 0 (anything else: CTDD_EINVAL): d_out (B D, E) goes to rows 1..D of
+ * d_enc (B, D + 1, E), row 0 of every sequence is written as zero. */
+int ctdd_bert_gather_bwd(const float* d_out, int B, int D, int cond, int E, float* d_enc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
