@@ -34,8 +34,9 @@ struct StepArgs {
   float* out_b;          // ratio | ll_xt
   int32_t* out_x;
   int32_t* out_changed;
-  // row-list launches (ctdd_tauleap_step_rows): launch row v < n_rows works on row rows[v] of the N*D row space -- loads,
-  // stores and the Philox counter all take rows[v]; the full launches leave both fields zero and use the identity
+  // row-list launches (the ctdd_*_rows entry points): launch row v < n_rows works on row rows[v] of the N*D row space -- loads,
+  // stores (out_x, out_a), the explicit noise E and the Philox counter all take rows[v]; the full launches leave both fields
+  // zero and use the identity
   const int32_t* rows;
   int64_t n_rows;
 };
@@ -127,8 +128,9 @@ __device__ inline float grp_scan(float v, int G, int li) {
 }
 
 constexpr int ROWS_PER_WAVE = 4;
-// ROWS: the row-list variant (MODE_TAULEAP only): R counts the listed rows, a row group's loads, stores and Philox counter go
-// through a.rows (dead lanes clamp to the last listed row); false is the full launch, unchanged.
+// ROWS: the row-list variant (MODE_TAULEAP, MODE_LBJF, MODE_MIDPOINT, MODE_EXACT and the pre_rates tails): R counts the listed
+// rows, a row group's loads, stores, noise reads (E) and Philox counter go through a.rows (dead lanes clamp to the last listed
+// row and store nothing, so the counters run over live listed rows only); false is the full launch, unchanged.
 template <int EPT, bool ROWS = false>
 __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -546,7 +548,9 @@ __global__ __launch_bounds__(256) void k_rows(const StepArgs a) {
 // states one int4 each way), both tables sit in LDS, and every row loop is unrolled straight-line code in the operation order
 // of k_rows with G = 1 (sequential sums in s order -- for S <= 4 bit-identical to it, for 5 <= S <= 8 the oracle's own order
 // where k_rows uses a lane tree).  Same Philox streams, same draw rules (draw.hpp).
-// ROWS (MODE_TAULEAP only): the thread's four rows are launch rows of the list a.rows, gathered one by one; false: unchanged.
+// ROWS (MODE_TAULEAP, MODE_LBJF, MODE_MIDPOINT): the thread's four rows are launch rows of the list a.rows, gathered one by
+// one, and every store / noise read / Philox counter takes the listed row P[r]; false: unchanged.  There is no row-list
+// MODE_RATES: its store path writes by launch row (small_rows_ok keeps it away).
 template <int S, int MODE, bool ROWS = false>
 __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
   __shared__ float Tq[S * S], Tr[S * S];
@@ -797,7 +801,14 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
 
 template <int S>
 static void launch_small_mode(const StepArgs& a, dim3 g, hipStream_t st) {
-  if (a.rows) { hipLaunchKernelGGL((k_rows_small<S, MODE_TAULEAP, true>), g, dim3(256), 0, st, a); return; }   // (tau-leap only)
+  if (a.rows) {                 // row-list launch (small_rows_ok admits no MODE_RATES here)
+    switch (a.mode) {
+      case MODE_TAULEAP: hipLaunchKernelGGL((k_rows_small<S, MODE_TAULEAP, true>), g, dim3(256), 0, st, a); break;
+      case MODE_LBJF: hipLaunchKernelGGL((k_rows_small<S, MODE_LBJF, true>), g, dim3(256), 0, st, a); break;
+      default: hipLaunchKernelGGL((k_rows_small<S, MODE_MIDPOINT, true>), g, dim3(256), 0, st, a); break;
+    }
+    return;
+  }
   switch (a.mode) {
     case MODE_RATES: hipLaunchKernelGGL((k_rows_small<S, MODE_RATES>), g, dim3(256), 0, st, a); break;
     case MODE_TAULEAP: hipLaunchKernelGGL((k_rows_small<S, MODE_TAULEAP>), g, dim3(256), 0, st, a); break;
@@ -809,6 +820,7 @@ static void launch_small_mode(const StepArgs& a, dim3 g, hipStream_t st) {
 static bool small_rows_ok(const StepArgs& a) {
   if (a.S > 8 || a.tidx || a.pre_rates) return false;
   if (a.mode != MODE_RATES && a.mode != MODE_TAULEAP && a.mode != MODE_LBJF && a.mode != MODE_MIDPOINT) return false;
+  if (a.rows && a.mode == MODE_RATES) return false;          // (k_rows_small stores rates by launch row)
   auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
   return al16(a.logits) && al16(a.x) && al16(a.x_base) && al16(a.out_x) && (a.mode != MODE_RATES || (al16(a.out_a) && al16(a.out_b)));
 }
@@ -844,7 +856,8 @@ static int launch_rows(const StepArgs& a0, void* stream) {
   CTDD_REQUIRE(grid > 0 && grid < (1ll << 31), CTDD_ERANGE, "rows out of range: %lld", (long long)R);
   hipStream_t st = (hipStream_t)stream;
   dim3 g((unsigned)grid), b(256);
-  if (a.rows) {                 // row-list launch (tau-leap only): the same kernels with the ROWS indirection
+  if (a.rows) {                 // row-list launch (tau-leap, LBJF, midpoint, exact and the pre_rates tails): the same kernels
+                                // with the ROWS indirection
     if (ept_need <= 1) hipLaunchKernelGGL((k_rows<1, true>), g, b, 0, st, a);
     else if (ept_need <= 2) hipLaunchKernelGGL((k_rows<2, true>), g, b, 0, st, a);
     else if (ept_need <= 4) hipLaunchKernelGGL((k_rows<4, true>), g, b, 0, st, a);
@@ -874,6 +887,18 @@ static int check_branch(int branch, int logit_type, const void* qt0, const void*
   CTDD_REQUIRE(qt0 || (branch == CTDD_BRANCH_CRM && logit_type == CTDD_LOGIT_DIRECT), CTDD_EINVAL,
                "qt0 table required for this branch/logit_type");
   return CTDD_OK;
+}
+
+// the row-list part of every ctdd_*_rows entry point (include/ctdd.h): 1 = launch, 0 = return *status (refused, or nothing to do)
+static int check_row_list(const int32_t* out_x, const int32_t* x, const int32_t* rows, int n_rows, int N, int D, int* status) {
+  *status = [&]() -> int {
+    CTDD_REQUIRE(out_x, CTDD_EINVAL, "null output");
+    CTDD_REQUIRE(out_x != x, CTDD_EINVAL, "out_x must not alias x (unlisted rows are not written)");
+    CTDD_REQUIRE(n_rows >= 0 && (int64_t)n_rows <= (int64_t)N * D, CTDD_ERANGE, "n_rows=%d outside [0, N*D]", n_rows);
+    CTDD_REQUIRE(n_rows == 0 || rows, CTDD_EINVAL, "null row list");
+    return CTDD_OK;
+  }();
+  return *status == CTDD_OK && n_rows > 0;
 }
 
 }  // namespace ctdd
@@ -1027,5 +1052,78 @@ extern "C" int ctdd_midpoint_from_rates(const float* rates, const int32_t* x, fl
   a.logits = rates; a.x = x; a.h = (float)(0.5 * (double)h); a.N = N; a.D = D; a.S = S;
   a.mode = MODE_MIDPOINT; a.pre_rates = 1;
   a.out_x = out_x;
+  return launch_rows(a, stream);
+}
+
+/* The LBJF, midpoint-predictor and exact steps and the two pre_rates tails on the listed rows only (include/ctdd.h, the
+ * contract above ctdd_tauleap_step_rows): the full entry point's StepArgs plus the row list; E and out_probs stay (N*D, S)
+ * and are indexed by the listed row. */
+extern "C" int ctdd_lbjf_step_rows(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
+                                   const float* base_rate, float beta, float eps, float h, uint32_t flags, const float* E,
+                                   uint64_t seed, uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
+                                   int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream) {
+  if (int rc = check_common(logits, x, N, D, S)) return rc;
+  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
+  int st;
+  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
+  StepArgs a{};
+  a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = base_rate; a.beta = beta; a.eps = eps; a.h = h;
+  a.flags = flags; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
+  a.branch = branch; a.logit_type = logit_type; a.mode = MODE_LBJF;
+  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed; a.rows = rows; a.n_rows = n_rows;
+  return launch_rows(a, stream);
+}
+
+extern "C" int ctdd_midpoint_predict_rows(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
+                                          const float* base_rate, float beta, float eps, float h, int N, int D, int S,
+                                          const int32_t* rows, int n_rows, int32_t* out_x, void* stream) {
+  if (int rc = check_common(logits, x, N, D, S)) return rc;
+  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
+  int st;
+  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
+  StepArgs a{};
+  a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = base_rate; a.beta = beta; a.eps = eps;
+  a.h = (float)(0.5 * (double)h);   // as ctdd_midpoint_predict
+  a.N = N; a.D = D; a.S = S; a.branch = branch; a.logit_type = logit_type; a.mode = MODE_MIDPOINT;
+  a.out_x = out_x; a.rows = rows; a.n_rows = n_rows;
+  return launch_rows(a, stream);
+}
+
+extern "C" int ctdd_exact_step_rows(const float* logits, const int32_t* x, const float* q_lo, const float* q_step, const float* E,
+                                    uint64_t seed, uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
+                                    int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream) {
+  if (int rc = check_common(logits, x, N, D, S)) return rc;
+  CTDD_REQUIRE(q_lo && q_step, CTDD_EINVAL, "exact step: null table");
+  int st;
+  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
+  StepArgs a{};
+  a.logits = logits; a.x = x; a.qt0 = q_lo; a.rate = q_step; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
+  a.branch = CTDD_BRANCH_CRM; a.logit_type = CTDD_LOGIT_DIRECT; a.mode = MODE_EXACT;
+  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed; a.rows = rows; a.n_rows = n_rows;
+  return launch_rows(a, stream);
+}
+
+extern "C" int ctdd_lbjf_from_rates_rows(const float* rates, const int32_t* x, float h, const float* E, uint64_t seed,
+                                         uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows, int32_t* out_x,
+                                         float* out_probs, int32_t* out_changed, void* stream) {
+  if (int rc = check_common(rates, x, N, D, S)) return rc;
+  int st;
+  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
+  StepArgs a{};
+  a.logits = rates; a.x = x; a.h = h; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
+  a.mode = MODE_LBJF; a.pre_rates = 1;
+  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed; a.rows = rows; a.n_rows = n_rows;
+  return launch_rows(a, stream);
+}
+
+extern "C" int ctdd_midpoint_from_rates_rows(const float* rates, const int32_t* x, float h, int N, int D, int S,
+                                             const int32_t* rows, int n_rows, int32_t* out_x, void* stream) {
+  if (int rc = check_common(rates, x, N, D, S)) return rc;
+  int st;
+  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
+  StepArgs a{};
+  a.logits = rates; a.x = x; a.h = (float)(0.5 * (double)h); a.N = N; a.D = D; a.S = S;
+  a.mode = MODE_MIDPOINT; a.pre_rates = 1;
+  a.out_x = out_x; a.rows = rows; a.n_rows = n_rows;
   return launch_rows(a, stream);
 }

@@ -48,6 +48,11 @@ _SIGS = {
     "ctdd_midpoint_predict": ([_I, _I, _P, _P, _P, _P, _F, _F, _F, _I, _I, _I, _P, _P], _I),
     "ctdd_lbjf_from_rates": ([_P, _P, _F, _P, _U64, _U64, _I, _I, _I, _P, _P, _P, _P], _I),
     "ctdd_midpoint_from_rates": ([_P, _P, _F, _I, _I, _I, _P, _P], _I),
+    "ctdd_lbjf_step_rows": ([_I, _I, _P, _P, _P, _P, _F, _F, _F, _U32, _P, _U64, _U64, _I, _I, _I, _P, _I, _P, _P, _P, _P], _I),
+    "ctdd_midpoint_predict_rows": ([_I, _I, _P, _P, _P, _P, _F, _F, _F, _I, _I, _I, _P, _I, _P, _P], _I),
+    "ctdd_exact_step_rows": ([_P, _P, _P, _P, _P, _U64, _U64, _I, _I, _I, _P, _I, _P, _P, _P, _P], _I),
+    "ctdd_lbjf_from_rates_rows": ([_P, _P, _F, _P, _U64, _U64, _I, _I, _I, _P, _I, _P, _P, _P, _P], _I),
+    "ctdd_midpoint_from_rates_rows": ([_P, _P, _F, _I, _I, _I, _P, _I, _P, _P], _I),
     "ctdd_argmax": ([_P, _I, _I, _I, _P, _P], _I),
     "ctdd_initial_samples": ([_P, _U64, _U64, _I, _I, _I, _P, _P], _I),
     "ctdd_philox_uniform": ([_U64, _U64, _I64, _I, _P, _P], _I),
@@ -321,6 +326,90 @@ def midpoint_from_rates(rates, x, h):
     return out
 
 
+def _rows_probs(want_probs, probs, like):
+    """out_probs of a row-list step: `probs` (full size, unlisted rows untouched) when given, else a fresh uninitialised tensor."""
+    if not want_probs:
+        return None
+    if probs is None:
+        return torch.empty(like.shape, dtype=f32, device=like.device)
+    if tuple(probs.shape) != tuple(like.shape):
+        raise CtddError(f"probs: expected shape {tuple(like.shape)}, got {tuple(probs.shape)}")
+    return probs
+
+
+def lbjf_step_rows(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows, flags=0, E=None, seed=0, offset=0,
+                   out=None, want_probs=False, probs=None, changed=None):
+    """lbjf_step on the rows listed in `rows` (see tauleap_step_rows): listed rows of the state and of the probabilities are
+    bit-identical to the full step's, the others are `out` / `probs` as given (default: a copy of x / uninitialised).  E, when
+    given, is the full (N*D, S) noise: a listed row reads its own row of it."""
+    N, D, S = logits.shape
+    rp, nr = _row_list(rows, N, D)
+    out = _prefilled(out, x, N, D)
+    probs = _rows_probs(want_probs, probs, logits)
+    rc = load().ctdd_lbjf_step_rows(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
+                                    _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"), float(beta), float(eps),
+                                    float(h), int(flags), _ptr(E, f32, "E"), seed, offset, N, D, S, rp, nr, _ptr(out, i32, "out"),
+                                    _ptr(probs, f32, "probs"), _ptr(changed, i32, "changed"), _stream())
+    _check(rc, "ctdd_lbjf_step_rows")
+    _count("ctdd_lbjf_step_rows")
+    return (out, probs) if want_probs else out
+
+
+def exact_step_rows(logits, x, q_lo, q_step, rows, E=None, seed=0, offset=0, out=None, want_probs=False, probs=None, changed=None):
+    """exact_step on the rows listed in `rows` (see lbjf_step_rows)."""
+    N, D, S = logits.shape
+    rp, nr = _row_list(rows, N, D)
+    out = _prefilled(out, x, N, D)
+    probs = _rows_probs(want_probs, probs, logits)
+    rc = load().ctdd_exact_step_rows(_ptr(logits, f32, "logits"), _ptr(x, i32, "x"), _ptr(q_lo, f32, "q_lo"), _ptr(q_step, f32, "q_step"),
+                                     _ptr(E, f32, "E"), seed, offset, N, D, S, rp, nr, _ptr(out, i32, "out"), _ptr(probs, f32, "probs"),
+                                     _ptr(changed, i32, "changed"), _stream())
+    _check(rc, "ctdd_exact_step_rows")
+    _count("ctdd_exact_step_rows")
+    return (out, probs) if want_probs else out
+
+
+def midpoint_predict_rows(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows, out=None):
+    """midpoint_predict on the rows listed in `rows`: x' of a listed row is the full launch's, every other row of the result is
+    `out` as given (default: a copy of x, i.e. x' = x on the unlisted rows)."""
+    N, D, S = logits.shape
+    rp, nr = _row_list(rows, N, D)
+    out = _prefilled(out, x, N, D)
+    rc = load().ctdd_midpoint_predict_rows(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
+                                           _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"), float(beta),
+                                           float(eps), float(h), N, D, S, rp, nr, _ptr(out, i32, "out"), _stream())
+    _check(rc, "ctdd_midpoint_predict_rows")
+    _count("ctdd_midpoint_predict_rows")
+    return out
+
+
+def lbjf_from_rates_rows(rates, x, h, rows, E=None, seed=0, offset=0, out=None, want_probs=False, probs=None, changed=None):
+    """lbjf_from_rates on the rows listed in `rows`: `rates` (N, D, S) is read at the listed rows only (what
+    tauleap_step_s256_rows(want_rates=True) wrote there)."""
+    N, D, S = rates.shape
+    rp, nr = _row_list(rows, N, D)
+    out = _prefilled(out, x, N, D)
+    probs = _rows_probs(want_probs, probs, rates)
+    rc = load().ctdd_lbjf_from_rates_rows(_ptr(rates, f32, "rates"), _ptr(x, i32, "x"), float(h), _ptr(E, f32, "E"), seed, offset,
+                                          N, D, S, rp, nr, _ptr(out, i32, "out"), _ptr(probs, f32, "probs"),
+                                          _ptr(changed, i32, "changed"), _stream())
+    _check(rc, "ctdd_lbjf_from_rates_rows")
+    _count("ctdd_lbjf_from_rates_rows")
+    return (out, probs) if want_probs else out
+
+
+def midpoint_from_rates_rows(rates, x, h, rows, out=None):
+    """midpoint_from_rates on the rows listed in `rows` (see midpoint_predict_rows, lbjf_from_rates_rows)."""
+    N, D, S = rates.shape
+    rp, nr = _row_list(rows, N, D)
+    out = _prefilled(out, x, N, D)
+    rc = load().ctdd_midpoint_from_rates_rows(_ptr(rates, f32, "rates"), _ptr(x, i32, "x"), float(h), N, D, S, rp, nr,
+                                              _ptr(out, i32, "out"), _stream())
+    _check(rc, "ctdd_midpoint_from_rates_rows")
+    _count("ctdd_midpoint_from_rates_rows")
+    return out
+
+
 def argmax(logits):
     N, D, S = logits.shape
     out = torch.empty((N, D), dtype=i32, device=logits.device)
@@ -542,14 +631,18 @@ def tauleap_step_s256(logits, x, tables, i, beta, h, flags, seed, offset, x_base
 
 
 def tauleap_step_s256_rows(logits, x, tables, i, beta, h, flags, seed, offset, rows, x_base=None, out=None, changed=None,
-                           want_rates=False, rates=None):
+                           want_rates=False, rates=None, want_x=True):
     """tauleap_step_s256 on the rows listed in `rows` (see tauleap_step_rows).  want_rates: also the masked reverse rates of the
-    listed rows, into `rates` (N, D, 256) f32 when given (unlisted rows untouched), else into a fresh uninitialised tensor."""
+    listed rows, into `rates` (N, D, 256) f32 when given (unlisted rows untouched), else into a fresh uninitialised tensor.
+    want_x=False (with want_rates): the listed rows' rates only -- no draw, no state, the returned state is None (the first
+    half of an S = 256 LBJF / midpoint step, as tauleap_step_s256(want_rates=True, want_x=False) is of the full one)."""
     N, D, S = logits.shape
     if S != 256:
         raise CtddError("tauleap_step_s256_rows needs S == 256")
+    if not want_x and not want_rates:
+        raise CtddError("tauleap_step_s256_rows: want_x=False needs want_rates=True")
     rp, nr = _row_list(rows, N, D)
-    out = _prefilled(out, x, N, D)
+    out = _prefilled(out, x, N, D) if want_x else None
     if want_rates and rates is None:
         rates = torch.empty(logits.shape, dtype=f32, device=logits.device)
     lflag = 0
@@ -562,7 +655,7 @@ def tauleap_step_s256_rows(logits, x, tables, i, beta, h, flags, seed, offset, r
                                             float(beta), float(h),
                                             int(flags) | (STEP_CRM if tables.crm else 0) | (STEP_BF16 if tables.bf16 else 0) | lflag,
                                             seed, offset, N, D, rp, nr, _ptr(rates, f32, "rates") if want_rates else None,
-                                            _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream())
+                                            _ptr(out, i32, "out") if want_x else None, _ptr(changed, i32, "changed"), _stream())
     _check(rc, "ctdd_tauleap_step_s256_rows")
     _count("ctdd_tauleap_step_s256_rows")
     return (out, rates) if want_rates else out

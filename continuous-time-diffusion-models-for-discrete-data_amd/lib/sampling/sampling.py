@@ -1,6 +1,7 @@
 """Samplers behind the reference's registry names (lib/sampling/sampling.py): TauL 82-234,
 LBJF 238-356, MidPointTauL 360-526, PCTauL 530-646, ConditionalTauLeaping 649-758,
-ConditionalPCTauLeaping 761-905.
+ConditionalPCTauLeaping 761-905, ExactSampling 975-1061; ConditionalLBJF, ConditionalMidPointTauL and
+ConditionalExactSampling (not in the reference) hold entries the way its two conditional samplers do.
 
 Same constructor `(cfg)`, same `sample(model, N)` return shapes; the per-step work is one fused
 libctdd launch (reverse rates -> jump draw -> state update) on int32 device state.  Differences
@@ -150,13 +151,14 @@ class _GridSampler:
         return native.tauleap_step(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta,
                                    self.eps_ratio, h, flags, key, offset, x_base=x_base, changed=changed)
 
-    def _leap_rows(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, rows, changed=None):
+    def _leap_rows(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, rows, changed=None, x_base=None):
         """_leap on the listed rows only (int32 device tensor of row indices into the N*D rows); the other rows of the returned
         state are those of x."""
         if fast is not None:
-            return native.tauleap_step_s256_rows(logits, x, fast, i, beta, h, flags, key, offset, rows, changed=changed)
+            return native.tauleap_step_s256_rows(logits, x, fast, i, beta, h, flags, key, offset, rows, x_base=x_base,
+                                                 changed=changed)
         return native.tauleap_step_rows(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta,
-                                        self.eps_ratio, h, flags, key, offset, rows, changed=changed)
+                                        self.eps_ratio, h, flags, key, offset, rows, x_base=x_base, changed=changed)
 
     def _lbjf(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, changed=None):
         """One Euler / LBJF step; at S = 256 the reverse rates come from the matrix-core kernel, the posterior and the
@@ -167,6 +169,16 @@ class _GridSampler:
             return native.lbjf_from_rates(rates, x, h, None, key, offset, changed=changed)
         return native.lbjf_step(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta, self.eps_ratio,
                                 h, flags, None, key, offset, changed=changed)
+
+    def _lbjf_rows(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, rows, rates=None, changed=None):
+        """_lbjf on the listed rows only; the other rows of the returned state are those of x.  `rates`: the (N, D, 256) buffer
+        the S = 256 pair passes the listed rows' rates through (allocated once per call by the sampler)."""
+        if fast is not None:
+            native.tauleap_step_s256_rows(logits, x, fast, i, beta, h, flags & native.STEP_CORRECTOR, key, offset, rows,
+                                          want_rates=True, rates=rates, want_x=False)
+            return native.lbjf_from_rates_rows(rates, x, h, rows, None, key, offset, changed=changed)
+        return native.lbjf_step_rows(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta, self.eps_ratio,
+                                     h, rows, flags, None, key, offset, changed=changed)
 
     @staticmethod
     def _t_ones(t32, i, N, device):
@@ -300,6 +312,11 @@ class LBJF(_GridSampler):
         self.num_corrector_steps = s.num_corrector_steps
 
     def sample(self, model, N):
+        return self._loop(model, N)
+
+    def _loop(self, model, N, held=None):
+        """The sampler loop.  held = (x_known int32, mask bool, free-row list), all on the device (ConditionalLBJF): the held
+        entries are scattered in after the initial draw, every step moves the listed rows only, and they are restored at the end."""
         dev = torch.device(model.device)
         key = self._key()
         with torch.no_grad(), self._borrow(model):
@@ -309,18 +326,27 @@ class LBJF(_GridSampler):
             changed = torch.zeros(self.num_steps, dtype=torch.int32, device=dev)
             fast = self._fast_tables(model, qt0)
             sub = 1 + max(int(self.num_corrector_steps), 0)
+            if held is None:
+                step = self._lbjf
+            else:
+                xk, m, rows = held
+                x = torch.where(m, xk, x)
+                rates = torch.empty((N, self.D, self.S), dtype=torch.float32, device=dev) if fast is not None else None
+                step = lambda *a, **kw: self._lbjf_rows(*a, rows, rates=rates, **kw)
             for i, t in enumerate(ts[:-1]):
                 h = float(np.float32(ts[i] - ts[i + 1]))
                 t_ones = self._t_ones(t32, i, N, dev)
                 q_i = qt0[i] if qt0 is not None else None
                 logits = self._net_logits(model, x, t_ones, fast)
-                x = self._lbjf(model, logits, x, q_i, fast, i, betas[i], h, 0, key, i * sub, changed=changed[i:i + 1])
+                x = step(model, logits, x, q_i, fast, i, betas[i], h, 0, key, i * sub, changed=changed[i:i + 1])
                 if t <= self.corrector_entry_time:
                     for c in range(self.num_corrector_steps):
                         logits = self._net_logits(model, x, t_ones, fast)
-                        x = self._lbjf(model, logits, x, q_i, fast, i, betas[i], h, native.STEP_CORRECTOR, key, i * sub + 1 + c)
+                        x = step(model, logits, x, q_i, fast, i, betas[i], h, native.STEP_CORRECTOR, key, i * sub + 1 + c)
             if self.loss_name == "CTElbo":
                 x = self._final_argmax(model, x, N)
+            if held is not None:
+                x = torch.where(m, xk, x)
             return x.cpu().numpy().astype(int), (changed.cpu().numpy() / N).tolist()
 
 
@@ -338,10 +364,18 @@ class MidPointTauL(_GridSampler):
         self.device = cfg.device
 
     def sample(self, model, N):
+        return self._loop(model, N)
+
+    def _loop(self, model, N, held=None):
+        """The sampler loop; held as in LBJF._loop (ConditionalMidPointTauL): both stages move the listed rows only, so x' = x
+        on the held rows."""
         dev = torch.device(model.device)
         key = self._key()
         with torch.no_grad(), self._borrow(model):
             x = self._initial(model, N, key, self.cfg.model.Q_sigma)
+            if held is not None:
+                xk, m, rows = held
+                x = torch.where(m, xk, x)
             h = (self.max_t - self.min_t) / self.num_steps
             full, half, t = [], [], self.max_t
             while t - 0.5 * h > self.min_t:
@@ -362,10 +396,29 @@ class MidPointTauL(_GridSampler):
             cnt = torch.zeros(nst, 5, dtype=torch.int32, device=dev)
             flags = (native.STEP_ORDINAL if self.is_ordinal else 0) | native.STEP_COUNT_RAW | native.STEP_COUNT_JUMPS
             hf = float(np.float32(h))
+            rates = (torch.empty((N, self.D, self.S), dtype=torch.float32, device=dev)
+                     if held is not None and fast_full is not None else None)
             for i in range(nst):
                 t_ones = torch.full((N,), float(t32[i]), device=dev)
                 t_05 = torch.full((N,), float(t32_half[i]), device=dev)
                 logits = self._net_logits(model, x, t_ones, fast_full)
+                if held is not None:                # the same two stages on the free rows
+                    if fast_full is not None:
+                        native.tauleap_step_s256_rows(logits, x, fast_full, i, b_full[i], hf, 0, key, 0, rows, want_rates=True,
+                                                      rates=rates, want_x=False)
+                        x_prime = native.midpoint_from_rates_rows(rates, x, h, rows)
+                    else:
+                        x_prime = native.midpoint_predict_rows(self.branch, self.logit_type, logits, x,
+                                                               q_full[i] if need_q else None, pr.base_rate, b_full[i],
+                                                               self.eps_ratio, h, rows)
+                    logits_p = self._net_logits(model, x_prime, t_05, fast_half)
+                    # (x_base = x' also on the held rows, where x' = x: _leap_rows' x_base is only read at the listed rows)
+                    x_new = self._leap_rows(model, logits_p, x, q_half[i] if need_q else None, fast_half, i, b_half[i], hf,
+                                            flags, key, i, rows, changed=cnt[i, 0:3], x_base=x_prime)
+                    cnt[i, 3] = (x != x_prime).sum()
+                    cnt[i, 4] = (x_prime != x_new).sum()
+                    x = x_new
+                    continue
                 if fast_full is not None:           # S = 256: rates from the matrix-core kernel, drift on them
                     _, rates = native.tauleap_step_s256(logits, x, fast_full, i, b_full[i], hf, 0, key, 0, want_rates=True,
                                                         want_x=False)
@@ -382,6 +435,8 @@ class MidPointTauL(_GridSampler):
                 x = x_new
             if self.loss_name == "CTElbo":
                 x = self._final_argmax(model, x, N)
+            if held is not None:
+                x = torch.where(m, xk, x)
             raw = cnt.cpu().numpy().astype(np.float64)
             c = raw / (N * self.D)
             # (samples, change_jump, change_dim, change_dim_first, change_1to2); change_jump = share of the jumping
@@ -604,10 +659,17 @@ class ExactSampling(_GridSampler):
         self.max_t = cfg.training.max_t
 
     def sample(self, model, N):
+        return self._loop(model, N)
+
+    def _loop(self, model, N, held=None):
+        """The sampler loop; held as in LBJF._loop (ConditionalExactSampling)."""
         dev = torch.device(model.device)
         key = self._key()
         with torch.no_grad(), borrow_engine_output(model, uniform_time=True):
             x = self._initial(model, N, key, self.cfg.model.Q_sigma).long()
+            if held is not None:
+                xk, m, rows = held
+                x = torch.where(m, xk.long(), x)
             ts = np.concatenate((np.linspace(self.max_t, self.min_t, self.num_steps), np.array([0])))
             pr = model.process
             t_hi = torch.from_numpy(ts[:-1]).to(torch.float32)
@@ -622,9 +684,68 @@ class ExactSampling(_GridSampler):
                 logits = model(x.long(), t_ones).float().contiguous()
                 # softmax, the S x S contraction with q_{t-h|0}, the column x_t of q_{t|t-h}, normalisation and the categorical
                 # draw (exponential race on Philox(key, i, row, s)) in ONE launch: ctdd_exact_step
-                x = native.exact_step(logits, x, q_lo[i], q_step[i], None, key, i, changed=moved[i:i + 1])
+                if held is not None:
+                    x = native.exact_step_rows(logits, x, q_lo[i], q_step[i], rows, None, key, i, changed=moved[i:i + 1])
+                else:
+                    x = native.exact_step(logits, x, q_lo[i], q_step[i], None, key, i, changed=moved[i:i + 1])
             change = moved.float() / float(N * self.D)
             return x.cpu().numpy().astype(int), change.cpu().tolist()
+
+
+class _ConditionedLoop(_Conditioned):
+    """ConditionalLBJF / ConditionalMidPointTauL / ConditionalExactSampling: the parent's loop (`_loop`) with held entries, see
+    _Conditioned.  Unlike the two tau-leaping samplers above, these follow the parent in everything but the held rows: branch
+    and logit type from cfg.loss, the grid from cfg.training.max_t, initial std cfg.model.Q_sigma, corrector / ordinal settings,
+    the final argmax exactly when the parent takes it, the parent's return tuple, and per-step counters with the parent's
+    normalisation that count free rows only.  The Philox counter is keyed by the row of the N*D space, so an all-free mask
+    returns the parent's samples bit for bit under the same seed on a deterministic model."""
+
+    def sample(self, model, N, conditioner):
+        x_known, mask = self._prefix(N, conditioner)
+        return self.inpaint(model, x_known, mask)
+
+    def inpaint(self, model, x_known, mask):
+        N, xk, m = self._held(x_known, mask)
+        if bool(m.all()):
+            return self._all_held(xk.numpy().astype(int))
+        dev = torch.device(model.device)
+        rows = self._free_rows(m, 1, dev)[0]
+        return self._loop(model, N, held=(xk.to(dev), m.to(dev), rows))
+
+    def _grid_len(self):
+        return self.num_steps
+
+    def _all_held(self, x):
+        """Nothing is free: x_known in the parent's return shape (no step ran, so every per-step counter is zero)."""
+        return x, [0.0] * self._grid_len()
+
+
+@sampling_utils.register_sampler
+class ConditionalLBJF(_ConditionedLoop, LBJF):
+    """LBJF with held entries (see _ConditionedLoop): `ctdd_lbjf_step_rows` per step and corrector; at S = 256 (CT-ELBO, or CRM
+    with reverse_prob logits) `ctdd_tauleap_step_s256_rows` for the listed rows' rates, then `ctdd_lbjf_from_rates_rows`."""
+
+
+@sampling_utils.register_sampler
+class ConditionalMidPointTauL(_ConditionedLoop, MidPointTauL):
+    """Midpoint tau-leaping with held entries (see _ConditionedLoop): stage 1 `ctdd_midpoint_predict_rows` (S = 256: the rates
+    pair with `ctdd_midpoint_from_rates_rows`), held rows of x' equal x; stage 2 the row-list tau-leap step with x_base = x'."""
+
+    def _grid_len(self):
+        h = (self.max_t - self.min_t) / self.num_steps
+        n, t = 0, self.max_t
+        while t - 0.5 * h > self.min_t:
+            n, t = n + 1, t - h
+        return n
+
+    def _all_held(self, x):
+        z = [0.0] * self._grid_len()
+        return x, ([float("nan")] * len(z) if self.is_ordinal else []), list(z), list(z), list(z)
+
+
+@sampling_utils.register_sampler
+class ConditionalExactSampling(_ConditionedLoop, ExactSampling):
+    """ExactSampling with held entries (see _ConditionedLoop): `ctdd_exact_step_rows` per step; no argmax at the end."""
 
 
 def lbjf_corrector_step(cfg, model, xt, t, h, N, device, xt_target=None, seed=None, E=None, want_probs=False):

@@ -170,6 +170,36 @@ int ctdd_lbjf_from_rates(const float* rates, const int32_t* x, float h, const fl
                          int N, int D, int S, int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream);
 int ctdd_midpoint_from_rates(const float* rates, const int32_t* x, float h, int N, int D, int S, int32_t* out_x, void* stream);
 
+/* ---- K7 / K8 / the exact step / the two tails above on the rows listed in `rows` only.  The contract is the one written above
+ * ctdd_tauleap_step_rows: rows = n_rows ascending, distinct int32 indices into the N*D rows; listed rows of every output (out_x,
+ * out_probs) are bit-identical to the full launch with the same seed / offset / flags / E -- the Philox counter and the E row
+ * are keyed by the row of the N*D space, not by its place in the list; unlisted rows of every output are not written, so out_x
+ * must not alias x (CTDD_EINVAL); out_changed counts listed rows only; n_rows == 0 is a no-op returning CTDD_OK; n_rows outside
+ * [0, N*D] is CTDD_ERANGE, a NULL rows with n_rows > 0 CTDD_EINVAL.  E and out_probs stay full-size (N*D, S).  These are the
+ * steps of the conditional LBJF / midpoint / exact samplers: the held-entry scheme of ConditionalTauLeaping
+ * (lib/sampling/sampling.py:649-758: the network sees the full state, only the free dimensions move) applied to the loops
+ * of LBJF, MidPointTauL and ExactSampling. */
+/* K7 on listed rows (lib/sampling/sampling.py:278-293, corrector 296-341). */
+int ctdd_lbjf_step_rows(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
+                        const float* base_rate, float beta, float eps, float h, uint32_t flags, const float* E,
+                        uint64_t seed, uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
+                        int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream);
+/* K8 on listed rows (lib/sampling/sampling.py:417-453): x' of a listed row is written at that row. */
+int ctdd_midpoint_predict_rows(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
+                               const float* base_rate, float beta, float eps, float h, int N, int D, int S,
+                               const int32_t* rows, int n_rows, int32_t* out_x, void* stream);
+/* ExactSampling step on listed rows (lib/sampling/sampling.py:975-1061). */
+int ctdd_exact_step_rows(const float* logits, const int32_t* x, const float* q_lo, const float* q_step, const float* E,
+                         uint64_t seed, uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
+                         int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream);
+/* The two tails on listed rows: rates (N,D,S) is read at the listed rows only (what ctdd_tauleap_step_s256_rows wrote there;
+ * lib/sampling/sampling.py:278-293 and 417-453). */
+int ctdd_lbjf_from_rates_rows(const float* rates, const int32_t* x, float h, const float* E, uint64_t seed, uint64_t offset,
+                              int N, int D, int S, const int32_t* rows, int n_rows, int32_t* out_x, float* out_probs,
+                              int32_t* out_changed, void* stream);
+int ctdd_midpoint_from_rates_rows(const float* rates, const int32_t* x, float h, int N, int D, int S, const int32_t* rows,
+                                  int n_rows, int32_t* out_x, void* stream);
+
 /* K10 final denoise: argmax_s softmax(logits) = first argmax of logits (sampling.py:223-229). */
 int ctdd_argmax(const float* logits, int N, int D, int S, int32_t* out_x, void* stream);
 
