@@ -348,6 +348,323 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
   }
 }
 
+// ---------------------------------------------------------------- k_resblock_mid: the same block for a sample of <= 208 pixels (14x14)
+//
+// Ownership as above (one workgroup of four waves per sample, wave w owns channels [48 w, 48 w + 48)), NPT = 13 pixel tiles, so a
+// weight fragment feeds 13 matrix instructions and the accumulators are 156 registers per lane.  What changes is what LDS holds:
+// ONE zero-bordered slab [(H+2)(W+2)][192 channels] (16x16 rows x 400 bytes = 100 KiB) and the reduction scratch, no raw copy of the
+// input.  GroupNorm 1 takes its statistics straight from global memory (all sources first: a group may straddle two sources), then
+// conv1 runs SOURCE BY SOURCE: normalise + Swish that source from global memory into the slab, barrier, nine taps over its
+// 64-channel chunks, barrier.  A source that is not a multiple of 64 channels (96) is padded to one: zero slab columns, zero packed
+// weights, so that no tap has half a chunk.  The 1x1 skip segments read the raw sources as B fragments straight from global memory
+// (a lane's 16 bytes = 8 consecutive channels of its pixel), before GroupNorm 2 so that conv2's first weights travel behind it.
+// The residual is added in the accumulator layout from global memory (one rounding of acc + bias + residual, as the launches it
+// replaces).  The weight ring is RM_PD = 3 chunks (72 registers: with 4 the kernel spills); the pixel fragments are buffered per k half (2 x 52 registers).
+constexpr int RM_NPT = 13, RM_PD = 3, RM_MAXHW = 208, RM_MAXROWS = 256, RM_MAXCS = 192;
+
+// the value again, as one the compiler knows nothing about: what is derived from it is computed where it is used instead of being
+// kept in registers (the pixel indices of the 13 tiles) from the start of the kernel to its epilogues
+__device__ inline int rm_again(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+__host__ __device__ inline RbLds rm_layout(int H, int W) {
+  RbLds L;
+  L.rsA = L.rs2 = RB_N * 2 + 16;
+  L.prows = (H + 2) * (W + 2);
+  L.raw = L.slab = 0;
+  L.part = L.prows * L.rs2;
+  L.red = L.part + RB_THREADS * RB_PST * 4;
+  L.scale = L.red + 2 * RB_MAXC * 8;
+  L.total = L.scale + 2 * RB_MAXC * 4;
+  return L;
+}
+
+// GroupNorm 1 statistics of the channel concatenation of the sample's sources (s1 / s2: the sample's first element), read from global
+// memory in rb_groupnorm's order (fp32 per thread over its pixels, fp64 across threads and group members); leaves scale / shift of all
+// C1 + C2 channels in LDS.  Ends with a barrier.
+__device__ __attribute__((always_inline)) inline void rm_gn1_stats(unsigned char* sm, const RbLds& L, const unsigned short* __restrict__ s1,
+                                                                  const unsigned short* __restrict__ s2, int C1, int C2, int HW, int G,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta, float eps) {
+  const int t = threadIdx.x, C = C1 + C2, noct = C >> 3;
+  const int npl = RB_THREADS / noct < HW ? RB_THREADS / noct : HW, T = noct * npl;
+  const bool act = t < T;
+  const int oct = act ? t % noct : 0, pl = act ? t / noct : 0, c0 = oct * 8;
+  const bool first = c0 < C1;
+  const unsigned short* src = first ? s1 + c0 : s2 + (c0 - C1);
+  const int cs = first ? C1 : C2;
+  float* part = (float*)(sm + L.part);
+  double* red = (double*)(sm + L.red);
+  float* scale = (float*)(sm + L.scale);
+  float* shift = scale + RB_MAXC;
+  float sx[8], sq[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { sx[j] = 0.0f; sq[j] = 0.0f; }
+  if (act) {
+#pragma unroll 4
+    for (int p = pl; p < HW; p += npl) {
+      const u32x4 u = *(const u32x4*)(src + (size_t)p * cs);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float x0 = __uint_as_float(u[j] << 16), x1 = __uint_as_float(u[j] & 0xFFFF0000u);
+        sx[2 * j] += x0; sq[2 * j] = fmaf(x0, x0, sq[2 * j]);
+        sx[2 * j + 1] += x1; sq[2 * j + 1] = fmaf(x1, x1, sq[2 * j + 1]);
+      }
+    }
+    float4* pt = (float4*)(part + t * RB_PST);
+    pt[0] = make_float4(sx[0], sx[1], sx[2], sx[3]); pt[1] = make_float4(sx[4], sx[5], sx[6], sx[7]);
+    pt[2] = make_float4(sq[0], sq[1], sq[2], sq[3]); pt[3] = make_float4(sq[4], sq[5], sq[6], sq[7]);
+  }
+  __syncthreads();
+  for (int r = t; r < 2 * C; r += RB_THREADS) {
+    const int m = r >= C ? 1 : 0, c = r - m * C;
+    const float* pp = part + (c >> 3) * RB_PST + m * 8 + (c & 7);
+    double acc = 0.0;
+    for (int q = 0; q < npl; ++q) acc += (double)pp[q * noct * RB_PST];
+    red[r] = acc;
+  }
+  __syncthreads();
+  const int cg = C / G;
+  for (int c = t; c < C; c += RB_THREADS) {
+    const int g0 = (c / cg) * cg;
+    double s = 0.0, q = 0.0;
+    for (int j = g0; j < g0 + cg; ++j) { s += red[j]; q += red[C + j]; }
+    const double n = (double)cg * (double)HW;
+    const double mean = s / n;
+    const double var = fmax(q / n - mean * mean, 0.0);
+    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    scale[c] = rstd * gamma[c];
+    shift[c] = beta[c] - (float)mean * rstd * gamma[c];
+  }
+  __syncthreads();
+}
+
+// bf16(swish(x * scale + shift)) of ONE source ([HW][cs] in global memory, channels [coff, coff + cs) of the concatenation) into
+// columns [0, cp) of the slab's interior rows; columns [cs, cp) (the padding to whole 64-channel chunks) are written as zeros.
+// No barrier of its own.
+__device__ __attribute__((always_inline)) inline void rm_gn1_apply(unsigned char* sm, const RbLds& L, const unsigned short* __restrict__ src, int cs,
+                                                                  int cp, int coff, int HW, int W) {
+  const int t = threadIdx.x, noct = cp >> 3, npl = RB_THREADS / noct;
+  if (t >= noct * npl) return;
+  const int oct = t % noct, pl = t / noct;
+  const bool real = oct * 8 < cs;
+  const float* scale = (const float*)(sm + L.scale) + (real ? coff + oct * 8 : 0);
+  const float* shift = scale + RB_MAXC;
+  const float4 sc0 = *(const float4*)scale, sc1 = *(const float4*)(scale + 4);
+  const float4 sh0 = *(const float4*)shift, sh1 = *(const float4*)(shift + 4);
+  const f32x2v scv[4] = {{sc0.x, sc0.y}, {sc0.z, sc0.w}, {sc1.x, sc1.y}, {sc1.z, sc1.w}};
+  const f32x2v shv[4] = {{sh0.x, sh0.y}, {sh0.z, sh0.w}, {sh1.x, sh1.y}, {sh1.z, sh1.w}};
+  const unsigned short* sp = src + (real ? oct * 8 : 0);
+#pragma unroll 4
+  for (int p = pl; p < HW; p += npl) {
+    const u32x4 u = *(const u32x4*)(sp + (size_t)p * cs);
+    unsigned ow[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                                // as rb_groupnorm: packed fma, hardware exp2 / rcp
+      const f32x2v x = {__uint_as_float(u[j] << 16), __uint_as_float(u[j] & 0xFFFF0000u)};
+      f32x2v y = __builtin_elementwise_fma(x, scv[j], shv[j]);
+      const f32x2v z = y * (f32x2v){-1.4426950408889634f, -1.4426950408889634f};
+      const f32x2v d = (f32x2v){__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)} + (f32x2v){1.0f, 1.0f};
+      y = y * (f32x2v){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+      ow[j] = real ? rb_pack2(y.x, y.y) : 0u;
+    }
+    *(uint4*)(sm + L.slab + rb_prow(p, W) * L.rs2 + oct * 16) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+  }
+}
+
+__device__ __attribute__((always_inline)) inline void rm_wprologue(u32x4 (&wr)[RM_PD][3][2], const unsigned short* __restrict__ wrow, int nchunks) {
+#pragma unroll
+  for (int u = 0; u < RM_PD; ++u)
+    if (u < nchunks) rb_wload(wr[u], wrow, u);
+}
+
+// One K loop over `nchunks` 64-channel chunks of the weight stream at wrow (ring wr holding its first RM_PD chunks): rb_gemm with the
+// pixel fragments buffered per k HALF.  xload(xf) delivers the 13 fragments of the next (chunk, half) of its own sequence (chunk 0
+// half 0, chunk 0 half 1, chunk 1 half 0, ...; one request past the end must stay a valid address).
+template <class XL>
+__device__ __attribute__((always_inline)) inline void rm_gemm(f32x4 (&acc)[3][RM_NPT], u32x4 (&wr)[RM_PD][3][2], const unsigned short* __restrict__ wrow,
+                                                             int nchunks, XL&& xload) {
+  bf16x8 xq[2][RM_NPT];
+  auto step = [&](u32x4 (&slot)[3][2], int ci, auto guard) {
+    constexpr bool GUARD = decltype(guard)::value;
+    if (GUARD && ci >= nchunks) return;
+    __builtin_amdgcn_sched_barrier(0);                          // (keeps the scheduler from hoisting later chunks' fragment loads: registers)
+    xload(xq[1]);
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int pt = 0; pt < RM_NPT; ++pt)
+        acc[t][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t][0]), xq[0][pt], acc[t][pt], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    xload(xq[0]);
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int pt = 0; pt < RM_NPT; ++pt)
+        acc[t][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t][1]), xq[1][pt], acc[t][pt], 0, 0, 0);
+    if (!GUARD || ci + RM_PD < nchunks) rb_wload(slot, wrow, ci + RM_PD);
+  };
+  xload(xq[0]);
+  int ci0 = 0;
+  for (; ci0 + 2 * RM_PD <= nchunks; ci0 += RM_PD) {
+#pragma unroll
+    for (int u = 0; u < RM_PD; ++u) step(wr[u], ci0 + u, std::false_type{});
+  }
+  for (; ci0 < nchunks; ci0 += RM_PD) {
+#pragma unroll
+    for (int u = 0; u < RM_PD; ++u) step(wr[u], ci0 + u, std::true_type{});
+  }
+}
+
+// the nine taps x cpt chunks of a 3x3 segment on the slab (b3: this lane's row of each pixel tile + its k quarter)
+__device__ __attribute__((always_inline)) inline void rm_gemm_slab(f32x4 (&acc)[3][RM_NPT], u32x4 (&wr)[RM_PD][3][2], const unsigned short* __restrict__ wrow,
+                                                                  int cpt, const unsigned char* sm, const int (&b3)[RM_NPT], int rs, int Wp) {
+  int tap = 0, cc = 0, hf = 0;
+  auto xload = [&](bf16x8 (&xf)[RM_NPT]) {
+    const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+    const int koff = (dy * Wp + dx) * rs + cc * 128 + hf * 64;
+#pragma unroll
+    for (int pt = 0; pt < RM_NPT; ++pt) xf[pt] = *(const bf16x8*)(sm + b3[pt] + koff);
+    const bool wrap = hf == 1 && cc + 1 == cpt;                 // (selects, not branches)
+    cc = hf == 1 ? (wrap ? 0 : cc + 1) : cc;
+    tap = wrap && tap < 8 ? tap + 1 : tap;                      // past the last chunk: tap 8 again, a valid address
+    hf ^= 1;
+  };
+  rm_gemm(acc, wr, wrow, 9 * cpt, xload);
+}
+
+__global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resblock_args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+  constexpr int NPT = RM_NPT;
+  const int t = threadIdx.x, b = blockIdx.x;
+  const int H = a.H, W = a.W, HW = H * W, C1 = a.C1, C2 = a.C2, Wp = W + 2;
+  const RbLds L = rm_layout(H, W);
+  const int lane = t & 63, wv = t >> 6, lj = lane & 15, lq = lane >> 4;
+  const int cp1 = (C1 + 63) & ~63, cp2 = (C2 + 63) & ~63;
+  const int nk1 = 9 * (cp1 + cp2) / 64, nsk = a.skip ? (cp1 + cp2) / 64 : 0, nk2 = 27 + nsk;
+  const unsigned short* w1p = (const unsigned short*)a.w1 + (size_t)wv * nk1 * 3072 + lane * 8;
+  const unsigned short* s1 = (const unsigned short*)a.s1_bf16 + (size_t)b * HW * C1;
+  const unsigned short* s2 = (const unsigned short*)a.s2_bf16 + (size_t)b * HW * C2;
+  u32x4 wr[RM_PD][3][2];                                      // the weight ring (rm_gemm)
+
+  // ---- phase A: zero the slab (its border rows stay zero to the end), GroupNorm 1 statistics from global memory
+  rm_wprologue(wr, w1p, 9 * cp1 / 64);
+  for (int v = t; v < (L.part >> 4); v += RB_THREADS) *(uint4*)(sm + v * 16) = make_uint4(0, 0, 0, 0);
+  rm_gn1_stats(sm, L, s1, s2, C1, C2, HW, a.G1, a.gamma1, a.beta1, a.eps1);
+
+  // this lane's pixel of each pixel tile (pixels past the sample repeat the last one: computed, never stored)
+  int b3[NPT];
+#pragma unroll
+  for (int pt = 0; pt < NPT; ++pt) {
+    const int p = pt * 16 + lj, pe = p < HW ? p : HW - 1;
+    b3[pt] = L.slab + rb_prow(pe, W) * L.rs2 + lq * 16;
+  }
+  const int n0 = wv * 48;                                     // this wave's first output channel
+  f32x4 acc[3][NPT];
+#pragma unroll
+  for (int tt = 0; tt < 3; ++tt)
+#pragma unroll
+    for (int pt = 0; pt < NPT; ++pt) acc[tt][pt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+
+  // ---- phase B: conv1, source by source (the slab never holds more than 192 channels)
+  for (int s = 0; s < (C2 ? 2 : 1); ++s) {
+    const int cs = s ? C2 : C1, cp = s ? cp2 : cp1;
+    rm_gn1_apply(sm, L, s ? s2 : s1, cs, cp, s ? C1 : 0, HW, W);
+    __syncthreads();
+    rm_gemm_slab(acc, wr, w1p + (size_t)(s ? 9 * cp1 / 64 : 0) * 3072, cp / 64, sm, b3, L.rs2, Wp);
+    __syncthreads();                                          // every wave has read its last fragment of this source
+    if (s == 0 && C2) rm_wprologue(wr, w1p + (size_t)(9 * cp1 / 64) * 3072, 9 * cp2 / 64);
+  }
+  // the next stream's first chunks travel during the epilogue: the skip segments' (after the 27 chunks of the 3x3 part) or conv2's
+  const int tw = rm_again(t);
+  const unsigned short* w2p = (const unsigned short*)a.w2 + (size_t)(tw >> 6) * nk2 * 3072 + (tw & 63) * 8;
+  rm_wprologue(wr, w2p + (size_t)(nsk ? 27 : 0) * 3072, nsk ? nsk : 27);
+  const int lj1 = rm_again(lj);
+#pragma unroll
+  for (int tt = 0; tt < 3; ++tt) {
+    const int n = n0 + tt * 16 + lq * 4;
+    const float4 bv = *(const float4*)(a.bias1 + n);
+    const float4 tb = a.tbias ? *(const float4*)(a.tbias + (size_t)b * a.tb_stride + n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float add[4] = {bv.x + tb.x, bv.y + tb.y, bv.z + tb.z, bv.w + tb.w};
+#pragma unroll
+    for (int pt = 0; pt < NPT; ++pt) {
+      const int p = pt * 16 + lj1;
+      if (p < HW) {
+        const f32x4 v = acc[tt][pt];
+        *(uint2*)(sm + b3[pt] + (n * 2 - lq * 16)) =            // (b3: this pixel's slab row + lq * 16)
+            make_uint2(rb_pack2(v[0] + add[0], v[1] + add[1]), rb_pack2(v[2] + add[2], v[3] + add[3]));
+      }
+      acc[tt][pt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+    }
+  }
+  __syncthreads();
+
+  // ---- phase C: the 1x1 skip segments on the raw sources, B fragments straight from global memory (conv2's sums start with them)
+  if (nsk) {
+    const int nc1 = cp1 / 64;
+    int cc = 0, hf = 0;
+    auto xload = [&](bf16x8 (&xf)[NPT]) {
+      const bool two = cc >= nc1;
+      const unsigned char* base = (const unsigned char*)(two ? s2 : s1);
+      const int cs = two ? C2 : C1, cb = (cc - (two ? nc1 : 0)) * 64 + hf * 32;
+      const bool ok = cb < cs;                                  // a padded source's last half chunk: zeros (its weights are zeros too)
+      const int off = (ok ? cb : 0) * 2 + lq * 16, ljs = rm_again(lj);
+#pragma unroll
+      for (int pt = 0; pt < NPT; ++pt) {
+        const int p = pt * 16 + ljs, pe = p < HW ? p : HW - 1;
+        const bf16x8 v = *(const bf16x8*)(base + (unsigned)(pe * cs * 2 + off));
+        xf[pt] = ok ? v : __builtin_bit_cast(bf16x8, (u32x4){0u, 0u, 0u, 0u});
+      }
+      cc = hf == 1 && cc + 1 < nsk ? cc + 1 : cc;               // past the last chunk: the last chunk again
+      hf ^= 1;
+    };
+    rm_gemm(acc, wr, w2p + (size_t)27 * 3072, nsk, xload);
+    rm_wprologue(wr, w2p, 27);                                // conv2's first chunks travel during GroupNorm 2
+  }
+
+  // ---- phase D: GroupNorm 2 + Swish of the bf16 h1, in place, then conv2 on a2
+  rb_groupnorm(sm, L, L.slab, L.rs2, true, L.slab, L.rs2, HW, W, RB_N, a.G2, a.gamma2, a.beta2, a.eps2);
+  rm_gemm_slab(acc, wr, w2p, RB_N / 64, sm, b3, L.rs2, Wp);
+  __syncthreads();                                            // a2 is dead: the slab becomes the [HW][N] output image
+  const int lj2 = rm_again(lj);
+#pragma unroll
+  for (int tt = 0; tt < 3; ++tt) {
+    const int n = n0 + tt * 16 + lq * 4;
+    const float4 bv = *(const float4*)(a.bias2 + n);
+    uint2 r[NPT] = {};
+    if (!a.skip) {                                            // residual: the raw input (C1 == N), in this lane's accumulator layout
+#pragma unroll
+      for (int pt = 0; pt < NPT; ++pt) {
+        const int p = pt * 16 + lj2;
+        r[pt] = *(const uint2*)(s1 + (size_t)(p < HW ? p : HW - 1) * RB_N + n);
+      }
+    }
+#pragma unroll
+    for (int pt = 0; pt < NPT; ++pt) {
+      const int p = pt * 16 + lj2;
+      if (p < HW) {
+        const f32x4 v = acc[tt][pt];
+        float o[4] = {v[0] + bv.x, v[1] + bv.y, v[2] + bv.z, v[3] + bv.w};
+        if (!a.skip) {
+          o[0] += __uint_as_float(r[pt].x << 16); o[1] += __uint_as_float(r[pt].x & 0xFFFF0000u);
+          o[2] += __uint_as_float(r[pt].y << 16); o[3] += __uint_as_float(r[pt].y & 0xFFFF0000u);
+        }
+        *(uint2*)(sm + L.slab + p * L.rs2 + n * 2) = make_uint2(rb_pack2(o[0], o[1]), rb_pack2(o[2], o[3]));
+      }
+    }
+  }
+  __syncthreads();
+  {
+    constexpr int npc = RB_N / 8;
+    unsigned short* out = (unsigned short*)a.out_bf16 + (size_t)b * HW * RB_N;
+    for (int v = t; v < HW * npc; v += RB_THREADS) {
+      const int p = v / npc, c0 = (v - p * npc) * 8;
+      *(uint4*)(out + (size_t)p * RB_N + c0) = *(const uint4*)(sm + L.slab + p * L.rs2 + c0 * 2);
+    }
+  }
+}
+
 }  // namespace
 }  // namespace ctdd
 
@@ -382,4 +699,29 @@ extern "C" int ctdd_unet_resblock_small(const void* args_, int f32, void* stream
     hipLaunchKernelGGL(k_resblock_small<4>, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, st, a);
   }
   return finish_launch("k_resblock_small");
+}
+
+// The same block for a sample of up to 208 pixels (the 14x14 level), k_resblock_mid.  Refuses (non-zero, ctdd_last_error set, nothing
+// launched): fp32 mode, H*W > 208 or more than 256 rows in the zero-bordered grid, N != 192, a source that is not a multiple of 32
+// channels or exceeds 192, groups that do not divide the channels, an LDS image over the CU's 160 KiB.
+extern "C" int ctdd_unet_resblock_mid(const void* args_, int f32, void* stream) {
+  CTDD_REQUIRE(args_, CTDD_EINVAL, "ctdd_unet_resblock_mid: null arguments");
+  const ctdd_resblock_args& a = *(const ctdd_resblock_args*)args_;
+  CTDD_REQUIRE(f32 == 0, CTDD_ERANGE, "ctdd_unet_resblock_mid: bf16 inference only (the fp32 mode keeps the four launches)");
+  CTDD_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.H * a.W <= RM_MAXHW && (a.H + 2) * (a.W + 2) <= RM_MAXROWS, CTDD_ERANGE,
+               "ctdd_unet_resblock_mid: a sample of %dx%d pixels does not fit the workgroup tile (H*W <= 208, (H+2)(W+2) <= 256)", a.H, a.W);
+  const int C = a.C1 + a.C2;
+  CTDD_REQUIRE(a.N == RB_N && a.C1 > 0 && a.C1 % 32 == 0 && a.C1 <= RM_MAXCS && a.C2 >= 0 && a.C2 % 32 == 0 && a.C2 <= RM_MAXCS, CTDD_ERANGE,
+               "ctdd_unet_resblock_mid: channel counts off the tile (N=%d, C1=%d, C2=%d; N = 192, sources in multiples of 32, <= 192 each)", a.N,
+               a.C1, a.C2);
+  CTDD_REQUIRE(a.G1 > 0 && C % a.G1 == 0 && a.G2 > 0 && RB_N % a.G2 == 0, CTDD_EINVAL, "ctdd_unet_resblock_mid: groups do not divide the channels");
+  CTDD_REQUIRE(a.skip || (a.C2 == 0 && a.C1 == RB_N), CTDD_EINVAL, "ctdd_unet_resblock_mid: a residual block needs C1 == N and one source");
+  CTDD_REQUIRE(a.s1_bf16 && (a.C2 == 0 || a.s2_bf16) && a.w1 && a.w2 && a.bias1 && a.bias2 && a.gamma1 && a.beta1 && a.gamma2 && a.beta2 &&
+                   a.out_bf16, CTDD_EINVAL, "ctdd_unet_resblock_mid: null pointer");
+  const RbLds L = rm_layout(a.H, a.W);
+  CTDD_REQUIRE(L.total <= 160 * 1024, CTDD_ERANGE, "ctdd_unet_resblock_mid: LDS image of %d bytes over the 160 KiB budget", L.total);
+  static bool attr_done[16] = {};
+  ensure_lds_ceiling((const void*)k_resblock_mid, attr_done);
+  hipLaunchKernelGGL(k_resblock_mid, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, (hipStream_t)stream, a);
+  return finish_launch("k_resblock_mid");
 }

@@ -78,6 +78,7 @@ def _lib():
                            ("ctdd_unet_gn_apply", [_P, _P]), ("ctdd_unet_gn_onepass", [_P, _I, _I, _P]), ("ctdd_unet_channel_stats", [_P, _I, _I, _I, _P, _P]),
                            ("ctdd_unet_time", [_P, _P, _P, _I, _P, _P]), ("ctdd_unet_time_uniform", [_P, _P, _P, _I, _P, _P]),
                            ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_resblock_small", [_P, _I, _P]),
+                           ("ctdd_unet_resblock_mid", [_P, _I, _P]),
                            ("ctdd_unet_logistic_head", [_P, _P])):
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argt, _I
@@ -123,6 +124,38 @@ def pack_resblock_weights(w2d):
     N, K = w2d.shape
     assert N == 192 and K % 64 == 0
     return w2d.reshape(4, 3, 16, K // 64, 2, 4, 8).permute(0, 3, 1, 4, 5, 2, 6).contiguous().reshape(N, K)
+
+
+def resblock_mid_covers(H, W, cs, cout, G1, G2):
+    """Shapes ctdd_unet_resblock_mid holds (csrc/unet_resblock_kernels.hip): a sample of <= 208 pixels whose zero-bordered grid has
+    <= 256 rows, 192 output channels, one or two sources in multiples of 32 channels (<= 192 each), and its LDS image (one 192-channel
+    slab + the reduction scratch) within the CU's 160 KiB."""
+    Ct = sum(cs)
+    if (H < 1 or W < 1 or H * W > 208 or (H + 2) * (W + 2) > 256 or cout != 192 or not 1 <= len(cs) <= 2
+            or any(c <= 0 or c % 32 or c > 192 for c in cs) or G1 <= 0 or G2 <= 0 or Ct % G1 or cout % G2):
+        return False
+    return (H + 2) * (W + 2) * (cout * 2 + 16) + 256 * 80 + 2 * 384 * 8 + 2 * 384 * 4 <= 160 * 1024
+
+
+def pack_resblock_mid_weights(w1, w2, cs):
+    """The [192][9 Ct] conv1 matrix (K = tap -> channel of the concatenation) and the [192][9 * 192 (+ Ct)] conv2 matrix (3x3 on a2, then
+    the 1x1 skip segments) in the order ctdd_unet_resblock_mid streams them: conv1's K as source -> tap -> channel with every source
+    padded by zero columns to whole 64-channel chunks (the kernel runs conv1 source by source and no tap has half a chunk), the skip
+    segments padded alike, both then in pack_resblock_weights' fragment order."""
+    N, Ct = w1.shape[0], sum(cs)
+    assert N == 192 and w1.shape[1] == 9 * Ct and w2.shape[1] in (9 * N, 9 * N + Ct)
+    w1v, k1, k2, c0 = w1.reshape(N, 9, Ct), [], [w2[:, :9 * N]], 0
+    for c in cs:
+        cp = -(-c // 64) * 64
+        blk = w1.new_zeros((N, 9, cp))
+        blk[:, :, :c] = w1v[:, :, c0:c0 + c]
+        k1.append(blk.reshape(N, 9 * cp))
+        if w2.shape[1] > 9 * N:
+            sk = w2.new_zeros((N, cp))
+            sk[:, :c] = w2[:, 9 * N + c0:9 * N + c0 + c]
+            k2.append(sk)
+        c0 += c
+    return pack_resblock_weights(torch.cat(k1, 1).contiguous()), pack_resblock_weights(torch.cat(k2, 1).contiguous())
 
 
 def _onepass_slab(B, HW, Cn, G, max_threads=1024):
@@ -369,7 +402,11 @@ class _PlanBuilder:
             tc.record_gn(self, srcs, norm, swish, eps, HW, out, drop_p)
         return out
 
-    def resblock_fused(self, rb, srcs):
+    def resblock_mid(self, rb, srcs):
+        """The block as ONE ctdd_unet_resblock_mid launch (the 14x14 level): as resblock_fused, weights in pack_resblock_mid_weights' order."""
+        return self.resblock_fused(rb, srcs, mid=True)
+
+    def resblock_fused(self, rb, srcs, mid=False):
         """The block as ONE ctdd_unet_resblock_small launch: the same [N][K] matrices in the kernel's fragment order, the same summed
         conv2 + skip bias."""
         eng, lib, B = self.eng, self.lib, self.B
@@ -385,7 +422,7 @@ class _PlanBuilder:
         a.gamma1, a.beta1, a.gamma2, a.beta2, a.bias1 = (ptr(p_) for p_ in par)
         a.G1, a.G2, a.eps1, a.eps2 = rb.norm1.num_groups, rb.norm2.num_groups, rb.norm1.eps, rb.norm2.eps
         a.tbias, a.tb_stride = self.tproj.data_ptr() + 4 * self.toff[id(rb)], self.tb_stride
-        w1, _ = eng._pack(pack_resblock_weights(eng._w2d([(rb.conv1.weight, 0)], [(None, Ct, SEG_3x3)])))
+        w1 = eng._w2d([(rb.conv1.weight, 0)], [(None, Ct, SEG_3x3)])
         segs, wsrc, bias2 = [(None, cout, SEG_3x3)], [(rb.conv2.weight, 0)], rb.conv2.bias.detach().float()
         if rb.skip is not None:
             c_ = 0
@@ -395,13 +432,16 @@ class _PlanBuilder:
                 c_ += cs_
             bias2 = bias2 + rb.skip.bias.detach().float()
         bias2 = bias2.contiguous()
-        w2, _ = eng._pack(pack_resblock_weights(eng._w2d(wsrc, segs)))
+        w2 = eng._w2d(wsrc, segs)
+        w1, w2 = pack_resblock_mid_weights(w1, w2, cs) if mid else (pack_resblock_weights(w1), pack_resblock_weights(w2))
+        (w1, _), (w2, _) = eng._pack(w1), eng._pack(w2)
         a.w1, a.w2, a.bias2, a.skip = ptr(w1), ptr(w2), ptr(bias2), int(rb.skip is not None)
         a.B, a.H, a.W, a.N, a.out_bf16 = B, Hc, Wc, cout, ptr(y.hi)
         self.keep.extend(par + [w1, w2, bias2, a])
         K1, K2 = w1.shape[1], w2.shape[1]
-        self.launch(lib.ctdd_unet_resblock_small, C.byref(a), 0, label=f"{Hc}x{Wc} resblock C={cs} N={cout} K={K1}+{K2}",
-                    flops=2 * B * Hc * Wc * cout * (K1 + K2))
+        # (flops: the block's own products; the zero columns that pad a source of the mid kernel to whole chunks are not counted)
+        self.launch(lib.ctdd_unet_resblock_mid if mid else lib.ctdd_unet_resblock_small, C.byref(a), 0,
+                    label=f"{Hc}x{Wc} resblock C={cs} N={cout} K={K1}+{K2}", flops=2 * B * Hc * Wc * cout * (9 * Ct + 9 * cout + (Ct if rb.skip is not None else 0)))
         return y
 
     def resblock(self, rb, srcs):
@@ -414,6 +454,10 @@ class _PlanBuilder:
         # tensors and h1 stay in LDS); cfg.model.resblock_fused = 0 keeps the four launches below
         if self.onepass_gn and eng._fuses_resblock(rb, Hc, Wc, cs, tc is not None) and all(s_.stats is None for s_ in srcs):
             return self.resblock_fused(rb, srcs)
+        # the 14x14 level's: ctdd_unet_resblock_mid, one 192-channel slab, conv1 source by source; cfg.model.resblock_fused_mid = 0
+        # keeps the four launches
+        if self.onepass_gn and eng._fuses_resblock_mid(rb, Hc, Wc, cs, tc is not None) and all(s_.stats is None for s_ in srcs):
+            return self.resblock_mid(rb, srcs)
         a1 = self.gn_apply(srcs, rb.norm1, True, rb.norm1.eps, Hc * Wc)
         h = _Tensor(self, Hc, Wc, cout)
         b1 = rb.conv1.bias.detach().float().contiguous()
@@ -675,6 +719,14 @@ class UNetEngine:
                     and Hc * Wc <= self._onepass_max_hw()
                     and resblock_small_covers(Hc, Wc, cs, rb.conv1.weight.shape[0], rb.norm1.num_groups, rb.norm2.num_groups))
 
+    def _fuses_resblock_mid(self, rb, Hc, Wc, cs, training):
+        """Whether such a plan runs this block as ONE ctdd_unet_resblock_mid launch: shapes the small kernel does not hold (whatever
+        resblock_fused says: the two knobs are independent), bf16 inference only, cfg.model.resblock_fused_mid (default on)."""
+        return bool(not training and not self.precise and int(getattr(self.cfg.model, "resblock_fused_mid", 1))
+                    and Hc * Wc <= self._onepass_max_hw()
+                    and not resblock_small_covers(Hc, Wc, cs, rb.conv1.weight.shape[0], rb.norm1.num_groups, rb.norm2.num_groups)
+                    and resblock_mid_covers(Hc, Wc, cs, rb.conv1.weight.shape[0], rb.norm1.num_groups, rb.norm2.num_groups))
+
     def _onepass_gn_covers(self, B, training):
         """Whether ctdd_unet_gn_onepass has a slab for every GroupNorm launch a one-pass plan would hold at its small levels (the
         fused blocks carry theirs inside): _PlanBuilder.build's walk over shapes alone, so that nothing is built to find out."""
@@ -688,7 +740,8 @@ class UNetEngine:
                 H, W = 2 * H, 2 * W
             else:
                 rb, c1 = layer.resblocks, layer.resblocks.norm1.num_channels
-                if not self._fuses_resblock(rb, H, W, [c] if c1 == c else [c, c1 - c], training):     # (c1 > c: the skip concatenation)
+                cs = [c] if c1 == c else [c, c1 - c]                                                   # (c1 > c: the skip concatenation)
+                if not (self._fuses_resblock(rb, H, W, cs, training) or self._fuses_resblock_mid(rb, H, W, cs, training)):
                     norms += [(H * W, rb.norm1), (H * W, rb.norm2)]
                 c = rb.norm2.num_channels
                 if layer.attention is not None:

@@ -94,6 +94,14 @@ typedef struct {
  * ((((wave * K / 64 + chunk) * 3 + tile) * 2 + half) * 64 + 16 q + i) * 8 + e (ctdd/unet_engine.py: pack_resblock_weights): each
  * wave-instruction of the kernel's weight stream reads 1 KiB of consecutive bytes. */
 int ctdd_unet_resblock_small(const void* resblock_args, int f32, void* stream);
+/* The same block, same argument struct, for a sample of up to 208 pixels (the 14x14 level): H * W <= 208 and (H + 2)(W + 2) <= 256,
+ * N = 192, C1 and C2 multiples of 32 with C1, C2 <= 192; f32 must be 0.  LDS holds one zero-bordered 192-channel slab and no copy of
+ * the input: GroupNorm 1 reads the sources from global memory and conv1 runs source by source.  Anything else: CTDD_ERANGE /
+ * CTDD_EINVAL, nothing launched.
+ * Weights: K of conv1 ordered source -> tap -> channel (not tap -> channel of the concatenation), every source padded with zero
+ * columns to a multiple of 64 channels; conv2 as above with each skip segment padded alike; both matrices then in the fragment
+ * order above with K the padded length (ctdd/unet_engine.py: pack_resblock_mid_weights). */
+int ctdd_unet_resblock_mid(const void* resblock_args, int f32, void* stream);
 
 typedef struct {
   const float* t; int B, ch, tdim;
