@@ -202,10 +202,17 @@ struct ElboArgs {
   float* grad;        // (B,D,S)
   float* out_loss;    // (1)
   int ll_in;          // ScoreElbo only: `logits` holds ll_all (reverse logit types); grad = d loss / d ll_all
+  const uint8_t* free_mask;   // (B,D) or null (K11 with Dl = D, doff = 0 only): rows with a zero byte are HELD -- they are left out of
+                      // every sum over dimensions (base_sum / Z, the normaliser, the regulariser, the cross entropy), their four
+                      // row sums and their gradient rows are written as zeros, and no pass forms anything else for them.  The two
+                      // row GEMMs run over the D rows in place (rows are independent: what they produce for a held row is never
+                      // read) and skip a 128-row tile without a free row
 };
 
 // row of the (B,Dl,S) logits / gradient that holds the objective's row (b, d)
 __device__ inline size_t elbo_lrow(const ElboArgs& a, int b, int d) { return (size_t)b * a.Dl + a.doff + d; }
+// row (b, d), d < D, is held by the mask
+__device__ inline bool elbo_held(const ElboArgs& a, int b, int d) { return a.free_mask && !a.free_mask[(size_t)b * a.D + d]; }
 
 // block reduction of LRB values per thread; result broadcast through red[]
 __device__ inline void block_sum8(float (&v)[LRB], float* red /* [4][LRB] */, float (&out)[LRB]) {
@@ -231,6 +238,35 @@ __device__ inline void block_max8(float (&v)[LRB], float* red, float (&out)[LRB]
 #pragma unroll
   for (int r = 0; r < LRB; ++r) out[r] = fmaxf(fmaxf(red[r], red[LRB + r]), fmaxf(red[2 * LRB + r], red[3 * LRB + r]));
   __syncthreads();
+}
+
+// A thread's share of base_sum[b] = sum_{d free} rs[x~_bd] under a mask, for a workgroup of 256 threads (all of them call).  The
+// unmasked loop gives thread t the rows t, t + 256, ..; here thread t gets the free rows of RANK t, t + 256, .. (rank = number of
+// free rows before it), added in that order: the fp32 sum is the one the dense / window entries form on the gathered free rows.
+// It matters: c_b takes base_sum through Z, and the gradient rows cancel to 1e-5 of their terms on peaked tables -- one ulp of
+// base_sum is 1e-4 of the largest gradient element there.
+__device__ inline float elbo_base_sum_ranked(const ElboArgs& a, int b, const float* __restrict__ R) {
+  __shared__ float slot[256];
+  __shared__ int wcnt[4];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, S = a.S;
+  slot[t] = 0.0f;
+  int before = 0;                                   // free rows in the chunks already done
+  for (int d0 = 0; d0 < a.D; d0 += 256) {           // 256 rows at a time: their ranks are distinct modulo 256
+    const int d = d0 + t;
+    const bool fr = d < a.D && a.free_mask[(size_t)b * a.D + d] != 0;
+    const unsigned long long m = __ballot(fr);
+    if (lane == 0) wcnt[w] = __popcll(m);
+    __syncthreads();
+    int rank = before + __popcll(m & ((1ull << lane) - 1ull));
+    for (int k = 0; k < w; ++k) rank += wcnt[k];
+    if (fr) {
+      const int x = min(max(a.xt[(size_t)b * a.D + d], 0), S - 1);
+      slot[rank & 255] -= R[(size_t)x * S + x];
+    }
+    before += (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    __syncthreads();
+  }
+  return slot[t];
 }
 
 // A table + base_sum.  grid (ceil(S/LRB), B): rows s0 of sample b.
@@ -264,7 +300,8 @@ __global__ __launch_bounds__(256) void k_elbo_atab(const ElboArgs a) {
   }
   if (blockIdx.x == 0) {                            // base_sum[b] = sum_d rs[x~_bd]
     float s = 0.0f;
-    for (int d = t; d < a.D; d += 256) {
+    if (a.free_mask) s = elbo_base_sum_ranked(a, b, R);
+    else for (int d = t; d < a.D; d += 256) {
       const int x = min(max(a.xt[(size_t)b * a.D + d], 0), S - 1);
       s -= R[(size_t)x * S + x];
     }
@@ -280,7 +317,7 @@ __global__ __launch_bounds__(256) void k_elbo_atab(const ElboArgs a) {
 // S % 32 == 0 (MNIST / CIFAR: S = 256) splits it around the matrix-core GEMM k_bgemm_f32:  PHASE 1 writes the left operand
 // rvec = p / (q[., x] + eps) (into the grad buffer, free until backward) and the reg / nll row sums,  PHASE 2 reads u = rvec @ q
 // back and forms the outer / norm row sums.
-template <int PHASE>
+template <int PHASE, bool MASKED = false>     // MASKED: a.free_mask is set (the unmasked instantiation carries none of its branches)
 __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
   __shared__ float rvec[LRB][256];
   __shared__ float red[4 * LRB];
@@ -303,6 +340,19 @@ __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
     l[r] = act ? a.logits[elbo_lrow(a, b, ok[r] ? d0 + r : D - 1) * S + t] : -INFINITY;
     tmp[r] = l[r];
   }
+  // held rows (masked objective): their four row sums are zeros and nothing else of theirs is written; the arithmetic of the
+  // other rows of the workgroup is untouched (every reduction is per row).  hd[] is the same in every thread.
+  bool hd[LRB], live = false;
+#pragma unroll
+  for (int r = 0; r < LRB; ++r) { hd[r] = MASKED && ok[r] && elbo_held(a, b, d0 + r); live = live || (ok[r] && !hd[r]); }
+  if (!live) {                                        // all eight held: the zeros only
+    if (t < LRB && d0 + t < D) {
+      double* dst = a.rows + ((size_t)b * D + d0 + t) * 4;
+      if (PHASE != 1) { dst[0] = 0.0; dst[1] = 0.0; }
+      if (PHASE != 2) { dst[2] = 0.0; dst[3] = 0.0; }
+    }
+    return;
+  }
   block_max8(tmp, red, mx);
 #pragma unroll
   for (int r = 0; r < LRB; ++r) tmp[r] = act ? expf(l[r] - mx[r]) : 0.0f;
@@ -314,7 +364,7 @@ __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
     const float L = mx[r] + logf(zs[r]);
     p[r] = act ? expf(l[r] - L) : 0.0f;
     const float den = act ? qT[(size_t)x[r] * S + t] + a.eps : 1.0f;
-    if (PHASE == 1) { if (act && ok[r]) a.grad[lrow_of(r) * S + t] = p[r] / den; }
+    if (PHASE == 1) { if (act && ok[r] && !hd[r]) a.grad[lrow_of(r) * S + t] = p[r] / den; }
     else rvec[r][t] = p[r] / den;
     regp[r] = act ? p[r] * a.Atab[((size_t)b * S + x[r]) * S + t] : 0.0f;
     nllp[r] = (act && t == x0[r]) ? -(l[r] - L) : 0.0f;
@@ -328,7 +378,7 @@ __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
       float v3 = 0, v4 = 0;
 #pragma unroll
       for (int r = 0; r < LRB; ++r)
-        if (r == t) { v3 = o3[r]; v4 = o4[r]; }
+        if (r == t && !hd[r]) { v3 = o3[r]; v4 = o4[r]; }
       dst[2] = v3; dst[3] = v4;
     }
     return;
@@ -371,7 +421,7 @@ __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
     float v1 = 0, v2 = 0, v3 = 0, v4 = 0;
 #pragma unroll
     for (int r = 0; r < LRB; ++r)
-      if (r == t) { v1 = o1[r]; v2 = o2[r]; if (PHASE == 0) { v3 = o3[r]; v4 = o4[r]; } }
+      if (r == t && !hd[r]) { v1 = o1[r]; v2 = o2[r]; if (PHASE == 0) { v3 = o3[r]; v4 = o4[r]; } }
     dst[0] = v1; dst[1] = v2;
     if (PHASE == 0) { dst[2] = v3; dst[3] = v4; }
   }
@@ -385,12 +435,22 @@ __global__ __launch_bounds__(256) void k_elbo_fwd(const ElboArgs a) {
 // g contracts k = 8 g .. 8 g + 7 of the chunk: each 16-byte read feeds four instructions.
 constexpr int GK = 16, GLD = GK + 4;
 template <int NT>
-__global__ __launch_bounds__(256) void k_bgemm_f32(const float* __restrict__ A, const float* __restrict__ W, float* __restrict__ Cm, int M, size_t sA, size_t sC) {
+__global__ __launch_bounds__(256) void k_bgemm_f32(const float* __restrict__ A, const float* __restrict__ W, float* __restrict__ Cm, int M, size_t sA, size_t sC,
+                                                   const uint8_t* __restrict__ live) {
   constexpr int N = 32 * NT, K = N, WV = (NT + 1) / 2;              // WV: float4 of W per thread and chunk (N * 16 / 4 / 256, rounded up)
   __shared__ __attribute__((aligned(16))) float As[2][128 * GLD];
   __shared__ __attribute__((aligned(16))) float Ws[2][N * GLD];
   using f32x16l = __attribute__((ext_vector_type(16))) float;
-  const int b = blockIdx.y, m0 = blockIdx.x * 128, t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, g = lane >> 5;
+  // live: (B, M) or null -- the masked objective's free rows.  A tile of 128 rows none of which is live has no reader for its result
+  // and leaves (the whole workgroup, before any barrier).  The grid is then (samples, tiles), sample fastest: workgroups are handed
+  // out in that order and a CU holds two of them, so with the tile fastest the surviving tiles of a sample started as neighbours
+  // on the same CUs next to idle ones (78 us against 44 for the same tiles of a window; a prefix mask of half the rows, B = 64).
+  const int b = live ? blockIdx.x : blockIdx.y, m0 = (live ? blockIdx.y : blockIdx.x) * 128;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, g = lane >> 5;
+  if (live) {
+    const int r = m0 + (t & 127);
+    if (!__syncthreads_or(t < 128 && r < M && live[(size_t)b * M + r] != 0)) return;
+  }
   const float* Ab = A + (size_t)b * sA;          // sA / sC: batch strides of A / C in floats (M K / M N when dense; a window of rows of a
                                                  // taller tensor has the taller one's).  Rows >= M are never read (zero operand) nor written.
   const float* Wb = W + (size_t)b * N * K;
@@ -477,7 +537,18 @@ __global__ __launch_bounds__(256) void k_elbo_sample_sums(const ElboArgs a, doub
     }
     __syncthreads();
   }
-  if (t < 4) sums[(size_t)b * 4 + t] = red[t][0];
+  // a sample without a free row (masked objective): all four sums are zero; its normaliser is set to 1 so that the
+  // sample adds 0 / 1 = 0 to the value and c_b stays finite (no row of the sample reads it)
+  __shared__ int nfree;
+  if (a.free_mask) {
+    if (t == 0) nfree = 0;
+    __syncthreads();
+    int c = 0;
+    for (int d = t; d < a.D; d += 256) c += a.free_mask[(size_t)b * a.D + d] ? 1 : 0;
+    if (c) atomicAdd(&nfree, c);
+    __syncthreads();
+  }
+  if (t < 4) sums[(size_t)b * 4 + t] = (t == 1 && a.free_mask && nfree == 0) ? 1.0 : red[t][0];
 }
 
 // per-sample sums -> c_b and the scalar loss.  one workgroup.
@@ -500,7 +571,7 @@ __global__ __launch_bounds__(256) void k_elbo_reduce(const ElboArgs a, const dou
 
 // backward rows.  grid (ceil(D/LRB), B).  PHASE 0: everything (fp32 FMA contraction);  PHASE 1: G rows -> the grad buffer (the
 // matrix-core GEMM then writes dr = G @ q^T over u);  PHASE 2: dr -> d/dlogits.
-template <int PHASE>
+template <int PHASE, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_elbo_bwd(const ElboArgs a) {
   __shared__ float gvec[LRB][256];
   __shared__ float red[4 * LRB];
@@ -511,7 +582,7 @@ __global__ __launch_bounds__(256) void k_elbo_bwd(const ElboArgs a) {
   const float* R = a.R + (size_t)b * S * S;
   const float cb = a.cb[b];
   int x[LRB], x0[LRB];
-  bool ok[LRB];
+  bool ok[LRB], hd[LRB], live = false;
   float l[LRB], mx[LRB], tmp[LRB], p[LRB];
 #pragma unroll
   for (int r = 0; r < LRB; ++r) {
@@ -529,10 +600,18 @@ __global__ __launch_bounds__(256) void k_elbo_bwd(const ElboArgs a) {
       const float qx0xt = q[(size_t)x0[r] * S + x[r]] + a.eps;
       G = cb * orate * (qx0 / qx0xt) / (a.u[row * S + t] + a.eps);
     }
-    if (PHASE == 1) { if (act && ok[r]) a.grad[elbo_lrow(a, b, d0 + r) * S + t] = G; }
-    else if (PHASE == 0) gvec[r][t] = G;
+    hd[r] = MASKED && ok[r] && elbo_held(a, b, d0 + r);   // held rows (masked objective): a zero gradient row, written by the last pass
+    live = live || (ok[r] && !hd[r]);
+    if (PHASE == 1) { if (act && ok[r] && !hd[r]) a.grad[elbo_lrow(a, b, d0 + r) * S + t] = G; }
+    else if (PHASE == 0) gvec[r][t] = hd[r] ? 0.0f : G;
   }
   if (PHASE == 1) return;
+  if (!live) {                                         // (the same in every thread) all eight held: the zeros only
+#pragma unroll
+    for (int r = 0; r < LRB; ++r)
+      if (act && ok[r]) a.grad[elbo_lrow(a, b, d0 + r) * S + t] = 0.0f;
+    return;
+  }
   block_max8(tmp, red, mx);                          // (contains the barrier that publishes gvec)
 #pragma unroll
   for (int r = 0; r < LRB; ++r) tmp[r] = act ? expf(l[r] - mx[r]) : 0.0f;
@@ -562,7 +641,7 @@ __global__ __launch_bounds__(256) void k_elbo_bwd(const ElboArgs a) {
 #pragma unroll
   for (int r = 0; r < LRB; ++r)
     if (act && ok[r])
-      a.grad[elbo_lrow(a, b, d0 + r) * S + t] = p[r] * (dp[r] - pdot[r]) + a.nll_scale * (p[r] - (t == x0[r] ? 1.0f : 0.0f));
+      a.grad[elbo_lrow(a, b, d0 + r) * S + t] = hd[r] ? 0.0f : p[r] * (dp[r] - pdot[r]) + a.nll_scale * (p[r] - (t == x0[r] ? 1.0f : 0.0f));
 }
 
 // ---- the regulariser table on the matrix cores (S % 32 == 0): A[b][x][s0] = sum_{s != x} q[s0][s] R[s][x] / (q[s0][x] + eps)
@@ -585,7 +664,8 @@ __global__ __launch_bounds__(256) void k_elbo_rt(const ElboArgs a) {
   if (blockIdx.x == 0 && blockIdx.y == 0) {           // base_sum[b] = sum_d rs[x~_bd]  (as k_elbo_atab)
     const int t = threadIdx.x;
     float sm = 0.0f;
-    for (int d = t; d < a.D; d += 256) {
+    if (a.free_mask) sm = elbo_base_sum_ranked(a, b, R);
+    else for (int d = t; d < a.D; d += 256) {
       const int x = min(max(a.xt[(size_t)b * a.D + d], 0), S - 1);
       sm -= R[(size_t)x * S + x];
     }
@@ -612,7 +692,7 @@ __global__ __launch_bounds__(256) void k_elbo_afix(const ElboArgs a) {
 // pass re-formed a softmax it does not use: 85 / 100 / 33 / 68 us for the four passes at 64 x 784 rows.  MODE 0: fwd<1> (rvec,
 // reg / nll sums), 1: fwd<2> (outer / norm sums from u), 2: bwd<1> (G), 3: bwd<2> (d/dlogits from dr).  RT must be set.
 constexpr int RV_ROWS = 4;                                     // rows per wave, two at a time
-template <int MODE>
+template <int MODE, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_elbo_rowsv(const ElboArgs a) {
   constexpr int S = 256;
   const int D = a.D, b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, s0 = 4 * lane;
@@ -634,7 +714,7 @@ __global__ __launch_bounds__(256) void k_elbo_rowsv(const ElboArgs a) {
   for (int r2 = 0; r2 < RV_ROWS; r2 += 2) {
     float4 lg[2], t1[2], t2[2], t3[2];
     int x[2], x0[2];
-    bool ok[2];
+    bool ok[2], hd[2];                                           // hd: held by the mask -- the same in all 64 lanes (a wave = a row)
     size_t row[2], lrow[2];                                      // compact (x0, x~, u, rows) / in the (B,Dl,S) logits and gradient
 #pragma unroll
     for (int e = 0; e < 2; ++e) {                                // everything the two rows need, requested together
@@ -644,6 +724,8 @@ __global__ __launch_bounds__(256) void k_elbo_rowsv(const ElboArgs a) {
       lrow[e] = elbo_lrow(a, b, ok[e] ? d : D - 1);
       x[e] = min(max(a.xt[row[e]], 0), S - 1);
       x0[e] = min(max(a.x0[row[e]], 0), S - 1);
+      hd[e] = MASKED && !a.free_mask[row[e]];
+      if (hd[e]) continue;                                       // a held row loads nothing
       if (MODE == 0 || MODE == 3) lg[e] = *(const float4*)(a.logits + lrow[e] * S + s0);
       if (MODE == 0 || MODE == 3) { t1[e] = *(const float4*)(qT + (size_t)x[e] * S + s0); t2[e] = *(const float4*)(At + (size_t)x[e] * S + s0); }
       if (MODE == 1 || MODE == 2) { t1[e] = *(const float4*)(RT + (size_t)x[e] * S + s0); t2[e] = *(const float4*)(q + (size_t)x0[e] * S + s0); }
@@ -651,6 +733,15 @@ __global__ __launch_bounds__(256) void k_elbo_rowsv(const ElboArgs a) {
     }
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
+      if (hd[e]) {                                               // ... and costs its zeros only: the row sums, the gradient row
+        if (ok[e]) {
+          double* dst = a.rows + row[e] * 4;
+          if (MODE == 0 && lane == 0) { dst[2] = 0.0; dst[3] = 0.0; }
+          if (MODE == 1 && lane == 0) { dst[0] = 0.0; dst[1] = 0.0; }
+          if (MODE == 3) *(float4*)(a.grad + lrow[e] * S + s0) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        continue;
+      }
       if (MODE == 0 || MODE == 3) {
         const float l4[4] = {lg[e].x, lg[e].y, lg[e].z, lg[e].w};
         const float mx = lwave_max(fmaxf(fmaxf(l4[0], l4[1]), fmaxf(l4[2], l4[3])));
@@ -739,7 +830,8 @@ extern "C" int64_t ctdd_ctelbo_scratch_bytes(int B, int D, int S) {
 
 static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
                        const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
-                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream);
+                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream,
+                       const uint8_t* free_mask = nullptr);
 extern "C" int ctdd_ctelbo_loss(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
                                 const float* rate, int B, int D, int S, float eps, float elbo_scale, float nll_scale,
                                 void* scratch, float* grad_logits, float* out_loss, void* stream) {
@@ -759,9 +851,18 @@ extern "C" int ctdd_ctelbo_loss_window(const float* logits, const int32_t* x0, c
   return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, Dl, d_off, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss,
                      stream);
 }
+// K11 under a per-sample mask of free rows: logits, x0, x_tilde, grad_logits full shape; held rows get an exact-zero gradient row
+extern "C" int ctdd_ctelbo_loss_masked(const float* logits, const int32_t* x0, const int32_t* x_tilde, const uint8_t* free_mask,
+                                       const float* qt0, const float* qt0T, const float* rate, int B, int D, int S, float eps,
+                                       float sig_scale, float reg_scale, float nll_scale, void* scratch, float* grad_logits,
+                                       float* out_loss, void* stream) {
+  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "ct-elbo masked: null mask");
+  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss,
+                     stream, free_mask);
+}
 static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
                        const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
-                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream) {
+                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream, const uint8_t* free_mask) {
   const float elbo_scale = sig_scale;
   CTDD_REQUIRE(logits && x0 && x_tilde && qt0 && qt0T && rate && scratch && grad_logits && out_loss, CTDD_EINVAL, "ct-elbo: null buffer");
   CTDD_REQUIRE(B > 0 && D > 0 && S >= 2 && S <= 256, CTDD_ERANGE, "ct-elbo: B=%d D=%d S=%d (S <= 256)", B, D, S);
@@ -770,7 +871,7 @@ static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_
   ElboArgs a;
   a.logits = logits; a.x0 = x0; a.xt = x_tilde; a.q = qt0; a.qT = qt0T; a.R = rate;
   a.B = B; a.D = D; a.S = S; a.eps = eps; a.elbo_scale = elbo_scale; a.nll_scale = nll_scale; a.reg_scale = reg_scale;
-  a.Dl = Dl; a.doff = d_off;
+  a.Dl = Dl; a.doff = d_off; a.free_mask = free_mask;
   a.Atab = (float*)sp; sp += al((int64_t)B * S * S * 4);
   a.u = (float*)sp; sp += al((int64_t)B * D * S * 4);
   a.rows = (double*)sp; sp += al((int64_t)B * D * 32);
@@ -782,23 +883,23 @@ static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_
   hipStream_t st = (hipStream_t)stream;
   const dim3 rg((D + LRB - 1) / LRB, B), gg((D + 127) / 128, B);
   const bool mfma = S % 32 == 0;                     // the S x S contractions on the exact-fp32 matrix instruction
-  auto gemm_m = [&](const float* Am, const float* Wm, float* Cm, int Mrows, size_t sA, size_t sC) {
-    const dim3 g2((Mrows + 127) / 128, B);
+  auto gemm_m = [&](const float* Am, const float* Wm, float* Cm, int Mrows, size_t sA, size_t sC, const uint8_t* live = nullptr) {
+    const dim3 g2 = live ? dim3(B, (Mrows + 127) / 128) : dim3((Mrows + 127) / 128, B);
     switch (S / 32) {
-      case 1: hipLaunchKernelGGL(k_bgemm_f32<1>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
-      case 2: hipLaunchKernelGGL(k_bgemm_f32<2>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
-      case 3: hipLaunchKernelGGL(k_bgemm_f32<3>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
-      case 4: hipLaunchKernelGGL(k_bgemm_f32<4>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
-      case 5: hipLaunchKernelGGL(k_bgemm_f32<5>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
-      case 6: hipLaunchKernelGGL(k_bgemm_f32<6>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
-      case 7: hipLaunchKernelGGL(k_bgemm_f32<7>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
-      default: hipLaunchKernelGGL(k_bgemm_f32<8>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC); break;
+      case 1: hipLaunchKernelGGL(k_bgemm_f32<1>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC, live); break;
+      case 2: hipLaunchKernelGGL(k_bgemm_f32<2>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC, live); break;
+      case 3: hipLaunchKernelGGL(k_bgemm_f32<3>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC, live); break;
+      case 4: hipLaunchKernelGGL(k_bgemm_f32<4>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC, live); break;
+      case 5: hipLaunchKernelGGL(k_bgemm_f32<5>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC, live); break;
+      case 6: hipLaunchKernelGGL(k_bgemm_f32<6>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC, live); break;
+      case 7: hipLaunchKernelGGL(k_bgemm_f32<7>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC, live); break;
+      default: hipLaunchKernelGGL(k_bgemm_f32<8>, g2, dim3(256), 0, st, Am, Wm, Cm, Mrows, sA, sC, live); break;
     }
     return finish_launch("k_bgemm_f32");
   };
   // the row GEMMs: left operand = the D window rows of the gradient buffer (batch stride Dl S), result = the compact u
   float* gwin = a.grad + (size_t)d_off * S;
-  auto gemm = [&](const float* Wm) { return gemm_m(gwin, Wm, a.u, D, (size_t)Dl * S, (size_t)D * S); };
+  auto gemm = [&](const float* Wm) { return gemm_m(gwin, Wm, a.u, D, (size_t)Dl * S, (size_t)D * S, free_mask); };
   if (Dl > D) {                                      // held rows: zeros, written once (the row passes never touch them)
     const size_t n = (size_t)(Dl - D) * S / (S % 4 == 0 ? 4 : 1);
     hipLaunchKernelGGL(k_elbo_zero_held, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), B), dim3(256), 0, st, a);
@@ -816,23 +917,26 @@ static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_
     hipLaunchKernelGGL(k_elbo_atab, dim3((S + LRB - 1) / LRB, B), dim3(256), 0, st, a);
     if (int rc = finish_launch("k_elbo_atab")) return rc;
   }
+  // the row passes: the MASKED instantiation under a mask, else the one without its branches
+#define ELBO_ROWS(K, M, G) \
+  do { if (free_mask) hipLaunchKernelGGL((K<M, true>), G, dim3(256), 0, st, a); else hipLaunchKernelGGL((K<M, false>), G, dim3(256), 0, st, a); } while (0)
   static const bool rows8 = [] { const char* e = getenv("CTDD_ELBO_ROWS8"); return e && e[0] == '1'; }();     // (A/B: the workgroup-per-8-rows passes)
   const bool wave_rows = mfma && S == 256 && !rows8;
   const dim3 wg((D + 4 * RV_ROWS - 1) / (4 * RV_ROWS), B);
   if (wave_rows) {
-    hipLaunchKernelGGL(k_elbo_rowsv<0>, wg, dim3(256), 0, st, a);               // rvec -> grad buffer; reg / nll row sums
+    ELBO_ROWS(k_elbo_rowsv, 0, wg);               // rvec -> grad buffer; reg / nll row sums
     if (int rc = finish_launch("k_elbo_rowsv<0>")) return rc;
     if (int rc = gemm(a.qT)) return rc;
-    hipLaunchKernelGGL(k_elbo_rowsv<1>, wg, dim3(256), 0, st, a);
+    ELBO_ROWS(k_elbo_rowsv, 1, wg);
     if (int rc = finish_launch("k_elbo_rowsv<1>")) return rc;
   } else if (mfma) {
-    hipLaunchKernelGGL(k_elbo_fwd<1>, rg, dim3(256), 0, st, a);                 // rvec -> grad buffer; reg / nll row sums
+    ELBO_ROWS(k_elbo_fwd, 1, rg);                 // rvec -> grad buffer; reg / nll row sums
     if (int rc = finish_launch("k_elbo_fwd<1>")) return rc;
     if (int rc = gemm(a.qT)) return rc;                                         // u[row][s] = sum_s0 rvec[row][s0] qT[s][s0]
-    hipLaunchKernelGGL(k_elbo_fwd<2>, rg, dim3(256), 0, st, a);
+    ELBO_ROWS(k_elbo_fwd, 2, rg);
     if (int rc = finish_launch("k_elbo_fwd<2>")) return rc;
   } else {
-    hipLaunchKernelGGL(k_elbo_fwd<0>, rg, dim3(256), 0, st, a);
+    ELBO_ROWS(k_elbo_fwd, 0, rg);
     if (int rc = finish_launch("k_elbo_fwd")) return rc;
   }
   hipLaunchKernelGGL(k_elbo_sample_sums, dim3(B), dim3(256), 0, st, a, sums);
@@ -840,20 +944,20 @@ static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_
   hipLaunchKernelGGL(k_elbo_reduce, dim3(1), dim3(256), 0, st, a, (const double*)sums);
   if (int rc = finish_launch("k_elbo_reduce")) return rc;
   if (wave_rows) {
-    hipLaunchKernelGGL(k_elbo_rowsv<2>, wg, dim3(256), 0, st, a);               // G -> grad buffer
+    ELBO_ROWS(k_elbo_rowsv, 2, wg);               // G -> grad buffer
     if (int rc = finish_launch("k_elbo_rowsv<2>")) return rc;
     if (int rc = gemm(a.q)) return rc;                                          // dr = G q^T (over u)
-    hipLaunchKernelGGL(k_elbo_rowsv<3>, wg, dim3(256), 0, st, a);
+    ELBO_ROWS(k_elbo_rowsv, 3, wg);
     return finish_launch("k_elbo_rowsv<3>");
   }
   if (mfma) {
-    hipLaunchKernelGGL(k_elbo_bwd<1>, rg, dim3(256), 0, st, a);                 // G -> grad buffer
+    ELBO_ROWS(k_elbo_bwd, 1, rg);                 // G -> grad buffer
     if (int rc = finish_launch("k_elbo_bwd<1>")) return rc;
     if (int rc = gemm(a.q)) return rc;                                          // dr[row][s0] = sum_s G[row][s] q[s0][s]   (over u)
-    hipLaunchKernelGGL(k_elbo_bwd<2>, rg, dim3(256), 0, st, a);
+    ELBO_ROWS(k_elbo_bwd, 2, rg);
     return finish_launch("k_elbo_bwd<2>");
   }
-  hipLaunchKernelGGL(k_elbo_bwd<0>, rg, dim3(256), 0, st, a);
+  ELBO_ROWS(k_elbo_bwd, 0, rg);
   return finish_launch("k_elbo_bwd");
 }
 
@@ -972,7 +1076,7 @@ static int score_elbo_impl(const float* logits, const int32_t* x0, const int32_t
   ElboArgs a;
   a.logits = logits; a.x0 = x0; a.xt = x_tilde; a.q = qt0; a.qT = qt0; a.R = rate;
   a.B = B; a.D = D; a.S = S; a.eps = eps; a.elbo_scale = 1.0f; a.nll_scale = nll_scale; a.reg_scale = 1.0f;
-  a.Dl = D; a.doff = 0;
+  a.Dl = D; a.doff = 0; a.free_mask = nullptr;
   a.Atab = (float*)sp; sp += al((int64_t)B * S * S * 4);
   a.u = (float*)sp; sp += al((int64_t)B * D * S * 4);
   a.rows = (double*)sp; sp += al((int64_t)B * D * 32);
@@ -1170,14 +1274,14 @@ __global__ __launch_bounds__(256) void k_lp_final(const float* __restrict__ logi
 template <typename F>
 static int launch_bgemm(int S, dim3 gg, hipStream_t st, const float* Am, const float* Wm, float* Cm, int M) {
   switch (S / 32) {
-    case 1: hipLaunchKernelGGL(k_bgemm_f32<1>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
-    case 2: hipLaunchKernelGGL(k_bgemm_f32<2>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
-    case 3: hipLaunchKernelGGL(k_bgemm_f32<3>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
-    case 4: hipLaunchKernelGGL(k_bgemm_f32<4>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
-    case 5: hipLaunchKernelGGL(k_bgemm_f32<5>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
-    case 6: hipLaunchKernelGGL(k_bgemm_f32<6>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
-    case 7: hipLaunchKernelGGL(k_bgemm_f32<7>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
-    default: hipLaunchKernelGGL(k_bgemm_f32<8>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S); break;
+    case 1: hipLaunchKernelGGL(k_bgemm_f32<1>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S, (const uint8_t*)nullptr); break;
+    case 2: hipLaunchKernelGGL(k_bgemm_f32<2>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S, (const uint8_t*)nullptr); break;
+    case 3: hipLaunchKernelGGL(k_bgemm_f32<3>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S, (const uint8_t*)nullptr); break;
+    case 4: hipLaunchKernelGGL(k_bgemm_f32<4>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S, (const uint8_t*)nullptr); break;
+    case 5: hipLaunchKernelGGL(k_bgemm_f32<5>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S, (const uint8_t*)nullptr); break;
+    case 6: hipLaunchKernelGGL(k_bgemm_f32<6>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S, (const uint8_t*)nullptr); break;
+    case 7: hipLaunchKernelGGL(k_bgemm_f32<7>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S, (const uint8_t*)nullptr); break;
+    default: hipLaunchKernelGGL(k_bgemm_f32<8>, gg, dim3(256), 0, st, Am, Wm, Cm, M, (size_t)M * S, (size_t)M * S, (const uint8_t*)nullptr); break;
   }
   return finish_launch("k_bgemm_f32");
 }

@@ -74,9 +74,12 @@ __device__ inline float block_max(float v, float* sv) {
   return t;
 }
 
-// one workgroup per batch row b
+// one workgroup per batch row b.  `free_mask` (B,D) uint8 or null: dimensions with a zero byte are held -- they carry no weight
+// and never enter the race, while the noise of a free dimension d stays the one keyed by (b, d) of the full space (an all-ones
+// mask is the unmasked draw bit for bit).  A sample with no free dimension comes back unchanged with dims = newval = -1.
 __global__ __launch_bounds__(256) void k_xtilde(const float* __restrict__ rate, const int32_t* __restrict__ tidx,
-                                                const int32_t* __restrict__ x_t, const float* __restrict__ E_dim,
+                                                const int32_t* __restrict__ x_t, const uint8_t* __restrict__ free_mask,
+                                                const float* __restrict__ E_dim,
                                                 const float* __restrict__ E_val, uint64_t seed, uint64_t offset,
                                                 int B, int D, int S, int32_t* __restrict__ out_dims,
                                                 int32_t* __restrict__ out_newval, int32_t* __restrict__ out_xt) {
@@ -86,6 +89,7 @@ __global__ __launch_bounds__(256) void k_xtilde(const float* __restrict__ rate, 
   const int tbl = tidx ? tidx[b] : b;
   const float* R = rate + (size_t)tbl * S * S;
   const int32_t* xr = x_t + (size_t)b * D;
+  const uint8_t* fr = free_mask ? free_mask + (size_t)b * D : nullptr;
   // weights w_d = sum_{s != x_d} R[x_d][s]; Categorical(probs=w) normalises by sum_d w_d.  The sum depends on the state only:
   // one table rs[x] per sample (thread = state, its row streamed in s order -- the same fp32 chain the per-dimension loop
   // ran 2 D / 256 times per thread: 231 us -> ~20 us at D = 784, S = 256), looked up per dimension.
@@ -105,11 +109,13 @@ __global__ __launch_bounds__(256) void k_xtilde(const float* __restrict__ rate, 
   }
   __syncthreads();
   float wsum = 0.0f;
-  for (int d = threadIdx.x; d < D; d += 256) wsum += rs[min(max(xr[d], 0), S - 1)];
+  for (int d = threadIdx.x; d < D; d += 256)
+    if (!fr || fr[d]) wsum += rs[min(max(xr[d], 0), S - 1)];
   const float W = block_sum(wsum, sv);
   float best = -INFINITY;
   int bi = 0x7fffffff;
   for (int d = threadIdx.x; d < D; d += 256) {
+    if (fr && !fr[d]) continue;
     const float w = rs[min(max(xr[d], 0), S - 1)];
     float Ev;
     if (E_dim) Ev = E_dim[(size_t)b * D + d];
@@ -118,6 +124,14 @@ __global__ __launch_bounds__(256) void k_xtilde(const float* __restrict__ rate, 
     if (v > best) { best = v; bi = d; }
   }
   block_argmax(best, bi, sv, si);
+  if (fr && bi == 0x7fffffff) {                       // (the same in every thread) nothing entered the race: no free dimension
+    for (int d = threadIdx.x; d < D; d += 256) out_xt[(size_t)b * D + d] = xr[d];
+    if (threadIdx.x == 0) {
+      if (out_dims) out_dims[b] = -1;
+      if (out_newval) out_newval[b] = -1;
+    }
+    return;
+  }
   const int dim = bi;
   const int xv = min(max(xr[dim], 0), S - 1);
   // new value ~ Categorical(logits = where(row<=0,-1e9,log row)), row = R[xv][:] with own state 0
@@ -193,7 +207,21 @@ extern "C" int ctdd_xtilde_sample(const float* rate, const int32_t* tidx, const 
   CTDD_REQUIRE((E_dim == nullptr) == (E_val == nullptr), CTDD_EINVAL, "E_dim and E_val must both be given or both null");
   CTDD_REQUIRE(B > 0 && D > 0, CTDD_EINVAL, "B=%d D=%d must be positive", B, D);
   CTDD_REQUIRE(S >= 2 && S <= CTDD_MAX_S, CTDD_ERANGE, "S=%d outside [2,%d]", S, CTDD_MAX_S);
-  hipLaunchKernelGGL(k_xtilde, dim3(B), dim3(256), 0, (hipStream_t)stream, rate, tidx, x_t, E_dim, E_val, seed,
+  hipLaunchKernelGGL(k_xtilde, dim3(B), dim3(256), 0, (hipStream_t)stream, rate, tidx, x_t, (const uint8_t*)nullptr, E_dim, E_val,
+                     seed, offset, B, D, S, out_dims, out_newval, out_xtilde);
+  return finish_launch("k_xtilde");
+}
+
+// K3 under a per-sample mask of free dimensions (inpainting training: x~ moves a free entry only)
+extern "C" int ctdd_xtilde_sample_masked(const float* rate, const int32_t* tidx, const int32_t* x_t, const uint8_t* free_mask,
+                                         const float* E_dim, const float* E_val, uint64_t seed, uint64_t offset,
+                                         int B, int D, int S, int32_t* out_dims, int32_t* out_newval,
+                                         int32_t* out_xtilde, void* stream) {
+  CTDD_REQUIRE(rate && x_t && free_mask && out_xtilde, CTDD_EINVAL, "null rate/x_t/free/out");
+  CTDD_REQUIRE((E_dim == nullptr) == (E_val == nullptr), CTDD_EINVAL, "E_dim and E_val must both be given or both null");
+  CTDD_REQUIRE(B > 0 && D > 0, CTDD_EINVAL, "B=%d D=%d must be positive", B, D);
+  CTDD_REQUIRE(S >= 2 && S <= CTDD_MAX_S, CTDD_ERANGE, "S=%d outside [2,%d]", S, CTDD_MAX_S);
+  hipLaunchKernelGGL(k_xtilde, dim3(B), dim3(256), 0, (hipStream_t)stream, rate, tidx, x_t, free_mask, E_dim, E_val, seed,
                      offset, B, D, S, out_dims, out_newval, out_xtilde);
   return finish_launch("k_xtilde");
 }

@@ -21,6 +21,7 @@ import torch
 
 from . import native
 from .plan_common import PlanBuilder, _lib as _hollow_lib, _P, _I, _F
+from .plan_launch import graph_capture
 from .unet_engine import _unwrap
 
 _NETS = ("BertEnumTransformer", "EnumerativeTransformer")
@@ -201,7 +202,7 @@ class BertEngine:
         graphs = []
         for plan in (st.chunk_plan, st.tail_plan):            # (the chunk graph reads r0 on the device at replay)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with graph_capture(g):
                 for step in plan:
                     step()
             graphs.append(g)

@@ -23,6 +23,7 @@ import torch
 
 from . import native
 from .plan_common import PlanBuilder, _AttnArgs, _EmbedArgs, _GemmArgs, _LnArgs, _lib  # noqa: F401  (part of this module's interface)
+from .plan_launch import graph_capture
 from .unet_engine import _unwrap
 
 
@@ -182,7 +183,7 @@ class HollowEngine:
             torch.cuda.synchronize()
             if getattr(self.net.config.model, "engine_graph", True):
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with graph_capture(g):
                     self._run_plan(st)
                 st.graph = g
         st.x_in.copy_(x.reshape(st.x_in.shape))

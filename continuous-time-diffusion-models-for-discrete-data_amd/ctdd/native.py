@@ -35,6 +35,7 @@ _SIGS = {
     "ctdd_rate_table": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P], _I),
     "ctdd_noise_categorical": ([_P, _P, _P, _P, _U64, _U64, _I, _I, _I, _P, _P], _I),
     "ctdd_xtilde_sample": ([_P, _P, _P, _P, _P, _U64, _U64, _I, _I, _I, _P, _P, _P, _P], _I),
+    "ctdd_xtilde_sample_masked": ([_P, _P, _P, _P, _P, _P, _U64, _U64, _I, _I, _I, _P, _P, _P, _P], _I),
     "ctdd_logprob": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P], _I),
     "ctdd_reverse_rates": ([_I, _I, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P], _I),
     "ctdd_tauleap_apply": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P], _I),
@@ -66,6 +67,7 @@ _SIGS = {
     "ctdd_ctelbo_loss": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_ctelbo_loss_terms": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_ctelbo_loss_window": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P], _I),
+    "ctdd_ctelbo_loss_masked": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_score_elbo_loss": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_crm_loss_ll": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P], _I),
     "ctdd_score_elbo_loss_ll": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
@@ -168,6 +170,37 @@ def xtilde_sample(rate, x_t, tidx=None, E_dim=None, E_val=None, seed=0, offset=0
                                    _ptr(E_dim, f32, "E_dim"), _ptr(E_val, f32, "E_val"), seed, offset, B, D, S,
                                    _ptr(dims), _ptr(newval), _ptr(xt), _stream())
     _check(rc, "ctdd_xtilde_sample")
+    return dims, newval, xt
+
+
+def _free_mask(free, B, D, what):
+    """The (B, D) mask of free entries as the kernels read it: uint8 (a bool tensor is reinterpreted, not copied)."""
+    if not isinstance(free, torch.Tensor) or free.dtype not in (torch.bool, torch.uint8):
+        raise CtddError(f"{what}: free must be a bool or uint8 tensor, got {getattr(free, 'dtype', type(free))}")
+    if tuple(free.shape) != (B, D):
+        raise CtddError(f"{what}: free {tuple(free.shape)} against states {(B, D)}")
+    return _ptr(free.view(torch.uint8) if free.dtype == torch.bool else free, torch.uint8, "free")
+
+
+def xtilde_sample_masked(rate, x_t, free, tidx=None, E_dim=None, E_val=None, seed=0, offset=0):
+    """K3 with the jump restricted to the free entries (`free` (B, D) bool / uint8): (dims, newval, x~); a sample without a
+    free entry comes back unchanged with dims = -1.  All free: xtilde_sample bit for bit under the same seed."""
+    B, D = x_t.shape
+    S = rate.shape[-1]
+    dev = x_t.device
+    fp = _free_mask(free, B, D, "xtilde_sample_masked")
+    if E_dim is not None and tuple(E_dim.shape) != (B, D):
+        raise CtddError(f"xtilde_sample_masked: E_dim {tuple(E_dim.shape)} against states {(B, D)}")
+    if E_val is not None and tuple(E_val.shape) != (B, S):
+        raise CtddError(f"xtilde_sample_masked: E_val {tuple(E_val.shape)} against {(B, S)}")
+    dims = torch.empty((B,), dtype=i32, device=dev)
+    newval = torch.empty((B,), dtype=i32, device=dev)
+    xt = torch.empty((B, D), dtype=i32, device=dev)
+    _count("ctdd_xtilde_sample_masked")
+    rc = load().ctdd_xtilde_sample_masked(_ptr(rate, f32, "rate"), _ptr(tidx, i32, "tidx"), _ptr(x_t, i32, "x_t"), fp,
+                                          _ptr(E_dim, f32, "E_dim"), _ptr(E_val, f32, "E_val"), seed, offset, B, D, S,
+                                          _ptr(dims), _ptr(newval), _ptr(xt), _stream())
+    _check(rc, "ctdd_xtilde_sample_masked")
     return dims, newval, xt
 
 
@@ -576,6 +609,33 @@ def ctelbo_loss_window(logits_full, x0, x_tilde, qt0, qt0T, rate, eps, sig_scale
                                        _ptr(qt0, torch.float32, "qt0"), _ptr(qt0T, torch.float32, "qt0T"), _ptr(rate, torch.float32, "rate"),
                                        B, D, S, Dl, int(d_off), float(eps), float(sig_scale), float(reg_scale), float(nll_scale),
                                        _ptr(scratch), _ptr(grad, torch.float32, "grad_out"), _ptr(out), _stream()), "ctdd_ctelbo_loss_window")
+    return out[0], grad
+
+
+def ctelbo_loss_masked(logits, x0, x_tilde, free, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale, grad_out=None):
+    """K11 on the free rows of every sample (`free` (B, D) bool / uint8; logits (B, D, S) read in place, x0 / x_tilde full shape).
+    Returns (loss scalar tensor, d loss / d logits): full shape, exact zeros on held rows, every element written by the call
+    (`grad_out`: write into this buffer instead of a fresh one).  Terms and weights as ctelbo_loss with `reg_scale` given."""
+    if logits.dim() != 3:
+        raise CtddError(f"ctelbo_loss_masked: logits {tuple(logits.shape)}, expected (B, D, S)")
+    B, D, S = logits.shape
+    if tuple(x0.shape) != (B, D) or tuple(x_tilde.shape) != (B, D):
+        raise CtddError(f"ctelbo_loss_masked: x0 {tuple(x0.shape)} / x_tilde {tuple(x_tilde.shape)} against logits {tuple(logits.shape)}")
+    for name, tab in (("qt0", qt0), ("qt0T", qt0T), ("rate", rate)):
+        if tuple(tab.shape) != (B, S, S):
+            raise CtddError(f"ctelbo_loss_masked: {name} {tuple(tab.shape)}, expected {(B, S, S)}")
+    fp = _free_mask(free, B, D, "ctelbo_loss_masked")
+    lib = load()
+    grad = torch.empty_like(logits) if grad_out is None else grad_out
+    if grad.shape != logits.shape:
+        raise CtddError(f"ctelbo_loss_masked: grad_out {tuple(grad.shape)} against logits {tuple(logits.shape)}")
+    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits.device)
+    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    _count("ctdd_ctelbo_loss_masked")
+    _check(lib.ctdd_ctelbo_loss_masked(_ptr(logits, torch.float32, "logits"), _ptr(x0, torch.int32, "x0"), _ptr(x_tilde, torch.int32, "x_tilde"),
+                                       fp, _ptr(qt0, torch.float32, "qt0"), _ptr(qt0T, torch.float32, "qt0T"), _ptr(rate, torch.float32, "rate"),
+                                       B, D, S, float(eps), float(sig_scale), float(reg_scale), float(nll_scale),
+                                       _ptr(scratch), _ptr(grad, torch.float32, "grad_out"), _ptr(out), _stream()), "ctdd_ctelbo_loss_masked")
     return out[0], grad
 
 

@@ -1,5 +1,8 @@
 """What every plan builder shares (ctdd/unet_engine.py, ctdd/plan_common.py, ctdd/hollow_train.py): the pointer helper, the
 pre-bound launch a plan is a list of, and the tile pick of the patch kernel run as a plain GEMM."""
+import contextlib
+import gc
+
 import torch
 
 from . import native
@@ -17,6 +20,24 @@ def bound_launch(fn, *args, label=None, flops=0):
             raise native.CtddError(f"{fn.__name__} failed ({rc}): {native.load().ctdd_last_error().decode()}")
     run.label, run.flops = (fn.__name__, label), flops      # flops: matrix FLOPs of the launch (bench.py's network roofline)
     return run
+
+
+@contextlib.contextmanager
+def graph_capture(graph):
+    """`torch.cuda.graph(graph)` with Python's cyclic collector held off.  The context no longer collects on entry
+    (torch.compiler.config.force_cudagraph_gc, off by default), and a collection that happens to start between capture_begin and
+    capture_end finalises whatever dead cycles hold -- device tensors, graphs, their pools -- from inside the capture, with runtime
+    calls a capturing stream does not allow: the process aborts, and whether it does depends on how many objects the interpreter
+    allocated before.  So: collect now, then no collection until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def patch_gemm_tiles(K, N):

@@ -19,7 +19,7 @@ import ctypes as C
 import torch
 
 from . import native
-from .plan_launch import bound_launch, ptr
+from .plan_launch import bound_launch, graph_capture, ptr
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SEG_3x3, SEG_1x1, SEG_3x3_S2, SEG_3x3_UP = 0, 1, 2, 3
@@ -784,7 +784,7 @@ class UNetEngine:
                 graphs = []
                 for run in runs:
                     graphs.append(torch.cuda.CUDAGraph())
-                    with torch.cuda.graph(graphs[-1]):
+                    with graph_capture(graphs[-1]):
                         run()
                 return graphs
             except native.CtddError:          # a kernel refused its arguments: never hide that

@@ -251,6 +251,124 @@ class CondCTElbo:
         return neg_elbo + self.nll_weight * self.cross_ent(l_sig.permute(0, 2, 1), data)
 
 
+class _CtElboMaskedFn(torch.autograd.Function):
+    """K11 on a per-sample set of free rows (ctdd_ctelbo_loss_masked): the network's (B, D, S) logits are read in place, x0 /
+    x_tilde are full shape, the gradient comes back full shape with exact zeros on the held rows."""
+
+    @staticmethod
+    def forward(ctx, logits, x0, x_tilde, free, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale):
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        val, grad = native.ctelbo_loss_masked(logits.detach().float().contiguous(), i32(x0), i32(x_tilde), free, qt0.contiguous(),
+                                              qt0T.contiguous(), rate.contiguous(), eps, sig_scale, reg_scale, nll_scale)
+        ctx.save_for_backward(grad)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 10
+
+
+def _ct_elbo_terms_masked(logits_reg, logits_sig, x0, reg_x, x_tilde, free, qt0, rate, eps):
+    """_ct_elbo_terms with every sum over dimensions restricted to the sample's free rows (`free` (B, D) bool): per sample the
+    negative CT-ELBO of its free rows alone; a sample without a free row contributes zero.  Full-shape operands."""
+    B = x0.shape[0]
+    n = torch.arange(B, device=x0.device).view(B, 1)
+    qT, rT = qt0.transpose(1, 2), rate.transpose(1, 2)
+    rows = lambda v: torch.where(free, v, torch.zeros_like(v)).sum(1)         # (B, D) -> (B): the free rows only
+    p_reg = F.softmax(logits_reg, dim=2)
+    reg_tmp = _masked_rows(rT, reg_x) @ qT
+    reg_term = rows(torch.sum((p_reg / (qT[n, reg_x] + eps)) * reg_tmp, dim=2))
+    p_sig = p_reg if logits_sig is logits_reg else F.softmax(logits_sig, dim=2)
+    inner = torch.log((p_sig / (qT[n, x_tilde] + eps)) @ qt0 + eps)
+    outer_rate = _masked_rows(rT, x_tilde)
+    q_x0 = qt0[n, x0]
+    q_x0_xt = torch.gather(q_x0, -1, x_tilde.unsqueeze(-1)) + eps
+    outer = rows(torch.sum(outer_rate * (q_x0 / q_x0_xt) * inner, dim=2))
+    row_sums = -torch.diagonal(rate, dim1=1, dim2=2)
+    base_tmp = row_sums[n, x_tilde]
+    Z = rows(base_tmp).view(B, 1, 1) - base_tmp.unsqueeze(-1) + row_sums.unsqueeze(1)
+    Z = torch.where(free.unsqueeze(-1), Z, torch.ones_like(Z))                # (a held row's Z is not a normaliser of anything)
+    sig_norm = rows(torch.sum(outer_rate * q_x0 / (Z * q_x0_xt), dim=2))
+    some = free.any(dim=1)
+    sig = torch.where(some, -outer / torch.where(some, sig_norm, torch.ones_like(sig_norm)), torch.zeros_like(outer))
+    return torch.mean(sig) + torch.mean(reg_term)
+
+
+@losses_utils.register_loss
+class InpaintCTElbo:
+    """CT-ELBO of a per-sample set of free entries given the held ones: what a model must be trained with for the samplers'
+    `inpaint(model, x_known, mask)` under masks that are not a prefix.  cfg.loss.mask names the mask distribution
+    (lib/losses/masks.py: prefix / bernoulli / half / box / mixture); the other fields are CondCTElbo's, and so are its
+    conventions: t ~ U(min_time, 1), the one forward pass is at x~, with two passes the cross entropy is on the x~ forward.
+
+    With free set F_b (n_b entries) of sample b:  x_t = x0 on held entries, ~ q_{t|0} on free ones;  x~ moves one free entry, chosen
+    with probability rs[x_t^d] / sum_{d' in F_b} rs[x_t^d'];  the network sees the full state (held values, not the mask);
+      loss = (1/B) sum_b neg_elbo_b + nll_weight * (sum_b sum_{d in F_b} CE_bd) / (sum_b n_b)
+    where neg_elbo_b is the negative CT-ELBO of sample b on its free rows alone.  With mask = "prefix" this is CondCTElbo."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.ratio_eps = cfg.loss.eps_ratio
+        self.nll_weight = cfg.loss.nll_weight
+        self.min_time = cfg.loss.min_time
+        self.one_forward_pass = cfg.loss.one_forward_pass
+        self.mask = cfg.loss.mask
+
+    def _noise(self, model, x0, free, ts):
+        """Tables and full-shape int64 x_t, x~: held entries of both are x0 bit for bit."""
+        if _FIXED_NOISE is not None:
+            qt0, qT, rate, _ = model.process.tables(ts, want_qt0=True, want_qt0T=True, want_rate=True)
+            pin = lambda k: torch.where(free, _FIXED_NOISE[k].to(x0.device).long(), x0)
+            return qt0, qT, rate, pin("x_t"), pin("x_tilde")
+        qt0, qT, rate, probs = model.process.tables(ts, want_qt0=True, want_qt0T=True, want_rate=True, want_noise_probs=True)
+        x0i = x0.to(torch.int32).contiguous()
+        x_t = torch.where(free, native.noise_categorical(probs, x0i, seed=_seed()), x0i)
+        _, _, x_tilde = native.xtilde_sample_masked(rate, x_t, free, seed=_seed())
+        return qt0, qT, rate, x_t.long(), x_tilde.long()
+
+    def calc_loss(self, minibatch, state=None, label=None):
+        import lib.losses.masks as masks
+        state, minibatch = _unpack(minibatch, state)
+        minibatch = _flatten(minibatch)
+        D = self.cfg.model.concat_dim
+        if minibatch.dim() != 2 or minibatch.shape[1] != D or minibatch.shape[0] < 1:
+            raise ValueError(f"InpaintCTElbo: minibatch of shape {tuple(minibatch.shape)}, model.concat_dim = {D}")
+        B = int(minibatch.shape[0])
+        if _FIXED_NOISE is not None and "free" in _FIXED_NOISE:
+            masks.check_mask_config(self.cfg, D)
+            free_host = torch.as_tensor(_FIXED_NOISE["free"]).cpu()
+            if free_host.dtype != torch.bool or tuple(free_host.shape) != (B, D):
+                raise ValueError(f"InpaintCTElbo: pinned free mask {free_host.dtype} {tuple(free_host.shape)}, expected bool {(B, D)}")
+        else:
+            free_host = masks.sample_free(self.cfg, B, D)
+        n_free = int(free_host.sum())                                  # on the host: the cross-entropy weight is a plain float
+        model = state["model"]
+        x0 = minibatch.long()
+        # the step's one upload of the mask: from pinned memory, asynchronous -- a pageable copy would make the host wait for the device
+        free = free_host.pin_memory().to(x0.device, non_blocking=True) if x0.is_cuda else free_host
+        ts = _draw_ts(B, model.device, self.min_time, 1.0)
+        qt0, qT, rate, x_t, x_tilde = self._noise(model, x0, free, ts)
+        eps, nll_scale = float(self.ratio_eps), float(self.nll_weight) / max(n_free, 1)
+        if self.one_forward_pass:                                      # (B, D, S): the network sees held values, not the mask
+            logits_sig = logits_reg = model(x_tilde, ts)
+            reg_x = x_tilde
+        else:
+            logits_reg = model(x_t, ts)
+            logits_sig = model(x_tilde, ts)
+            reg_x = x_t
+        fused = logits_sig.is_cuda and logits_sig.shape[-1] <= 256 and getattr(self.cfg.loss, "fused", True)
+        if fused and self.one_forward_pass:
+            return _CtElboMaskedFn.apply(logits_sig, x0, x_tilde, free, qt0, qT, rate, eps, 1.0, 1.0, nll_scale)
+        if fused:
+            reg = _CtElboMaskedFn.apply(logits_reg, x0, x_t, free, qt0, qT, rate, eps, 0.0, 1.0, 0.0)
+            sig = _CtElboMaskedFn.apply(logits_sig, x0, x_tilde, free, qt0, qT, rate, eps, 1.0, 0.0, nll_scale)
+            return reg + sig
+        neg_elbo = _ct_elbo_terms_masked(logits_reg, logits_sig, x0, reg_x, x_tilde, free, qt0, rate, self.ratio_eps)
+        ce = F.cross_entropy(logits_sig.permute(0, 2, 1), x0, reduction="none")
+        return neg_elbo + nll_scale * torch.where(free, ce, torch.zeros_like(ce)).sum()
+
+
 def _crm_loss(cfg, model, xt, t, ll_all, ll_xt):
     """Categorical ratio matching objectives (losses.py:794-836): rm / mle / elbo, per (b,d)."""
     S = cfg.data.S

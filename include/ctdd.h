@@ -90,6 +90,17 @@ int ctdd_xtilde_sample(const float* rate, const int32_t* tidx, const int32_t* x_
                        int B, int D, int S, int32_t* out_dims, int32_t* out_newval,
                        int32_t* out_xtilde, void* stream);
 
+/* K3 under a per-sample mask: free (B,D) uint8, non-zero = free.  Held dimensions carry no weight and never win the race: the
+ * dimension is drawn with probability w_d / sum_{d' free} w_d' over the free ones, the new value as above.  The Philox counters
+ * (and the rows of E_dim) stay keyed by (b, d) of the full space: with every byte non-zero the result is ctdd_xtilde_sample's
+ * bit for bit under the same seed.  A sample with no free entry: out_xtilde = x_t, out_dims[b] = out_newval[b] = -1.
+ * (Training under arbitrary inpainting masks -- the held-entry scheme of lib/sampling/sampling.py:649-758 applied to the
+ * x~ draw of lib/losses/losses.py:61-101.) */
+int ctdd_xtilde_sample_masked(const float* rate, const int32_t* tidx, const int32_t* x_t, const uint8_t* free,
+                              const float* E_dim, const float* E_val, uint64_t seed, uint64_t offset,
+                              int B, int D, int S, int32_t* out_dims, int32_t* out_newval,
+                              int32_t* out_xtilde, void* stream);
+
 /* A6  SDDM log-probabilities (lib/models/model_utils.py:30-60): ll_all (N,D,S), ll_xt (N,D). */
 int ctdd_logprob(const float* logits, const int32_t* x, const float* qt0, const int32_t* tidx,
                  int logit_type, int N, int D, int S, float* out_ll_all, float* out_ll_xt,
@@ -279,6 +290,19 @@ int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, const int32_t
 int ctdd_ctelbo_loss_window(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
                             const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
                             float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream);
+
+/* K11 under a per-sample mask of free rows: free (B,D) uint8, non-zero = free; logits, grad_logits (B,D,S) and x0, x_tilde (B,D)
+ * all full shape.  Terms and weights exactly as ctdd_ctelbo_loss_terms with every sum over dimensions -- base_sum / Z, the
+ * per-sample normaliser, the regulariser, the signal term, the cross entropy -- running over the sample's free rows only
+ * (CondCTElbo's objective, lib/losses/losses.py:547-781, with the window replaced by any set of rows; a prefix mask gives
+ * ctdd_ctelbo_loss_window's value).  The logits are read in place and never written; every element of grad_logits is written,
+ * held rows as exact zeros.  A sample with no free row adds zero to the value and has a zero gradient.  The row passes skip
+ * held rows (a wave or a workgroup at a time); the two row GEMMs skip 128-row tiles without a free row.
+ * scratch: ctdd_ctelbo_scratch_bytes(B, D, S). */
+int ctdd_ctelbo_loss_masked(const float* logits, const int32_t* x0, const int32_t* x_tilde, const uint8_t* free,
+                            const float* qt0, const float* qt0T, const float* rate, int B, int D, int S, float eps,
+                            float sig_scale, float reg_scale, float nll_scale, void* scratch, float* grad_logits,
+                            float* out_loss, void* stream);
 
 /* ---- ScoreElbo with direct logits (lib/losses/losses.py:1255-1500), value and d/dlogits:
  * out_loss = mean_b(-sig_b / norm_b) + mean_b(reg_b) + nll_scale * sum_{b,d} -log_softmax(logits)[x~]   (nll_scale = nll_weight / B).

@@ -1,14 +1,18 @@
-"""Prefix-conditioned training on the MNIST shapes (B = 64, D = 784, condition_dim = 392, S = 256), two measurements:
+"""Conditional training on the MNIST shapes (B = 64, D = 784, condition_dim = 392, S = 256), two measurements:
 
 1. the objective: K11 on the window of free rows, in place (ctdd_ctelbo_loss_window), against what it replaces -- copy
    logits[:, 392:] to a contiguous tensor, ctdd_ctelbo_loss_terms on it, scatter the gradient into a zero-filled full tensor --
-   and, for scale, the dense objective on all 784 rows.  The two conditional paths must agree bit for bit.
-2. one Standard.step of config_tauUnet_mnist_cond (CondCTElbo) against one of config_tauUnet_mnist (CTElbo), random-init weights.
+   and, for scale, the dense objective on all 784 rows.  The two conditional paths must agree bit for bit.  Next to them K11
+   under a per-sample mask (ctdd_ctelbo_loss_masked) with the same prefix as a mask, and with one draw of the shipped mixture.
+2. one Standard.step of config_tauUnet_mnist_cond (CondCTElbo) against one of config_tauUnet_mnist (CTElbo), and of InpaintCTElbo
+   with the same prefix as its mask and with the mixture of config_tauUnet_mnist_inpaint, random-init weights.
 
 The compared cases alternate inside every repeat; a repeat is a device-synchronised window of `--iters` calls after a warm-up of
 every case.  Reported: the median over the repeats and their min .. max (the run-to-run spread on this box).
 
     python tools/time_cond_loss.py [--repeats 7] [--iters 400] [--steps 30] [--only objective|step]
+    rocprofv3 --kernel-trace --stats --output-format csv -d prof_out/obj -o obj -- python tools/time_cond_loss.py --profile masked-prefix
+--profile CASE (window | dense | masked-prefix | masked-mixture) runs `--iters` calls of that objective and nothing else.
 """
 import argparse
 import os
@@ -43,7 +47,7 @@ def _alternate(torch, cases, repeats, iters, unit=1e6):
     return {k: (statistics.median(v), min(v), max(v)) for k, v in out.items()}
 
 
-def objective(torch, repeats, iters):
+def objective(torch, repeats, iters, profile=None):
     from ctdd import native
     from ctdd.process import DeviceForwardProcess
     gen = torch.Generator().manual_seed(0)
@@ -69,9 +73,31 @@ def objective(torch, repeats, iters):
     def dense():
         return native.ctelbo_loss(logits, x0, x_tilde, qt0, qT, rate, 1e-9, 1.0, 0.001 / (B * DL))
 
+    # the masked entry: full-shape states (held entries at x0), the prefix as a mask and one draw of the shipped mixture
+    import lib.losses.masks as masks
+    from config.mnist_config.config_tauUnet_mnist_inpaint import get_config as inpaint
+    free_p = torch.ones(B, DL, dtype=torch.bool)
+    free_p[:, :K] = False
+    torch.manual_seed(0)
+    free_m = masks.sample_free(inpaint(), B, DL)
+    share = free_m.float().mean().item()
+
+    def masked_case(free_host):
+        free = free_host.cuda()
+        xt_f = torch.where(free, x_t, x0)
+        _, _, xtl_f = native.xtilde_sample_masked(rate, xt_f, free, seed=2)
+        nll_m = 0.001 / int(free_host.sum())
+        return lambda: native.ctelbo_loss_masked(logits, x0, xtl_f, free, qt0, qT, rate, 1e-9, 1.0, 1.0, nll_m)
+
+    masked_prefix, masked_mix = masked_case(free_p), masked_case(free_m)
+    if profile is not None:
+        fn = {"window": window, "dense": dense, "masked-prefix": masked_prefix, "masked-mixture": masked_mix}[profile]
+        print(f"{profile}: {iters} calls, {_window(torch, fn, iters) * 1e6:.1f} us per call under the profiler")
+        return
     (v1, g1), (v2, g2) = window(), slice_pad()
     assert torch.equal(v1, v2) and torch.equal(g1, g2), "the window entry and slice-copy-and-pad must agree bit for bit"
-    res = _alternate(torch, {"window, in place": window, "slice copy + K11 + zero-pad scatter": slice_pad, "dense K11, all 784 rows": dense},
+    res = _alternate(torch, {"window, in place": window, "slice copy + K11 + zero-pad scatter": slice_pad, "dense K11, all 784 rows": dense,
+                             "masked, prefix 392 as a mask": masked_prefix, f"masked, mixture draw ({100 * share:.0f} % free)": masked_mix},
                      repeats, iters)
     print(f"objective, B {B}, D {DL}, condition_dim {K}, S {S}: {repeats} repeats x {iters} calls, us per call (median, min .. max)")
     for k, (med, lo, hi) in res.items():
@@ -89,9 +115,16 @@ def train_step(torch, repeats, steps):
     import lib.optimizers.optimizers_utils as ou
     from config.mnist_config.config_tauUnet_mnist import get_config as base
     from config.mnist_config.config_tauUnet_mnist_cond import get_config as cond
+    from config.mnist_config.config_tauUnet_mnist_inpaint import get_config as inpaint
+
+    def inpaint_prefix():
+        c = inpaint()
+        c.loss.update(mask="prefix", condition_dim=K)
+        return c
     mb = torch.randint(0, S, (B, 1, 28, 28), device="cuda")
     cases = {}
-    for name, get in (("CTElbo      (config_tauUnet_mnist)", base), ("CondCTElbo  (config_tauUnet_mnist_cond)", cond)):
+    for name, get in (("CTElbo         (config_tauUnet_mnist)", base), ("CondCTElbo     (config_tauUnet_mnist_cond)", cond),
+                      ("InpaintCTElbo  (mask = prefix 392)", inpaint_prefix), ("InpaintCTElbo  (config_tauUnet_mnist_inpaint)", inpaint)):
         cfg = get()
         torch.manual_seed(0)
         model = mu.create_model(cfg, torch.device("cuda"))
@@ -106,8 +139,9 @@ def train_step(torch, repeats, steps):
     print(f"Standard.step, batch {B}: {repeats} repeats x {steps} steps, ms per step (median, min .. max)")
     for k, (med, lo, hi) in res.items():
         print(f"  {k:42s} {med:7.2f}  ({lo:.2f} .. {hi:.2f})")
-    (b_med, b_lo, b_hi), (c_med, _, _) = res.values()
+    (b_med, b_lo, b_hi), (c_med, _, _), (p_med, _, _), (m_med, _, _) = res.values()
     print(f"  conditional / unconditional = {c_med / b_med:.3f}; spread of the unconditional step {100 * (b_hi - b_lo) / b_med:.1f} %")
+    print(f"  InpaintCTElbo / CondCTElbo: prefix mask {p_med / c_med:.3f}, mixture {m_med / c_med:.3f}")
 
 
 def main():
@@ -116,11 +150,14 @@ def main():
     ap.add_argument("--iters", type=int, default=400)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--only", choices=("objective", "step"), default=None)
+    ap.add_argument("--profile", choices=("window", "dense", "masked-prefix", "masked-mixture"), default=None)
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("time_cond_loss.py measures on the GPU: no device found")
     print(torch.cuda.get_device_name(0))
+    if a.profile is not None:
+        return objective(torch, a.repeats, a.iters, a.profile)
     if a.only != "step":
         objective(torch, a.repeats, a.iters)
     if a.only != "objective":
