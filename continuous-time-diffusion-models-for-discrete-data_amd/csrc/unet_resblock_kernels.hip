@@ -11,7 +11,8 @@
 //
 // Matrix mapping (v_mfma_f32_16x16x32_bf16, weights as the A operand, pixels as the B operand, so that a lane's four result
 // registers are four CONSECUTIVE channels of one pixel = one 8-byte bf16 store): wave w of four owns output channels
-// [48 w, 48 w + 48) (three 16-row weight tiles) x all pixel tiles (NPT = 4 of 16 pixels, 1 for H*W <= 16).  No two waves
+// [48 w, 48 w + 48) (three 16-row weight tiles) x all pixel tiles (NPT = 4 tiles of 16 consecutive slab rows, 5 for 8x8, one
+// tile of flattened pixels for H*W <= 16: rb_tile_pixel).  No two waves
 // read the same weight element, so the weights are streamed global -> registers by the wave that uses them, from a copy of
 // the [N][K] matrix packed in fragment order (every wave-instruction reads 1 KiB of consecutive bytes), PD chunks ahead; there is no
 // weight image in LDS, no ring and no barrier inside a K loop.  The pixel operand is read from a zero-bordered LDS slab in
@@ -19,8 +20,14 @@
 // 6 NPT matrix instructions.
 //
 // LDS: raw input [HW][C] (kept for the skip segments / the residual), slab [(H+2)(W+2)][C] for a1, reused as the
-// [(H+2)(W+2)][N] slab of h1 / a2 and as the output image; rows are padded by 16 bytes (row stride = 4 banks mod 64:
-// conflict-free 16-byte reads of 16 consecutive rows).  7x7, C = 384: 38 + 62 + 29 (reduction scratch) = 129 KB.
+// [(H+2)(W+2)][N] slab of h1 / a2 and as the output image; rows are padded by 32 bytes (row stride 2 C + 32 = 8 mod 16
+// dwords).  A ds_read_b128 is served in four groups of 16 lanes that are NOT the four quarter waves ({0-3, 12-15, 20-27}, ...:
+// two k quarters of eight rows each), so a row padding of 16 bytes, which this file had and called conflict-free, put the two
+// k quarters of a group on the same banks, and the flattened 16-pixel tiles it used jump two slab rows where a grid row wraps:
+// 12 LDS cycles per fragment read instead of 4 (tools/lds_bank_model.py; SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.54 for
+// this kernel, 0.63 for k_resblock_mid).  With 32 bytes and tiles of 16 consecutive slab rows every tap of every tile is 4
+// cycles under that model (measured ratios 0.21 / 0.31, what is left being the GroupNorm passes and the epilogues' 8-byte stores).
+// 7x7, C = 384: 38 + 63 + 29 (reduction scratch) = 130 KB.
 #include <type_traits>
 
 #include "common.hpp"
@@ -48,8 +55,8 @@ struct RbLds {                       // byte offsets into the dynamic LDS block
 };
 __host__ __device__ inline RbLds rb_layout(int H, int W, int C) {
   RbLds L;
-  L.rsA = C * 2 + 16;
-  L.rs2 = RB_N * 2 + 16;
+  L.rsA = C * 2 + 32;
+  L.rs2 = RB_N * 2 + 32;
   L.prows = (H + 2) * (W + 2);
   const int slabA = L.prows * L.rsA, slab2 = L.prows * L.rs2;
   L.raw = 0;
@@ -61,16 +68,32 @@ __host__ __device__ inline RbLds rb_layout(int H, int W, int C) {
   return L;
 }
 
-__device__ inline int rb_prow(int p, int W) {
+// slab row of pixel p of an H x W sample on a zero-bordered grid of `pitch` positions per row (W + 2, or 16 in k_resblock_mid)
+__device__ inline int rb_prow(int p, int W, int pitch) {
   const int y = p / W;
-  return (y + 1) * (W + 2) + (p - y * W) + 1;
+  return (y + 1) * pitch + (p - y * W) + 1;
+}
+// Pixel tiles of the K loops (NPT > 1): tile pt = the 16 CONSECUTIVE slab rows from Wp + 1 + 16 pt (Wp + 1: the first interior
+// row), so that lane j reads row Wp + 1 + 16 pt + j + (dy Wp + dx) for tap (dy, dx): 16 consecutive rows at a stride of
+// 2 C + 32 bytes (8 mod 16 dwords) whatever the tap, conflict-free under the lane groups of ds_read_b128
+// (tools/lds_bank_model.py).  Lanes on border positions (and rows past the grid) compute a value that is never stored; their
+// row is clamped to the interior range [Wp + 1, prows - Wp - 2], which keeps every tap of every lane inside the slab.
+struct RbPix { int row, p; bool ok; };
+__device__ inline RbPix rb_tile_pixel(int pt, int lj, int H, int W) {
+  const int Wp = W + 2, r = Wp + 1 + pt * 16 + lj, last = H * Wp + W;
+  const int yy = r / Wp, xx = r - yy * Wp;
+  RbPix q;
+  q.ok = r <= last && xx >= 1 && xx <= W;
+  q.row = r < last ? r : last;
+  q.p = q.ok ? (yy - 1) * W + xx - 1 : 0;
+  return q;
 }
 
 // GroupNorm + Swish of an [HW][C] bf16 image in LDS (`src`, rows p or padded rows): statistics as k_gn_onepass takes them
 // (fp32 per thread over its pixels, fp64 across threads and group members), then bf16(swish(x * scale + shift)) into the padded
 // rows of `dst` (which may be `src` itself: every element is read and written by the same thread).  Ends with a barrier.
 __device__ __attribute__((always_inline)) inline void rb_groupnorm(unsigned char* sm, const RbLds& L, int src, int src_rs, bool src_padded, int dst, int dst_rs,
-                                                      int HW, int W, int C, int G, const float* __restrict__ gamma,
+                                                      int HW, int W, int pitch, int C, int G, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, float eps) {
   const int t = threadIdx.x, noct = C >> 3;
   const int npl = RB_THREADS / noct < HW ? RB_THREADS / noct : HW, T = noct * npl;
@@ -85,7 +108,7 @@ __device__ __attribute__((always_inline)) inline void rb_groupnorm(unsigned char
   for (int j = 0; j < 8; ++j) { sx[j] = 0.0f; sq[j] = 0.0f; }
   if (act) {
     for (int p = pl; p < HW; p += npl) {
-      const int row = src_padded ? rb_prow(p, W) : p;
+      const int row = src_padded ? rb_prow(p, W, pitch) : p;
       const uint4 u = *(const uint4*)(sm + src + row * src_rs + oct * 16);
       const unsigned w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
@@ -127,7 +150,7 @@ __device__ __attribute__((always_inline)) inline void rb_groupnorm(unsigned char
     const f32x2v scv[4] = {{sc0.x, sc0.y}, {sc0.z, sc0.w}, {sc1.x, sc1.y}, {sc1.z, sc1.w}};
     const f32x2v shv[4] = {{sh0.x, sh0.y}, {sh0.z, sh0.w}, {sh1.x, sh1.y}, {sh1.z, sh1.w}};
     for (int p = pl; p < HW; p += npl) {
-      const int prow = rb_prow(p, W);
+      const int prow = rb_prow(p, W, pitch);
       const uint4 u = *(const uint4*)(sm + src + (src_padded ? prow : p) * src_rs + oct * 16);
       const unsigned w[4] = {u.x, u.y, u.z, u.w};
       unsigned ow[4];
@@ -258,18 +281,25 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
     const int nz = (L.part - L.slab) >> 4;
     for (int v = t; v < nz; v += RB_THREADS) *(uint4*)(sm + L.slab + v * 16) = make_uint4(0, 0, 0, 0);
     __syncthreads();
-    rb_groupnorm(sm, L, L.raw, L.rsA, false, L.slab, L.rsA, HW, W, C, a.G1, a.gamma1, a.beta1, a.eps1);
+    rb_groupnorm(sm, L, L.raw, L.rsA, false, L.slab, L.rsA, HW, W, Wp, C, a.G1, a.gamma1, a.beta1, a.eps1);
   }
 
-  // this lane's pixel of each pixel tile (pixels past the sample repeat the last one: computed, never stored)
-  int pix[NPT], b3[NPT], b1[NPT];
+  // this lane's pixel of each pixel tile (rb_tile_pixel; one tile, H * W <= 16: the flattened pixels; pix < 0: computed, never stored)
+  int pix[NPT], prow[NPT], b3[NPT], b1[NPT];
 #pragma unroll
   for (int pt = 0; pt < NPT; ++pt) {
-    const int p = pt * 16 + lj;
-    pix[pt] = p;
-    const int pe = p < HW ? p : HW - 1;
-    b3[pt] = L.slab + rb_prow(pe, W) * L.rsA + lq * 16;
-    b1[pt] = L.raw + pe * L.rsA + lq * 16;
+    if constexpr (NPT == 1) {
+      const int pe = lj < HW ? lj : HW - 1;
+      pix[pt] = lj < HW ? lj : -1;
+      prow[pt] = rb_prow(pe, W, Wp);
+      b1[pt] = L.raw + pe * L.rsA + lq * 16;
+    } else {
+      const RbPix q = rb_tile_pixel(pt, lj, H, W);
+      pix[pt] = q.ok ? q.p : -1;
+      prow[pt] = q.row;
+      b1[pt] = L.raw + q.p * L.rsA + lq * 16;
+    }
+    b3[pt] = L.slab + prow[pt] * L.rsA + lq * 16;
   }
   const int n0 = wv * 48;                                     // this wave's first output channel
   f32x4 acc[3][NPT];
@@ -297,9 +327,9 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
       const float add[4] = {bv.x + tb.x, bv.y + tb.y, bv.z + tb.z, bv.w + tb.w};
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt) {
-        if (pix[pt] < HW) {
+        if (pix[pt] >= 0) {
           const f32x4 v = acc[tt][pt];
-          *(uint2*)(sm + L.slab + rb_prow(pix[pt], W) * L.rs2 + n * 2) =
+          *(uint2*)(sm + L.slab + prow[pt] * L.rs2 + n * 2) =
               make_uint2(rb_pack2(v[0] + add[0], v[1] + add[1]), rb_pack2(v[2] + add[2], v[3] + add[3]));
         }
         acc[tt][pt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
@@ -309,14 +339,11 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
   __syncthreads();
 
   // ---- phase C: GroupNorm 2 + Swish of the bf16 h1, in place
-  rb_groupnorm(sm, L, L.slab, L.rs2, true, L.slab, L.rs2, HW, W, RB_N, a.G2, a.gamma2, a.beta2, a.eps2);
+  rb_groupnorm(sm, L, L.slab, L.rs2, true, L.slab, L.rs2, HW, W, Wp, RB_N, a.G2, a.gamma2, a.beta2, a.eps2);
 
   // ---- phase D: conv2 on a2, then the 1x1 skip segments on the raw input
 #pragma unroll
-  for (int pt = 0; pt < NPT; ++pt) {
-    const int pe = pix[pt] < HW ? pix[pt] : HW - 1;
-    b3[pt] = L.slab + rb_prow(pe, W) * L.rs2 + lq * 16;
-  }
+  for (int pt = 0; pt < NPT; ++pt) b3[pt] = L.slab + prow[pt] * L.rs2 + lq * 16;
   rb_gemm<NPT, PD>(acc, wr, w2p, K2 / 64, 9 * RB_N / 64, RB_N / 64, sm, b3, L.rs2, Wp, b1);
   __syncthreads();                                            // a2 is dead: the slab becomes the [HW][N] output image
 #pragma unroll
@@ -325,7 +352,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
     const float4 bv = *(const float4*)(a.bias2 + n);
 #pragma unroll
     for (int pt = 0; pt < NPT; ++pt) {
-      if (pix[pt] < HW) {
+      if (pix[pt] >= 0) {
         const f32x4 v = acc[tt][pt];
         float o[4] = {v[0] + bv.x, v[1] + bv.y, v[2] + bv.z, v[3] + bv.w};
         if (!a.skip) {                                        // residual: the raw input (C1 == N)
@@ -348,19 +375,28 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
   }
 }
 
-// ---------------------------------------------------------------- k_resblock_mid: the same block for a sample of <= 208 pixels (14x14)
+// ---------------------------------------------------------------- k_resblock_mid: the same block for a sample of <= 14 x 14 pixels
 //
-// Ownership as above (one workgroup of four waves per sample, wave w owns channels [48 w, 48 w + 48)), NPT = 13 pixel tiles, so a
-// weight fragment feeds 13 matrix instructions and the accumulators are 156 registers per lane.  What changes is what LDS holds:
-// ONE zero-bordered slab [(H+2)(W+2)][192 channels] (16x16 rows x 400 bytes = 100 KiB) and the reduction scratch, no raw copy of the
-// input.  GroupNorm 1 takes its statistics straight from global memory (all sources first: a group may straddle two sources), then
-// conv1 runs SOURCE BY SOURCE: normalise + Swish that source from global memory into the slab, barrier, nine taps over its
-// 64-channel chunks, barrier.  A source that is not a multiple of 64 channels (96) is padded to one: zero slab columns, zero packed
-// weights, so that no tap has half a chunk.  The 1x1 skip segments read the raw sources as B fragments straight from global memory
-// (a lane's 16 bytes = 8 consecutive channels of its pixel), before GroupNorm 2 so that conv2's first weights travel behind it.
-// The residual is added in the accumulator layout from global memory (one rounding of acc + bias + residual, as the launches it
-// replaces).  The weight ring is RM_PD = 3 chunks (72 registers: with 4 the kernel spills); the pixel fragments are buffered per k half (2 x 52 registers).
-constexpr int RM_NPT = 13, RM_PD = 3, RM_MAXHW = 208, RM_MAXROWS = 256, RM_MAXCS = 192;
+// Ownership as above (one workgroup of four waves per sample, wave w owns channels [48 w, 48 w + 48)).  What changes is what LDS
+// holds and what a pixel tile is.  LDS: ONE zero-bordered slab of 192 channels and the reduction scratch, no raw copy of the input.
+// The slab has a FIXED PITCH of 16 positions per padded grid row whatever W <= 14 (position 0 and positions > W are zero), one
+// guard row before and after: ((H + 2) 16 + 2) rows x 416 bytes = 105 KiB at H = 14.  Pixel tile y = output row y, lane j = padded
+// column j (pixel x = j - 1; lanes 0 and > W compute a value that is never stored), RM_NPT = 14 tiles (168 accumulator registers), tiles
+// y >= H skipped wave-uniformly.  The fragment that tap (dy, dx) needs for row y is then the fragment of padded row y + 1 + dy at
+// column shift dx: lane j reads slab row 1 + 16 (y + 1 + dy) + j + dx, 16 consecutive rows at a stride of 416 bytes (104 dwords,
+// 8 mod 16: conflict-free under the lane groups of ds_read_b128, tools/lds_bank_model.py; the shifts of lanes 0 and 15 of the
+// first and last padded row land in the guard rows).  The K loop's unit is (32 channels, dx): the up-to-16 row fragments of that
+// column shift are read ONCE, and output row y takes nine matrix instructions (three dy x three 16-channel weight tiles) on F[y],
+// F[y+1], F[y+2] from registers: 16 ds_read_b128 per 126 matrix instructions (the flattened 16-pixel tiles this replaced took 39 per 117).  The weights are streamed in
+// that order (unit -> dy -> tile, 9 KiB per wave and unit) through a ring of two units (72 registers).
+// GroupNorm 1 takes its statistics straight from global memory (all sources first: a group may straddle two sources), then
+// conv1 runs SOURCE BY SOURCE in 32-channel units (a 96-channel source is three of them: nothing is padded): normalise + Swish
+// that source from global memory into the slab, barrier, its units, barrier.  The 1x1 skip segments read the raw sources as B
+// fragments straight from global memory (a lane's 16 bytes = 8 consecutive channels of its pixel), before GroupNorm 2 so that
+// conv2's first weights travel behind it.  The residual is added in the accumulator layout from global memory (one rounding of
+// acc + bias + residual, as the launches it replaces).
+constexpr int RM_NPT = 14, RM_PITCH = 16, RM_MAXH = 14, RM_MAXCS = 192;
+constexpr int RM_UNIT = 9 * 512;                               // bf16 elements of one unit of a wave's 3x3 weight stream
 
 // the value again, as one the compiler knows nothing about: what is derived from it is computed where it is used instead of being
 // kept in registers (the pixel indices of the 13 tiles) from the start of the kernel to its epilogues
@@ -371,10 +407,11 @@ __device__ inline int rm_again(int v) {
 
 __host__ __device__ inline RbLds rm_layout(int H, int W) {
   RbLds L;
-  L.rsA = L.rs2 = RB_N * 2 + 16;
-  L.prows = (H + 2) * (W + 2);
-  L.raw = L.slab = 0;
-  L.part = L.prows * L.rs2;
+  (void)W;                                                    // (the pitch is fixed)
+  L.rsA = L.rs2 = RB_N * 2 + 32;
+  L.prows = (H + 2) * RM_PITCH;
+  L.raw = L.slab = L.rs2;                                     // padded position 0 (after the guard row)
+  L.part = (L.prows + 2) * L.rs2;
   L.red = L.part + RB_THREADS * RB_PST * 4;
   L.scale = L.red + 2 * RB_MAXC * 8;
   L.total = L.scale + 2 * RB_MAXC * 4;
@@ -441,21 +478,19 @@ __device__ __attribute__((always_inline)) inline void rm_gn1_stats(unsigned char
 }
 
 // bf16(swish(x * scale + shift)) of ONE source ([HW][cs] in global memory, channels [coff, coff + cs) of the concatenation) into
-// columns [0, cp) of the slab's interior rows; columns [cs, cp) (the padding to whole 64-channel chunks) are written as zeros.
-// No barrier of its own.
+// columns [0, cs) of the slab's interior rows.  No barrier of its own.
 __device__ __attribute__((always_inline)) inline void rm_gn1_apply(unsigned char* sm, const RbLds& L, const unsigned short* __restrict__ src, int cs,
-                                                                  int cp, int coff, int HW, int W) {
-  const int t = threadIdx.x, noct = cp >> 3, npl = RB_THREADS / noct;
+                                                                  int coff, int HW, int W) {
+  const int t = threadIdx.x, noct = cs >> 3, npl = RB_THREADS / noct;
   if (t >= noct * npl) return;
   const int oct = t % noct, pl = t / noct;
-  const bool real = oct * 8 < cs;
-  const float* scale = (const float*)(sm + L.scale) + (real ? coff + oct * 8 : 0);
+  const float* scale = (const float*)(sm + L.scale) + coff + oct * 8;
   const float* shift = scale + RB_MAXC;
   const float4 sc0 = *(const float4*)scale, sc1 = *(const float4*)(scale + 4);
   const float4 sh0 = *(const float4*)shift, sh1 = *(const float4*)(shift + 4);
   const f32x2v scv[4] = {{sc0.x, sc0.y}, {sc0.z, sc0.w}, {sc1.x, sc1.y}, {sc1.z, sc1.w}};
   const f32x2v shv[4] = {{sh0.x, sh0.y}, {sh0.z, sh0.w}, {sh1.x, sh1.y}, {sh1.z, sh1.w}};
-  const unsigned short* sp = src + (real ? oct * 8 : 0);
+  const unsigned short* sp = src + oct * 8;
 #pragma unroll 4
   for (int p = pl; p < HW; p += npl) {
     const u32x4 u = *(const u32x4*)(sp + (size_t)p * cs);
@@ -467,99 +502,165 @@ __device__ __attribute__((always_inline)) inline void rm_gn1_apply(unsigned char
       const f32x2v z = y * (f32x2v){-1.4426950408889634f, -1.4426950408889634f};
       const f32x2v d = (f32x2v){__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)} + (f32x2v){1.0f, 1.0f};
       y = y * (f32x2v){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-      ow[j] = real ? rb_pack2(y.x, y.y) : 0u;
+      ow[j] = rb_pack2(y.x, y.y);
     }
-    *(uint4*)(sm + L.slab + rb_prow(p, W) * L.rs2 + oct * 16) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    *(uint4*)(sm + L.slab + rb_prow(p, W, RM_PITCH) * L.rs2 + oct * 16) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
   }
 }
 
-__device__ __attribute__((always_inline)) inline void rm_wprologue(u32x4 (&wr)[RM_PD][3][2], const unsigned short* __restrict__ wrow, int nchunks) {
+// one unit of a wave's 3x3 weight stream: [dy][tile] fragments of 1 KiB each (ctdd_unet.h)
+__device__ __attribute__((always_inline)) inline void rm_wload9(u32x4 (&dst)[3][3], const unsigned short* __restrict__ wrow, int u) {
 #pragma unroll
-  for (int u = 0; u < RM_PD; ++u)
-    if (u < nchunks) rb_wload(wr[u], wrow, u);
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int t = 0; t < 3; ++t) dst[dy][t] = *(const u32x4*)(wrow + (size_t)u * RM_UNIT + (dy * 3 + t) * 512);
+}
+// the first two units of a 3x3 weight stream (issued before the phase that precedes the K loop)
+__device__ __attribute__((always_inline)) inline void rm_wprologue(u32x4 (&wr)[2][3][3], const unsigned short* __restrict__ wrow, int nunits) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (u < nunits) rm_wload9(wr[u], wrow, u);
+}
+// one 32-channel unit of the 1x1 skip stream: [tile] fragments
+__device__ __attribute__((always_inline)) inline void rm_wload3(u32x4 (&dst)[3], const unsigned short* __restrict__ wrow, int u) {
+#pragma unroll
+  for (int t = 0; t < 3; ++t) dst[t] = *(const u32x4*)(wrow + (size_t)u * 1536 + t * 512);
 }
 
-// One K loop over `nchunks` 64-channel chunks of the weight stream at wrow (ring wr holding its first RM_PD chunks): rb_gemm with the
-// pixel fragments buffered per k HALF.  xload(xf) delivers the 13 fragments of the next (chunk, half) of its own sequence (chunk 0
-// half 0, chunk 0 half 1, chunk 1 half 0, ...; one request past the end must stay a valid address).
-template <class XL>
-__device__ __attribute__((always_inline)) inline void rm_gemm(f32x4 (&acc)[3][RM_NPT], u32x4 (&wr)[RM_PD][3][2], const unsigned short* __restrict__ wrow,
-                                                             int nchunks, XL&& xload) {
-  bf16x8 xq[2][RM_NPT];
-  auto step = [&](u32x4 (&slot)[3][2], int ci, auto guard) {
+// The K loop of a 3x3 segment of nunits / 3 32-channel blocks held in the slab's columns [0, 32 nunits / 3): units in the order
+// (channel block, dx), weight ring wr holding units 0 and 1 (rm_wprologue).  fb: byte address of this lane's position of padded
+// row 0 (slab + lj * RM_RS) + its k quarter.  Unit u: F[r] = the fragment of padded row r at that column shift, r <= H + 1, read
+// ONCE; output row y takes acc[t][y] += W[dy][t] F[y + dy].  The fragments of unit u + 1 are requested while unit u computes
+// (F[y + 2] ahead of row y's matrix instructions, so at most 19 fragments are alive), the weights of unit u + 2 when unit u has
+// consumed its slot.  The request past the last unit repeats the last unit's addresses.
+constexpr int RM_RS = RB_N * 2 + 32;
+template <bool FULL>
+__device__ __attribute__((always_inline)) inline void rm_gemm_rows(f32x4 (&acc)[3][RM_NPT], u32x4 (&wr)[2][3][3], const unsigned short* __restrict__ wrow,
+                                                                  int nunits, const unsigned char* sm, int fb, int H) {
+  int un = 0, dxn = 0, cbn = 0;                                 // the unit whose fragments are requested next
+  auto xaddr = [&]() {                                         // (selects, not branches)
+    const int o = fb + (dxn - 1) * RM_RS + cbn * 64;
+    const bool more = un + 1 < nunits, wrap = dxn == 2;
+    un += more ? 1 : 0;
+    cbn += more && wrap ? 1 : 0;
+    dxn = more ? (wrap ? 0 : dxn + 1) : dxn;
+    return o;
+  };
+  auto fload = [&](bf16x8& f, int o, int r) { f = *(const bf16x8*)(sm + o + r * (RM_PITCH * RM_RS)); };
+  auto step = [&](u32x4 (&slot)[3][3], bf16x8 (&fc)[RM_NPT + 2], bf16x8 (&fn)[RM_NPT + 2], int u, auto guard) {
     constexpr bool GUARD = decltype(guard)::value;
-    if (GUARD && ci >= nchunks) return;
-    __builtin_amdgcn_sched_barrier(0);                          // (keeps the scheduler from hoisting later chunks' fragment loads: registers)
-    xload(xq[1]);
+    if (GUARD && u >= nunits) return;
+    const int o = xaddr();
+    fload(fn[0], o, 0);
+    fload(fn[1], o, 1);
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+    for (int y = 0; y < RM_NPT; ++y) {
+      if (FULL || y < H) {                                      // (wave-uniform; FULL: H = 14, one straight line)
+        fload(fn[y + 2], o, y + 2);
 #pragma unroll
-      for (int pt = 0; pt < RM_NPT; ++pt)
-        acc[t][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t][0]), xq[0][pt], acc[t][pt], 0, 0, 0);
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+          for (int t = 0; t < 3; ++t)
+            acc[t][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[dy][t]), fc[y + dy], acc[t][y], 0, 0, 0);
+        // (pins the request for F[y + 2] to this row: left alone, the scheduler gathers a unit's requests at the end of the unit
+        // before, where the first rows wait for them, and sinks both slots' weight loads to the end of the loop body, where the
+        // next iteration drains them with vmcnt(0))
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (!GUARD || u + 2 < nunits) rm_wload9(slot, wrow, u + 2);
     __builtin_amdgcn_sched_barrier(0);
-    xload(xq[0]);
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int pt = 0; pt < RM_NPT; ++pt)
-        acc[t][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t][1]), xq[1][pt], acc[t][pt], 0, 0, 0);
-    if (!GUARD || ci + RM_PD < nchunks) rb_wload(slot, wrow, ci + RM_PD);
   };
-  xload(xq[0]);
-  int ci0 = 0;
-  for (; ci0 + 2 * RM_PD <= nchunks; ci0 += RM_PD) {
+  bf16x8 F[2][RM_NPT + 2];
+  {
+    const int o = xaddr();
 #pragma unroll
-    for (int u = 0; u < RM_PD; ++u) step(wr[u], ci0 + u, std::false_type{});
+    for (int r = 0; r < RM_NPT + 2; ++r)
+      if (FULL || r < H + 2) fload(F[0][r], o, r);
   }
-  for (; ci0 < nchunks; ci0 += RM_PD) {
-#pragma unroll
-    for (int u = 0; u < RM_PD; ++u) step(wr[u], ci0 + u, std::true_type{});
+  // vmcnt(0): the ring's first two units have landed (they were requested a phase ago).  Entered with loads of unknown age in
+  // flight, the loop's own waits are merged with that state and come out as vmcnt(8 .. 0) at the top of every iteration: the
+  // ring drained once per two units.  Entered with nothing in flight they are the counted vmcnt(9 ..) of the ring.
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  int u0 = 0;
+  for (; u0 + 4 <= nunits; u0 += 2) {
+    step(wr[0], F[0], F[1], u0, std::false_type{});
+    step(wr[1], F[1], F[0], u0 + 1, std::false_type{});
+  }
+  for (; u0 < nunits; u0 += 2) {
+    step(wr[0], F[0], F[1], u0, std::true_type{});
+    step(wr[1], F[1], F[0], u0 + 1, std::true_type{});
   }
 }
 
-// the nine taps x cpt chunks of a 3x3 segment on the slab (b3: this lane's row of each pixel tile + its k quarter)
-__device__ __attribute__((always_inline)) inline void rm_gemm_slab(f32x4 (&acc)[3][RM_NPT], u32x4 (&wr)[RM_PD][3][2], const unsigned short* __restrict__ wrow,
-                                                                  int cpt, const unsigned char* sm, const int (&b3)[RM_NPT], int rs, int Wp) {
-  int tap = 0, cc = 0, hf = 0;
-  auto xload = [&](bf16x8 (&xf)[RM_NPT]) {
-    const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-    const int koff = (dy * Wp + dx) * rs + cc * 128 + hf * 64;
+// The 1x1 skip segments: nsk 32-channel units of the raw sources, B fragments straight from global memory (lane j of tile y: pixel
+// (y, j - 1), columns off the sample clamped into it: computed, never stored), weight ring ws holding units 0 and 1.
+template <bool FULL>
+__device__ __attribute__((always_inline)) inline void rm_gemm_skip(f32x4 (&acc)[3][RM_NPT], u32x4 (&ws)[2][3], const unsigned short* __restrict__ wrow, int nsk,
+                                                                  const unsigned short* __restrict__ s1, const unsigned short* __restrict__ s2,
+                                                                  int C1, int C2, int xc, int lq, int H, int W) {
+  const int nc1 = C1 >> 5;
+  auto gload = [&](bf16x8 (&g)[RM_NPT], int u) {
+    const int ue = u < nsk ? u : nsk - 1;                       // past the last unit: the last unit again
+    const bool two = ue >= nc1;
+    const unsigned char* base = (const unsigned char*)(two ? s2 : s1);
+    const int cs = two ? C2 : C1, cb = (ue - (two ? nc1 : 0)) * 32 + lq * 8;
 #pragma unroll
-    for (int pt = 0; pt < RM_NPT; ++pt) xf[pt] = *(const bf16x8*)(sm + b3[pt] + koff);
-    const bool wrap = hf == 1 && cc + 1 == cpt;                 // (selects, not branches)
-    cc = hf == 1 ? (wrap ? 0 : cc + 1) : cc;
-    tap = wrap && tap < 8 ? tap + 1 : tap;                      // past the last chunk: tap 8 again, a valid address
-    hf ^= 1;
+    for (int y = 0; y < RM_NPT; ++y) {
+      const int ye = FULL || y < H ? y : H - 1;
+      g[y] = *(const bf16x8*)(base + (unsigned)(((ye * W + xc) * cs + cb) * 2));
+    }
   };
-  rm_gemm(acc, wr, wrow, 9 * cpt, xload);
+  auto step = [&](u32x4 (&slot)[3], bf16x8 (&gc)[RM_NPT], bf16x8 (&gn)[RM_NPT], int u, auto guard) {
+    constexpr bool GUARD = decltype(guard)::value;
+    if (GUARD && u >= nsk) return;
+    gload(gn, u + 1);
+#pragma unroll
+    for (int y = 0; y < RM_NPT; ++y) {
+      if (FULL || y < H) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+          acc[t][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t]), gc[y], acc[t][y], 0, 0, 0);
+      }
+    }
+    if (!GUARD || u + 2 < nsk) rm_wload3(slot, wrow, u + 2);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  bf16x8 G[2][RM_NPT];
+  gload(G[0], 0);
+  __builtin_amdgcn_s_waitcnt(0x0F70);                           // vmcnt(0), as in rm_gemm_rows (unit 0's fragments are needed at once)
+  int u0 = 0;
+  for (; u0 + 4 <= nsk; u0 += 2) {
+    step(ws[0], G[0], G[1], u0, std::false_type{});
+    step(ws[1], G[1], G[0], u0 + 1, std::false_type{});
+  }
+  for (; u0 < nsk; u0 += 2) {
+    step(ws[0], G[0], G[1], u0, std::true_type{});
+    step(ws[1], G[1], G[0], u0 + 1, std::true_type{});
+  }
 }
 
+// FULL: H = 14, the K loops without their row tests (one straight line per unit)
+template <bool FULL>
 __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resblock_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   constexpr int NPT = RM_NPT;
   const int t = threadIdx.x, b = blockIdx.x;
-  const int H = a.H, W = a.W, HW = H * W, C1 = a.C1, C2 = a.C2, Wp = W + 2;
+  const int H = FULL ? RM_NPT : a.H, W = a.W, HW = H * W, C1 = a.C1, C2 = a.C2;
   const RbLds L = rm_layout(H, W);
   const int lane = t & 63, wv = t >> 6, lj = lane & 15, lq = lane >> 4;
-  const int cp1 = (C1 + 63) & ~63, cp2 = (C2 + 63) & ~63;
-  const int nk1 = 9 * (cp1 + cp2) / 64, nsk = a.skip ? (cp1 + cp2) / 64 : 0, nk2 = 27 + nsk;
-  const unsigned short* w1p = (const unsigned short*)a.w1 + (size_t)wv * nk1 * 3072 + lane * 8;
+  const int nu1a = 3 * (C1 >> 5), nu1b = 3 * (C2 >> 5), nsk = a.skip ? (C1 + C2) >> 5 : 0;
+  const unsigned short* w1p = (const unsigned short*)a.w1 + (size_t)wv * (nu1a + nu1b) * RM_UNIT + lane * 8;
   const unsigned short* s1 = (const unsigned short*)a.s1_bf16 + (size_t)b * HW * C1;
   const unsigned short* s2 = (const unsigned short*)a.s2_bf16 + (size_t)b * HW * C2;
-  u32x4 wr[RM_PD][3][2];                                      // the weight ring (rm_gemm)
+  u32x4 wr[2][3][3];                                          // the weight ring (rm_gemm_rows)
 
-  // ---- phase A: zero the slab (its border rows stay zero to the end), GroupNorm 1 statistics from global memory
-  rm_wprologue(wr, w1p, 9 * cp1 / 64);
+  // ---- phase A: zero the slab and its guard rows (border positions stay zero to the end), GroupNorm 1 statistics from global memory
+  rm_wprologue(wr, w1p, nu1a);
   for (int v = t; v < (L.part >> 4); v += RB_THREADS) *(uint4*)(sm + v * 16) = make_uint4(0, 0, 0, 0);
   rm_gn1_stats(sm, L, s1, s2, C1, C2, HW, a.G1, a.gamma1, a.beta1, a.eps1);
 
-  // this lane's pixel of each pixel tile (pixels past the sample repeat the last one: computed, never stored)
-  int b3[NPT];
-#pragma unroll
-  for (int pt = 0; pt < NPT; ++pt) {
-    const int p = pt * 16 + lj, pe = p < HW ? p : HW - 1;
-    b3[pt] = L.slab + rb_prow(pe, W) * L.rs2 + lq * 16;
-  }
+  const int fb = L.slab + lj * RM_RS + lq * 16;               // this lane's position of padded row 0 + its k quarter
   const int n0 = wv * 48;                                     // this wave's first output channel
   f32x4 acc[3][NPT];
 #pragma unroll
@@ -569,18 +670,24 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
 
   // ---- phase B: conv1, source by source (the slab never holds more than 192 channels)
   for (int s = 0; s < (C2 ? 2 : 1); ++s) {
-    const int cs = s ? C2 : C1, cp = s ? cp2 : cp1;
-    rm_gn1_apply(sm, L, s ? s2 : s1, cs, cp, s ? C1 : 0, HW, W);
+    rm_gn1_apply(sm, L, s ? s2 : s1, s ? C2 : C1, s ? C1 : 0, HW, W);
     __syncthreads();
-    rm_gemm_slab(acc, wr, w1p + (size_t)(s ? 9 * cp1 / 64 : 0) * 3072, cp / 64, sm, b3, L.rs2, Wp);
+    rm_gemm_rows<FULL>(acc, wr, w1p + (size_t)(s ? nu1a : 0) * RM_UNIT, s ? nu1b : nu1a, sm, fb, H);
     __syncthreads();                                          // every wave has read its last fragment of this source
-    if (s == 0 && C2) rm_wprologue(wr, w1p + (size_t)(9 * cp1 / 64) * 3072, 9 * cp2 / 64);
+    if (s == 0 && C2) rm_wprologue(wr, w1p + (size_t)nu1a * RM_UNIT, nu1b);
   }
-  // the next stream's first chunks travel during the epilogue: the skip segments' (after the 27 chunks of the 3x3 part) or conv2's
+  // the next stream's first units travel during the epilogue: the skip segments' (after the 18 units of the 3x3 part) or conv2's
   const int tw = rm_again(t);
-  const unsigned short* w2p = (const unsigned short*)a.w2 + (size_t)(tw >> 6) * nk2 * 3072 + (tw & 63) * 8;
-  rm_wprologue(wr, w2p + (size_t)(nsk ? 27 : 0) * 3072, nsk ? nsk : 27);
+  const unsigned short* w2p = (const unsigned short*)a.w2 + (size_t)(tw >> 6) * (18 * RM_UNIT + nsk * 1536) + (tw & 63) * 8;
+  u32x4 ws[2][3];
+  if (nsk) {
+    rm_wload3(ws[0], w2p + (size_t)18 * RM_UNIT, 0);
+    if (nsk > 1) rm_wload3(ws[1], w2p + (size_t)18 * RM_UNIT, 1);
+  } else {
+    rm_wprologue(wr, w2p, 18);
+  }
   const int lj1 = rm_again(lj);
+  const bool own1 = lj1 >= 1 && lj1 <= W;                      // this lane's column is a pixel
 #pragma unroll
   for (int tt = 0; tt < 3; ++tt) {
     const int n = n0 + tt * 16 + lq * 4;
@@ -588,46 +695,31 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
     const float4 tb = a.tbias ? *(const float4*)(a.tbias + (size_t)b * a.tb_stride + n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const float add[4] = {bv.x + tb.x, bv.y + tb.y, bv.z + tb.z, bv.w + tb.w};
 #pragma unroll
-    for (int pt = 0; pt < NPT; ++pt) {
-      const int p = pt * 16 + lj1;
-      if (p < HW) {
-        const f32x4 v = acc[tt][pt];
-        *(uint2*)(sm + b3[pt] + (n * 2 - lq * 16)) =            // (b3: this pixel's slab row + lq * 16)
+    for (int y = 0; y < NPT; ++y) {
+      if (y < H && own1) {
+        const f32x4 v = acc[tt][y];
+        *(uint2*)(sm + L.slab + ((y + 1) * RM_PITCH + lj1) * RM_RS + n * 2) =
             make_uint2(rb_pack2(v[0] + add[0], v[1] + add[1]), rb_pack2(v[2] + add[2], v[3] + add[3]));
       }
-      acc[tt][pt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+      acc[tt][y] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
     }
   }
   __syncthreads();
 
   // ---- phase C: the 1x1 skip segments on the raw sources, B fragments straight from global memory (conv2's sums start with them)
   if (nsk) {
-    const int nc1 = cp1 / 64;
-    int cc = 0, hf = 0;
-    auto xload = [&](bf16x8 (&xf)[NPT]) {
-      const bool two = cc >= nc1;
-      const unsigned char* base = (const unsigned char*)(two ? s2 : s1);
-      const int cs = two ? C2 : C1, cb = (cc - (two ? nc1 : 0)) * 64 + hf * 32;
-      const bool ok = cb < cs;                                  // a padded source's last half chunk: zeros (its weights are zeros too)
-      const int off = (ok ? cb : 0) * 2 + lq * 16, ljs = rm_again(lj);
-#pragma unroll
-      for (int pt = 0; pt < NPT; ++pt) {
-        const int p = pt * 16 + ljs, pe = p < HW ? p : HW - 1;
-        const bf16x8 v = *(const bf16x8*)(base + (unsigned)(pe * cs * 2 + off));
-        xf[pt] = ok ? v : __builtin_bit_cast(bf16x8, (u32x4){0u, 0u, 0u, 0u});
-      }
-      cc = hf == 1 && cc + 1 < nsk ? cc + 1 : cc;               // past the last chunk: the last chunk again
-      hf ^= 1;
-    };
-    rm_gemm(acc, wr, w2p + (size_t)27 * 3072, nsk, xload);
-    rm_wprologue(wr, w2p, 27);                                // conv2's first chunks travel during GroupNorm 2
+    const int ljs = rm_again(lj), xc = ljs < 1 ? 0 : (ljs > W ? W - 1 : ljs - 1);
+    rm_gemm_skip<FULL>(acc, ws, w2p + (size_t)18 * RM_UNIT, nsk, s1, s2, C1, C2, xc, lq, H, W);
+    rm_wprologue(wr, w2p, 18);                                // conv2's first units travel during GroupNorm 2
   }
 
   // ---- phase D: GroupNorm 2 + Swish of the bf16 h1, in place, then conv2 on a2
-  rb_groupnorm(sm, L, L.slab, L.rs2, true, L.slab, L.rs2, HW, W, RB_N, a.G2, a.gamma2, a.beta2, a.eps2);
-  rm_gemm_slab(acc, wr, w2p, RB_N / 64, sm, b3, L.rs2, Wp);
+  rb_groupnorm(sm, L, L.slab, L.rs2, true, L.slab, L.rs2, HW, W, RM_PITCH, RB_N, a.G2, a.gamma2, a.beta2, a.eps2);
+  rm_gemm_rows<FULL>(acc, wr, w2p, 18, sm, fb, H);
   __syncthreads();                                            // a2 is dead: the slab becomes the [HW][N] output image
   const int lj2 = rm_again(lj);
+  const bool own2 = lj2 >= 1 && lj2 <= W;
+  const int x2 = own2 ? lj2 - 1 : 0;
 #pragma unroll
   for (int tt = 0; tt < 3; ++tt) {
     const int n = n0 + tt * 16 + lq * 4;
@@ -635,22 +727,18 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
     uint2 r[NPT] = {};
     if (!a.skip) {                                            // residual: the raw input (C1 == N), in this lane's accumulator layout
 #pragma unroll
-      for (int pt = 0; pt < NPT; ++pt) {
-        const int p = pt * 16 + lj2;
-        r[pt] = *(const uint2*)(s1 + (size_t)(p < HW ? p : HW - 1) * RB_N + n);
-      }
+      for (int y = 0; y < NPT; ++y) r[y] = *(const uint2*)(s1 + (size_t)((y < H ? y : H - 1) * W + x2) * RB_N + n);
     }
 #pragma unroll
-    for (int pt = 0; pt < NPT; ++pt) {
-      const int p = pt * 16 + lj2;
-      if (p < HW) {
-        const f32x4 v = acc[tt][pt];
+    for (int y = 0; y < NPT; ++y) {
+      if (y < H && own2) {
+        const f32x4 v = acc[tt][y];
         float o[4] = {v[0] + bv.x, v[1] + bv.y, v[2] + bv.z, v[3] + bv.w};
         if (!a.skip) {
-          o[0] += __uint_as_float(r[pt].x << 16); o[1] += __uint_as_float(r[pt].x & 0xFFFF0000u);
-          o[2] += __uint_as_float(r[pt].y << 16); o[3] += __uint_as_float(r[pt].y & 0xFFFF0000u);
+          o[0] += __uint_as_float(r[y].x << 16); o[1] += __uint_as_float(r[y].x & 0xFFFF0000u);
+          o[2] += __uint_as_float(r[y].y << 16); o[3] += __uint_as_float(r[y].y & 0xFFFF0000u);
         }
-        *(uint2*)(sm + L.slab + p * L.rs2 + n * 2) = make_uint2(rb_pack2(o[0], o[1]), rb_pack2(o[2], o[3]));
+        *(uint2*)(sm + L.slab + (y * W + x2) * RM_RS + n * 2) = make_uint2(rb_pack2(o[0], o[1]), rb_pack2(o[2], o[3]));
       }
     }
   }
@@ -660,7 +748,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
     unsigned short* out = (unsigned short*)a.out_bf16 + (size_t)b * HW * RB_N;
     for (int v = t; v < HW * npc; v += RB_THREADS) {
       const int p = v / npc, c0 = (v - p * npc) * 8;
-      *(uint4*)(out + (size_t)p * RB_N + c0) = *(const uint4*)(sm + L.slab + p * L.rs2 + c0 * 2);
+      *(uint4*)(out + (size_t)p * RB_N + c0) = *(const uint4*)(sm + L.slab + p * RM_RS + c0 * 2);
     }
   }
 }
@@ -670,15 +758,18 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
 
 using namespace ctdd;
 
-// Refuses (non-zero, ctdd_last_error set, nothing launched) what the kernel cannot hold: fp32 mode, H*W > 64 or W > 8, N != 192,
+// Refuses (non-zero, ctdd_last_error set, nothing launched) what the kernel cannot hold: fp32 mode, H*W > 64 or W > 8, more than
+// 16 pixels whose interior spans more than 80 rows of the zero-bordered grid (five tiles of 16 consecutive rows), N != 192,
 // source channel counts that are not multiples of 64 or exceed 384 in all, groups that do not divide the channels, an LDS
 // image over the CU's 160 KiB.
 extern "C" int ctdd_unet_resblock_small(const void* args_, int f32, void* stream) {
   CTDD_REQUIRE(args_, CTDD_EINVAL, "ctdd_unet_resblock_small: null arguments");
   const ctdd_resblock_args& a = *(const ctdd_resblock_args*)args_;
   CTDD_REQUIRE(f32 == 0, CTDD_ERANGE, "ctdd_unet_resblock_small: bf16 inference only (the fp32 mode keeps the four launches)");
-  CTDD_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.W <= 8 && a.H * a.W <= 64, CTDD_ERANGE,
-               "ctdd_unet_resblock_small: a sample of %dx%d pixels does not fit the workgroup tile (H*W <= 64, W <= 8)", a.H, a.W);
+  // the interior span of the zero-bordered grid, first to last interior row of the slab: what the tiles of 16 consecutive rows cover
+  const int span = (a.H - 1) * (a.W + 2) + a.W;
+  CTDD_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.W <= 8 && a.H * a.W <= 64 && (a.H * a.W <= 16 || span <= 80), CTDD_ERANGE,
+               "ctdd_unet_resblock_small: a sample of %dx%d pixels does not fit the workgroup tile (H*W <= 64, W <= 8, (H-1)(W+2)+W <= 80)", a.H, a.W);
   const int C = a.C1 + a.C2;
   CTDD_REQUIRE(a.N == RB_N && a.C1 > 0 && a.C1 % 64 == 0 && a.C2 >= 0 && a.C2 % 64 == 0 && C <= RB_MAXC, CTDD_ERANGE,
                "ctdd_unet_resblock_small: channel counts off the tile (N=%d, C1=%d, C2=%d; N = 192, sources in multiples of 64, <= 384)", a.N,
@@ -690,10 +781,13 @@ extern "C" int ctdd_unet_resblock_small(const void* args_, int f32, void* stream
   const RbLds L = rb_layout(a.H, a.W, C);
   CTDD_REQUIRE(L.total <= 160 * 1024, CTDD_ERANGE, "ctdd_unet_resblock_small: LDS image of %d bytes over the 160 KiB budget", L.total);
   hipStream_t st = (hipStream_t)stream;
-  static bool attr_done[2][16] = {};
+  static bool attr_done[3][16] = {};
   if (a.H * a.W <= 16) {
     ensure_lds_ceiling((const void*)k_resblock_small<1>, attr_done[0]);
     hipLaunchKernelGGL(k_resblock_small<1>, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, st, a);
+  } else if (span > 64) {                                     // 8x8: five tiles of slab rows
+    ensure_lds_ceiling((const void*)k_resblock_small<5>, attr_done[2]);
+    hipLaunchKernelGGL(k_resblock_small<5>, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, st, a);
   } else {
     ensure_lds_ceiling((const void*)k_resblock_small<4>, attr_done[1]);
     hipLaunchKernelGGL(k_resblock_small<4>, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, st, a);
@@ -701,15 +795,15 @@ extern "C" int ctdd_unet_resblock_small(const void* args_, int f32, void* stream
   return finish_launch("k_resblock_small");
 }
 
-// The same block for a sample of up to 208 pixels (the 14x14 level), k_resblock_mid.  Refuses (non-zero, ctdd_last_error set, nothing
-// launched): fp32 mode, H*W > 208 or more than 256 rows in the zero-bordered grid, N != 192, a source that is not a multiple of 32
+// The same block for a sample of up to 14 x 14 pixels (the 14x14 level), k_resblock_mid.  Refuses (non-zero, ctdd_last_error set, nothing
+// launched): fp32 mode, H > 14 or W > 14 (the slab's pitch of 16 positions), N != 192, a source that is not a multiple of 32
 // channels or exceeds 192, groups that do not divide the channels, an LDS image over the CU's 160 KiB.
 extern "C" int ctdd_unet_resblock_mid(const void* args_, int f32, void* stream) {
   CTDD_REQUIRE(args_, CTDD_EINVAL, "ctdd_unet_resblock_mid: null arguments");
   const ctdd_resblock_args& a = *(const ctdd_resblock_args*)args_;
   CTDD_REQUIRE(f32 == 0, CTDD_ERANGE, "ctdd_unet_resblock_mid: bf16 inference only (the fp32 mode keeps the four launches)");
-  CTDD_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.H * a.W <= RM_MAXHW && (a.H + 2) * (a.W + 2) <= RM_MAXROWS, CTDD_ERANGE,
-               "ctdd_unet_resblock_mid: a sample of %dx%d pixels does not fit the workgroup tile (H*W <= 208, (H+2)(W+2) <= 256)", a.H, a.W);
+  CTDD_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.H <= RM_MAXH && a.W <= RM_PITCH - 2, CTDD_ERANGE,
+               "ctdd_unet_resblock_mid: a sample of %dx%d pixels does not fit the workgroup tile (H <= 14, W <= 14)", a.H, a.W);
   const int C = a.C1 + a.C2;
   CTDD_REQUIRE(a.N == RB_N && a.C1 > 0 && a.C1 % 32 == 0 && a.C1 <= RM_MAXCS && a.C2 >= 0 && a.C2 % 32 == 0 && a.C2 <= RM_MAXCS, CTDD_ERANGE,
                "ctdd_unet_resblock_mid: channel counts off the tile (N=%d, C1=%d, C2=%d; N = 192, sources in multiples of 32, <= 192 each)", a.N,
@@ -720,8 +814,13 @@ extern "C" int ctdd_unet_resblock_mid(const void* args_, int f32, void* stream) 
                    a.out_bf16, CTDD_EINVAL, "ctdd_unet_resblock_mid: null pointer");
   const RbLds L = rm_layout(a.H, a.W);
   CTDD_REQUIRE(L.total <= 160 * 1024, CTDD_ERANGE, "ctdd_unet_resblock_mid: LDS image of %d bytes over the 160 KiB budget", L.total);
-  static bool attr_done[16] = {};
-  ensure_lds_ceiling((const void*)k_resblock_mid, attr_done);
-  hipLaunchKernelGGL(k_resblock_mid, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, (hipStream_t)stream, a);
+  static bool attr_done[2][16] = {};
+  if (a.H == RM_NPT) {
+    ensure_lds_ceiling((const void*)k_resblock_mid<true>, attr_done[1]);
+    hipLaunchKernelGGL(k_resblock_mid<true>, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, (hipStream_t)stream, a);
+  } else {
+    ensure_lds_ceiling((const void*)k_resblock_mid<false>, attr_done[0]);
+    hipLaunchKernelGGL(k_resblock_mid<false>, dim3(a.B), dim3(RB_THREADS), (size_t)L.total, (hipStream_t)stream, a);
+  }
   return finish_launch("k_resblock_mid");
 }

@@ -109,12 +109,16 @@ def training_supported(model):
 
 
 def resblock_small_covers(H, W, cs, cout, G1, G2):
-    """Shapes ctdd_unet_resblock_small holds (csrc/unet_resblock_kernels.hip): a sample of <= 64 pixels in rows of <= 8, 192 output
-    channels, one or two sources in multiples of 64 channels (<= 384 in all), and its LDS image within the CU's 160 KiB."""
+    """Shapes ctdd_unet_resblock_small holds (csrc/unet_resblock_kernels.hip): a sample of <= 64 pixels in rows of <= 8 whose interior
+    spans at most 80 rows of the zero-bordered slab (five tiles of 16 consecutive rows; one tile of flattened pixels for <= 16
+    pixels), 192 output channels, one or two sources in multiples of 64 channels (<= 384 in all), and its LDS image (row stride
+    2 C + 32 bytes) within the CU's 160 KiB."""
     Ct = sum(cs)
     if H * W > 64 or W > 8 or cout != 192 or len(cs) > 2 or any(c % 64 for c in cs) or Ct > 384 or Ct % G1 or cout % G2:
         return False
-    rs_a, rs_2, prows = Ct * 2 + 16, cout * 2 + 16, (H + 2) * (W + 2)
+    if H * W > 16 and (H - 1) * (W + 2) + W > 80:
+        return False
+    rs_a, rs_2, prows = Ct * 2 + 32, cout * 2 + 32, (H + 2) * (W + 2)
     return H * W * rs_a + prows * max(rs_a, rs_2) + 256 * 80 + 2 * 384 * 8 + 2 * 384 * 4 <= 160 * 1024
 
 
@@ -127,35 +131,43 @@ def pack_resblock_weights(w2d):
 
 
 def resblock_mid_covers(H, W, cs, cout, G1, G2):
-    """Shapes ctdd_unet_resblock_mid holds (csrc/unet_resblock_kernels.hip): a sample of <= 208 pixels whose zero-bordered grid has
-    <= 256 rows, 192 output channels, one or two sources in multiples of 32 channels (<= 192 each), and its LDS image (one 192-channel
-    slab + the reduction scratch) within the CU's 160 KiB."""
+    """Shapes ctdd_unet_resblock_mid holds (csrc/unet_resblock_kernels.hip): a sample of <= 14 x 14 pixels (one row tile per output row
+    on a slab of 16 positions per padded grid row), 192 output channels, one or two sources in multiples of 32 channels (<= 192
+    each), and its LDS image (the 192-channel slab with its two guard rows + the reduction scratch) within the CU's 160 KiB."""
     Ct = sum(cs)
-    if (H < 1 or W < 1 or H * W > 208 or (H + 2) * (W + 2) > 256 or cout != 192 or not 1 <= len(cs) <= 2
+    if (H < 1 or W < 1 or H > 14 or W > 14 or cout != 192 or not 1 <= len(cs) <= 2
             or any(c <= 0 or c % 32 or c > 192 for c in cs) or G1 <= 0 or G2 <= 0 or Ct % G1 or cout % G2):
         return False
-    return (H + 2) * (W + 2) * (cout * 2 + 16) + 256 * 80 + 2 * 384 * 8 + 2 * 384 * 4 <= 160 * 1024
+    return ((H + 2) * 16 + 2) * (cout * 2 + 32) + 256 * 80 + 2 * 384 * 8 + 2 * 384 * 4 <= 160 * 1024
 
 
 def pack_resblock_mid_weights(w1, w2, cs):
     """The [192][9 Ct] conv1 matrix (K = tap -> channel of the concatenation) and the [192][9 * 192 (+ Ct)] conv2 matrix (3x3 on a2, then
-    the 1x1 skip segments) in the order ctdd_unet_resblock_mid streams them: conv1's K as source -> tap -> channel with every source
-    padded by zero columns to whole 64-channel chunks (the kernel runs conv1 source by source and no tap has half a chunk), the skip
-    segments padded alike, both then in pack_resblock_weights' fragment order."""
+    the 1x1 skip segments) in the order ctdd_unet_resblock_mid streams them (include/ctdd_unet.h): per wave (48 output channels), a 3x3
+    segment as source -> 32-channel block -> dx -> dy -> 16-channel tile, the skip segments as source -> 32-channel block -> tile,
+    every (tile, 32 channels) fragment as [q][i][8] (1 KiB of consecutive bytes per wave-instruction).  Nothing is padded.  Returned as
+    [192][K] views of the flat streams ([4 waves][48 K])."""
     N, Ct = w1.shape[0], sum(cs)
-    assert N == 192 and w1.shape[1] == 9 * Ct and w2.shape[1] in (9 * N, 9 * N + Ct)
-    w1v, k1, k2, c0 = w1.reshape(N, 9, Ct), [], [w2[:, :9 * N]], 0
+    assert N == 192 and w1.shape[1] == 9 * Ct and w2.shape[1] in (9 * N, 9 * N + Ct) and all(c % 32 == 0 for c in cs)
+
+    def seg3(w, c0, c):        # [N][9][C] columns [c0, c0 + c) -> [4][c / 32 * 3 * 3 * 3 * 512]
+        v = w[:, :, c0:c0 + c].reshape(4, 3, 16, 3, 3, c // 32, 4, 8)          # wave, tile, i, dy, dx, block, q, e
+        return v.permute(0, 5, 4, 3, 1, 6, 2, 7).reshape(4, -1)                 # wave, block, dx, dy, tile, q, i, e
+
+    def seg1(w, c0, c):        # [N][C] columns [c0, c0 + c) -> [4][c / 32 * 3 * 512]
+        v = w[:, c0:c0 + c].reshape(4, 3, 16, c // 32, 4, 8)                   # wave, tile, i, block, q, e
+        return v.permute(0, 3, 1, 4, 2, 5).reshape(4, -1)                       # wave, block, tile, q, i, e
+
+    w1v, k1, k2, c0 = w1.reshape(N, 9, Ct), [], [seg3(w2[:, :9 * N].reshape(N, 9, N), 0, N)], 0
     for c in cs:
-        cp = -(-c // 64) * 64
-        blk = w1.new_zeros((N, 9, cp))
-        blk[:, :, :c] = w1v[:, :, c0:c0 + c]
-        k1.append(blk.reshape(N, 9 * cp))
-        if w2.shape[1] > 9 * N:
-            sk = w2.new_zeros((N, cp))
-            sk[:, :c] = w2[:, 9 * N + c0:9 * N + c0 + c]
-            k2.append(sk)
+        k1.append(seg3(w1v, c0, c))
         c0 += c
-    return pack_resblock_weights(torch.cat(k1, 1).contiguous()), pack_resblock_weights(torch.cat(k2, 1).contiguous())
+    if w2.shape[1] > 9 * N:
+        c0 = 0
+        for c in cs:
+            k2.append(seg1(w2[:, 9 * N:], c0, c))
+            c0 += c
+    return torch.cat(k1, 1).contiguous().reshape(N, 9 * Ct), torch.cat(k2, 1).contiguous().reshape(N, w2.shape[1])
 
 
 def _onepass_slab(B, HW, Cn, G, max_threads=1024):

@@ -88,19 +88,25 @@ typedef struct {
 } ctdd_resblock_args;
 /* A whole ResBlock (unet.py:100-140, eval mode) of a small level in one launch, bf16: GroupNorm + Swish -> conv3x3 + bias + time bias
  * -> GroupNorm + Swish -> conv3x3 (+ 1x1 skip | + residual), one workgroup per sample, intermediates in LDS, the rounding points of
- * the four launches it replaces (ctdd_unet_gn_onepass, ctdd_unet_conv_patch, twice).  H * W <= 64, W <= 8, N = 192, C1 and C2
- * multiples of 64 with C1 + C2 <= 384; f32 must be 0.  Anything else: CTDD_ERANGE / CTDD_EINVAL, nothing launched.
+ * the four launches it replaces (ctdd_unet_gn_onepass, ctdd_unet_conv_patch, twice).  H * W <= 64, W <= 8, and for more than 16
+ * pixels (H - 1)(W + 2) + W <= 80 (the pixel tiles are 16 consecutive rows of the zero-bordered LDS image, row stride 2 C + 32
+ * bytes, five tiles at most); N = 192, C1 and C2 multiples of 64 with C1 + C2 <= 384; f32 must be 0.  Anything else: CTDD_ERANGE /
+ * CTDD_EINVAL, nothing launched.
  * Weights in fragment order: element (n, k) of the [N][K] matrix, n = 48 wave + 16 tile + i, k = 64 chunk + 32 half + 8 q + e, is at
  * ((((wave * K / 64 + chunk) * 3 + tile) * 2 + half) * 64 + 16 q + i) * 8 + e (ctdd/unet_engine.py: pack_resblock_weights): each
  * wave-instruction of the kernel's weight stream reads 1 KiB of consecutive bytes. */
 int ctdd_unet_resblock_small(const void* resblock_args, int f32, void* stream);
-/* The same block, same argument struct, for a sample of up to 208 pixels (the 14x14 level): H * W <= 208 and (H + 2)(W + 2) <= 256,
- * N = 192, C1 and C2 multiples of 32 with C1, C2 <= 192; f32 must be 0.  LDS holds one zero-bordered 192-channel slab and no copy of
- * the input: GroupNorm 1 reads the sources from global memory and conv1 runs source by source.  Anything else: CTDD_ERANGE /
- * CTDD_EINVAL, nothing launched.
- * Weights: K of conv1 ordered source -> tap -> channel (not tap -> channel of the concatenation), every source padded with zero
- * columns to a multiple of 64 channels; conv2 as above with each skip segment padded alike; both matrices then in the fragment
- * order above with K the padded length (ctdd/unet_engine.py: pack_resblock_mid_weights). */
+/* The same block, same argument struct, for a sample of up to 14 x 14 pixels (the 14x14 level): H <= 14, W <= 14, N = 192, C1 and C2
+ * multiples of 32 with C1, C2 <= 192; f32 must be 0.  LDS holds one zero-bordered 192-channel slab (16 positions per padded grid
+ * row whatever W, row stride 416 bytes, a guard row at either end) and no copy of the input: GroupNorm 1 reads the sources from
+ * global memory and conv1 runs source by source.  A pixel tile is one output row; the K loop's unit is (32 channels, dx), whose row
+ * fragments are read once and used by the three dy.  Anything else: CTDD_ERANGE / CTDD_EINVAL, nothing launched.
+ * Weights (ctdd/unet_engine.py: pack_resblock_mid_weights): a stream per wave (output channels [48 wave, 48 wave + 48)), the four
+ * streams one after the other, each a sequence of 1 KiB fragments.  A fragment is (tile, 32 channels of K): element
+ * (n = 48 wave + 16 tile + i, k = 8 q + e of the 32) at (16 q + i) * 8 + e.  conv1: for each source, for each 32-channel block of
+ * it, for dx = -1, 0, 1, for dy = -1, 0, 1, for tile = 0, 1, 2: the fragment of tap (dy, dx) on that block (27 (C1 + C2) / 32
+ * fragments per wave; nothing is padded).  conv2: the 3x3 segment on a2 in the same order (162 fragments), then for each source,
+ * for each 32-channel block of it, for tile = 0, 1, 2: the fragment of the 1x1 skip segment (3 (C1 + C2) / 32 fragments). */
 int ctdd_unet_resblock_mid(const void* resblock_args, int f32, void* stream);
 
 typedef struct {

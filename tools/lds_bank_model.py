@@ -1,0 +1,61 @@
+"""LDS-array cycles of one `ds_read_b128` wave-instruction for a given lane -> byte address function, under the lane groups of
+the CDNA4 LDS: the 64 lanes are served in four fixed groups of 16, one cycle per group when conflict-free; the bank of byte
+address a is (a / 4) mod 64, a lane's 16 bytes cover four consecutive banks, and every further DISTINCT dword address on a
+busy bank of a group adds one cycle (lanes that read the same dword are one access).  A model, not a measurement: the
+counters it stands for are SQ_LDS_BANK_CONFLICT (the extra cycles) against SQ_LDS_IDX_ACTIVE (all of them).
+
+    python tools/lds_bank_model.py          # the fragment reads of the fused ResBlock kernels, before and after the row tiles
+
+Pure Python, importable: b128_cycles(addr) with addr a function lane -> byte address (or a sequence of 64 addresses)."""
+
+GROUPS_B128 = tuple(
+    tuple(l + h for r in rs for l in range(*r))
+    for h in (0, 32)
+    for rs in (((0, 4), (12, 16), (20, 28)), ((4, 12), (16, 20), (28, 32))))
+
+
+def b128_cycles(addr):
+    """Cycles of one ds_read_b128 (4 when conflict-free).  addr: callable lane -> byte address, or a sequence of 64."""
+    a = [addr(l) for l in range(64)] if callable(addr) else list(addr)
+    assert len(a) == 64 and all(x % 16 == 0 for x in a)
+    total = 0
+    for grp in GROUPS_B128:
+        banks = {}
+        for l in grp:
+            for d in range(a[l] // 4, a[l] // 4 + 4):
+                banks.setdefault(d % 64, set()).add(d)
+        total += max(len(s) for s in banks.values())
+    return total
+
+
+def fragment_addr(row_of_lj, rs, koff=0):
+    """The pixel-operand fragment read of the fused ResBlock kernels: lane 16 q + j reads 16 bytes at row_of_lj(j) * rs + 16 q."""
+    return lambda lane: row_of_lj(lane & 15) * rs + (lane >> 4) * 16 + koff
+
+
+def flat_row(pt, H, W):
+    """Slab row of lane j of the flattened 16-pixel tile pt on a zero-bordered (H + 2) x (W + 2) grid (pixels past the sample repeat
+    the last one)."""
+    def row(j):
+        p = min(pt * 16 + j, H * W - 1)
+        y = p // W
+        return (y + 1) * (W + 2) + (p - y * W) + 1
+    return row
+
+
+def _report(name, tiles, rs, taps):
+    cyc = [[b128_cycles(fragment_addr(lambda j, t=t, s=s: t(j) + s, rs)) for s in taps] for t in tiles]
+    flat = [c for row in cyc for c in row]
+    print(f"{name:58s} rs={rs:4d}  per tile (tap 0): {[row[len(taps) // 2] for row in cyc]}  all taps: min {min(flat)} max {max(flat)} "
+          f"mean {sum(flat) / len(flat):.2f}")
+
+
+if __name__ == "__main__":
+    taps14 = [dy * 16 + dx for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
+    taps7 = [dy * 9 + dx for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
+    _report("14x14, 13 flattened pixel tiles (before)", [flat_row(pt, 14, 14) for pt in range(13)], 400, taps14)
+    _report("14x14, 14 row tiles of pitch 16 (after)", [lambda j, y=y: 1 + (y + 1) * 16 + j for y in range(14)], 416, taps14)
+    for rs in (400, 784):
+        _report("7x7, 4 flattened pixel tiles (before)", [flat_row(pt, 7, 7) for pt in range(4)], rs, taps7)
+    for rs in (416, 800):
+        _report("7x7, 4 tiles of 16 consecutive slab rows from row 10 (after)", [lambda j, pt=pt: 10 + pt * 16 + j for pt in range(4)], rs, taps7)
