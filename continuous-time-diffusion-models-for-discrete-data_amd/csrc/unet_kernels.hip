@@ -170,9 +170,12 @@ __device__ inline void conv_epilogue_tile(const ConvArgs& a, const f32x16& acc, 
 // Each lane keeps its piece's column sums / sums of squares in fp32 over the <= 8 rows it visits per
 // sample and adds them to the workgroup's fp64 LDS statistics.
 // xt = this wave's [32][32*BNT + 4] fp32 region; rows wrow0 .. wrow0 + 32*MT of the output.
-template <int BNT, int MT, bool EXT = false>   // EXT: activation + second bf16 output term (the plain-GEMM users); compiled out of the U-Net kernels
+// UP (k_conv_ring_up): the rows are low-resolution pixels (b, y, x) of a W = up_w wide grid and leave for phase
+// (py, px) = (up_ph >> 1, up_ph & 1) of the 2x grid, output row b 4HW + (2y + py) 2W + 2x + px; statistics stay per (b, column).
+template <int BNT, int MT, bool EXT = false, bool UP = false>   // EXT: activation + second bf16 output term (the plain-GEMM users); compiled out of the U-Net kernels
 __device__ __attribute__((always_inline)) inline void conv_epilogue_rows(const ConvArgs& a, const f32x16 (&acc)[MT][BNT], float* xt, int64_t wrow0, int n0,
-                                          int64_t M, int HW, const TileStats& ts, unsigned long long* epi_t = nullptr) {
+                                          int64_t M, int HW, const TileStats& ts, unsigned long long* epi_t = nullptr,
+                                          int up_w = 1, int up_ph = 0) {
 #ifdef CTDD_RES_STAMPS
   unsigned long long e0, e1, e2, e3;
 #define ESTAMP(t_) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory");
@@ -278,7 +281,14 @@ __device__ __attribute__((always_inline)) inline void conv_epilogue_rows(const C
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = 0.5f * v[j] * (1.0f + erff(v[j] * 0.70710678118654752f));
         }
-        const size_t o = (size_t)p * aN + nc;
+        size_t orow = (size_t)p;
+        if (UP) {
+          const int b = b_first + (second ? 1 : 0);
+          const unsigned r = (unsigned)(p - (int64_t)b * HW);
+          const unsigned y = r / (unsigned)up_w, x = r - y * (unsigned)up_w;
+          orow = (size_t)b * 4 * HW + (size_t)(2 * y + (up_ph >> 1)) * 2 * up_w + 2 * x + (up_ph & 1);
+        }
+        const size_t o = orow * aN + nc;
         if (p_res_bf16) {
           const uint4 rr = rres[step];
           const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
@@ -1627,6 +1637,159 @@ __global__ __launch_bounds__(256) void k_conv_ring_s2(const ConvArgs a) {
   tile_stats_flush(a, ts);
 }
 
+// ------------------------------------------------------------------ upsample-phase ring convolution (Upsample, bf16)
+// The 3x3 convolution on the nearest-2x grid of a low-resolution tensor, never materialised.  The three rows
+// 2y + py - 1 .. 2y + py + 1 of the 2x grid are source rows {y-1, y, y} (py = 0) or {y, y, y+1} (py = 1), columns alike,
+// so each output phase (py, px) is a 2x2-tap convolution of the source whose weights are sums of the original ones
+// (ctdd/unet_engine.py: fold_upsample_weights; [4][N][4 C] bf16, phase = 2 py + px, K = tap 2 i + j -> channel).  Tap (i, j)
+// of phase (py, px) reads the source pixel that tap (py + i, px + j) of a 3x3 convolution on the source grid reads, and
+// the zero pad of the 2x grid is the zero pad of the source grid: slab, halo, swizzle, DMA pieces, A-fragment offsets and
+// validity bits are those of k_conv_ring on the flattened low-resolution pixels (M = B h w, 512 per workgroup), four taps
+// of its nine.  blockIdx.y = phase * (N / BN) + column tile; a unit is the slab pieces plus 4 BNT weight pieces.  The
+// per-lane DMA sources of unit 0 are computed once (as in k_conv_ring_s2); unit u adds its 32-byte channel offset.
+template <int BNT, int NBUF>
+__global__ __launch_bounds__(512) void k_conv_ring_up(const ConvArgs a) {
+  constexpr int BK = 16, NW = 8, WM = 64, MT = 2;
+  constexpr int BN = 32 * BNT, BMP = NW * WM;
+  constexpr int SP = (BMP + 2 * 34 + 31) / 32;                   // slab pieces of 32 rows >= BMP + 2*(33+1) rows
+  constexpr int SLABB = SP * 1024, BUFB = SLABB + 4 * BN * 32;
+  constexpr int TOTAL = SP + 4 * BNT, OPS = (TOTAL + NW - 1) / NW;   // DMA ops per wave and unit
+  constexpr int DEPTH = NBUF - 1;
+  static_assert(DEPTH == 1 || DEPTH == 2, "ring of two or three unit buffers");
+  static_assert(OPS <= 8, "at most two DMA ops per tap");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, g = lane >> 5;
+  const int Hs = a.Hin, Ws = a.Win, HW = Hs * Ws;                // the source grid; the output grid is (2 Hs, 2 Ws)
+  const int64_t M = (int64_t)a.B * HW;
+  const int64_t p0 = (int64_t)blockIdx.x * BMP;
+  const int Ntot = a.N, Ktot = a.Ktot, Cin = a.seg[0].C;
+  const int ntn = Ntot / BN;
+  const int ph = (int)blockIdx.y / ntn, py = ph >> 1, px = ph & 1;
+  const int n0 = ((int)blockIdx.y - ph * ntn) * BN;
+  const int halo = Ws + 1;
+  const int nunits = Cin / BK;
+  const unsigned char* const x_base = (const unsigned char*)a.seg[0].hi;
+  const unsigned char* const w_base = (const unsigned char*)a.w_hi + (size_t)ph * Ntot * Ktot * 2;
+
+  // DMA op j of this wave: piece = wave + 8 j (clamped: the last pieces may be issued twice, same bytes to the same place).
+  // Lane l fills LDS bytes [16 l, 16 l + 16) of the piece = row l/2, stored half l&1.  Slab rows outside the tensor read
+  // clamped addresses: they are only consumed under a cleared validity bit.
+  const int rl = lane >> 1;
+  const unsigned swz16 = (unsigned)(((lane & 1) ^ ((rl >> 3) & 1)) << 4);   // byte offset of the lane's half
+  const unsigned wlane = (unsigned)rl * (unsigned)Ktot * 2u + swz16;
+  const unsigned char* opsrc[OPS];
+#pragma unroll
+  for (int j = 0; j < OPS; ++j) {
+    int p = wave + NW * j;
+    p = p < TOTAL ? p : TOTAL - 1;
+    if (p < SP) {
+      int64_t q = p0 - halo + p * 32 + rl;
+      q = q < 0 ? 0 : (q >= M ? M - 1 : q);
+      opsrc[j] = x_base + (size_t)q * Cin * 2 + swz16;
+    } else {
+      const int wp = p - SP;                                     // = tap * BNT + t
+      const int tap = wp / BNT;
+      opsrc[j] = w_base + ((size_t)(n0 + (wp - tap * BNT) * 32) * Ktot + (size_t)tap * Cin) * 2 + wlane;   // (N % BN == 0: no clamp)
+    }
+  }
+  auto issue_op = [&](int u, int buf, int j) {
+    int p = wave + NW * j;
+    p = p < TOTAL ? p : TOTAL - 1;
+    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(opsrc[j] + (size_t)u * (BK * 2)),
+                                     (void __attribute__((address_space(3)))*)(smem + (size_t)buf * BUFB + (size_t)p * 1024), 16, 0, 0);
+  };
+
+  f32x16 acc[MT][BNT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int t = 0; t < BNT; ++t)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[mt][t][i] = 0.0f;
+
+  // ---- prologue: the first DEPTH units, all ops at once
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d)
+    if (d < nunits)
+      for (int j = 0; j < OPS; ++j) issue_op(d, d, j);
+
+  // slab byte offset (swizzled) of this lane's A fragment under the phase's four taps, row tile 0 (x + 32 has the same
+  // bit 3: row tile 1 = +1024 B), and per-lane validity of (tap, row tile): bit tap*MT + mt (32-bit arithmetic: M < 2^31)
+  unsigned aoff[4], vmask = 0;
+#pragma unroll
+  for (int tap = 0; tap < 4; ++tap) {
+    const int x = halo + wave * WM + li + (py + (tap >> 1) - 1) * Ws + (px + (tap & 1) - 1);
+    aoff[tap] = (unsigned)(x * 32 + ((g ^ ((x >> 3) & 1)) << 4));
+  }
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int64_t p = p0 + wave * WM + mt * 32 + li;
+    const bool in = p < M;
+    const unsigned r = (unsigned)(in ? p : 0) % (unsigned)HW;
+    const int oy = (int)(r / (unsigned)Ws), ox = (int)(r % (unsigned)Ws);
+#pragma unroll
+    for (int tap = 0; tap < 4; ++tap) {
+      const bool ok = in && (unsigned)(oy + py + (tap >> 1) - 1) < (unsigned)Hs && (unsigned)(ox + px + (tap & 1) - 1) < (unsigned)Ws;
+      vmask |= (ok ? 1u : 0u) << (tap * MT + mt);
+    }
+  }
+  const unsigned boff = (unsigned)(SLABB + li * 32 + ((g ^ ((li >> 3) & 1)) << 4));          // weight rows: bit 3 of the row = bit 3 of li
+
+  // B first, A last: the wait for A (the first thing a tap touches) covers the whole set
+  auto read_frags = [&](unsigned ao, unsigned bo, u32x4 (&af)[MT], u32x4 (&bf)[BNT]) {
+#pragma unroll
+    for (int t = 0; t < BNT; ++t) bf[t] = *(const u32x4*)(smem + bo + t * 1024);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) af[mt] = *(const u32x4*)(smem + ao + mt * 1024);
+  };
+
+  int buf = 0, k = 0;
+  // one unit; FETCH (a compile-time flag: the tap sequence has no branch): unit k + DEPTH is requested between the taps
+  auto run_unit = [&](auto fetch_c) {
+    constexpr bool FETCH = decltype(fetch_c)::value;
+    // unit k has landed once at most the ops of the younger unit in flight remain
+    if (DEPTH == 2 && k + 1 < nunits) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();          // everyone's pieces of unit k are in LDS; unit k-1's buffer is out of use
+    const int kn = k + DEPTH;              // the unit to start fetching now, into the buffer unit k-1 used
+    const int nbuf = buf == 0 ? NBUF - 1 : buf - 1;
+    const unsigned sb = (unsigned)buf * BUFB;
+    u32x4 fa[2][MT], fb[2][BNT];
+    read_frags(sb + aoff[0], sb + boff, fa[0], fb[0]);
+#pragma unroll
+    for (int tap = 0; tap < 4; ++tap) {
+      // wait + mask this tap's A | read the next tap's set | the tap's share of the DMA ops | matrix instructions
+#pragma unroll
+      for (int mt = MT - 1; mt >= 0; --mt) fa[tap & 1][mt] &= (unsigned)__builtin_amdgcn_sbfe(vmask, tap * MT + mt, 1);   // 0 or ~0
+      __builtin_amdgcn_sched_barrier(0);
+      if (tap + 1 < 4) read_frags(sb + aoff[tap + 1], sb + boff + (tap + 1) * BN * 32, fa[(tap + 1) & 1], fb[(tap + 1) & 1]);
+      if (FETCH && tap < OPS) issue_op(kn, nbuf, tap);
+      if (FETCH && tap + 4 < OPS) issue_op(kn, nbuf, tap + 4);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < BNT; ++t)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          acc[mt][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[tap & 1][mt]),
+                                                               __builtin_bit_cast(bf16x8, fb[tap & 1][t]), acc[mt][t], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    buf = buf + 1 == NBUF ? 0 : buf + 1;
+    ++k;
+  };
+  while (k + DEPTH < nunits) run_unit(std::true_type{});
+  while (k < nunits) run_unit(std::false_type{});
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+  const TileStats ts = tile_stats_begin(a, smem, p0, BMP, n0, BN, M, HW);     // (barrier: the LDS tiles are out of use)
+  if (!ts.lds) __syncthreads();
+  float* xt = (float*)(smem + (size_t)tile_stats_samples(BMP, HW) * BN * 16) + (size_t)wave * 32 * (BN + 4);
+  conv_epilogue_rows<BNT, MT, false, true>(a, acc, xt, p0 + wave * WM, n0, M, HW, ts, nullptr, Ws, ph);
+  tile_stats_flush(a, ts);
+}
+
 // split-K finish: acc_buf (+ bias, time bias, residual) -> outputs and GroupNorm statistics
 __global__ __launch_bounds__(256) void k_conv_finish(const ConvArgs a) {
   const int HW = a.H * a.W;
@@ -2612,6 +2775,46 @@ extern "C" int ctdd_unet_conv_ring(const void* args_, int bnt, void* stream) {
     case 13: return launch_ring<3, 2, 4>(a, st);
   }
   CTDD_REQUIRE(false, CTDD_ERANGE, "unsupported ring conv tile bnt=%d", bnt);
+}
+
+template <int BNT>
+static int launch_ring_up(const ConvArgs& a, hipStream_t st) {
+  constexpr int NBUF = 3, BMP = 512, SP = (BMP + 2 * 34 + 31) / 32;
+  const int HW = a.Hin * a.Win;
+  const int64_t M = (int64_t)a.B * HW;
+  dim3 g((unsigned)((M + BMP - 1) / BMP), (unsigned)(4 * (a.N / (32 * BNT))));
+  size_t lds = (size_t)NBUF * (SP * 1024 + 4 * 32 * BNT * 32);
+  const size_t epi_lds = epilogue_rows_lds(8, BNT, BMP, HW);
+  if (lds < epi_lds) lds = epi_lds;
+  CTDD_REQUIRE(lds <= 160 * 1024, CTDD_ERANGE, "upsample-phase conv: %zu bytes of LDS", lds);
+  static bool attr_done[16] = {};
+  ensure_lds_ceiling((const void*)k_conv_ring_up<BNT, NBUF>, attr_done);
+  hipLaunchKernelGGL((k_conv_ring_up<BNT, NBUF>), g, dim3(512), lds, st, a);
+  return finish_launch("k_conv_ring_up");
+}
+
+extern "C" int ctdd_unet_conv_up_phases(const void* args_, int f32, void* stream) {
+  CTDD_REQUIRE(args_ != nullptr, CTDD_EINVAL, "null args");
+  const ConvArgs& a = *(const ConvArgs*)args_;
+  CTDD_REQUIRE(f32 == 0, CTDD_EINVAL, "upsample-phase conv is bf16 only");
+  CTDD_REQUIRE(a.nseg == 1 && a.seg[0].kind == SEG_3x3_UP && a.seg[0].hi && a.w_hi, CTDD_EINVAL,
+               "upsample-phase conv: one CTDD_SEG_3x3_UP segment (nseg=%d kind=%d)", a.nseg, a.seg[0].kind);
+  const int Cin = a.seg[0].C;
+  CTDD_REQUIRE(Cin >= 16 && Cin % 16 == 0 && a.Ktot == 4 * Cin, CTDD_EINVAL, "upsample-phase conv: C=%d Ktot=%d (need C %% 16 == 0, Ktot = 4 C)",
+               Cin, a.Ktot);
+  CTDD_REQUIRE(a.N > 0 && (a.N % 96 == 0 || a.N % 64 == 0), CTDD_ERANGE, "upsample-phase conv: N=%d is not on 64- or 96-column tiles", a.N);
+  CTDD_REQUIRE(a.B >= 1 && a.Hin >= 1 && a.Win >= 1 && a.Win <= 33 && a.H == 2 * a.Hin && a.W == 2 * a.Win, CTDD_EINVAL,
+               "upsample-phase conv: output %dx%d from %dx%d (need the 2x grid, source W <= 33)", a.H, a.W, a.Hin, a.Win);
+  CTDD_REQUIRE((int64_t)a.Hin * a.Win >= 32, CTDD_ERANGE, "upsample-phase conv needs a source grid of H*W >= 32 pixels (a 32-row slice spans two samples at most)");
+  CTDD_REQUIRE(a.ksplit <= 1, CTDD_EINVAL, "upsample-phase conv has no split-K");
+  CTDD_REQUIRE(a.out_hi && !a.out_f32 && !a.out_lo && a.logits_C <= 0 && a.act == 0 && !a.res_f32 && !a.res_bf16 && !a.tbias, CTDD_EINVAL,
+               "upsample-phase conv: bf16 output + bias (+ statistics) only");
+  CTDD_REQUIRE((((uintptr_t)a.seg[0].hi | (uintptr_t)a.w_hi | (uintptr_t)a.out_hi) & 15) == 0, CTDD_EINVAL,
+               "upsample-phase conv: tensors must be 16-byte aligned");
+  CTDD_REQUIRE((int64_t)a.Ktot * 64 < (int64_t)1 << 31, CTDD_ERANGE, "upsample-phase conv: Ktot=%d too large for 32-bit lane offsets", a.Ktot);
+  CTDD_REQUIRE((int64_t)a.B * a.H * a.W < (int64_t)1 << 31, CTDD_ERANGE, "upsample-phase conv: B*H*W does not fit 31 bits");
+  hipStream_t st = (hipStream_t)stream;
+  return a.N % 96 == 0 ? launch_ring_up<3>(a, st) : launch_ring_up<2>(a, st);
 }
 
 extern "C" int ctdd_unet_upsample2x(const void* x, int B, int H, int W, int C, void* out, void* stream) {

@@ -74,7 +74,7 @@ def _lib():
     lib = native.load()
     if not _sigs_done:
         for name, argt in (("ctdd_unet_conv", [_P, _I, _I, _I, _P]), ("ctdd_unet_conv_patch", [_P, _I, _I, _I, _P]), ("ctdd_unet_conv_res", [_P, _I, _P]), ("ctdd_unet_conv_ring", [_P, _I, _P]),
-                           ("ctdd_unet_upsample2x", [_P, _I, _I, _I, _I, _P, _P]), ("ctdd_unet_first_conv", [_P, _P]),
+                           ("ctdd_unet_conv_up_phases", [_P, _I, _P]), ("ctdd_unet_upsample2x", [_P, _I, _I, _I, _I, _P, _P]), ("ctdd_unet_first_conv", [_P, _P]),
                            ("ctdd_unet_gn_apply", [_P, _P]), ("ctdd_unet_gn_onepass", [_P, _I, _I, _P]), ("ctdd_unet_channel_stats", [_P, _I, _I, _I, _P, _P]),
                            ("ctdd_unet_time", [_P, _P, _P, _I, _P, _P]), ("ctdd_unet_time_uniform", [_P, _P, _P, _I, _P, _P]),
                            ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_resblock_small", [_P, _I, _P]),
@@ -168,6 +168,25 @@ def pack_resblock_mid_weights(w1, w2, cs):
             k2.append(seg1(w2[:, 9 * N:], c0, c))
             c0 += c
     return torch.cat(k1, 1).contiguous().reshape(N, 9 * Ct), torch.cat(k2, 1).contiguous().reshape(N, w2.shape[1])
+
+
+def fold_upsample_weights(w):
+    """The Upsample convolution's [N][C][3][3] weights -> [4][N][4 C] (include/ctdd_unet.h: ctdd_unet_conv_up_phases): the 3x3
+    convolution on the nearest-2x grid as four 2x2-tap convolutions of the source.  Output pixel (2y + py, 2x + px) reads rows
+    {y-1, y, y} (py = 0) or {y, y, y+1} (py = 1) of the source, columns alike, so phase 2 py + px has taps (i, j) on source pixel
+    (y + py + i - 1, x + px + j - 1) with the weights of the 3x3 taps that land there summed: rows {W[0], W[1] + W[2]} for py = 0,
+    {W[0] + W[1], W[2]} for py = 1.  K = tap 2 i + j -> channel.  Summed in the dtype of `w` (fp32 in the engine: rounded to bf16
+    once, afterwards)."""
+    N, Cn = w.shape[:2]
+    assert tuple(w.shape[2:]) == (3, 3)
+    sel = torch.tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]], dtype=w.dtype, device=w.device)    # [phase][tap i][3x3 row]
+    return torch.einsum("pia,qjb,ncab->pqnijc", sel, sel, w).reshape(4, N, 4 * Cn).contiguous()
+
+
+def upsample_phases_covers(B, Hs, Ws, Cn, N):
+    """Shapes ctdd_unet_conv_up_phases takes (source grid Hs x Ws)."""
+    return bool(Cn >= 16 and Cn % 16 == 0 and (N % 96 == 0 or N % 64 == 0) and N > 0 and 1 <= Ws <= 33 and Hs * Ws >= 32
+                and 4 * Cn * 64 < 2 ** 31 and 4 * B * Hs * Ws < 2 ** 31)
 
 
 def _onepass_slab(B, HW, Cn, G, max_threads=1024):
@@ -268,6 +287,26 @@ class _PlanBuilder:
             return 2
         return 1
 
+    def pick_kernel(self, only3, M_, N, Hout, Wout):
+        """cfg.model.conv_kernel, "auto" resolved to "ring" or "patch" for a bf16 convolution of M_ = B Hout Wout pixels (only3: every
+        segment is a stride-1 3x3 one)."""
+        m = self.m
+        which = getattr(m, "conv_kernel", "auto")
+        if which == "auto":
+            # measured at batch 256 (MNIST net): the LDS-DMA ring wins where 512-pixel tiles give >= 160
+            # workgroups and every unit has nine taps (28x28, 14x14); the patch kernel (128/256-pixel tiles, two
+            # workgroups per CU) elsewhere.  Split-K lost everywhere it was tried (fp32 atomics + finish pass).
+            ring_min = int(getattr(m, "ring_min_tiles", 80))
+            which = "ring" if (only3 and -(-M_ // 512) * -(-N // 96) >= ring_min and N % 96 == 0) else "patch"
+            # (CIFAR net, N = 256 at 16x16: 64-column ring tiles beat the 128-column patch tiles, 49 vs 54 / 69 vs 104 us at batch 128)
+            if which == "patch" and only3 and N % 64 == 0 and N % 96 != 0 and Hout * Wout <= 256 and -(-M_ // 512) * (N // 64) >= ring_min:
+                which = "ring"
+            # (MNIST net's S = 256 output convolution, 28x28 K = 864: 64-column ring tiles 88 us, the 128-column patch tiles 105 us,
+            #  128-column ring tiles 179 us at batch 128; +1.4 % on the sampler loop)
+            if which == "patch" and only3 and N % 64 == 0 and N % 96 != 0 and N >= 256 and -(-M_ // 512) * (N // 64) >= ring_min:
+                which = "ring"
+        return which
+
     def conv(self, segs, wsrc, bias, N, Hout, Wout, Hin, Win, out, tb=None, res=None, logits_C=0, out_f32_tensor=None, bias_params=None,
              packed=None, back=True):
         """segs: list of (_Tensor, channels, kind); wsrc: per segment (weight parameter [N][Cin_tot][k][k], channel offset) --
@@ -318,21 +357,8 @@ class _PlanBuilder:
         lab = f"{Hout}x{Wout} K={Ktot} N={N} segs={[(c_, k_) for _, c_, k_ in segs]}"
         if tc is not None and back:
             tc.record_conv(segs, wsrc, bias_params, N, Hout, Wout, Hin, Win, out, tb, res, logits_C, out_f32_tensor)
-        which = getattr(m, "conv_kernel", "auto")
         only3 = all(s[2] == SEG_3x3 for s in segs)
-        if which == "auto":
-            # measured at batch 256 (MNIST net): the LDS-DMA ring wins where 512-pixel tiles give >= 160
-            # workgroups and every unit has nine taps (28x28, 14x14); the patch kernel (128/256-pixel tiles, two
-            # workgroups per CU) elsewhere.  Split-K lost everywhere it was tried (fp32 atomics + finish pass).
-            ring_min = int(getattr(m, "ring_min_tiles", 80))
-            which = "ring" if (only3 and -(-M_ // 512) * -(-N // 96) >= ring_min and N % 96 == 0) else "patch"
-            # (CIFAR net, N = 256 at 16x16: 64-column ring tiles beat the 128-column patch tiles, 49 vs 54 / 69 vs 104 us at batch 128)
-            if which == "patch" and only3 and N % 64 == 0 and N % 96 != 0 and Hout * Wout <= 256 and -(-M_ // 512) * (N // 64) >= ring_min:
-                which = "ring"
-            # (MNIST net's S = 256 output convolution, 28x28 K = 864: 64-column ring tiles 88 us, the 128-column patch tiles 105 us,
-            #  128-column ring tiles 179 us at batch 128; +1.4 % on the sampler loop)
-            if which == "patch" and only3 and N % 64 == 0 and N % 96 != 0 and N >= 256 and -(-M_ // 512) * (N // 64) >= ring_min:
-                which = "ring"
+        which = self.pick_kernel(only3, M_, N, Hout, Wout)
         resident = which == "res" and patchable and all(c % 32 == 0 for c in cs) and N % 32 == 0
         ring = which == "ring" and patchable and all(c % 16 == 0 for c in cs) and N % 32 == 0
         if resident or ring:
@@ -584,11 +610,45 @@ class _PlanBuilder:
                   cv.bias.detach().float().contiguous(), cur.C, Ho, Wo, cur.H, cur.W, y, bias_params=[cv.bias])
         return y
 
+    def upsample_in_phases(self, cur):
+        """Whether the Upsample convolution on `cur` runs as ONE ctdd_unet_conv_up_phases launch: bf16 inference plans, where the
+        stride-1 convolution on the materialised 2x grid would have gone to the plain 512-pixel ring (no split-K, not the
+        four-wave variant) and the entry takes the shape; cfg.model.upsample_phases = 0 keeps the two launches."""
+        eng, m, B, Cn = self.eng, self.m, self.B, cur.C
+        if self.tc is not None or eng.precise or not int(getattr(m, "upsample_phases", 1)):
+            return False
+        Ho, Wo = cur.H * 2, cur.W * 2
+        ring = self.pick_kernel(True, B * Ho * Wo, Cn, Ho, Wo) == "ring" and Wo <= 33 and Cn % 32 == 0
+        if not ring or (getattr(m, "conv_ksplit", 1) > 1 and Cn // 16 >= 2) or getattr(m, "ring_small_tiles", 0):
+            return False
+        return upsample_phases_covers(B, cur.H, cur.W, Cn, Cn)
+
+    def upsample_phases(self, cv, cur, y):
+        """The four 2x2-tap phase convolutions of the source in one launch (csrc/unet_kernels.hip: k_conv_ring_up), weights folded
+        per weights version (fold_upsample_weights)."""
+        eng, B, Cn = self.eng, self.B, cur.C
+        a = _ConvArgs()
+        a.nseg = 1
+        a.seg[0].hi, a.seg[0].C, a.seg[0].kind = ptr(cur.hi), Cn, SEG_3x3_UP
+        whi, _ = eng._pack(fold_upsample_weights(cv.weight.detach().float()).reshape(4 * Cn, 4 * Cn))
+        bias = cv.bias.detach().float().contiguous()
+        a.w_hi, a.bias = ptr(whi), ptr(bias)
+        a.B, a.H, a.W, a.Hin, a.Win, a.N, a.Ktot = B, y.H, y.W, cur.H, cur.W, Cn, 4 * Cn
+        a.out_hi = ptr(y.hi)
+        if y.stats is not None and not y.stats_by_gn:
+            self.stats_views.append((a, y.stats, "stats"))
+        self.keep.extend([whi, bias, a])
+        # (flops: the products executed, four taps per output pixel)
+        self.launch(self.lib.ctdd_unet_conv_up_phases, C.byref(a), 0, label=f"{y.H}x{y.W} K=4x{4 * Cn} N={Cn} up-phases of {cur.H}x{cur.W}",
+                    flops=2 * B * y.H * y.W * Cn * 4 * Cn)
+
     def upsample(self, cv, cur):
         """Upsample: nearest x2 folded into the conv's addressing (fp32 inference), or materialised before a stride-1 convolution."""
         eng, tc, B, lib = self.eng, self.tc, self.B, self.lib
         y = _Tensor(self, cur.H * 2, cur.W * 2, cur.C)
-        if eng.precise and tc is None:
+        if self.upsample_in_phases(cur):
+            self.upsample_phases(cv, cur, y)
+        elif eng.precise and tc is None:
             self.conv([(cur, cur.C, SEG_3x3_UP)], [(cv.weight, 0)],
                       cv.bias.detach().float().contiguous(), cur.C, cur.H * 2, cur.W * 2, cur.H, cur.W, y)
         else:                                  # materialise the 2x grid (cheap), then a stride-1 convolution (training: both modes)

@@ -55,7 +55,16 @@ int ctdd_unet_conv_res(const void* conv_args, int bnt, void* stream);
  * registers, one barrier per unit); segment channel counts must be multiples of 16; bnt in {2,3,4}: 512-pixel
  * tiles, eight waves; bnt in {12,13}: N-tile 64/96 with 256-pixel tiles, four waves, two workgroups per CU */
 int ctdd_unet_conv_ring(const void* conv_args, int bnt, void* stream);
-int ctdd_unet_upsample2x(const void* x_bf16, int B, int H, int W, int C, void* out_bf16, void* stream);   /* unet.py:79-85 */
+/* The Upsample convolution (unet.py:79-85: 3x3, pad 1, on the nearest-2x grid) as four 2x2-tap phase convolutions of the
+ * low-resolution tensor, one launch, the 2x grid never materialised; bf16 only (f32 must be 0).  One CTDD_SEG_3x3_UP segment
+ * [B][Hin][Win][C]; (H, W) = (2 Hin, 2 Win) is the output grid; Ktot = 4 C and w_hi is [4][N][4 C]: phase 2 py + px of output
+ * pixel (2y + py, 2x + px), K = tap 2 i + j -> channel, tap (i, j) on source pixel (y + py + i - 1, x + px + j - 1), its weight
+ * the sum of the 3x3 weights that read that pixel: rows {W[0], W[1] + W[2]} for py = 0, {W[0] + W[1], W[2]} for py = 1, columns
+ * alike with px (ctdd/unet_engine.py: fold_upsample_weights).  out_hi + bias (+ stats, summed over the four phases) only.
+ * C % 16 == 0, N % 96 == 0 or N % 64 == 0, Win <= 33, Hin * Win >= 32, ksplit <= 1, 16-byte aligned tensors; anything else:
+ * CTDD_EINVAL / CTDD_ERANGE, nothing launched. */
+int ctdd_unet_conv_up_phases(const void* conv_args, int f32, void* stream);
+int ctdd_unet_upsample2x(const void* x_bf16,int B, int H, int W, int C, void* out_bf16, void* stream);   /* unet.py:79-85 */
 
 typedef struct {
   const int64_t* x64; const int32_t* x32; float lo, hi; const float* w; const float* bias;

@@ -38,6 +38,9 @@ def _model(config):
     # the snapshot pins the plans with the 14x14 blocks as four launches each (the plan cfg.model.resblock_fused_mid = 0 must keep,
     # launch for launch); the plans with ctdd_unet_resblock_mid are pinned by tests/test_gpu_resblock_mid.py
     cfg.model.resblock_fused_mid = 0
+    # likewise the Upsample convolutions as ctdd_unet_upsample2x + a stride-1 ring launch (cfg.model.upsample_phases = 0); the plans
+    # with ctdd_unet_conv_up_phases are pinned by tests/test_gpu_upsample_phases.py
+    cfg.model.upsample_phases = 0
     torch.manual_seed(0)
     return mu.create_model(cfg, torch.device("cuda"))
 
