@@ -53,6 +53,12 @@ class _ResblockArgs(C.Structure):
                 ("w2", _P), ("bias2", _P), ("skip", _I), ("B", _I), ("H", _I), ("W", _I), ("N", _I), ("out_bf16", _P)]
 
 
+class _ConvRowsArgs(C.Structure):
+    _fields_ = [("s1_bf16", _P), ("st1", _P), ("C1", _I), ("s2_bf16", _P), ("st2", _P), ("C2", _I), ("gamma", _P), ("beta", _P), ("G", _I),
+                ("eps", _F), ("w", _P), ("bias", _P), ("tbias", _P), ("tb_stride", _I), ("r1_bf16", _P), ("RC1", _I), ("r2_bf16", _P),
+                ("RC2", _I), ("res_bf16", _P), ("out_bf16", _P), ("out_stats", _P), ("B", _I), ("H", _I), ("W", _I), ("N", _I)]
+
+
 class _TimeArgs(C.Structure):
     _fields_ = [("t", _P), ("B", _I), ("ch", _I), ("tdim", _I), ("w1", _P), ("b1", _P), ("w2", _P), ("b2", _P),
                 ("hid", _P), ("act", _P)]
@@ -78,7 +84,7 @@ def _lib():
                            ("ctdd_unet_gn_apply", [_P, _P]), ("ctdd_unet_gn_onepass", [_P, _I, _I, _P]), ("ctdd_unet_channel_stats", [_P, _I, _I, _I, _P, _P]),
                            ("ctdd_unet_time", [_P, _P, _P, _I, _P, _P]), ("ctdd_unet_time_uniform", [_P, _P, _P, _I, _P, _P]),
                            ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_resblock_small", [_P, _I, _P]),
-                           ("ctdd_unet_resblock_mid", [_P, _I, _P]),
+                           ("ctdd_unet_resblock_mid", [_P, _I, _P]), ("ctdd_unet_conv_rows", [_P, _I, _P]),
                            ("ctdd_unet_logistic_head", [_P, _P])):
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argt, _I
@@ -168,6 +174,42 @@ def pack_resblock_mid_weights(w1, w2, cs):
             k2.append(seg1(w2[:, 9 * N:], c0, c))
             c0 += c
     return torch.cat(k1, 1).contiguous().reshape(N, 9 * Ct), torch.cat(k2, 1).contiguous().reshape(N, w2.shape[1])
+
+
+# default of cfg.model.conv_rows_min_wgs (UNetEngine._runs_conv_rows).  Graph replay of one MNIST plan, pairs | ctdd_unet_conv_rows:
+# batch 16 (32 workgroups) 1157 | 1302 us, batch 32 (64) 1219 | 1305 us, batch 40 (80) 1264-1288 | 1303-1305 us, batch 48 (96)
+# 1471-1485 | 1329-1331 us, batch 56 (112) 1519-1523 | 1344-1346 us, batch 64 (128) 1538 | 1381 us, batch 128 (256) 1710 | 1549 us
+# (tools/conv_table.py): the smallest measured grid at which the one launch wins
+CONV_ROWS_MIN_WGS = 96
+
+
+def conv_rows_covers(H, W, cs, rcs, cout, G, residual=False):
+    """Shapes ctdd_unet_conv_rows takes (csrc/unet_rows_kernels.hip): rows of <= 28 pixels (a slab of 32 positions per padded row, bands
+    of 14 output rows), 96 output channels, one or two GroupNorm sources `cs` and up to two raw 1x1 sources `rcs` in multiples of 32
+    channels (<= 384 per concatenation), groups dividing the GroupNorm channels, 1x1 segments or a residual but not both."""
+    return bool(H >= 1 and 1 <= W <= 28 and cout == 96 and 1 <= len(cs) <= 2 and len(rcs) <= 2 and all(c > 0 and c % 32 == 0 for c in [*cs, *rcs])
+                and sum(cs) <= 384 and sum(rcs) <= 384 and G > 0 and sum(cs) % G == 0 and not (rcs and residual))
+
+
+def pack_conv_rows_weights(w, cs, rcs):
+    """The [96][9 sum(cs) + sum(rcs)] matrix of a convolution (K = the 3x3 segment as tap -> channel of the concatenation of `cs`, then
+    the 1x1 segments on `rcs`) in the order ctdd_unet_conv_rows streams it (include/ctdd_unet.h): pack_resblock_mid_weights' order
+    with two 48-channel streams instead of four -- per stream the 3x3 segment as source -> 32-channel block -> dx -> dy -> 16-channel
+    tile, then the 1x1 segments as source -> block -> tile, every (tile, 32 channels) fragment as [q][i][8].  Nothing is padded.
+    Returned as a [96][K] view of the flat streams ([2 streams][48 K])."""
+    N, Ct, Rt = w.shape[0], sum(cs), sum(rcs)
+    assert N == 96 and w.shape[1] == 9 * Ct + Rt and all(c % 32 == 0 for c in [*cs, *rcs])
+    w3, parts, c0 = w[:, :9 * Ct].reshape(N, 9, Ct), [], 0
+    for c in cs:
+        v = w3[:, :, c0:c0 + c].reshape(2, 3, 16, 3, 3, c // 32, 4, 8)              # stream, tile, i, dy, dx, block, q, e
+        parts.append(v.permute(0, 5, 4, 3, 1, 6, 2, 7).reshape(2, -1))              # stream, block, dx, dy, tile, q, i, e
+        c0 += c
+    c0 = 9 * Ct
+    for c in rcs:
+        v = w[:, c0:c0 + c].reshape(2, 3, 16, c // 32, 4, 8)                        # stream, tile, i, block, q, e
+        parts.append(v.permute(0, 3, 1, 4, 2, 5).reshape(2, -1))                    # stream, block, tile, q, i, e
+        c0 += c
+    return torch.cat(parts, 1).contiguous().reshape(N, w.shape[1])
 
 
 def fold_upsample_weights(w):
@@ -440,6 +482,43 @@ class _PlanBuilder:
             tc.record_gn(self, srcs, norm, swish, eps, HW, out, drop_p)
         return out
 
+    def conv_rows(self, srcs, norm, w_conv, bias, out, tb=None, res=None, raws=(), w_skip=None):
+        """GroupNorm `norm` + Swish of the concatenation of `srcs`, the 3x3 convolution `w_conv` on it (+ the 1x1 convolution `w_skip` on
+        the raw concatenation of `raws` | + the residual `res`) as ONE ctdd_unet_conv_rows launch: the gn_apply + conv pair without the
+        activated tensor.  bias: the summed bias of the segments."""
+        eng, lib, B = self.eng, self.lib, self.B
+        Hc, Wc, N = srcs[0].H, srcs[0].W, out.C
+        cs, rcs = [s_.C for s_ in srcs], [s_.C for s_ in raws]
+        a = _ConvRowsArgs()
+        for i, s_ in enumerate(srcs):
+            setattr(a, f"s{i + 1}_bf16", ptr(s_.hi))
+            setattr(a, f"C{i + 1}", s_.C)
+            self.stats_views.append((a, s_.stats, f"st{i + 1}"))
+        for i, s_ in enumerate(raws):
+            setattr(a, f"r{i + 1}_bf16", ptr(s_.hi))
+            setattr(a, f"RC{i + 1}", s_.C)
+        g, b_ = norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()
+        a.gamma, a.beta, a.G, a.eps = ptr(g), ptr(b_), norm.num_groups, norm.eps
+        segs, wsrc, c_ = [(None, sum(cs), SEG_3x3)], [(w_conv, 0)], 0
+        for c in rcs:
+            segs.append((None, c, SEG_1x1))
+            wsrc.append((w_skip, c_))
+            c_ += c
+        w, _ = eng._pack(pack_conv_rows_weights(eng._w2d(wsrc, segs), cs, rcs))
+        a.w, a.bias = ptr(w), ptr(bias)
+        if tb is not None:
+            a.tbias, a.tb_stride = tb
+        if res is not None:
+            a.res_bf16 = ptr(res.hi)
+        a.out_bf16 = ptr(out.hi)
+        if out.stats is not None and not out.stats_by_gn:
+            self.stats_views.append((a, out.stats, "out_stats"))
+        a.B, a.H, a.W, a.N = B, Hc, Wc, N
+        self.keep.extend([g, b_, w, bias, a])
+        Ktot = w.shape[1]
+        self.launch(lib.ctdd_unet_conv_rows, C.byref(a), 0, label=f"{Hc}x{Wc} K={Ktot} N={N} gn+conv rows C={cs} raw={rcs}",
+                    flops=2 * B * Hc * Wc * N * Ktot)
+
     def resblock_mid(self, rb, srcs):
         """The block as ONE ctdd_unet_resblock_mid launch (the 14x14 level): as resblock_fused, weights in pack_resblock_mid_weights' order."""
         return self.resblock_fused(rb, srcs, mid=True)
@@ -496,11 +575,25 @@ class _PlanBuilder:
         # keeps the four launches
         if self.onepass_gn and eng._fuses_resblock_mid(rb, Hc, Wc, cs, tc is not None) and all(s_.stats is None for s_ in srcs):
             return self.resblock_mid(rb, srcs)
-        a1 = self.gn_apply(srcs, rb.norm1, True, rb.norm1.eps, Hc * Wc)
+        # a level whose samples do not fit one workgroup (28x28): each GroupNorm + convolution pair as ONE ctdd_unet_conv_rows launch
+        # (csrc/unet_rows_kernels.hip) when the producers left statistics; cfg.model.conv_rows = 0 keeps the pairs
+        tbias = (self.tproj.data_ptr() + 4 * self.toff[id(rb)], self.tb_stride)
         h = _Tensor(self, Hc, Wc, cout)
         b1 = rb.conv1.bias.detach().float().contiguous()
-        self.conv([(a1, a1.C, SEG_3x3)], [(rb.conv1.weight, 0)], b1, cout, Hc, Wc,
-                  Hc, Wc, h, tb=(self.tproj.data_ptr() + 4 * self.toff[id(rb)], self.tb_stride), bias_params=[rb.conv1.bias])
+        if eng._runs_conv_rows(self.B, Hc, Wc, cs, [], cout, rb.norm1.num_groups, False, tc is not None) and all(s_.stats is not None for s_ in srcs):
+            self.conv_rows(srcs, rb.norm1, rb.conv1.weight, b1, h, tb=tbias)
+        else:
+            a1 = self.gn_apply(srcs, rb.norm1, True, rb.norm1.eps, Hc * Wc)
+            self.conv([(a1, a1.C, SEG_3x3)], [(rb.conv1.weight, 0)], b1, cout, Hc, Wc, Hc, Wc, h, tb=tbias, bias_params=[rb.conv1.bias])
+        rcs = cs if rb.skip is not None else []
+        if eng._runs_conv_rows(self.B, Hc, Wc, [cout], rcs, cout, rb.norm2.num_groups, rb.skip is None, tc is not None) and h.stats is not None:
+            y = _Tensor(self, Hc, Wc, cout)
+            if rb.skip is not None:
+                self.conv_rows([h], rb.norm2, rb.conv2.weight, (rb.conv2.bias.detach().float() + rb.skip.bias.detach().float()).contiguous(), y,
+                               raws=srcs, w_skip=rb.skip.weight)
+            else:
+                self.conv_rows([h], rb.norm2, rb.conv2.weight, rb.conv2.bias.detach().float().contiguous(), y, res=srcs[0])
+            return y
         drop = float(rb.dropout.p) if (tc is not None and tc.dropout) else 0.0
         a2 = self.gn_apply([h], rb.norm2, True, rb.norm2.eps, Hc * Wc, drop_p=drop)
         y = _Tensor(self, Hc, Wc, cout)
@@ -798,6 +891,15 @@ class UNetEngine:
                     and Hc * Wc <= self._onepass_max_hw()
                     and not resblock_small_covers(Hc, Wc, cs, rb.conv1.weight.shape[0], rb.norm1.num_groups, rb.norm2.num_groups)
                     and resblock_mid_covers(Hc, Wc, cs, rb.conv1.weight.shape[0], rb.norm1.num_groups, rb.norm2.num_groups))
+
+    def _runs_conv_rows(self, B, Hc, Wc, cs, rcs, cout, G, residual, training):
+        """Whether a GroupNorm + convolution pair of the four-launch ResBlock runs as ONE ctdd_unet_conv_rows launch: bf16 inference
+        only, cfg.model.conv_rows (default on), a shape the kernel takes, and at least cfg.model.conv_rows_min_wgs workgroups (one per
+        sample and band of 14 rows: below that the pair's smaller tiles fill the chip better)."""
+        m = self.cfg.model
+        return bool(not training and not self.precise and int(getattr(m, "conv_rows", 1))
+                    and conv_rows_covers(Hc, Wc, cs, rcs, cout, G, residual)
+                    and B * -(-Hc // 14) >= int(getattr(m, "conv_rows_min_wgs", CONV_ROWS_MIN_WGS)))
 
     def _onepass_gn_covers(self, B, training):
         """Whether ctdd_unet_gn_onepass has a slab for every GroupNorm launch a one-pass plan would hold at its small levels (the

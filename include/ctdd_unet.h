@@ -119,6 +119,31 @@ int ctdd_unet_resblock_small(const void* resblock_args, int f32, void* stream);
 int ctdd_unet_resblock_mid(const void* resblock_args, int f32, void* stream);
 
 typedef struct {
+  const void* s1_bf16; const double* st1; int C1;   /* GroupNorm sources [B][H][W][C1] (+ [B][H][W][C2]) and their [B][C][2] fp64 sums */
+  const void* s2_bf16; const double* st2; int C2;   /* (the statistics format of ctdd_conv_args.stats / ctdd_gn_args.st1) */
+  const float* gamma; const float* beta; int G; float eps;   /* GroupNorm over the C1 + C2 channels of the concatenation */
+  const void* w; const float* bias; const float* tbias; int tb_stride;   /* [N][9 (C1 + C2) + RC1 + RC2] bf16 in stream order (below) */
+  const void* r1_bf16; int RC1; const void* r2_bf16; int RC2;   /* raw sources of the 1x1 segments (RC1 = 0: none) */
+  const void* res_bf16;                             /* residual [B][H][W][N] or null */
+  void* out_bf16; double* out_stats;                /* [B][H][W][N]; [B][N][2] fp64 sums of the output, added to (or null) */
+  int B, H, W, N;
+} ctdd_conv_rows_args;
+/* GroupNorm + Swish + 3x3 convolution in one launch for a level whose samples do not fit one workgroup (csrc/unet_rows_kernels.hip):
+ *   out = bf16(conv3x3(bf16(swish(GN(concat(s1[, s2]))))) [+ 1x1 on raw r1[, r2]] + bias [+ tbias[b]] [+ residual])
+ * the ctdd_unet_gn_apply + ctdd_unet_conv_ring / ctdd_unet_conv_patch pair without the activated tensor in memory; scale / shift come
+ * from st1 / st2 as in ctdd_unet_gn_apply, the output's sums (taken before the bf16 rounding) are added into out_stats
+ * by one fp64 atomic per band (bit-reproducible from a zeroed buffer for H <= 28, two bands; beyond that up to the order of the adds).  One
+ * workgroup per (sample, band of 14 output rows).  1 <= W <= 28, any H, N = 96, C1, C2, RC1, RC2 multiples of 32 (C2, RC1, RC2 may
+ * be 0; RC2 > 0 needs RC1 > 0; <= 384 channels per concatenation), G divides C1 + C2, every GroupNorm source with statistics,
+ * 1x1 segments or a residual but not both (a ResBlock has one of them), 16-byte aligned tensors, f32 must be 0.  Anything else: CTDD_ERANGE / CTDD_EINVAL, nothing launched.
+ * Weights (ctdd/unet_engine.py: pack_conv_rows_weights): two streams (output channels [48 s, 48 s + 48)), one after the other, each a
+ * sequence of 1 KiB fragments.  A fragment is (tile, 32 channels of K): element (n = 48 s + 16 tile + i, k = 8 q + e of the 32) at
+ * (16 q + i) * 8 + e.  Per stream: for each GroupNorm source, for each 32-channel block of it, for dx = -1, 0, 1, for dy = -1, 0, 1,
+ * for tile = 0, 1, 2: the fragment of tap (dy, dx) on that block (27 (C1 + C2) / 32 fragments); then for each raw source, for each
+ * 32-channel block of it, for tile = 0, 1, 2: the fragment of the 1x1 segment (3 (RC1 + RC2) / 32 fragments).  Nothing is padded. */
+int ctdd_unet_conv_rows(const void* conv_rows_args, int f32, void* stream);
+
+typedef struct {
   const float* t; int B, ch, tdim;
   const float* w1; const float* b1; const float* w2; const float* b2;   /* Linear weights transposed to [in][out] */
   float* hid; float* act;                                                /* [B][tdim] scratch, [B][tdim] = swish(temb) */

@@ -41,6 +41,9 @@ def _model(config):
     # likewise the Upsample convolutions as ctdd_unet_upsample2x + a stride-1 ring launch (cfg.model.upsample_phases = 0); the plans
     # with ctdd_unet_conv_up_phases are pinned by tests/test_gpu_upsample_phases.py
     cfg.model.upsample_phases = 0
+    # and the 28x28 GroupNorm + convolution pairs as two launches each (cfg.model.conv_rows = 0); the plans with
+    # ctdd_unet_conv_rows are pinned by tests/test_gpu_conv_rows.py
+    cfg.model.conv_rows = 0
     torch.manual_seed(0)
     return mu.create_model(cfg, torch.device("cuda"))
 

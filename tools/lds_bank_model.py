@@ -59,3 +59,8 @@ if __name__ == "__main__":
         _report("7x7, 4 flattened pixel tiles (before)", [flat_row(pt, 7, 7) for pt in range(4)], rs, taps7)
     for rs in (416, 800):
         _report("7x7, 4 tiles of 16 consecutive slab rows from row 10 (after)", [lambda j, pt=pt: 10 + pt * 16 + j for pt in range(4)], rs, taps7)
+    # k_conv_rows (csrc/unet_rows_kernels.hip): 96-channel slab, 32 positions per padded row, tile = (output row y, column half h)
+    taps28 = [dy * 32 + dx for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
+    for rs in (192, 208, 224):
+        _report("28x28 band, 14 x 2 row tiles of pitch 32 (k_conv_rows)",
+                [lambda j, y=y, h=h: 1 + (y + 1) * 32 + 16 * h + j for y in range(14) for h in (0, 1)], rs, taps28)

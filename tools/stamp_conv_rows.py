@@ -1,0 +1,69 @@
+"""Phase durations of k_conv_rows (csrc/unet_rows_kernels.hip) from the stamps build (tools/build_conv_stamps.sh, -DCTDD_ROWS_STAMPS:
+thread 0 of every workgroup leaves s_memtime at the phase boundaries in the buffer passed as out_stats; the statistics are off in
+that build).  Printed as raw s_memtime ticks (shader cycles), mean / min / max over the workgroups of the third launch.
+
+    bash tools/build_conv_stamps.sh && python tools/stamp_conv_rows.py [--batch 128]
+"""
+import argparse
+import ctypes as C
+import os
+import sys
+
+_R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [_R, os.path.join(_R, "continuous-time-diffusion-models-for-discrete-data_amd")]
+import torch  # noqa: E402
+
+from ctdd import unet_engine as ue  # noqa: E402
+
+PHASES = ["prologue (zero fill, scale/shift)", "3x3 pieces (fill + K loop)", "1x1 segments", "epilogue to LDS", "store"]
+
+
+def run(lib, B, cs, rcs, res):
+    H = W = 28
+    M, N, Ct = B * H * W, 96, sum(cs)
+    rn = lambda *s: torch.randn(s, device="cuda")
+    xs, rs = [rn(M, c).to(torch.bfloat16) for c in cs], [rn(M, c).to(torch.bfloat16) for c in rcs]
+    sts = []
+    for x in xs:
+        xd = x.double().view(B, H * W, -1)
+        sts.append(torch.stack([xd.sum(1), (xd * xd).sum(1)], -1).contiguous())
+    K = 9 * Ct + sum(rcs)
+    w = ue.pack_conv_rows_weights((rn(N, K) / K ** 0.5).to(torch.bfloat16), cs, rcs)
+    gamma, beta, bias = torch.ones(Ct, device="cuda"), torch.zeros(Ct, device="cuda"), torch.zeros(N, device="cuda")
+    r = rn(M, N).to(torch.bfloat16) if res else None
+    out = torch.empty((M, N), dtype=torch.bfloat16, device="cuda")
+    nwg = B * 2
+    buf = torch.zeros((nwg, 8), dtype=torch.int64, device="cuda")
+    a = ue._ConvRowsArgs()
+    for i, (x, st) in enumerate(zip(xs, sts)):
+        setattr(a, f"s{i + 1}_bf16", x.data_ptr()); setattr(a, f"st{i + 1}", st.data_ptr()); setattr(a, f"C{i + 1}", x.shape[1])
+    for i, x in enumerate(rs):
+        setattr(a, f"r{i + 1}_bf16", x.data_ptr()); setattr(a, f"RC{i + 1}", x.shape[1])
+    a.gamma, a.beta, a.G, a.eps, a.w, a.bias = gamma.data_ptr(), beta.data_ptr(), 32, 1e-5, w.data_ptr(), bias.data_ptr()
+    if r is not None:
+        a.res_bf16 = r.data_ptr()
+    a.out_bf16, a.out_stats, a.B, a.H, a.W, a.N = out.data_ptr(), buf.data_ptr(), B, H, W, N
+    st_ = torch.cuda.current_stream().cuda_stream
+    for _ in range(3):
+        assert lib.ctdd_unet_conv_rows(C.byref(a), 0, st_) == 0, lib.ctdd_last_error().decode()
+    torch.cuda.synchronize()
+    d = buf.cpu().double()
+    dur = d[:, 1:6] - d[:, 0:5]
+    print(f"B={B} 28x28 C={cs} raw={rcs} res={res}: {nwg} workgroups, per workgroup {float((d[:, 5] - d[:, 0]).mean()):.0f} cycles")
+    for i, nm in enumerate(PHASES):
+        print(f"   {nm:36s} mean {float(dur[:, i].mean()):8.0f}  min {float(dur[:, i].min()):8.0f}  max {float(dur[:, i].max()):8.0f}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=128)
+    a = ap.parse_args()
+    lib = C.CDLL(os.path.join(_R, "continuous-time-diffusion-models-for-discrete-data_amd", "librows_stamps.so"))
+    lib.ctdd_unet_conv_rows.argtypes, lib.ctdd_unet_conv_rows.restype = [C.c_void_p, C.c_int, C.c_void_p], C.c_int
+    lib.ctdd_last_error.restype = C.c_char_p
+    for cs, rcs, res in (([96], [], False), ([96], [], True), ([96, 96], [], False), ([192, 96], [], False), ([96], [96, 96], False)):
+        run(lib, a.batch, cs, rcs, res)
+
+
+if __name__ == "__main__":
+    main()
