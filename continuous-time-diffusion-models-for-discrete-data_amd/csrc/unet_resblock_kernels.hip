@@ -28,24 +28,11 @@
 // this kernel, 0.63 for k_resblock_mid).  With 32 bytes and tiles of 16 consecutive slab rows every tap of every tile is 4
 // cycles under that model (measured ratios 0.21 / 0.31, what is left being the GroupNorm passes and the epilogues' 8-byte stores).
 // 7x7, C = 384: 38 + 63 + 29 (reduction scratch) = 130 KB.
-#include <type_traits>
-
-#include "common.hpp"
+#include "row_tile.hpp"
 #include "../../include/ctdd_unet.h"
 
 namespace ctdd {
 namespace {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2v = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2v = __attribute__((ext_vector_type(2))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
-__device__ inline unsigned rb_pack2(float a, float b) {
-  f32x2v v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-}
 
 constexpr int RB_THREADS = 256, RB_N = 192, RB_PST = 20, RB_MAXC = 384;
 
@@ -161,7 +148,7 @@ __device__ __attribute__((always_inline)) inline void rb_groupnorm(unsigned char
         const f32x2v z = y * (f32x2v){-1.4426950408889634f, -1.4426950408889634f};
         const f32x2v d = (f32x2v){__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)} + (f32x2v){1.0f, 1.0f};
         y = y * (f32x2v){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-        ow[j] = rb_pack2(y.x, y.y);
+        ow[j] = rt_pack2(y.x, y.y);
       }
       *(uint4*)(sm + dst + prow * dst_rs + oct * 16) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
     }
@@ -330,7 +317,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
         if (pix[pt] >= 0) {
           const f32x4 v = acc[tt][pt];
           *(uint2*)(sm + L.slab + prow[pt] * L.rs2 + n * 2) =
-              make_uint2(rb_pack2(v[0] + add[0], v[1] + add[1]), rb_pack2(v[2] + add[2], v[3] + add[3]));
+              make_uint2(rt_pack2(v[0] + add[0], v[1] + add[1]), rt_pack2(v[2] + add[2], v[3] + add[3]));
         }
         acc[tt][pt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
       }
@@ -360,7 +347,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
           o[0] += __uint_as_float(r.x << 16); o[1] += __uint_as_float(r.x & 0xFFFF0000u);
           o[2] += __uint_as_float(r.y << 16); o[3] += __uint_as_float(r.y & 0xFFFF0000u);
         }
-        *(uint2*)(sm + L.slab + pix[pt] * L.rs2 + n * 2) = make_uint2(rb_pack2(o[0], o[1]), rb_pack2(o[2], o[3]));
+        *(uint2*)(sm + L.slab + pix[pt] * L.rs2 + n * 2) = make_uint2(rt_pack2(o[0], o[1]), rt_pack2(o[2], o[3]));
       }
     }
   }
@@ -385,7 +372,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
 // y >= H skipped wave-uniformly.  The fragment that tap (dy, dx) needs for row y is then the fragment of padded row y + 1 + dy at
 // column shift dx: lane j reads slab row 1 + 16 (y + 1 + dy) + j + dx, 16 consecutive rows at a stride of 416 bytes (104 dwords,
 // 8 mod 16: conflict-free under the lane groups of ds_read_b128, tools/lds_bank_model.py; the shifts of lanes 0 and 15 of the
-// first and last padded row land in the guard rows).  The K loop's unit is (32 channels, dx): the up-to-16 row fragments of that
+// first and last padded row land in the guard rows).  The K loop (rt_gemm_rows, row_tile.hpp) has the unit (32 channels, dx): the up-to-16 row fragments of that
 // column shift are read ONCE, and output row y takes nine matrix instructions (three dy x three 16-channel weight tiles) on F[y],
 // F[y+1], F[y+2] from registers: 16 ds_read_b128 per 126 matrix instructions (the flattened 16-pixel tiles this replaced took 39 per 117).  The weights are streamed in
 // that order (unit -> dy -> tile, 9 KiB per wave and unit) through a ring of two units (72 registers).
@@ -396,14 +383,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_small(const ctdd_res
 // conv2's first weights travel behind it.  The residual is added in the accumulator layout from global memory (one rounding of
 // acc + bias + residual, as the launches it replaces).
 constexpr int RM_NPT = 14, RM_PITCH = 16, RM_MAXH = 14, RM_MAXCS = 192;
-constexpr int RM_UNIT = 9 * 512;                               // bf16 elements of one unit of a wave's 3x3 weight stream
-
-// the value again, as one the compiler knows nothing about: what is derived from it is computed where it is used instead of being
-// kept in registers (the pixel indices of the 13 tiles) from the start of the kernel to its epilogues
-__device__ inline int rm_again(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
+constexpr int RM_RS = RB_N * 2 + 32;                           // bytes per slab position
 
 __host__ __device__ inline RbLds rm_layout(int H, int W) {
   RbLds L;
@@ -502,95 +482,17 @@ __device__ __attribute__((always_inline)) inline void rm_gn1_apply(unsigned char
       const f32x2v z = y * (f32x2v){-1.4426950408889634f, -1.4426950408889634f};
       const f32x2v d = (f32x2v){__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)} + (f32x2v){1.0f, 1.0f};
       y = y * (f32x2v){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-      ow[j] = rb_pack2(y.x, y.y);
+      ow[j] = rt_pack2(y.x, y.y);
     }
     *(uint4*)(sm + L.slab + rb_prow(p, W, RM_PITCH) * L.rs2 + oct * 16) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
   }
 }
 
-// one unit of a wave's 3x3 weight stream: [dy][tile] fragments of 1 KiB each (ctdd_unet.h)
-__device__ __attribute__((always_inline)) inline void rm_wload9(u32x4 (&dst)[3][3], const unsigned short* __restrict__ wrow, int u) {
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int t = 0; t < 3; ++t) dst[dy][t] = *(const u32x4*)(wrow + (size_t)u * RM_UNIT + (dy * 3 + t) * 512);
-}
 // the first two units of a 3x3 weight stream (issued before the phase that precedes the K loop)
 __device__ __attribute__((always_inline)) inline void rm_wprologue(u32x4 (&wr)[2][3][3], const unsigned short* __restrict__ wrow, int nunits) {
 #pragma unroll
   for (int u = 0; u < 2; ++u)
-    if (u < nunits) rm_wload9(wr[u], wrow, u);
-}
-// one 32-channel unit of the 1x1 skip stream: [tile] fragments
-__device__ __attribute__((always_inline)) inline void rm_wload3(u32x4 (&dst)[3], const unsigned short* __restrict__ wrow, int u) {
-#pragma unroll
-  for (int t = 0; t < 3; ++t) dst[t] = *(const u32x4*)(wrow + (size_t)u * 1536 + t * 512);
-}
-
-// The K loop of a 3x3 segment of nunits / 3 32-channel blocks held in the slab's columns [0, 32 nunits / 3): units in the order
-// (channel block, dx), weight ring wr holding units 0 and 1 (rm_wprologue).  fb: byte address of this lane's position of padded
-// row 0 (slab + lj * RM_RS) + its k quarter.  Unit u: F[r] = the fragment of padded row r at that column shift, r <= H + 1, read
-// ONCE; output row y takes acc[t][y] += W[dy][t] F[y + dy].  The fragments of unit u + 1 are requested while unit u computes
-// (F[y + 2] ahead of row y's matrix instructions, so at most 19 fragments are alive), the weights of unit u + 2 when unit u has
-// consumed its slot.  The request past the last unit repeats the last unit's addresses.
-constexpr int RM_RS = RB_N * 2 + 32;
-template <bool FULL>
-__device__ __attribute__((always_inline)) inline void rm_gemm_rows(f32x4 (&acc)[3][RM_NPT], u32x4 (&wr)[2][3][3], const unsigned short* __restrict__ wrow,
-                                                                  int nunits, const unsigned char* sm, int fb, int H) {
-  int un = 0, dxn = 0, cbn = 0;                                 // the unit whose fragments are requested next
-  auto xaddr = [&]() {                                         // (selects, not branches)
-    const int o = fb + (dxn - 1) * RM_RS + cbn * 64;
-    const bool more = un + 1 < nunits, wrap = dxn == 2;
-    un += more ? 1 : 0;
-    cbn += more && wrap ? 1 : 0;
-    dxn = more ? (wrap ? 0 : dxn + 1) : dxn;
-    return o;
-  };
-  auto fload = [&](bf16x8& f, int o, int r) { f = *(const bf16x8*)(sm + o + r * (RM_PITCH * RM_RS)); };
-  auto step = [&](u32x4 (&slot)[3][3], bf16x8 (&fc)[RM_NPT + 2], bf16x8 (&fn)[RM_NPT + 2], int u, auto guard) {
-    constexpr bool GUARD = decltype(guard)::value;
-    if (GUARD && u >= nunits) return;
-    const int o = xaddr();
-    fload(fn[0], o, 0);
-    fload(fn[1], o, 1);
-#pragma unroll
-    for (int y = 0; y < RM_NPT; ++y) {
-      if (FULL || y < H) {                                      // (wave-uniform; FULL: H = 14, one straight line)
-        fload(fn[y + 2], o, y + 2);
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-          for (int t = 0; t < 3; ++t)
-            acc[t][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[dy][t]), fc[y + dy], acc[t][y], 0, 0, 0);
-        // (pins the request for F[y + 2] to this row: left alone, the scheduler gathers a unit's requests at the end of the unit
-        // before, where the first rows wait for them, and sinks both slots' weight loads to the end of the loop body, where the
-        // next iteration drains them with vmcnt(0))
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (!GUARD || u + 2 < nunits) rm_wload9(slot, wrow, u + 2);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  bf16x8 F[2][RM_NPT + 2];
-  {
-    const int o = xaddr();
-#pragma unroll
-    for (int r = 0; r < RM_NPT + 2; ++r)
-      if (FULL || r < H + 2) fload(F[0][r], o, r);
-  }
-  // vmcnt(0): the ring's first two units have landed (they were requested a phase ago).  Entered with loads of unknown age in
-  // flight, the loop's own waits are merged with that state and come out as vmcnt(8 .. 0) at the top of every iteration: the
-  // ring drained once per two units.  Entered with nothing in flight they are the counted vmcnt(9 ..) of the ring.
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  int u0 = 0;
-  for (; u0 + 4 <= nunits; u0 += 2) {
-    step(wr[0], F[0], F[1], u0, std::false_type{});
-    step(wr[1], F[1], F[0], u0 + 1, std::false_type{});
-  }
-  for (; u0 < nunits; u0 += 2) {
-    step(wr[0], F[0], F[1], u0, std::true_type{});
-    step(wr[1], F[1], F[0], u0 + 1, std::true_type{});
-  }
+    if (u < nunits) rt_wload9(wr[u], wrow, u);
 }
 
 // The 1x1 skip segments: nsk 32-channel units of the raw sources, B fragments straight from global memory (lane j of tile y: pixel
@@ -623,12 +525,12 @@ __device__ __attribute__((always_inline)) inline void rm_gemm_skip(f32x4 (&acc)[
           acc[t][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t]), gc[y], acc[t][y], 0, 0, 0);
       }
     }
-    if (!GUARD || u + 2 < nsk) rm_wload3(slot, wrow, u + 2);
+    if (!GUARD || u + 2 < nsk) rt_wload3(slot, wrow, u + 2);
     __builtin_amdgcn_sched_barrier(0);
   };
   bf16x8 G[2][RM_NPT];
   gload(G[0], 0);
-  __builtin_amdgcn_s_waitcnt(0x0F70);                           // vmcnt(0), as in rm_gemm_rows (unit 0's fragments are needed at once)
+  __builtin_amdgcn_s_waitcnt(0x0F70);                           // vmcnt(0), as in rt_gemm_rows (unit 0's fragments are needed at once)
   int u0 = 0;
   for (; u0 + 4 <= nsk; u0 += 2) {
     step(ws[0], G[0], G[1], u0, std::false_type{});
@@ -650,10 +552,10 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
   const RbLds L = rm_layout(H, W);
   const int lane = t & 63, wv = t >> 6, lj = lane & 15, lq = lane >> 4;
   const int nu1a = 3 * (C1 >> 5), nu1b = 3 * (C2 >> 5), nsk = a.skip ? (C1 + C2) >> 5 : 0;
-  const unsigned short* w1p = (const unsigned short*)a.w1 + (size_t)wv * (nu1a + nu1b) * RM_UNIT + lane * 8;
+  const unsigned short* w1p = (const unsigned short*)a.w1 + (size_t)wv * (nu1a + nu1b) * RT_UNIT + lane * 8;
   const unsigned short* s1 = (const unsigned short*)a.s1_bf16 + (size_t)b * HW * C1;
   const unsigned short* s2 = (const unsigned short*)a.s2_bf16 + (size_t)b * HW * C2;
-  u32x4 wr[2][3][3];                                          // the weight ring (rm_gemm_rows)
+  u32x4 wr[2][3][3];                                          // the weight ring (rt_gemm_rows)
 
   // ---- phase A: zero the slab and its guard rows (border positions stay zero to the end), GroupNorm 1 statistics from global memory
   rm_wprologue(wr, w1p, nu1a);
@@ -672,21 +574,21 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
   for (int s = 0; s < (C2 ? 2 : 1); ++s) {
     rm_gn1_apply(sm, L, s ? s2 : s1, s ? C2 : C1, s ? C1 : 0, HW, W);
     __syncthreads();
-    rm_gemm_rows<FULL>(acc, wr, w1p + (size_t)(s ? nu1a : 0) * RM_UNIT, s ? nu1b : nu1a, sm, fb, H);
+    rt_gemm_rows<FULL, RM_RS, RM_PITCH>(acc, wr, w1p + (size_t)(s ? nu1a : 0) * RT_UNIT, s ? nu1b : nu1a, sm, fb, H);
     __syncthreads();                                          // every wave has read its last fragment of this source
-    if (s == 0 && C2) rm_wprologue(wr, w1p + (size_t)nu1a * RM_UNIT, nu1b);
+    if (s == 0 && C2) rm_wprologue(wr, w1p + (size_t)nu1a * RT_UNIT, nu1b);
   }
   // the next stream's first units travel during the epilogue: the skip segments' (after the 18 units of the 3x3 part) or conv2's
-  const int tw = rm_again(t);
-  const unsigned short* w2p = (const unsigned short*)a.w2 + (size_t)(tw >> 6) * (18 * RM_UNIT + nsk * 1536) + (tw & 63) * 8;
+  const int tw = rt_again(t);
+  const unsigned short* w2p = (const unsigned short*)a.w2 + (size_t)(tw >> 6) * (18 * RT_UNIT + nsk * 1536) + (tw & 63) * 8;
   u32x4 ws[2][3];
   if (nsk) {
-    rm_wload3(ws[0], w2p + (size_t)18 * RM_UNIT, 0);
-    if (nsk > 1) rm_wload3(ws[1], w2p + (size_t)18 * RM_UNIT, 1);
+    rt_wload3(ws[0], w2p + (size_t)18 * RT_UNIT, 0);
+    if (nsk > 1) rt_wload3(ws[1], w2p + (size_t)18 * RT_UNIT, 1);
   } else {
     rm_wprologue(wr, w2p, 18);
   }
-  const int lj1 = rm_again(lj);
+  const int lj1 = rt_again(lj);
   const bool own1 = lj1 >= 1 && lj1 <= W;                      // this lane's column is a pixel
 #pragma unroll
   for (int tt = 0; tt < 3; ++tt) {
@@ -699,7 +601,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
       if (y < H && own1) {
         const f32x4 v = acc[tt][y];
         *(uint2*)(sm + L.slab + ((y + 1) * RM_PITCH + lj1) * RM_RS + n * 2) =
-            make_uint2(rb_pack2(v[0] + add[0], v[1] + add[1]), rb_pack2(v[2] + add[2], v[3] + add[3]));
+            make_uint2(rt_pack2(v[0] + add[0], v[1] + add[1]), rt_pack2(v[2] + add[2], v[3] + add[3]));
       }
       acc[tt][y] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
     }
@@ -708,16 +610,16 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
 
   // ---- phase C: the 1x1 skip segments on the raw sources, B fragments straight from global memory (conv2's sums start with them)
   if (nsk) {
-    const int ljs = rm_again(lj), xc = ljs < 1 ? 0 : (ljs > W ? W - 1 : ljs - 1);
-    rm_gemm_skip<FULL>(acc, ws, w2p + (size_t)18 * RM_UNIT, nsk, s1, s2, C1, C2, xc, lq, H, W);
+    const int ljs = rt_again(lj), xc = ljs < 1 ? 0 : (ljs > W ? W - 1 : ljs - 1);
+    rm_gemm_skip<FULL>(acc, ws, w2p + (size_t)18 * RT_UNIT, nsk, s1, s2, C1, C2, xc, lq, H, W);
     rm_wprologue(wr, w2p, 18);                                // conv2's first units travel during GroupNorm 2
   }
 
   // ---- phase D: GroupNorm 2 + Swish of the bf16 h1, in place, then conv2 on a2
   rb_groupnorm(sm, L, L.slab, L.rs2, true, L.slab, L.rs2, HW, W, RM_PITCH, RB_N, a.G2, a.gamma2, a.beta2, a.eps2);
-  rm_gemm_rows<FULL>(acc, wr, w2p, 18, sm, fb, H);
+  rt_gemm_rows<FULL, RM_RS, RM_PITCH>(acc, wr, w2p, 18, sm, fb, H);
   __syncthreads();                                            // a2 is dead: the slab becomes the [HW][N] output image
-  const int lj2 = rm_again(lj);
+  const int lj2 = rt_again(lj);
   const bool own2 = lj2 >= 1 && lj2 <= W;
   const int x2 = own2 ? lj2 - 1 : 0;
 #pragma unroll
@@ -738,7 +640,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void k_resblock_mid(const ctdd_resbl
           o[0] += __uint_as_float(r[y].x << 16); o[1] += __uint_as_float(r[y].x & 0xFFFF0000u);
           o[2] += __uint_as_float(r[y].y << 16); o[3] += __uint_as_float(r[y].y & 0xFFFF0000u);
         }
-        *(uint2*)(sm + L.slab + (y * W + x2) * RM_RS + n * 2) = make_uint2(rb_pack2(o[0], o[1]), rb_pack2(o[2], o[3]));
+        *(uint2*)(sm + L.slab + (y * W + x2) * RM_RS + n * 2) = make_uint2(rt_pack2(o[0], o[1]), rt_pack2(o[2], o[3]));
       }
     }
   }

@@ -1,5 +1,5 @@
 // unet_rows_kernels.hip -- GroupNorm + Swish + 3x3 convolution (+ 1x1 skip segments | + residual) of a level whose samples do
-// NOT fit one workgroup (28x28, N = 96), as ONE launch on the row-tile K loop of k_resblock_mid (unet_resblock_kernels.hip).
+// NOT fit one workgroup (28x28, N = 96), as ONE launch on the row-tile K loop of k_resblock_mid (row_tile.hpp).
 //
 //   out = bf16( conv3x3( bf16(swish(GN(concat(s1[, s2])))) ) [+ 1x1 on raw r1[, r2]] + bias [+ tbias[b]] [+ residual] )
 //
@@ -24,40 +24,19 @@
 // through registers, barrier, the piece's (32 channels, dx) units, barrier.  Unit: the 16 row fragments of that column shift are
 // read ONCE, output row y takes nine matrix instructions (three dy x three weight tiles) on F[y], F[y + 1], F[y + 2]: 16
 // ds_read_b128 per 126 matrix instructions.  The weights stream global -> registers through a ring of two units (ctdd_unet.h:
-// pack_conv_rows_weights' order; the two column halves of a channel group read the same stream).  Border positions, positions
+// pack_conv_rows_weights = pack_row_tile_weights' order in two streams; the two column halves of a channel group read the same stream).  Border positions, positions
 // past W and rows outside the image are never written after the prologue's zero fill.
-#include <type_traits>
-
-#include "common.hpp"
+#include "row_tile.hpp"
 #include "../../include/ctdd_unet.h"
 
 namespace ctdd {
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2v = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2v = __attribute__((ext_vector_type(2))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
-__device__ inline unsigned cr_pack2(float a, float b) {
-  f32x2v v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-}
-// the value again, as one the compiler knows nothing about (what is derived from it is computed where it is used instead of being
-// kept in registers across the K loops)
-__device__ inline int cr_again(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
 constexpr int CR_THREADS = 256, CR_N = 96, CR_BAND = 14, CR_PITCH = 32, CR_RS = 224, CR_MAXW = 28, CR_MAXC = 384, CR_PIECE = 96;
-constexpr int CR_ROWSTEP = CR_PITCH * CR_RS;                     // bytes between padded rows
 constexpr int CR_SLAB = ((CR_BAND + 2) * CR_PITCH + 2) * CR_RS;  // 115 136
 constexpr int CR_SCALE = CR_SLAB;                                // float scale[CR_MAXC], shift[CR_MAXC]
 constexpr int CR_RED = CR_SCALE + 2 * CR_MAXC * 4;               // double [column half][channel][moment]
 constexpr int CR_TOTAL = CR_RED + 2 * CR_N * 2 * 8;
-constexpr int CR_UNIT = 9 * 512;                                 // bf16 elements of one (32 channels, dx) unit of a stream
 constexpr int CR_FB = 12;                                        // pixels per thread in flight in the fill
 static_assert(CR_BAND * CR_MAXW * CR_RS <= CR_SLAB, "the output image reuses the slab");
 
@@ -99,82 +78,11 @@ __device__ __attribute__((always_inline)) inline void cr_fill(unsigned char* sm,
         const f32x2v z = y * (f32x2v){-1.4426950408889634f, -1.4426950408889634f};
         const f32x2v d = (f32x2v){__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)} + (f32x2v){1.0f, 1.0f};
         y = y * (f32x2v){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-        ow[j] = cr_pack2(y.x, y.y);
+        ow[j] = rt_pack2(y.x, y.y);
       }
       const unsigned rr = p / uW, x = p - rr * uW;
       if (p < npix) *(uint4*)(dst + (rr * CR_PITCH + x) * CR_RS) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
     }
-  }
-}
-
-// one unit of a 3x3 weight stream: [dy][tile] fragments of 1 KiB each
-__device__ __attribute__((always_inline)) inline void cr_wload9(u32x4 (&dst)[3][3], const unsigned short* __restrict__ wrow, int u) {
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int t = 0; t < 3; ++t) dst[dy][t] = *(const u32x4*)(wrow + (size_t)u * CR_UNIT + (dy * 3 + t) * 512);
-}
-// one 32-channel unit of the 1x1 stream: [tile] fragments
-__device__ __attribute__((always_inline)) inline void cr_wload3(u32x4 (&dst)[3], const unsigned short* __restrict__ wrow, int u) {
-#pragma unroll
-  for (int t = 0; t < 3; ++t) dst[t] = *(const u32x4*)(wrow + (size_t)u * 1536 + t * 512);
-}
-
-// The K loop of one piece held in the slab's columns [0, 32 nunits / 3): rm_gemm_rows of k_resblock_mid on this slab's pitch, all
-// 14 row tiles (rows past the image read zeros and are never stored).  Units in the order (channel block, dx), weight ring wr
-// holding units 0 and 1 (requested before the fill).  fb: byte address of this lane's position of padded row 0 + its k quarter.
-// Unit u: F[r] = the fragment of padded row r at that column shift, read ONCE; acc[t][y] += W[dy][t] F[y + dy].  The fragments of
-// unit u + 1 are requested while unit u computes (F[y + 2] ahead of row y's matrix instructions), the weights of unit u + 2
-// when unit u has consumed its slot.  The request past the last unit repeats the last unit's addresses.
-__device__ __attribute__((always_inline)) inline void cr_gemm_rows(f32x4 (&acc)[3][CR_BAND], u32x4 (&wr)[2][3][3], const unsigned short* __restrict__ wrow,
-                                                                  int nunits, const unsigned char* sm, int fb) {
-  int un = 0, dxn = 0, cbn = 0;                                 // the unit whose fragments are requested next
-  auto xaddr = [&]() {                                         // (selects, not branches)
-    const int o = fb + (dxn - 1) * CR_RS + cbn * 64;
-    const bool more = un + 1 < nunits, wrap = dxn == 2;
-    un += more ? 1 : 0;
-    cbn += more && wrap ? 1 : 0;
-    dxn = more ? (wrap ? 0 : dxn + 1) : dxn;
-    return o;
-  };
-  auto fload = [&](bf16x8& f, int o, int r) { f = *(const bf16x8*)(sm + o + r * CR_ROWSTEP); };
-  auto step = [&](u32x4 (&slot)[3][3], bf16x8 (&fc)[CR_BAND + 2], bf16x8 (&fn)[CR_BAND + 2], int u, auto guard) {
-    constexpr bool GUARD = decltype(guard)::value;
-    if (GUARD && u >= nunits) return;
-    const int o = xaddr();
-    fload(fn[0], o, 0);
-    fload(fn[1], o, 1);
-#pragma unroll
-    for (int y = 0; y < CR_BAND; ++y) {
-      fload(fn[y + 2], o, y + 2);
-#pragma unroll
-      for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-          acc[t][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[dy][t]), fc[y + dy], acc[t][y], 0, 0, 0);
-      // (pins the request for F[y + 2] to this row, as in rm_gemm_rows)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (!GUARD || u + 2 < nunits) cr_wload9(slot, wrow, u + 2);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  bf16x8 F[2][CR_BAND + 2];
-  {
-    const int o = xaddr();
-#pragma unroll
-    for (int r = 0; r < CR_BAND + 2; ++r) fload(F[0][r], o, r);
-  }
-  // vmcnt(0): the ring's first two units have landed; entered with nothing in flight, the loop's own waits are the counted
-  // vmcnt of the ring (rm_gemm_rows)
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  int u0 = 0;
-  for (; u0 + 4 <= nunits; u0 += 2) {
-    step(wr[0], F[0], F[1], u0, std::false_type{});
-    step(wr[1], F[1], F[0], u0 + 1, std::false_type{});
-  }
-  for (; u0 < nunits; u0 += 2) {
-    step(wr[0], F[0], F[1], u0, std::true_type{});
-    step(wr[1], F[1], F[0], u0 + 1, std::true_type{});
   }
 }
 
@@ -204,7 +112,7 @@ __device__ __attribute__((always_inline)) inline void cr_gemm_skip(f32x4 (&acc)[
 #pragma unroll
       for (int t = 0; t < 3; ++t)
         acc[t][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t]), gc[y], acc[t][y], 0, 0, 0);
-    if (!GUARD || u + 2 < nsk) cr_wload3(slot, wrow, u + 2);
+    if (!GUARD || u + 2 < nsk) rt_wload3(slot, wrow, u + 2);
     __builtin_amdgcn_sched_barrier(0);
   };
   bf16x8 G[2][CR_BAND];
@@ -245,14 +153,14 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
   const int b = blockIdx.x / nbands, y0 = (blockIdx.x - b * nbands) * CR_BAND;
   const int lane = t & 63, wv = t >> 6, lj = lane & 15, lq = lane >> 4, cg = wv >> 1, hh = wv & 1;
   const int nu3 = 3 * (C >> 5), nsk = SKIP ? (a.RC1 + a.RC2) >> 5 : 0;
-  const unsigned short* wrow = (const unsigned short*)a.w + (size_t)cg * ((size_t)nu3 * CR_UNIT + (size_t)nsk * 1536) + lane * 8;
-  u32x4 wr[2][3][3];                                          // the weight ring (cr_gemm_rows)
+  const unsigned short* wrow = (const unsigned short*)a.w + (size_t)cg * ((size_t)nu3 * RT_UNIT + (size_t)nsk * 1536) + lane * 8;
+  u32x4 wr[2][3][3];                                          // the weight ring (rt_gemm_rows)
   CR_STAMP(0);
 
   // ---- prologue: the first piece's first two units, zero the slab (border positions stay zero to the end), scale / shift of all
   // source channels from the producers' sums (the head of k_gn_apply: fp64, a group may straddle the sources)
-  cr_wload9(wr[0], wrow, 0);
-  cr_wload9(wr[1], wrow, 1);
+  rt_wload9(wr[0], wrow, 0);
+  rt_wload9(wr[1], wrow, 1);
   for (int v = t; v < (CR_SLAB >> 4); v += CR_THREADS) *(uint4*)(sm + v * 16) = make_uint4(0, 0, 0, 0);
   {
     float* scale = (float*)(sm + CR_SCALE);
@@ -292,12 +200,13 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
       const int pc = cs - c0 < CR_PIECE ? cs - c0 : CR_PIECE, nun = 3 * (pc >> 5);
       cr_fill(sm, src + c0, cs, pc, coff + c0, y0, H, W);
       __syncthreads();
-      cr_gemm_rows(acc, wr, wrow + (size_t)ub * CR_UNIT, nun, sm, fb);
+      // (all 14 row tiles whatever H: rows past the image read zeros and are never stored)
+      rt_gemm_rows<true, CR_RS, CR_PITCH>(acc, wr, wrow + (size_t)ub * RT_UNIT, nun, sm, fb, CR_BAND);
       __syncthreads();                                        // every wave has read its last fragment of this piece
       ub += nun;
       if (ub < nu3) {                                         // the next piece's first two units travel behind its fill (a piece has >= 3)
-        cr_wload9(wr[0], wrow + (size_t)ub * CR_UNIT, 0);
-        cr_wload9(wr[1], wrow + (size_t)ub * CR_UNIT, 1);
+        rt_wload9(wr[0], wrow + (size_t)ub * RT_UNIT, 0);
+        rt_wload9(wr[1], wrow + (size_t)ub * RT_UNIT, 1);
       }
     }
   }
@@ -305,11 +214,11 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
 
   // ---- the 1x1 segments on the raw sources
   if constexpr (SKIP) {
-    const unsigned short* wsk = wrow + (size_t)nu3 * CR_UNIT;
+    const unsigned short* wsk = wrow + (size_t)nu3 * RT_UNIT;
     u32x4 ws[2][3];
-    cr_wload3(ws[0], wsk, 0);
-    if (nsk > 1) cr_wload3(ws[1], wsk, 1);
-    const int cs_ = 16 * hh + cr_again(lj), xc = cs_ < 1 ? 0 : (cs_ > W ? W - 1 : cs_ - 1);
+    rt_wload3(ws[0], wsk, 0);
+    if (nsk > 1) rt_wload3(ws[1], wsk, 1);
+    const int cs_ = 16 * hh + rt_again(lj), xc = cs_ < 1 ? 0 : (cs_ > W ? W - 1 : cs_ - 1);
     cr_gemm_skip(acc, ws, wsk, nsk, (const unsigned short*)a.r1_bf16 + (size_t)b * HW * a.RC1,
                  (const unsigned short*)a.r2_bf16 + (size_t)b * HW * a.RC2, a.RC1, a.RC2, xc, lq, y0, H, W);
   }
@@ -318,7 +227,7 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
   // ---- epilogue: acc + bias + time bias + residual in the accumulator layout, one rounding, into the [pixels][N] output image
   // (the slab is dead: every wave passed the barrier after the last piece); statistics on the fp32 value: fp32 over a lane's <= 14
   // rows, fp64 across the 16 lanes of a column half, the two halves meet in LDS
-  const int col = 16 * hh + cr_again(lj);
+  const int col = 16 * hh + rt_again(lj);
   const bool own = col >= 1 && col <= W;                       // this lane's column is a pixel
   const int x2 = own ? col - 1 : 0;
   const int nrows = H - y0 < CR_BAND ? H - y0 : CR_BAND;
@@ -354,7 +263,7 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) { s[i] += o[i]; q[i] = fmaf(o[i], o[i], q[i]); }
-        *(uint2*)(sm + (y * W + x2) * CR_RS + n * 2) = make_uint2(cr_pack2(o[0], o[1]), cr_pack2(o[2], o[3]));
+        *(uint2*)(sm + (y * W + x2) * CR_RS + n * 2) = make_uint2(rt_pack2(o[0], o[1]), rt_pack2(o[2], o[3]));
       }
     }
 #ifndef CTDD_ROWS_STAMPS

@@ -147,33 +147,38 @@ def resblock_mid_covers(H, W, cs, cout, G1, G2):
     return ((H + 2) * 16 + 2) * (cout * 2 + 32) + 256 * 80 + 2 * 384 * 8 + 2 * 384 * 4 <= 160 * 1024
 
 
-def pack_resblock_mid_weights(w1, w2, cs):
-    """The [192][9 Ct] conv1 matrix (K = tap -> channel of the concatenation) and the [192][9 * 192 (+ Ct)] conv2 matrix (3x3 on a2, then
-    the 1x1 skip segments) in the order ctdd_unet_resblock_mid streams them (include/ctdd_unet.h): per wave (48 output channels), a 3x3
-    segment as source -> 32-channel block -> dx -> dy -> 16-channel tile, the skip segments as source -> 32-channel block -> tile,
-    every (tile, 32 channels) fragment as [q][i][8] (1 KiB of consecutive bytes per wave-instruction).  Nothing is padded.  Returned as
-    [192][K] views of the flat streams ([4 waves][48 K])."""
-    N, Ct = w1.shape[0], sum(cs)
-    assert N == 192 and w1.shape[1] == 9 * Ct and w2.shape[1] in (9 * N, 9 * N + Ct) and all(c % 32 == 0 for c in cs)
-
-    def seg3(w, c0, c):        # [N][9][C] columns [c0, c0 + c) -> [4][c / 32 * 3 * 3 * 3 * 512]
-        v = w[:, :, c0:c0 + c].reshape(4, 3, 16, 3, 3, c // 32, 4, 8)          # wave, tile, i, dy, dx, block, q, e
-        return v.permute(0, 5, 4, 3, 1, 6, 2, 7).reshape(4, -1)                 # wave, block, dx, dy, tile, q, i, e
-
-    def seg1(w, c0, c):        # [N][C] columns [c0, c0 + c) -> [4][c / 32 * 3 * 512]
-        v = w[:, c0:c0 + c].reshape(4, 3, 16, c // 32, 4, 8)                   # wave, tile, i, block, q, e
-        return v.permute(0, 3, 1, 4, 2, 5).reshape(4, -1)                       # wave, block, tile, q, i, e
-
-    w1v, k1, k2, c0 = w1.reshape(N, 9, Ct), [], [seg3(w2[:, :9 * N].reshape(N, 9, N), 0, N)], 0
+def pack_row_tile_weights(w, cs, rcs, streams):
+    """The [48 streams][9 sum(cs) + sum(rcs)] matrix of a convolution (K = the 3x3 segment as tap -> channel of the concatenation of `cs`,
+    then the 1x1 segments on `rcs`) in the order the row-tile K loops stream it (include/ctdd_unet.h; csrc/row_tile.hpp): one stream
+    per 48 output channels -- four waves of ctdd_unet_resblock_mid, two channel groups of ctdd_unet_conv_rows -- holding the 3x3 segment
+    as source -> 32-channel block -> dx -> dy -> 16-channel tile, then the 1x1 segments as source -> 32-channel block -> tile, every
+    (tile, 32 channels) fragment as [q][i][8] (1 KiB of consecutive bytes per wave-instruction).  Nothing is padded.  Returned as an
+    [N][K] view of the flat streams ([streams][48 K])."""
+    N, Ct, Rt = w.shape[0], sum(cs), sum(rcs)
+    assert N == 48 * streams and w.shape[1] == 9 * Ct + Rt and all(c % 32 == 0 for c in [*cs, *rcs])
+    w3, parts, c0 = w[:, :9 * Ct].reshape(N, 9, Ct), [], 0
     for c in cs:
-        k1.append(seg3(w1v, c0, c))
+        v = w3[:, :, c0:c0 + c].reshape(streams, 3, 16, 3, 3, c // 32, 4, 8)        # stream, tile, i, dy, dx, block, q, e
+        parts.append(v.permute(0, 5, 4, 3, 1, 6, 2, 7).reshape(streams, -1))        # stream, block, dx, dy, tile, q, i, e
         c0 += c
-    if w2.shape[1] > 9 * N:
-        c0 = 0
-        for c in cs:
-            k2.append(seg1(w2[:, 9 * N:], c0, c))
-            c0 += c
-    return torch.cat(k1, 1).contiguous().reshape(N, 9 * Ct), torch.cat(k2, 1).contiguous().reshape(N, w2.shape[1])
+    c0 = 9 * Ct
+    for c in rcs:
+        v = w[:, c0:c0 + c].reshape(streams, 3, 16, c // 32, 4, 8)                  # stream, tile, i, block, q, e
+        parts.append(v.permute(0, 3, 1, 4, 2, 5).reshape(streams, -1))              # stream, block, tile, q, i, e
+        c0 += c
+    return torch.cat(parts, 1).contiguous().reshape(N, w.shape[1])
+
+
+def pack_resblock_mid_weights(w1, w2, cs):
+    """ctdd_unet_resblock_mid's [192][9 Ct] conv1 matrix and [192][9 * 192 (+ Ct)] conv2 matrix (3x3 on a2, then the 1x1 skip segments
+    on the sources): pack_row_tile_weights, one stream per wave."""
+    N = w1.shape[0]
+    return pack_row_tile_weights(w1, cs, [], 4), pack_row_tile_weights(w2, [N], cs if w2.shape[1] > 9 * N else [], 4)
+
+
+def pack_conv_rows_weights(w, cs, rcs):
+    """ctdd_unet_conv_rows' [96][9 sum(cs) + sum(rcs)] matrix: pack_row_tile_weights, one stream per channel group."""
+    return pack_row_tile_weights(w, cs, rcs, 2)
 
 
 # default of cfg.model.conv_rows_min_wgs (UNetEngine._runs_conv_rows).  Graph replay of one MNIST plan, pairs | ctdd_unet_conv_rows:
@@ -189,27 +194,6 @@ def conv_rows_covers(H, W, cs, rcs, cout, G, residual=False):
     channels (<= 384 per concatenation), groups dividing the GroupNorm channels, 1x1 segments or a residual but not both."""
     return bool(H >= 1 and 1 <= W <= 28 and cout == 96 and 1 <= len(cs) <= 2 and len(rcs) <= 2 and all(c > 0 and c % 32 == 0 for c in [*cs, *rcs])
                 and sum(cs) <= 384 and sum(rcs) <= 384 and G > 0 and sum(cs) % G == 0 and not (rcs and residual))
-
-
-def pack_conv_rows_weights(w, cs, rcs):
-    """The [96][9 sum(cs) + sum(rcs)] matrix of a convolution (K = the 3x3 segment as tap -> channel of the concatenation of `cs`, then
-    the 1x1 segments on `rcs`) in the order ctdd_unet_conv_rows streams it (include/ctdd_unet.h): pack_resblock_mid_weights' order
-    with two 48-channel streams instead of four -- per stream the 3x3 segment as source -> 32-channel block -> dx -> dy -> 16-channel
-    tile, then the 1x1 segments as source -> block -> tile, every (tile, 32 channels) fragment as [q][i][8].  Nothing is padded.
-    Returned as a [96][K] view of the flat streams ([2 streams][48 K])."""
-    N, Ct, Rt = w.shape[0], sum(cs), sum(rcs)
-    assert N == 96 and w.shape[1] == 9 * Ct + Rt and all(c % 32 == 0 for c in [*cs, *rcs])
-    w3, parts, c0 = w[:, :9 * Ct].reshape(N, 9, Ct), [], 0
-    for c in cs:
-        v = w3[:, :, c0:c0 + c].reshape(2, 3, 16, 3, 3, c // 32, 4, 8)              # stream, tile, i, dy, dx, block, q, e
-        parts.append(v.permute(0, 5, 4, 3, 1, 6, 2, 7).reshape(2, -1))              # stream, block, dx, dy, tile, q, i, e
-        c0 += c
-    c0 = 9 * Ct
-    for c in rcs:
-        v = w[:, c0:c0 + c].reshape(2, 3, 16, c // 32, 4, 8)                        # stream, tile, i, block, q, e
-        parts.append(v.permute(0, 3, 1, 4, 2, 5).reshape(2, -1))                    # stream, block, tile, q, i, e
-        c0 += c
-    return torch.cat(parts, 1).contiguous().reshape(N, w.shape[1])
 
 
 def fold_upsample_weights(w):
@@ -482,10 +466,10 @@ class _PlanBuilder:
             tc.record_gn(self, srcs, norm, swish, eps, HW, out, drop_p)
         return out
 
-    def conv_rows(self, srcs, norm, w_conv, bias, out, tb=None, res=None, raws=(), w_skip=None):
-        """GroupNorm `norm` + Swish of the concatenation of `srcs`, the 3x3 convolution `w_conv` on it (+ the 1x1 convolution `w_skip` on
-        the raw concatenation of `raws` | + the residual `res`) as ONE ctdd_unet_conv_rows launch: the gn_apply + conv pair without the
-        activated tensor.  bias: the summed bias of the segments."""
+    def conv_rows(self, srcs, norm, segs, wsrc, bias, out, tb=None, res=None, raws=()):
+        """GroupNorm `norm` + Swish of the concatenation of `srcs`, the 3x3 convolution on it (+ the 1x1 segments on the raw tensors
+        `raws` | + the residual `res`) as ONE ctdd_unet_conv_rows launch: the gn_apply + conv pair without the activated tensor.
+        segs, wsrc: the weights as `conv` takes them (the 3x3 segment, then one 1x1 segment per raw tensor); bias: their summed bias."""
         eng, lib, B = self.eng, self.lib, self.B
         Hc, Wc, N = srcs[0].H, srcs[0].W, out.C
         cs, rcs = [s_.C for s_ in srcs], [s_.C for s_ in raws]
@@ -499,11 +483,6 @@ class _PlanBuilder:
             setattr(a, f"RC{i + 1}", s_.C)
         g, b_ = norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()
         a.gamma, a.beta, a.G, a.eps = ptr(g), ptr(b_), norm.num_groups, norm.eps
-        segs, wsrc, c_ = [(None, sum(cs), SEG_3x3)], [(w_conv, 0)], 0
-        for c in rcs:
-            segs.append((None, c, SEG_1x1))
-            wsrc.append((w_skip, c_))
-            c_ += c
         w, _ = eng._pack(pack_conv_rows_weights(eng._w2d(wsrc, segs), cs, rcs))
         a.w, a.bias = ptr(w), ptr(bias)
         if tb is not None:
@@ -519,13 +498,26 @@ class _PlanBuilder:
         self.launch(lib.ctdd_unet_conv_rows, C.byref(a), 0, label=f"{Hc}x{Wc} K={Ktot} N={N} gn+conv rows C={cs} raw={rcs}",
                     flops=2 * B * Hc * Wc * N * Ktot)
 
-    def resblock_mid(self, rb, srcs):
-        """The block as ONE ctdd_unet_resblock_mid launch (the 14x14 level): as resblock_fused, weights in pack_resblock_mid_weights' order."""
-        return self.resblock_fused(rb, srcs, mid=True)
+    def conv2_operands(self, rb, a2, srcs):
+        """conv2 of a ResBlock as ONE K-segmented convolution: the 3x3 segment on the activated tensor `a2` (None where the kernel
+        makes it itself) and, for a block with a linear skip, a 1x1 segment on each raw source.  Returns segs, wsrc, the bias
+        parameters and their sum (training: the recorder's buffer, filled before the plan runs)."""
+        tc = self.tc
+        segs, wsrc, bias_params = [(a2, rb.conv2.weight.shape[0], SEG_3x3)], [(rb.conv2.weight, 0)], [rb.conv2.bias]
+        bias = rb.conv2.bias.detach().float()
+        if rb.skip is not None:
+            c_ = 0
+            for s_ in srcs:
+                segs.append((s_, s_.C, SEG_1x1))
+                wsrc.append((rb.skip.weight, c_))
+                c_ += s_.C
+            bias_params.append(rb.skip.bias)
+            bias = tc.summed_bias(bias_params) if tc is not None else bias + rb.skip.bias.detach().float()
+        return segs, wsrc, bias_params, bias.contiguous()
 
     def resblock_fused(self, rb, srcs, mid=False):
-        """The block as ONE ctdd_unet_resblock_small launch: the same [N][K] matrices in the kernel's fragment order, the same summed
-        conv2 + skip bias."""
+        """The block as ONE ctdd_unet_resblock_small launch (mid: ctdd_unet_resblock_mid, the 14x14 level): the same [N][K] matrices in
+        the kernel's fragment order, the same summed conv2 + skip bias."""
         eng, lib, B = self.eng, self.lib, self.B
         Hc, Wc = srcs[0].H, srcs[0].W
         cs = [s.C for s in srcs]
@@ -540,15 +532,7 @@ class _PlanBuilder:
         a.G1, a.G2, a.eps1, a.eps2 = rb.norm1.num_groups, rb.norm2.num_groups, rb.norm1.eps, rb.norm2.eps
         a.tbias, a.tb_stride = self.tproj.data_ptr() + 4 * self.toff[id(rb)], self.tb_stride
         w1 = eng._w2d([(rb.conv1.weight, 0)], [(None, Ct, SEG_3x3)])
-        segs, wsrc, bias2 = [(None, cout, SEG_3x3)], [(rb.conv2.weight, 0)], rb.conv2.bias.detach().float()
-        if rb.skip is not None:
-            c_ = 0
-            for cs_ in cs:
-                segs.append((None, cs_, SEG_1x1))
-                wsrc.append((rb.skip.weight, c_))
-                c_ += cs_
-            bias2 = bias2 + rb.skip.bias.detach().float()
-        bias2 = bias2.contiguous()
+        segs, wsrc, _, bias2 = self.conv2_operands(rb, None, srcs)
         w2 = eng._w2d(wsrc, segs)
         w1, w2 = pack_resblock_mid_weights(w1, w2, cs) if mid else (pack_resblock_weights(w1), pack_resblock_weights(w2))
         (w1, _), (w2, _) = eng._pack(w1), eng._pack(w2)
@@ -574,44 +558,28 @@ class _PlanBuilder:
         # the 14x14 level's: ctdd_unet_resblock_mid, one 192-channel slab, conv1 source by source; cfg.model.resblock_fused_mid = 0
         # keeps the four launches
         if self.onepass_gn and eng._fuses_resblock_mid(rb, Hc, Wc, cs, tc is not None) and all(s_.stats is None for s_ in srcs):
-            return self.resblock_mid(rb, srcs)
+            return self.resblock_fused(rb, srcs, mid=True)
         # a level whose samples do not fit one workgroup (28x28): each GroupNorm + convolution pair as ONE ctdd_unet_conv_rows launch
         # (csrc/unet_rows_kernels.hip) when the producers left statistics; cfg.model.conv_rows = 0 keeps the pairs
         tbias = (self.tproj.data_ptr() + 4 * self.toff[id(rb)], self.tb_stride)
         h = _Tensor(self, Hc, Wc, cout)
         b1 = rb.conv1.bias.detach().float().contiguous()
         if eng._runs_conv_rows(self.B, Hc, Wc, cs, [], cout, rb.norm1.num_groups, False, tc is not None) and all(s_.stats is not None for s_ in srcs):
-            self.conv_rows(srcs, rb.norm1, rb.conv1.weight, b1, h, tb=tbias)
+            self.conv_rows(srcs, rb.norm1, [(None, sum(cs), SEG_3x3)], [(rb.conv1.weight, 0)], b1, h, tb=tbias)
         else:
             a1 = self.gn_apply(srcs, rb.norm1, True, rb.norm1.eps, Hc * Wc)
             self.conv([(a1, a1.C, SEG_3x3)], [(rb.conv1.weight, 0)], b1, cout, Hc, Wc, Hc, Wc, h, tb=tbias, bias_params=[rb.conv1.bias])
-        rcs = cs if rb.skip is not None else []
+        rcs, res = (cs, None) if rb.skip is not None else ([], srcs[0])    # linear skip as 1x1 K-segments on the raw input | residual
         if eng._runs_conv_rows(self.B, Hc, Wc, [cout], rcs, cout, rb.norm2.num_groups, rb.skip is None, tc is not None) and h.stats is not None:
             y = _Tensor(self, Hc, Wc, cout)
-            if rb.skip is not None:
-                self.conv_rows([h], rb.norm2, rb.conv2.weight, (rb.conv2.bias.detach().float() + rb.skip.bias.detach().float()).contiguous(), y,
-                               raws=srcs, w_skip=rb.skip.weight)
-            else:
-                self.conv_rows([h], rb.norm2, rb.conv2.weight, rb.conv2.bias.detach().float().contiguous(), y, res=srcs[0])
+            segs, wsrc, _, bias2 = self.conv2_operands(rb, None, srcs)
+            self.conv_rows([h], rb.norm2, segs, wsrc, bias2, y, res=res, raws=srcs if rb.skip is not None else ())
             return y
         drop = float(rb.dropout.p) if (tc is not None and tc.dropout) else 0.0
         a2 = self.gn_apply([h], rb.norm2, True, rb.norm2.eps, Hc * Wc, drop_p=drop)
         y = _Tensor(self, Hc, Wc, cout)
-        wsrc = [(rb.conv2.weight, 0)]
-        bias2, bias_params = rb.conv2.bias.detach().float(), [rb.conv2.bias]
-        segs = [(a2, cout, SEG_3x3)]
-        res = None
-        if rb.skip is not None:
-            c_ = 0
-            for s_ in srcs:                       # linear skip folded in as 1x1 K-segments on the raw input
-                segs.append((s_, s_.C, SEG_1x1))
-                wsrc.append((rb.skip.weight, c_))
-                c_ += s_.C
-            bias_params.append(rb.skip.bias)
-            bias2 = tc.summed_bias(bias_params) if tc is not None else bias2 + rb.skip.bias.detach().float()
-        else:
-            res = srcs[0]
-        self.conv(segs, wsrc, bias2.contiguous(), cout, Hc, Wc, Hc, Wc, y, res=res, bias_params=bias_params)
+        segs, wsrc, bias_params, bias2 = self.conv2_operands(rb, a2, srcs)
+        self.conv(segs, wsrc, bias2, cout, Hc, Wc, Hc, Wc, y, res=res, bias_params=bias_params)
         return y
 
     def block(self, layer, srcs):

@@ -110,7 +110,7 @@ int ctdd_unet_resblock_small(const void* resblock_args, int f32, void* stream);
  * row whatever W, row stride 416 bytes, a guard row at either end) and no copy of the input: GroupNorm 1 reads the sources from
  * global memory and conv1 runs source by source.  A pixel tile is one output row; the K loop's unit is (32 channels, dx), whose row
  * fragments are read once and used by the three dy.  Anything else: CTDD_ERANGE / CTDD_EINVAL, nothing launched.
- * Weights (ctdd/unet_engine.py: pack_resblock_mid_weights): a stream per wave (output channels [48 wave, 48 wave + 48)), the four
+ * Weights (ctdd/unet_engine.py: pack_resblock_mid_weights = pack_row_tile_weights, four streams): a stream per wave (output channels [48 wave, 48 wave + 48)), the four
  * streams one after the other, each a sequence of 1 KiB fragments.  A fragment is (tile, 32 channels of K): element
  * (n = 48 wave + 16 tile + i, k = 8 q + e of the 32) at (16 q + i) * 8 + e.  conv1: for each source, for each 32-channel block of
  * it, for dx = -1, 0, 1, for dy = -1, 0, 1, for tile = 0, 1, 2: the fragment of tap (dy, dx) on that block (27 (C1 + C2) / 32
@@ -136,7 +136,7 @@ typedef struct {
  * workgroup per (sample, band of 14 output rows).  1 <= W <= 28, any H, N = 96, C1, C2, RC1, RC2 multiples of 32 (C2, RC1, RC2 may
  * be 0; RC2 > 0 needs RC1 > 0; <= 384 channels per concatenation), G divides C1 + C2, every GroupNorm source with statistics,
  * 1x1 segments or a residual but not both (a ResBlock has one of them), 16-byte aligned tensors, f32 must be 0.  Anything else: CTDD_ERANGE / CTDD_EINVAL, nothing launched.
- * Weights (ctdd/unet_engine.py: pack_conv_rows_weights): two streams (output channels [48 s, 48 s + 48)), one after the other, each a
+ * Weights (ctdd/unet_engine.py: pack_conv_rows_weights = pack_row_tile_weights, the same order in two streams): two streams (output channels [48 s, 48 s + 48)), one after the other, each a
  * sequence of 1 KiB fragments.  A fragment is (tile, 32 channels of K): element (n = 48 s + 16 tile + i, k = 8 q + e of the 32) at
  * (16 q + i) * 8 + e.  Per stream: for each GroupNorm source, for each 32-channel block of it, for dx = -1, 0, 1, for dy = -1, 0, 1,
  * for tile = 0, 1, 2: the fragment of tap (dy, dx) on that block (27 (C1 + C2) / 32 fragments); then for each raw source, for each

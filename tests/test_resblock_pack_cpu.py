@@ -64,7 +64,8 @@ def _unpack(w1p, w2p, cs, skip):
     return w1.reshape(N, 9 * Ct), w2
 
 
-@pytest.mark.parametrize("cs", [[192], [192, 96], [96]])
+# ([64, 32]: two sources of different sizes, each of its own number of blocks -- the source -> block order)
+@pytest.mark.parametrize("cs", [[192], [192, 96], [96], [64, 32]])
 @pytest.mark.parametrize("skip", [True, False])
 def test_pack_mid_weights_is_undone_by_the_documented_order(cs, skip):
     from ctdd import unet_engine as ue          # (imports without a GPU: the library is loaded on first use)
