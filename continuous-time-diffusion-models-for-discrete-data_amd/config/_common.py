@@ -47,7 +47,9 @@ def hollow(c, embed_dim, num_layers, mlp_dim, concat_dim, S):
 
 def encoder(c, name, embed_dim, num_layers, mlp_dim, concat_dim, S, num_output_ffresiduals=2):
     """Single-stream transformer score models (x0-prediction "BERT" and masked): hollow_networks.BertEnumTransformer /
-    EnumerativeTransformer.  Training runs the autograd module (engine_train = "torch")."""
+    EnumerativeTransformer.  Training runs the autograd module (engine_train = "torch").  To train on the HIP kernels set
+    c.model.engine_train = "hip-encoder" for an x0-prediction model (ctdd/bert_train.py) or "hip-masked" for a masked model
+    (ctdd/masked_train.py); c.model.engine_train_precision = "bf16" (default) or "fp32"."""
     c.model.update(name=name, is_ebm=False, use_cat=False, use_one_hot_input=False, embed_dim=embed_dim, readout="resnet",
                    dropout_rate=0.1, concat_dim=concat_dim, num_layers=num_layers, num_heads=8, attention_dropout_rate=0.1,
                    transformer_norm_type="prenorm", mlp_dim=mlp_dim, out_dim=S, readout_dim=S,

@@ -16,6 +16,7 @@
 //   k_bert_attention_short  unmasked attention for Tq, Tk <= 64: one wave per (sequence, head), K / V resident in LDS
 //   k_bert_gather           encoder rows 1..D of every sequence, or row p of sequence (b, p) -> the readout input
 //   k_bert_embed_bwd, k_bert_gather_bwd   their backward in plain mode (the x0-prediction model's training path)
+//   k_bert_embed_enum_bwd, k_bert_gather_enum_bwd   their backward in enumerate mode over a window of the enumeration (the masked model's)
 #include "common.hpp"
 
 namespace ctdd {
@@ -700,6 +701,65 @@ __global__ __launch_bounds__(256) void k_bert_gather_bwd(const float* __restrict
   for (int e = lane; e < E; e += 64) d_enc[(size_t)r * E + e] = src ? src[e] : 0.0f;
 }
 
+// ------------------------------------------------------------------ backward of the enumerate modes (training: ctdd/masked_train.py)
+// k_bert_embed, enumerate mode, over the window [r0, r0 + rows) of the (B D') enumeration: chunk row r is sequence g = r0 + r =
+// (b, p) and g (rows, D + 1, E) the gradient of the chunk's encoder input, so  dw_in[e] += sum_{r,d} g[r][1 + d][e] xn(r, d),
+// db_in[e] += sum_{r,d} g[r][1 + d][e]  with xn the forward's expression (the mask value S at d == p).  A workgroup takes a
+// contiguous run of the rows * D token rows: thread = (column e, sub-row), the sub-rows' partial sums meet in LDS and ONE atomic
+// per column and workgroup leaves it (2 E addresses: per-wave atomics on them serialise, see k_hollow_ln_bwd_v4).
+struct BertEmbedEnumBwdArgs {
+  const int64_t* x64; const int32_t* x32; const float* g; int B, D, E, S, cond, rows; int64_t r0; float* dw; float* db;
+};
+__global__ __launch_bounds__(256) void k_bert_embed_enum_bwd(const BertEmbedEnumBwdArgs a) {
+  __shared__ float red[2][256];
+  const int E = a.E, D = a.D, Dp = D - a.cond;
+  const int ncol = E < 256 ? E : 256, nsub = 256 / ncol;
+  const int col = threadIdx.x % ncol, sub = threadIdx.x / ncol;
+  const bool active = sub < nsub;
+  const int ntok = a.rows * D;                                   // (host: rows * D and B * D' fit an int)
+  const int per = (ntok + gridDim.x - 1) / gridDim.x;
+  const int t0 = blockIdx.x * per, t1 = min(ntok, t0 + per);
+  const float inv = 1.0f / (float)(a.S - 1);
+  for (int e0 = 0; e0 < E; e0 += ncol) {
+    const int e = e0 + col;
+    float sw = 0.0f, sb = 0.0f;
+    if (active && e < E) {
+      for (int tk = t0 + sub; tk < t1; tk += nsub) {
+        const int r = tk / D, d = tk - r * D;
+        const int g = (int)a.r0 + r;
+        const int b = g / Dp, p = a.cond + (g - b * Dp);
+        const float xr = d == p ? (float)a.S : (a.x64 ? (float)a.x64[(size_t)b * D + d] : (float)a.x32[(size_t)b * D + d]);
+        const float xn = (xr * inv) * 2.0f - 1.0f;
+        const float gv = a.g[((size_t)r * (D + 1) + 1 + d) * E + e];
+        sw = fmaf(gv, xn, sw); sb += gv;
+      }
+    }
+    __syncthreads();                                             // (red of the previous column block has been read)
+    red[0][threadIdx.x] = sw; red[1][threadIdx.x] = sb;
+    __syncthreads();
+    if (sub == 0 && e < E) {
+      for (int s_ = 1; s_ < nsub; ++s_) { sw += red[0][s_ * ncol + col]; sb += red[1][s_ * ncol + col]; }
+      atomicAdd(a.dw + e, sw);
+      atomicAdd(a.db + e, sb);
+    }
+  }
+}
+// k_bert_gather, enumerate mode: row g = r0 + r of the (B D', E) readout-input gradient goes to row 1 + p of sequence r of the
+// chunk's (rows, D + 1, E) encoder-output gradient, every other row is written as zero (every element of d_enc is written; rows
+// of d_out outside the window are never read).  One wave per row of d_enc.
+__global__ __launch_bounds__(256) void k_bert_gather_enum_bwd(const float* __restrict__ d_out, int64_t r0, int64_t nrows, int D, int cond, int E,
+                                                             float* __restrict__ d_enc) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);          // row (r, j) of d_enc
+  if (row >= nrows) return;
+  const int64_t r = row / (D + 1);
+  const int j = (int)(row % (D + 1));
+  const int64_t g = r0 + r;
+  const int p = cond + (int)(g % (D - cond));
+  const float* src = j == 1 + p ? d_out + (size_t)g * E : nullptr;
+  for (int e = lane; e < E; e += 64) d_enc[(size_t)row * E + e] = src ? src[e] : 0.0f;
+}
+
 // Unmasked attention for short sequences (Tq, Tk <= 64: T = D + 1 = 33 in three of the four shipped encoder configurations, where
 // the generic kernels' 128-query workgroups leave three quarters of their lanes idle).  One wave owns one (sequence, head) pair:
 // lane = query, the pair's whole K and V resident in LDS (staged once, read as wave-uniform float4s), NW pairs per workgroup.
@@ -841,6 +901,31 @@ extern "C" int ctdd_bert_gather_bwd(const float* d_out, int B, int D, int cond, 
   const int64_t rows = (int64_t)B * (D + 1);
   hipLaunchKernelGGL(k_bert_gather_bwd, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_out, rows, D, E, d_enc);
   return finish_launch("k_bert_gather_bwd");
+}
+
+extern "C" int ctdd_bert_embed_enum_bwd(const void* args_, void* stream) {
+  const BertEmbedEnumBwdArgs& a = *(const BertEmbedEnumBwdArgs*)args_;
+  CTDD_REQUIRE((a.x64 || a.x32) && a.g && a.dw && a.db, CTDD_EINVAL, "bert embed enum bwd: null buffer");
+  CTDD_REQUIRE(a.E >= 1 && a.S >= 2 && a.D >= 1 && a.B >= 1 && a.cond >= 0 && a.cond < a.D && a.rows >= 1, CTDD_EINVAL,
+               "bert embed enum bwd: E=%d S=%d D=%d B=%d cond=%d rows=%d", a.E, a.S, a.D, a.B, a.cond, a.rows);
+  const int64_t total = (int64_t)a.B * (a.D - a.cond);
+  CTDD_REQUIRE(a.r0 >= 0 && a.r0 + a.rows <= total && total <= INT32_MAX && (int64_t)a.rows * a.D <= INT32_MAX, CTDD_ERANGE,
+               "bert embed enum bwd: window [%lld, +%d) of %lld sequences", (long long)a.r0, a.rows, (long long)total);
+  const int nsub = a.E < 256 ? 256 / a.E : 1;
+  int64_t gx = ((int64_t)a.rows * a.D + 32 * nsub - 1) / (32 * nsub);          // >= 32 token rows per thread, at most 256 workgroups
+  gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
+  hipLaunchKernelGGL(k_bert_embed_enum_bwd, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, a);
+  return finish_launch("k_bert_embed_enum_bwd");
+}
+
+extern "C" int ctdd_bert_gather_enum_bwd(const float* d_out, int64_t r0, int rows, int B, int D, int cond, int E, float* d_enc, void* stream) {
+  CTDD_REQUIRE(d_out && d_enc && B > 0 && D > 0 && E > 0 && rows > 0 && cond >= 0 && cond < D, CTDD_EINVAL, "bert gather enum bwd: bad arguments");
+  CTDD_REQUIRE(r0 >= 0 && r0 + rows <= (int64_t)B * (D - cond), CTDD_ERANGE, "bert gather enum bwd: window [%lld, +%d) of %lld sequences",
+               (long long)r0, rows, (long long)B * (D - cond));
+  const int64_t nrows = (int64_t)rows * (D + 1);
+  CTDD_REQUIRE((nrows + 3) / 4 <= INT32_MAX, CTDD_ERANGE, "bert gather enum bwd: %lld rows", (long long)nrows);
+  hipLaunchKernelGGL(k_bert_gather_enum_bwd, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_out, r0, nrows, D, cond, E, d_enc);
+  return finish_launch("k_bert_gather_enum_bwd");
 }
 
 extern "C" int ctdd_bert_attention_short(const void* args_, void* stream) {

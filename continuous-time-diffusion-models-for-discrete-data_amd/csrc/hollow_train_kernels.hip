@@ -6,6 +6,7 @@
 //   LayerNorm (+ add, + FiLM) backward      k_hollow_ln_bwd<KN>   four rows in flight per wave; dgamma / dbeta through LDS into replicated accumulators
 //   attention, fp32 FMA (parity mode)       k_hollow_attn_train (thread = query, online softmax, writes (max, sum) per query),
 //                                           k_hollow_attn_bwd_q (thread = query: D_i = dO.O, dQ), k_hollow_attn_bwd_kv (thread = key: dK, dV)
+//   attention, fp32, T <= 64, hd 4 / 8      k_bert_attn_short_train, k_bert_attn_short_bwd (mode 3: one wave per (sequence, head), operands in LDS)
 //   attention, matrix cores (bf16 mode)     k_hollow_attn_q_mfma<HD, BWD, NW> (forward / dQ), k_hollow_attn_kv_mfma<HD, NW> (dK, dV)
 //                                           -- no atomics, the scores are recomputed in both backward kernels; the same dropout masks
 //   ReLU / GELU (+ dropout)                 k_hollow_act (fp32), k_hollow_relu_bf16 (the bf16-only MLP hidden tensor)
@@ -515,6 +516,213 @@ __global__ __launch_bounds__(TQ) void k_hollow_attn_bwd_kv(const AttnTrainArgs a
     float* ov = a.dv + (size_t)b * a.dv_bs + (size_t)j * a.dv_rs + h * HD;
 #pragma unroll
     for (int c = 0; c < HD; ++c) { ok_[c] = dk[c]; ov[c] = dv[c]; }          // (Qs holds scale q: dK = sum dS (scale q))
+  }
+}
+
+// ============================================================================ unmasked training attention for short sequences
+// Tq == Tk = T <= 64, head dimensions 4 and 8 (ctdd_bert.h: the masked model's T = D + 1 = 33 sequences, where the kernels above
+// run 128-thread workgroups with 33 live lanes).  One wave owns one (sequence, head) pair, SHORT_NW pairs per workgroup, the
+// pair's operands resident in LDS as [row][HD] and read as wave-uniform float4s (one address per instruction: a broadcast, no
+// bank conflicts); the contract, the stats rows and the Philox keep bits are those of the kernels above.
+constexpr int SHORT_NW = 4;
+// keep bits of query i of pair (b, h): bit j = attn_keep(a, b, h, i, j), one Philox block per eight keys
+__device__ inline uint64_t short_keep_row(const AttnTrainArgs& a, int b, int h, int i) {
+  const int octs = (a.Tk + 7) / 8;
+  const uint64_t base = (((uint64_t)b * a.H + h) * a.Tq + i) * (uint64_t)octs, seed = a.rng[0], ctr = a.rng[1] * 4096u + a.layer;
+  const unsigned thr = attn_thr(a.drop_p);
+  uint64_t bits = 0;
+  for (int o = 0; o < octs; ++o) bits |= (uint64_t)keep8v(seed, ctr, base + o, thr) << (8 * o);
+  return bits;
+}
+template <int HD>
+__global__ __launch_bounds__(64 * SHORT_NW) void k_bert_attn_short_train(const AttnTrainArgs a) {
+  __shared__ __attribute__((aligned(16))) float Ks[SHORT_NW][64 * HD];
+  __shared__ __attribute__((aligned(16))) float Vs[SHORT_NW][64 * HD];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, T = a.Tq;
+  const int64_t pair = (int64_t)blockIdx.x * SHORT_NW + wave;
+  const bool live = pair < (int64_t)a.B * a.H;
+  const int b = live ? (int)(pair / a.H) : 0, h = live ? (int)(pair % a.H) : 0;
+  const int T4 = (T + 3) & ~3;                                  // keys are consumed four at a time: rows T .. T4 - 1 hold zeros
+  if (live) {
+    for (int idx = lane; idx < T4 * (HD / 4); idx += 64) {
+      const int j = idx / (HD / 4), c4 = idx % (HD / 4);
+      float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
+      if (j < T) {
+        kv = *(const float4*)(a.k + (size_t)b * a.k_bs + (size_t)j * a.k_rs + h * HD + c4 * 4);
+        vv = *(const float4*)(a.v + (size_t)b * a.v_bs + (size_t)j * a.v_rs + h * HD + c4 * 4);
+      }
+      *(float4*)(&Ks[wave][j * HD + c4 * 4]) = kv;
+      *(float4*)(&Vs[wave][j * HD + c4 * 4]) = vv;
+    }
+  }
+  __syncthreads();                                              // (the only barrier: nothing below is shared between waves)
+  const int i = lane;
+  if (!live || i >= T) return;
+  float qv[HD], acc[HD];
+  const float* qr = a.q + (size_t)b * a.q_bs + (size_t)i * a.q_rs + h * HD;
+#pragma unroll
+  for (int c = 0; c < HD; c += 4) {
+    const float4 u = *(const float4*)(qr + c);
+    qv[c] = u.x * a.scale; qv[c + 1] = u.y * a.scale; qv[c + 2] = u.z * a.scale; qv[c + 3] = u.w * a.scale;
+    acc[c] = acc[c + 1] = acc[c + 2] = acc[c + 3] = 0.0f;
+  }
+  const bool drop = a.drop_p > 0.0f;
+  const float inv_keep = attn_inv_keep(a.drop_p);
+  const uint64_t keep = drop ? short_keep_row(a, b, h, i) : ~0ull;
+  float m = -INFINITY, l = 0.0f;
+  for (int jj = 0; jj < T4; jj += 4) {
+    float s[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float* kr = &Ks[wave][(jj + u) * HD];
+      float d = 0.0f;
+#pragma unroll
+      for (int c = 0; c < HD; c += 4) {
+        const float4 kv = *(const float4*)(kr + c);
+        d = fmaf(qv[c], kv.x, d); d = fmaf(qv[c + 1], kv.y, d); d = fmaf(qv[c + 2], kv.z, d); d = fmaf(qv[c + 3], kv.w, d);
+      }
+      s[u] = jj + u < T ? d : -INFINITY;
+    }
+    const float mn = fmaxf(fmaxf(m, fmaxf(s[0], s[1])), fmaxf(s[2], s[3]));      // (finite: key jj exists)
+    const float corr = expf(m - mn);
+    float p[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) p[u] = expf(s[u] - mn);
+    l = l * corr + ((p[0] + p[1]) + (p[2] + p[3]));
+#pragma unroll
+    for (int c = 0; c < HD; ++c) acc[c] *= corr;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float pd = drop ? (((keep >> (jj + u)) & 1ull) ? p[u] * inv_keep : 0.0f) : p[u];
+      const float* vr = &Vs[wave][(jj + u) * HD];
+#pragma unroll
+      for (int c = 0; c < HD; c += 4) {
+        const float4 vv = *(const float4*)(vr + c);
+        acc[c] = fmaf(pd, vv.x, acc[c]); acc[c + 1] = fmaf(pd, vv.y, acc[c + 1]);
+        acc[c + 2] = fmaf(pd, vv.z, acc[c + 2]); acc[c + 3] = fmaf(pd, vv.w, acc[c + 3]);
+      }
+    }
+    m = mn;
+  }
+  const float inv = 1.0f / l;
+  float* o = a.out + ((size_t)b * T + i) * a.out_rs + h * HD;
+#pragma unroll
+  for (int c = 0; c < HD; c += 4) *(float4*)(o + c) = make_float4(acc[c] * inv, acc[c + 1] * inv, acc[c + 2] * inv, acc[c + 3] * inv);
+  float* st = a.stats + (((size_t)b * a.H + h) * T + i) * 4;
+  st[0] = m; st[1] = l;
+}
+// The whole backward in one launch: lane = query stages its scaled q_i, dO_i, (max, 1 / sum, D_i = dO_i . O_i) and its keep
+// bits next to the pair's K and V; then lane = query walks the keys (dQ_i), then lane = key walks the staged queries (dK_j, dV_j)
+// with the keep bits of the first pass.  No atomics; stats[2] receives D_i as in k_hollow_attn_bwd_q.
+template <int HD>
+__global__ __launch_bounds__(64 * SHORT_NW) void k_bert_attn_short_bwd(const AttnTrainArgs a) {
+  __shared__ __attribute__((aligned(16))) float Qs[SHORT_NW][64 * HD];
+  __shared__ __attribute__((aligned(16))) float Ds[SHORT_NW][64 * HD];
+  __shared__ __attribute__((aligned(16))) float Ks[SHORT_NW][64 * HD];
+  __shared__ __attribute__((aligned(16))) float Vs[SHORT_NW][64 * HD];
+  __shared__ __attribute__((aligned(16))) float St[SHORT_NW][64 * 4];     // max, 1 / sum, D_i, spare
+  __shared__ __attribute__((aligned(8))) uint2 Kp[SHORT_NW][64];          // keep bits of query i: keys 0..31, 32..63
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, T = a.Tq;
+  const int64_t pair = (int64_t)blockIdx.x * SHORT_NW + wave;
+  const bool live = pair < (int64_t)a.B * a.H;
+  const int b = live ? (int)(pair / a.H) : 0, h = live ? (int)(pair % a.H) : 0;
+  const bool ok = live && lane < T;                             // lane is a query of the first pass and a key of the second
+  const bool drop = a.drop_p > 0.0f;
+  const float inv_keep = attn_inv_keep(a.drop_p);
+  float qv[HD], dO[HD], kv[HD], vv[HD];
+  float m = 0.0f, il = 0.0f, Di = 0.0f;
+  uint64_t keep = ~0ull;
+  if (ok) {
+    const float* qr = a.q + (size_t)b * a.q_bs + (size_t)lane * a.q_rs + h * HD;
+    const float* kr = a.k + (size_t)b * a.k_bs + (size_t)lane * a.k_rs + h * HD;
+    const float* vr = a.v + (size_t)b * a.v_bs + (size_t)lane * a.v_rs + h * HD;
+    const float* dr = a.d_out + ((size_t)b * T + lane) * a.out_rs + h * HD;
+    const float* orow = a.out + ((size_t)b * T + lane) * a.out_rs + h * HD;
+#pragma unroll
+    for (int c = 0; c < HD; c += 4) {
+      const float4 q4 = *(const float4*)(qr + c), k4 = *(const float4*)(kr + c), v4 = *(const float4*)(vr + c), d4 = *(const float4*)(dr + c),
+                   o4 = *(const float4*)(orow + c);
+      qv[c] = q4.x * a.scale; qv[c + 1] = q4.y * a.scale; qv[c + 2] = q4.z * a.scale; qv[c + 3] = q4.w * a.scale;
+      kv[c] = k4.x; kv[c + 1] = k4.y; kv[c + 2] = k4.z; kv[c + 3] = k4.w;
+      vv[c] = v4.x; vv[c + 1] = v4.y; vv[c + 2] = v4.z; vv[c + 3] = v4.w;
+      dO[c] = d4.x; dO[c + 1] = d4.y; dO[c + 2] = d4.z; dO[c + 3] = d4.w;
+      Di = fmaf(d4.x, o4.x, Di); Di = fmaf(d4.y, o4.y, Di); Di = fmaf(d4.z, o4.z, Di); Di = fmaf(d4.w, o4.w, Di);
+      *(float4*)(&Qs[wave][lane * HD + c]) = make_float4(qv[c], qv[c + 1], qv[c + 2], qv[c + 3]);
+      *(float4*)(&Ds[wave][lane * HD + c]) = d4;
+      *(float4*)(&Ks[wave][lane * HD + c]) = k4;
+      *(float4*)(&Vs[wave][lane * HD + c]) = v4;
+    }
+    float* st = a.stats + (((size_t)b * a.H + h) * T + lane) * 4;
+    m = st[0]; il = 1.0f / st[1];
+    st[2] = Di;
+    if (drop) keep = short_keep_row(a, b, h, lane);
+    *(float4*)(&St[wave][lane * 4]) = make_float4(m, il, Di, 0.0f);
+    Kp[wave][lane] = make_uint2((unsigned)keep, (unsigned)(keep >> 32));
+  }
+  __syncthreads();                                              // (the only barrier: nothing below is shared between waves)
+  if (!ok) return;
+  // ---- lane = query i:  dQ_i = scale sum_j dS_ij k_j,  dS_ij = p_ij (keep_ij / (1 - p) dO_i . v_j - D_i)
+  float dq[HD];
+#pragma unroll
+  for (int c = 0; c < HD; ++c) dq[c] = 0.0f;
+  for (int j = 0; j < T; ++j) {
+    const float* kr = &Ks[wave][j * HD];
+    const float* vr = &Vs[wave][j * HD];
+    float kj[HD];
+    float s = 0.0f, dp = 0.0f;
+#pragma unroll
+    for (int c = 0; c < HD; c += 4) {
+      const float4 k4 = *(const float4*)(kr + c), v4 = *(const float4*)(vr + c);
+      kj[c] = k4.x; kj[c + 1] = k4.y; kj[c + 2] = k4.z; kj[c + 3] = k4.w;
+      s = fmaf(qv[c], k4.x, s); s = fmaf(qv[c + 1], k4.y, s); s = fmaf(qv[c + 2], k4.z, s); s = fmaf(qv[c + 3], k4.w, s);
+      dp = fmaf(dO[c], v4.x, dp); dp = fmaf(dO[c + 1], v4.y, dp); dp = fmaf(dO[c + 2], v4.z, dp); dp = fmaf(dO[c + 3], v4.w, dp);
+    }
+    const float p = expf(s - m) * il;
+    if (drop) dp = ((keep >> j) & 1ull) ? dp * inv_keep : 0.0f;
+    const float ds = p * (dp - Di) * a.scale;
+#pragma unroll
+    for (int c = 0; c < HD; ++c) dq[c] = fmaf(ds, kj[c], dq[c]);
+  }
+  {
+    float* o = a.dq + (size_t)b * a.dq_bs + (size_t)lane * a.dq_rs + h * HD;
+#pragma unroll
+    for (int c = 0; c < HD; c += 4) *(float4*)(o + c) = make_float4(dq[c], dq[c + 1], dq[c + 2], dq[c + 3]);
+  }
+  // ---- lane = key j:  dV_j = sum_i p_ij keep_ij / (1 - p) dO_i,  dK_j = sum_i dS_ij (scale q_i)
+  float dk[HD], dv[HD];
+#pragma unroll
+  for (int c = 0; c < HD; ++c) { dk[c] = 0.0f; dv[c] = 0.0f; }
+  for (int i = 0; i < T; ++i) {
+    const float* qr = &Qs[wave][i * HD];
+    const float* dr = &Ds[wave][i * HD];
+    const float4 st = *(const float4*)(&St[wave][i * 4]);
+    float qi[HD], di[HD];
+    float s = 0.0f, dp = 0.0f;
+#pragma unroll
+    for (int c = 0; c < HD; c += 4) {
+      const float4 q4 = *(const float4*)(qr + c), d4 = *(const float4*)(dr + c);
+      qi[c] = q4.x; qi[c + 1] = q4.y; qi[c + 2] = q4.z; qi[c + 3] = q4.w;
+      di[c] = d4.x; di[c + 1] = d4.y; di[c + 2] = d4.z; di[c + 3] = d4.w;
+      s = fmaf(q4.x, kv[c], s); s = fmaf(q4.y, kv[c + 1], s); s = fmaf(q4.z, kv[c + 2], s); s = fmaf(q4.w, kv[c + 3], s);
+      dp = fmaf(d4.x, vv[c], dp); dp = fmaf(d4.y, vv[c + 1], dp); dp = fmaf(d4.z, vv[c + 2], dp); dp = fmaf(d4.w, vv[c + 3], dp);
+    }
+    const float p = expf(s - st.x) * st.y;
+    float pk = p;
+    if (drop) {
+      const uint2 kb = Kp[wave][i];
+      const bool kp = ((lane < 32 ? kb.x >> lane : kb.y >> (lane - 32)) & 1u) != 0u;
+      pk = kp ? p * inv_keep : 0.0f; dp = kp ? dp * inv_keep : 0.0f;
+    }
+    const float ds = p * (dp - st.z);
+#pragma unroll
+    for (int c = 0; c < HD; ++c) { dv[c] = fmaf(pk, di[c], dv[c]); dk[c] = fmaf(ds, qi[c], dk[c]); }
+  }
+  float* ok_ = a.dk + (size_t)b * a.dk_bs + (size_t)lane * a.dk_rs + h * HD;
+  float* ov = a.dv + (size_t)b * a.dv_bs + (size_t)lane * a.dv_rs + h * HD;
+#pragma unroll
+  for (int c = 0; c < HD; c += 4) {
+    *(float4*)(ok_ + c) = make_float4(dk[c], dk[c + 1], dk[c + 2], dk[c + 3]);
+    *(float4*)(ov + c) = make_float4(dv[c], dv[c + 1], dv[c + 2], dv[c + 3]);
   }
 }
 
@@ -1117,6 +1325,39 @@ extern "C" int ctdd_hollow_attention_bwd(const void* args_, void* stream) {
 }
 #undef HD_DISPATCH
 #undef HD_DISPATCH_
+
+// short sequences (ctdd_bert.h): mode 3, Tq == Tk <= 64, head dimension 4 or 8, rows of whole 16-byte pieces
+static int attn_check_short(const AttnTrainArgs& a) {
+  if (int rc = attn_check(a)) return rc;
+  CTDD_REQUIRE(a.mode == 3 && a.Tq == a.Tk && a.Tq >= 1 && a.Tq <= 64 && a.B > 0 && a.H > 0, CTDD_EINVAL,
+               "short attention (training): mode %d (3) with Tq=%d Tk=%d (equal, <= 64)", a.mode, a.Tq, a.Tk);
+  CTDD_REQUIRE(a.hd == 4 || a.hd == 8, CTDD_ERANGE, "short attention (training): head dimension %d (4 or 8)", a.hd);
+  CTDD_REQUIRE((int64_t)a.B * a.H <= (int64_t)SHORT_NW * INT32_MAX, CTDD_ERANGE, "short attention (training): %lld pairs", (long long)a.B * a.H);
+  auto al16 = [](const void* p_) { return ((uintptr_t)p_ & 15) == 0; };
+  CTDD_REQUIRE(a.q_rs % 4 == 0 && a.k_rs % 4 == 0 && a.v_rs % 4 == 0 && a.out_rs % 4 == 0 && a.q_bs % 4 == 0 && a.k_bs % 4 == 0 && a.v_bs % 4 == 0 &&
+               al16(a.q) && al16(a.k) && al16(a.v) && al16(a.out) && al16(a.stats), CTDD_EINVAL, "short attention (training): rows must be 16-byte aligned");
+  return CTDD_OK;
+}
+extern "C" int ctdd_bert_attention_short_train(const void* args_, void* stream) {
+  const AttnTrainArgs& a = *(const AttnTrainArgs*)args_;
+  if (int rc = attn_check_short(a)) return rc;
+  const dim3 grid((unsigned)(((int64_t)a.B * a.H + SHORT_NW - 1) / SHORT_NW));
+  if (a.hd == 4) hipLaunchKernelGGL(k_bert_attn_short_train<4>, grid, dim3(64 * SHORT_NW), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_bert_attn_short_train<8>, grid, dim3(64 * SHORT_NW), 0, (hipStream_t)stream, a);
+  return finish_launch("k_bert_attn_short_train");
+}
+extern "C" int ctdd_bert_attention_short_bwd(const void* args_, void* stream) {
+  const AttnTrainArgs& a = *(const AttnTrainArgs*)args_;
+  if (int rc = attn_check_short(a)) return rc;
+  auto al16 = [](const void* p_) { return ((uintptr_t)p_ & 15) == 0; };
+  CTDD_REQUIRE(a.d_out && a.dq && a.dk && a.dv, CTDD_EINVAL, "short attention bwd: null gradient buffer");
+  CTDD_REQUIRE(a.dq_rs % 4 == 0 && a.dk_rs % 4 == 0 && a.dv_rs % 4 == 0 && a.dq_bs % 4 == 0 && a.dk_bs % 4 == 0 && a.dv_bs % 4 == 0 && al16(a.d_out) &&
+               al16(a.dq) && al16(a.dk) && al16(a.dv), CTDD_EINVAL, "short attention bwd: gradient rows must be 16-byte aligned");
+  const dim3 grid((unsigned)(((int64_t)a.B * a.H + SHORT_NW - 1) / SHORT_NW));
+  if (a.hd == 4) hipLaunchKernelGGL(k_bert_attn_short_bwd<4>, grid, dim3(64 * SHORT_NW), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_bert_attn_short_bwd<8>, grid, dim3(64 * SHORT_NW), 0, (hipStream_t)stream, a);
+  return finish_launch("k_bert_attn_short_bwd");
+}
 
 constexpr int ATT_NW = CTDD_ATT_NW;
 #define HD_LAUNCH_MFMA(KERNEL16, KERNEL32, GRIDX)                                                                     \

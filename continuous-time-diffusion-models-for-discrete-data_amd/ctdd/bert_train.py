@@ -12,7 +12,8 @@ the hollow transformer's: every operation a libctdd launch, autograd as the tape
 
 Precisions as there: "fp32" (parity mode) and "bf16" (default; head dimensions 16 and 32 run the matrix-core attention, 4 and 8
 the fp32 kernels).  Dropout masks are Philox(seed, step, layer, element); every training forward carries its own {seed, step}.
-The masked (enumerative) model has no training kernels: `training_supported` is false for it.
+The masked (enumerative) model trains on ctdd/masked_train.py (cfg.model.engine_train = "hip-masked"): `training_supported` here
+is false for it.
 """
 import ctypes as C
 

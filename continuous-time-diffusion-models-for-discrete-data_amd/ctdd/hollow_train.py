@@ -67,6 +67,7 @@ def lib():
         for name, argt in (("ctdd_hollow_layernorm_bwd", [_P, _P]), ("ctdd_hollow_attention_train", [_P, _P]),
                            ("ctdd_hollow_attention_bwd", [_P, _P]), ("ctdd_hollow_attention_train_bf16", [_P, _P]),
                            ("ctdd_hollow_attention_bwd_bf16", [_P, _P]),
+                           ("ctdd_bert_attention_short_train", [_P, _P]), ("ctdd_bert_attention_short_bwd", [_P, _P]),
                            ("ctdd_hollow_act", [_P, _P, _P, _P, _I64, _I, _F, _P, _U64, _P]), ("ctdd_hollow_embed_bwd", [_P, _P]),
                            ("ctdd_hollow_relu_bf16", [_P, _P, _P, _I64, _F, _P, _U64, _P]),
                            ("ctdd_hollow_colsum", [_P, _P, _I64, _I, _I, _P, _I, _I, _P]),
@@ -296,8 +297,13 @@ def _attn_args(q, k, v, B, Tq, Tk, H, hd, mode, drop_p, rng, layer):
     return a
 
 
-def _attention_fwd(q, k, v, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16):
-    """-> (ctx fp32 (B*Tq, E), bf16 copy or None, stats)."""
+def short_attention_applies(Tq, Tk, hd, mode):
+    """The shapes ctdd_bert_attention_short_train / _bwd take (include/ctdd_bert.h)."""
+    return mode == 3 and Tq == Tk and Tq <= 64 and hd in (4, 8)
+
+
+def _attention_fwd(q, k, v, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16, short=False):
+    """-> (ctx fp32 (B*Tq, E), bf16 copy or None, stats).  short: the short-sequence fp32 kernels (short_attention_applies)."""
     E = H * hd
     dev = q.device
     out = torch.empty((B * Tq, E), dtype=torch.float32, device=dev)
@@ -309,11 +315,14 @@ def _attention_fwd(q, k, v, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16):
         a.out_bf16 = out_hi.data_ptr()
         _ck(lib().ctdd_hollow_attention_train_bf16(C.byref(a), _st()), "ctdd_hollow_attention_train_bf16")
         return out, out_hi, stats
-    _ck(lib().ctdd_hollow_attention_train(C.byref(a), _st()), "ctdd_hollow_attention_train")
+    if short:
+        _ck(lib().ctdd_bert_attention_short_train(C.byref(a), _st()), "ctdd_bert_attention_short_train")
+    else:
+        _ck(lib().ctdd_hollow_attention_train(C.byref(a), _st()), "ctdd_hollow_attention_train")
     return out, (_cast(out, B * Tq, E, E, True) if bf16 else None), stats
 
 
-def _attention_bwd(q, k, v, out, stats, dout, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16, want_f32=True):
+def _attention_bwd(q, k, v, out, stats, dout, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16, want_f32=True, short=False):
     """-> (dq, dk, dv) fp32 (dqkv, None, None for packed rows) and their bf16 copies when the matrix-core kernels ran."""
     E = H * hd
     mfma = bf16 and hd in (16, 32)
@@ -341,6 +350,8 @@ def _attention_bwd(q, k, v, out, stats, dout, B, Tq, Tk, H, hd, mode, drop_p, rn
             a.dq_bf16, a.dk_bf16, a.dv_bf16 = (t.data_ptr() for t in hi)
     if mfma:
         _ck(lib().ctdd_hollow_attention_bwd_bf16(C.byref(a), _st()), "ctdd_hollow_attention_bwd_bf16")
+    elif short:
+        _ck(lib().ctdd_bert_attention_short_bwd(C.byref(a), _st()), "ctdd_bert_attention_short_bwd")
     else:
         _ck(lib().ctdd_hollow_attention_bwd(C.byref(a), _st()), "ctdd_hollow_attention_bwd")
     return grads, hi
@@ -436,37 +447,39 @@ class AttentionFn(torch.autograd.Function):
     self-attention: qkv (B*T, 3E) with k = None;  readout: q (B*Tq, E), k, v (B*Tk, E)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16=False):
+    def forward(ctx, q, k, v, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16=False, short=False):
         q = q.contiguous()
         if k is not None:
             k, v = k.contiguous(), v.contiguous()
-        out, _, stats = _attention_fwd(q, k, v, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16)
+        out, _, stats = _attention_fwd(q, k, v, B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16, short=short)
         ctx.save_for_backward(q, k, v, out, stats, rng)
-        ctx.meta = (B, Tq, Tk, H, hd, mode, float(drop_p), int(layer), bf16)
+        ctx.meta = (B, Tq, Tk, H, hd, mode, float(drop_p), int(layer), bf16, bool(short))
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, stats, rng = ctx.saved_tensors
-        B, Tq, Tk, H, hd, mode, drop_p, layer, bf16 = ctx.meta
-        grads, _ = _attention_bwd(q, k, v, out, stats, dout.contiguous(), B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16)
-        return grads + (None,) * 10
+        B, Tq, Tk, H, hd, mode, drop_p, layer, bf16, short = ctx.meta
+        grads, _ = _attention_bwd(q, k, v, out, stats, dout.contiguous(), B, Tq, Tk, H, hd, mode, drop_p, rng, layer, bf16, short=short)
+        return grads + (None,) * 11
 
 
 class AttnBlockFn(torch.autograd.Function):
     """h + dropout(out_proj(attention(in_proj(LayerNorm(h))))): one prenorm self-attention block (hollow_networks.py:311-340)
     with a hand-scheduled backward: bf16 operand copies come out of the producing kernels, the residual stream's gradient
-    is accumulated by the LayerNorm backward."""
+    is accumulated by the LayerNorm backward.  meta may carry a 14th element: True asks for the short-sequence attention
+    kernels (short_attention_applies; masked_train.MaskedTrainer) -- absent or False, the kernels are the generic ones."""
 
     @staticmethod
     def forward(ctx, h, ln_w, ln_b, w_in, b_in, w_out, b_out, rng, meta):
-        B, D, H, hd, mode, p_att, p_drop, l_att, l_drop, bf16, eps, pk_in, pk_out = meta
+        B, D, H, hd, mode, p_att, p_drop, l_att, l_drop, bf16, eps, pk_in, pk_out = meta[:13]
+        short = len(meta) > 13 and bool(meta[13])
         E, R = H * hd, B * D
         h = h.contiguous()
         z, z_hi = _layernorm(h, None, ln_w, ln_b, None, eps, want_f32=not bf16, want_hi=bf16)
         z_op = (z_hi if bf16 else z).view(R, E)
         qkv, _ = _gemm(z_op, pk_in[0], b_in.detach(), None, R, E, 3 * E, bf16)
-        att, att_hi, stats = _attention_fwd(qkv, None, None, B, D, D, H, hd, mode, p_att, rng if p_att > 0 else None, l_att, bf16)
+        att, att_hi, stats = _attention_fwd(qkv, None, None, B, D, D, H, hd, mode, p_att, rng if p_att > 0 else None, l_att, bf16, short=short)
         att_op = att_hi if bf16 else att
         if p_drop > 0.0 and not _gemm_fusable(E, E, bf16):
             o, _ = _gemm(att_op, pk_out[0], b_out.detach(), None, R, E, E, bf16)
@@ -480,7 +493,8 @@ class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         h, ln_w, ln_b, w_in, w_out, z_op, qkv, att, att_op, stats, rng = ctx.saved_tensors
-        B, D, H, hd, mode, p_att, p_drop, l_att, l_drop, bf16, eps, pk_in, pk_out = ctx.meta
+        B, D, H, hd, mode, p_att, p_drop, l_att, l_drop, bf16, eps, pk_in, pk_out = ctx.meta[:13]
+        short = len(ctx.meta) > 13 and bool(ctx.meta[13])
         E, R = H * hd, B * D
         dout = dout.contiguous()
         zw_out, zb_out, zw_in, zb_in, rep = _zeros(dout.device, (E, E), (COLSUM_REPLICAS, E), (3 * E, E), (COLSUM_REPLICAS, 3 * E), (LN_REPLICAS, 2 * E))
@@ -490,7 +504,7 @@ class AttnBlockFn(torch.autograd.Function):
             do, do_hi = (_dropout(dout.view(R, E), p_drop, rng, l_drop)[0] if p_drop > 0.0 else dout.view(R, E)), None
         datt, dw_out, db_out = _linear_bwd(att_op, w_out, do, R, bf16, True, dy_hi=do_hi, wt=pk_out[1], bufs=(zw_out, zb_out))
         (dqkv, _, _), hi = _attention_bwd(qkv, None, None, att, stats, datt, B, D, D, H, hd, mode, p_att, rng if p_att > 0 else None, l_att, bf16,
-                                          want_f32=False)
+                                          want_f32=False, short=short)
         dz, dw_in, db_in = _linear_bwd(z_op, w_in, dqkv, R, bf16, True, dy_hi=hi[0], wt=pk_in[1], bufs=(zw_in, zb_in))
         dh, dg, dbeta, _ = _layernorm_bwd(h, None, ln_w, ln_b, None, eps, dz.view(B, D, E), dres=dout, rep=rep)
         return dh, dg, dbeta, dw_in, db_in, dw_out, db_out, None, None

@@ -88,7 +88,9 @@ UNET_TRAIN_EXPORTS = ("ctdd_unet_wgrad", "ctdd_unet_gn_bwd", "ctdd_unet_dropout"
 HOLLOW_TRAIN_EXPORTS = ("ctdd_hollow_layernorm_bwd", "ctdd_hollow_attention_train", "ctdd_hollow_attention_bwd", "ctdd_hollow_attention_train_bf16", "ctdd_hollow_attention_bwd_bf16", "ctdd_hollow_act", "ctdd_hollow_relu_bf16", "ctdd_hollow_colsum", "ctdd_hollow_dropout",
                         "ctdd_hollow_embed_bwd")                                       # bound in ctdd/hollow_train.py
 BERT_EXPORTS = ("ctdd_bert_embed", "ctdd_bert_gather", "ctdd_bert_attention_short",                               # bound in ctdd/bert_engine.py
-                "ctdd_bert_embed_bwd", "ctdd_bert_gather_bwd")                                                    # bound in ctdd/bert_train.py
+                "ctdd_bert_embed_bwd", "ctdd_bert_gather_bwd",                                                    # bound in ctdd/bert_train.py
+                "ctdd_bert_embed_enum_bwd", "ctdd_bert_gather_enum_bwd",                                          # bound in ctdd/masked_train.py
+                "ctdd_bert_attention_short_train", "ctdd_bert_attention_short_bwd")                               # bound in ctdd/hollow_train.py
 EXPORTS = tuple(_SIGS) + UNET_EXPORTS + HOLLOW_EXPORTS + UNET_TRAIN_EXPORTS + HOLLOW_TRAIN_EXPORTS + BERT_EXPORTS
 
 

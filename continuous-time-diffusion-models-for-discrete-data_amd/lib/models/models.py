@@ -270,7 +270,8 @@ class _EncoderModel(nn.Module):
     EnumerativeTransformer).  Inference under eval() / no_grad runs the HIP plan of ctdd/bert_engine.py.  With gradients enabled
     or in train mode the autograd module runs -- one RuntimeWarning per model unless cfg.model.engine_train == "torch" says that
     this is meant -- except under cfg.model.engine_train == "hip-encoder", which trains the x0-prediction model on the HIP
-    kernels of ctdd/bert_train.py (the masked models have no training kernels: one RuntimeWarning, then the module)."""
+    kernels of ctdd/bert_train.py, and "hip-masked", which trains the masked model on those of ctdd/masked_train.py.  Each
+    value covers its own family only: on the other one, or outside the kernels' coverage, one RuntimeWarning, then the module."""
 
     _net_class = None
     _engine_int32_states = True          # forward() takes the samplers' int32 states as they are
@@ -286,10 +287,14 @@ class _EncoderModel(nn.Module):
     def forward(self, x, times):
         mode = self._use_engine(x)
         if mode == "train":
-            from ctdd import bert_train
             if self._trainer is None:
                 # cfg.model.engine_train_precision: "bf16" (default) or "fp32", as for the hollow transformer
-                self._trainer = bert_train.BertTrainer(self)
+                if getattr(self.cfg.model, "engine_train", "hip") == "hip-masked":
+                    from ctdd import masked_train
+                    self._trainer = masked_train.MaskedTrainer(self)
+                else:
+                    from ctdd import bert_train
+                    self._trainer = bert_train.BertTrainer(self)
             inner = unwrap(self.net)
             inner._engine_hook = self._trainer          # through DistributedDataParallel.forward when wrapped
             try:
@@ -318,6 +323,12 @@ class _EncoderModel(nn.Module):
                     return "train"
                 _warn_once(self, "bert-train-encoder", "this network, shape or state dtype is outside the HIP encoder training kernels' "
                                                        "coverage (x0-prediction models only); training runs on torch device ops")
+            elif engine_train == "hip-masked":
+                from ctdd import masked_train
+                if isinstance(self, MaskedModel) and x.dtype in (torch.int64, torch.int32) and masked_train.training_supported(self):
+                    return "train"
+                _warn_once(self, "masked-train", "this network, readout, shape or state dtype is outside the HIP masked training kernels' "
+                                                 "coverage (masked models with the resnet readout only); training runs on torch device ops")
             elif engine_train != "torch":
                 _warn_once(self, "bert-train", "no HIP training kernels for this network; training runs on torch device ops "
                                                "(set cfg.model.engine_train = 'torch' to say so)")

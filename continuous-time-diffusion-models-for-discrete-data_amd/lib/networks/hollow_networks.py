@@ -400,6 +400,9 @@ class EnumerativeTransformer(nn.Module):
         self.transformer = MaskedTransformer(config)
 
     def forward(self, x, t):
+        hook = getattr(self, "_engine_hook", None)       # the HIP training path (ctdd/masked_train.py), entered through
+        if hook is not None:                             # this forward so a DistributedDataParallel wrapper sees the call
+            return hook(x, t)
         temb = transformer_timestep_embedding(t * self.temb_scale, self.embed_dim)
         shape = x.shape
         x = x.view(x.shape[0], -1)

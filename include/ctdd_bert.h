@@ -45,6 +45,29 @@ int ctdd_bert_embed_bwd(const void* embed_bwd_args, void* stream);
  * d_enc (B, D + 1, E), row 0 of every sequence is written as zero. */
 int ctdd_bert_gather_bwd(const float* d_out, int B, int D, int cond, int E, float* d_enc, void* stream);
 
+/* backward of ctdd_bert_embed in enumerate mode over the window [r0, r0 + rows) of the (B D') enumeration (r0 a host value; the
+ * window may cross sample borders): g (rows, D + 1, E) is the gradient of the chunk's `out`; with chunk row r = sequence
+ * (b, p) as there,  dw_in[e] += sum_{r,d} g[r][1 + d][e] xn(r, d),  db_in[e] += sum_{r,d} g[r][1 + d][e],  xn = 2 x / (S - 1) - 1
+ * with x the mask value S at d == p.  dw and db are ACCUMULATED into (one fp32 atomic per column and workgroup), so the chunks
+ * of one enumeration add up: the caller zeroes them before the first.  A window outside the enumeration: CTDD_ERANGE. */
+typedef struct {
+  const int64_t* x64; const int32_t* x32; const float* g; int B, D, E, S, cond, rows; int64_t r0; float* dw; float* db;
+} ctdd_bert_embed_enum_bwd_args;
+int ctdd_bert_embed_enum_bwd(const void* embed_enum_bwd_args, void* stream);
+
+/* backward of ctdd_bert_gather in enumerate mode over the same window: row g = r0 + r of d_out (B D', E) goes to row 1 + p of
+ * sequence r of d_enc (rows, D + 1, E); every other row of d_enc is written as zero (every element is written), and rows of
+ * d_out outside the window are never read. */
+int ctdd_bert_gather_enum_bwd(const float* d_out, int64_t r0, int rows, int B, int D, int cond, int E, float* d_enc, void* stream);
+
+/* training attention for short sequences on ctdd_hollow_attention_train / _bwd's contract (a ctdd_hollow_attn_train_args block,
+ * ctdd_hollow_train.h: same strides, same stats rows, the same Philox keep bits on equal {seed, step, layer}) for mode 3 with
+ * Tq == Tk <= 64 and head dimension 4 or 8, rows and buffers 16-byte aligned: one wave per (sequence, head) with the pair's
+ * operands resident in LDS, fp32 arithmetic, the backward one launch without atomics.  Anything else returns CTDD_EINVAL /
+ * CTDD_ERANGE and launches nothing. */
+int ctdd_bert_attention_short_train(const void* attn_train_args, void* stream);
+int ctdd_bert_attention_short_bwd(const void* attn_train_args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
