@@ -19,6 +19,7 @@
 // optionally straight in the (B, D, S) logits layout, and accumulates per-(b, channel) sum /
 // sum-of-squares for the next GroupNorm with one atomic per lane.
 #include "common.hpp"
+#include "conv_ring.hpp"
 #include <type_traits>
 
 namespace ctdd {
@@ -1173,15 +1174,9 @@ __global__ __launch_bounds__(512) void k_conv_res(const ConvArgs a) {
 // branchy body keep the accumulators in place).
 template <int BNT, int NBUF, int NW>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_conv_ring(const ConvArgs a) {
-  constexpr int BK = 16, WM = 64, MT = 2;
-  constexpr int BN = 32 * BNT, BMP = NW * WM;
-  constexpr int SP = (BMP + 2 * 34 + 31) / 32;                   // slab pieces of 32 rows >= BMP + 2*(33+1) rows
-  constexpr int SLABB = SP * 1024, BUFB = SLABB + 9 * BN * 32;
-  constexpr int OPS3 = (SP + 9 * BNT + NW - 1) / NW;             // DMA ops per wave for a 3x3 unit
-  constexpr int OPS1 = (BMP / 32 + BNT + NW - 1) / NW;           // ... for a 1x1 unit (BMP rows, one tap)
-  constexpr int DEPTH = NBUF - 1;                                // units in flight ahead of the one computed
-  static_assert(DEPTH == 1 || DEPTH == 2, "ring of two or three unit buffers");
-  static_assert(OPS3 <= 18, "at most two DMA ops per tap");
+  using G = RingS1<BNT, NBUF, NW>;
+  constexpr int BK = RING_BK, WM = G::WM, MT = G::MT, BN = G::BN, BMP = G::BMP, SP = G::SP, SLABB = G::SLABB, BUFB = G::BUFB;
+  constexpr int OPS3 = G::OPS, OPS1 = G::OPS1, DEPTH = G::DEPTH;   // DMA ops per wave for a 3x3 unit, for a 1x1 unit
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #ifdef CTDD_RES_STAMPS
   unsigned long long tentry;
@@ -1251,11 +1246,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_conv_ring(const Co
   // base plus one 32-bit per-lane offset.  Slab rows outside the tensor read clamped addresses:
   // they are only consumed under a cleared validity bit.  Column tiles that would start beyond N
   // re-read the last 32 weight rows: never written back.
-  const int rl = lane >> 1;
-  const unsigned swz16 = (unsigned)(((lane & 1) ^ ((rl >> 3) & 1)) << 4);   // byte offset of the lane's half
+  const int rl = lane >> 1;                                      // (ring_lane written out: see conv_ring.hpp)
+  const unsigned swz16 = (unsigned)RING_HALF(rl, lane & 1);      // byte offset of the lane's half
   const unsigned wlane = (unsigned)rl * (unsigned)Ktot * 2u + swz16;
   auto issue_op = [&](const Unit& un, unsigned slane, int buf, int j) {      // slane = rl * C * 2 + swz16 for un.C
-    const int nsp = un.one ? BMP / 32 : SP;
+    const int nsp = un.one ? G::SP1 : SP;
     const int total = nsp + (un.one ? BNT : 9 * BNT);
     int p = wave + NW * j;
     p = p < total ? p : total - 1;
@@ -1270,17 +1265,16 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_conv_ring(const Co
         q = q < 0 ? 0 : (q >= M ? M - 1 : q);
         src = un.src + (size_t)q * un.C * 2 + swz16;
       }
-      dst += (size_t)p * 1024;
+      dst += (size_t)p * RING_PIECE;
     } else {
       const int wp = p - nsp;                                    // = tap * BNT + t
       const int tap = wp / BNT;
       int nb = n0 + (wp - tap * BNT) * 32;
       nb = nb + 32 <= Ntot ? nb : Ntot - 32;
       src = un.wsrc + ((size_t)nb * Ktot + (size_t)tap * un.C) * 2 + wlane;
-      dst += SLABB + (size_t)wp * 1024;
+      dst += SLABB + (size_t)wp * RING_PIECE;
     }
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                     (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
+    ring_dma16(src, dst);
   };
   auto slane_of = [&](const Unit& un) { return (unsigned)rl * (unsigned)un.C * 2u + swz16; };
 
@@ -1324,10 +1318,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_conv_ring(const Co
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
     const int x = halo + wave * WM + li + (tap / 3 - 1) * Wd + (tap % 3 - 1);
-    aoff[tap] = (unsigned)(x * 32 + ((g ^ ((x >> 3) & 1)) << 4));
+    aoff[tap] = (unsigned)(x * RING_ROWB + RING_HALF(x, g));
   }
-  const unsigned aoff1 = (unsigned)((wave * WM + li) * 32 + ((g ^ ((li >> 3) & 1)) << 4));   // (wave*64 + li: bit 3 = bit 3 of li)
-  const unsigned boff = (unsigned)(SLABB + li * 32 + ((g ^ ((li >> 3) & 1)) << 4));          // weight rows: bit 3 of the row = bit 3 of li
+  const unsigned aoff1 = (unsigned)((wave * WM + li) * RING_ROWB + RING_HALF(li, g));   // (wave*64 + li: bit 3 = bit 3 of li)
+  const unsigned boff = (unsigned)(SLABB + li * RING_ROWB + RING_HALF(li, g));          // weight rows: bit 3 of the row = bit 3 of li
 
 #ifdef CTDD_RES_STAMPS
   unsigned long long tk0, tk1, tk2, tk3, tk4, dur[6] = {0, 0, 0, 0, 0, 0}, tstart;
@@ -1500,14 +1494,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_conv_ring(const Co
 // and the weight matrix, what they fetch there is only consumed under a cleared bit or never written back.
 template <int BNT, int NBUF>
 __global__ __launch_bounds__(256) void k_conv_ring_s2(const ConvArgs a) {
-  constexpr int BK = 16, NW = 4, WM = 32, MT = 1;
-  constexpr int BN = 32 * BNT, BMP = NW * WM;
-  constexpr int PP = 10, PLR = PP * 32, SP = 2 * PP;             // pieces per parity plane: 4*127 + 6*16 + 1 = 605 pixels <= 2 * 320 (W <= 16)
-  constexpr int SLABB = SP * 1024, BUFB = SLABB + 9 * BN * 32;
-  constexpr int OPS = (SP + 9 * BNT + NW - 1) / NW;              // DMA ops per wave and unit
-  constexpr int DEPTH = NBUF - 1;
-  static_assert(DEPTH == 1 || DEPTH == 2, "ring of two or three unit buffers");
-  static_assert(OPS <= 18, "at most two DMA ops per tap");
+  using G = RingS2<BNT, NBUF>;
+  constexpr int BK = RING_BK, NW = G::NW, WM = G::WM, MT = G::MT, BN = G::BN, BMP = G::BMP;
+  constexpr int PP = G::PP, PLR = G::PLR, SP = G::SP, SLABB = G::SLABB, BUFB = G::BUFB, TOTAL = G::TOTAL, OPS = G::OPS, DEPTH = G::DEPTH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1527,9 +1516,7 @@ __global__ __launch_bounds__(256) void k_conv_ring_s2(const ConvArgs a) {
   // DMA op j of this wave for unit u into ring buffer `buf`: piece = wave + 4 j (clamped: the last pieces may be issued
   // twice, same bytes to the same place).  Lane l fills LDS bytes [16 l, 16 l + 16) of the piece = row l/2, stored half l&1.
   // Slab piece p: plane p / PP, rows 32 (p % PP) .. + 31 of it = input pixels q0 + plane + 2 (32 (p % PP) + l/2).
-  const int rl = lane >> 1;
-  const unsigned swz16 = (unsigned)(((lane & 1) ^ ((rl >> 3) & 1)) << 4);   // byte offset of the lane's half
-  const unsigned wlane = (unsigned)rl * (unsigned)Ktot * 2u + swz16;
+  const RingLane dl = ring_lane(lane, Ktot);
   // The source of op j differs from unit to unit by the unit's channel offset (32 bytes) only, for slab and weight pieces
   // alike: the per-lane source pointers of unit 0 are computed once, and an op in the loop is one 64-bit add, M0 and the
   // DMA instruction (computed per op, with its branches on the piece's kind, the address arithmetic was ~30 of the ~40
@@ -1537,29 +1524,26 @@ __global__ __launch_bounds__(256) void k_conv_ring_s2(const ConvArgs a) {
   const unsigned char* opsrc[OPS];
 #pragma unroll
   for (int j = 0; j < OPS; ++j) {
-    constexpr int total = SP + 9 * BNT;
     int p = wave + NW * j;
-    p = p < total ? p : total - 1;
+    p = p < TOTAL ? p : TOTAL - 1;
     if (p < SP) {
       const int plane = p >= PP ? 1 : 0;
       const int64_t qf = q0 + plane + 64 * (p - plane * PP);     // wave-uniform first pixel of the piece
-      int64_t q = qf + 2 * rl;
+      int64_t q = qf + 2 * dl.rl;
       q = q < Min ? q : Min - 1;
-      opsrc[j] = x_base + (size_t)q * Cin * 2 + swz16;
+      opsrc[j] = x_base + (size_t)q * Cin * 2 + dl.swz16;
     } else {
       const int wp = p - SP;                                     // = tap * BNT + t
       const int tap = wp / BNT;
       int nb = n0 + (wp - tap * BNT) * 32;
       nb = nb + 32 <= Ntot ? nb : Ntot - 32;
-      opsrc[j] = w_base + ((size_t)nb * Ktot + (size_t)tap * Cin) * 2 + wlane;
+      opsrc[j] = w_base + ((size_t)nb * Ktot + (size_t)tap * Cin) * 2 + dl.wlane;
     }
   }
   auto issue_op = [&](int u, int buf, int j) {
-    constexpr int total = SP + 9 * BNT;
     int p = wave + NW * j;
-    p = p < total ? p : total - 1;
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(opsrc[j] + (size_t)u * (BK * 2)),
-                                     (void __attribute__((address_space(3)))*)(smem + (size_t)buf * BUFB + (size_t)p * 1024), 16, 0, 0);
+    p = p < TOTAL ? p : TOTAL - 1;
+    ring_dma16(opsrc[j] + (size_t)u * (BK * 2), smem + (size_t)buf * BUFB + (size_t)p * RING_PIECE);
   };
 
   f32x16 acc[MT][BNT];
@@ -1584,11 +1568,11 @@ __global__ __launch_bounds__(256) void k_conv_ring_s2(const ConvArgs a) {
   for (int tap = 0; tap < 9; ++tap) {
     const int dy = tap / 3, dx = tap % 3;
     const int r = (dx & 1) * PLR + rbase + dy * Wd + (dx >> 1);
-    aoff[tap] = (unsigned)(r * 32 + ((g ^ ((r >> 3) & 1)) << 4));
+    aoff[tap] = (unsigned)(r * RING_ROWB + RING_HALF(r, g));
     const bool ok = po < M && 2 * oy + dy < a.Hin && 2 * ox + dx < a.Win;
     vmask |= (ok ? 1u : 0u) << tap;
   }
-  const unsigned boff = (unsigned)(SLABB + li * 32 + ((g ^ ((li >> 3) & 1)) << 4));
+  const unsigned boff = (unsigned)(SLABB + li * RING_ROWB + RING_HALF(li, g));
 
   auto read_frags = [&](unsigned ao, unsigned bo, u32x4& af, u32x4 (&bf)[BNT]) {     // B first, A last: the wait for A covers the set
 #pragma unroll
@@ -1649,14 +1633,9 @@ __global__ __launch_bounds__(256) void k_conv_ring_s2(const ConvArgs a) {
 // per-lane DMA sources of unit 0 are computed once (as in k_conv_ring_s2); unit u adds its 32-byte channel offset.
 template <int BNT, int NBUF>
 __global__ __launch_bounds__(512) void k_conv_ring_up(const ConvArgs a) {
-  constexpr int BK = 16, NW = 8, WM = 64, MT = 2;
-  constexpr int BN = 32 * BNT, BMP = NW * WM;
-  constexpr int SP = (BMP + 2 * 34 + 31) / 32;                   // slab pieces of 32 rows >= BMP + 2*(33+1) rows
-  constexpr int SLABB = SP * 1024, BUFB = SLABB + 4 * BN * 32;
-  constexpr int TOTAL = SP + 4 * BNT, OPS = (TOTAL + NW - 1) / NW;   // DMA ops per wave and unit
-  constexpr int DEPTH = NBUF - 1;
-  static_assert(DEPTH == 1 || DEPTH == 2, "ring of two or three unit buffers");
-  static_assert(OPS <= 8, "at most two DMA ops per tap");
+  using G = RingUp<BNT, NBUF>;
+  constexpr int BK = RING_BK, NW = G::NW, WM = G::WM, MT = G::MT, BN = G::BN, BMP = G::BMP;
+  constexpr int SP = G::SP, SLABB = G::SLABB, BUFB = G::BUFB, TOTAL = G::TOTAL, OPS = G::OPS, DEPTH = G::DEPTH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1676,29 +1655,26 @@ __global__ __launch_bounds__(512) void k_conv_ring_up(const ConvArgs a) {
   // DMA op j of this wave: piece = wave + 8 j (clamped: the last pieces may be issued twice, same bytes to the same place).
   // Lane l fills LDS bytes [16 l, 16 l + 16) of the piece = row l/2, stored half l&1.  Slab rows outside the tensor read
   // clamped addresses: they are only consumed under a cleared validity bit.
-  const int rl = lane >> 1;
-  const unsigned swz16 = (unsigned)(((lane & 1) ^ ((rl >> 3) & 1)) << 4);   // byte offset of the lane's half
-  const unsigned wlane = (unsigned)rl * (unsigned)Ktot * 2u + swz16;
+  const RingLane dl = ring_lane(lane, Ktot);
   const unsigned char* opsrc[OPS];
 #pragma unroll
   for (int j = 0; j < OPS; ++j) {
     int p = wave + NW * j;
     p = p < TOTAL ? p : TOTAL - 1;
     if (p < SP) {
-      int64_t q = p0 - halo + p * 32 + rl;
+      int64_t q = p0 - halo + p * 32 + dl.rl;
       q = q < 0 ? 0 : (q >= M ? M - 1 : q);
-      opsrc[j] = x_base + (size_t)q * Cin * 2 + swz16;
+      opsrc[j] = x_base + (size_t)q * Cin * 2 + dl.swz16;
     } else {
       const int wp = p - SP;                                     // = tap * BNT + t
       const int tap = wp / BNT;
-      opsrc[j] = w_base + ((size_t)(n0 + (wp - tap * BNT) * 32) * Ktot + (size_t)tap * Cin) * 2 + wlane;   // (N % BN == 0: no clamp)
+      opsrc[j] = w_base + ((size_t)(n0 + (wp - tap * BNT) * 32) * Ktot + (size_t)tap * Cin) * 2 + dl.wlane;   // (N % BN == 0: no clamp)
     }
   }
   auto issue_op = [&](int u, int buf, int j) {
     int p = wave + NW * j;
     p = p < TOTAL ? p : TOTAL - 1;
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(opsrc[j] + (size_t)u * (BK * 2)),
-                                     (void __attribute__((address_space(3)))*)(smem + (size_t)buf * BUFB + (size_t)p * 1024), 16, 0, 0);
+    ring_dma16(opsrc[j] + (size_t)u * (BK * 2), smem + (size_t)buf * BUFB + (size_t)p * RING_PIECE);
   };
 
   f32x16 acc[MT][BNT];
@@ -1721,7 +1697,7 @@ __global__ __launch_bounds__(512) void k_conv_ring_up(const ConvArgs a) {
 #pragma unroll
   for (int tap = 0; tap < 4; ++tap) {
     const int x = halo + wave * WM + li + (py + (tap >> 1) - 1) * Ws + (px + (tap & 1) - 1);
-    aoff[tap] = (unsigned)(x * 32 + ((g ^ ((x >> 3) & 1)) << 4));
+    aoff[tap] = (unsigned)(x * RING_ROWB + RING_HALF(x, g));
   }
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
@@ -1735,7 +1711,7 @@ __global__ __launch_bounds__(512) void k_conv_ring_up(const ConvArgs a) {
       vmask |= (ok ? 1u : 0u) << (tap * MT + mt);
     }
   }
-  const unsigned boff = (unsigned)(SLABB + li * 32 + ((g ^ ((li >> 3) & 1)) << 4));          // weight rows: bit 3 of the row = bit 3 of li
+  const unsigned boff = (unsigned)(SLABB + li * RING_ROWB + RING_HALF(li, g));          // weight rows: bit 3 of the row = bit 3 of li
 
   // B first, A last: the wait for A (the first thing a tap touches) covers the whole set
   auto read_frags = [&](unsigned ao, unsigned bo, u32x4 (&af)[MT], u32x4 (&bf)[BNT]) {
@@ -2563,18 +2539,36 @@ static int launch_conv(const ConvArgs& a, hipStream_t st) {
   return finish_launch("k_conv_igemm");
 }
 
+// Launch of a slab kernel with the row-major epilogue: KERNEL (one ceiling flag array per instantiation) on NW waves per
+// workgroup, tiles of BMP rows x 32 BNT columns, `lds` bytes of operand tiles or what the epilogue needs on a grid of HW
+// pixels per sample if that is more; then k_conv_finish under split-K.  `what` names the kernel in the LDS refusal.
+template <auto KERNEL, int NW, int BNT, int BMP>
+static int launch_slab(const char* name, const char* what, const ConvArgs& a, dim3 g, size_t lds, int HW, hipStream_t st) {
+  const size_t epi_lds = epilogue_rows_lds(NW, BNT, BMP, HW);
+  if (lds < epi_lds) lds = epi_lds;
+  CTDD_REQUIRE(lds <= 160 * 1024, CTDD_ERANGE, "%s: %zu bytes of LDS", what, lds);
+  static bool attr_done[16] = {};
+  ensure_lds_ceiling((const void*)KERNEL, attr_done);
+  hipLaunchKernelGGL(KERNEL, g, dim3(NW * 64), lds, st, a);
+  if (int rc = finish_launch(name)) return rc;
+  if (a.ksplit > 1) {
+    hipLaunchKernelGGL(k_conv_finish, dim3((a.N + 31) / 32, a.B), dim3(256), 0, st, a);
+    return finish_launch("k_conv_finish");
+  }
+  return CTDD_OK;
+}
+// ... of a ring kernel: everything but the grid comes from its geometry G
+template <auto KERNEL, class G>
+static int launch_ring_geom(const char* name, const char* what, const ConvArgs& a, dim3 g, int HW, hipStream_t st) {
+  return launch_slab<KERNEL, G::NW, G::BNT, G::BMP>(name, what, a, g, (size_t)G::LDS, HW, st);
+}
+
 template <int BNT>
 static int launch_ring_s2(const ConvArgs& a, hipStream_t st) {
-  constexpr int NBUF = 3, BMP = 128;
+  using G = RingS2<BNT, 3>;
   const int64_t M = (int64_t)a.B * a.H * a.W;
-  dim3 g((unsigned)((M + BMP - 1) / BMP), (unsigned)((a.N + 32 * BNT - 1) / (32 * BNT)));
-  size_t lds = (size_t)NBUF * (20 * 1024 + 9 * 32 * BNT * 32);
-  const size_t epi_lds = epilogue_rows_lds(4, BNT, BMP, a.H * a.W);
-  if (lds < epi_lds) lds = epi_lds;
-  static bool attr_done[16] = {};
-  ensure_lds_ceiling((const void*)k_conv_ring_s2<BNT, NBUF>, attr_done);
-  hipLaunchKernelGGL((k_conv_ring_s2<BNT, NBUF>), g, dim3(256), lds, st, a);
-  return finish_launch("k_conv_ring_s2");
+  dim3 g((unsigned)((M + G::BMP - 1) / G::BMP), (unsigned)((a.N + G::BN - 1) / G::BN));
+  return launch_ring_geom<k_conv_ring_s2<BNT, 3>, G>("k_conv_ring_s2", "stride-2 ring conv", a, g, a.H * a.W, st);
 }
 
 // Does the stride-2 ring kernel take this call of ctdd_unet_conv?  Everything else stays on k_conv_igemm.
@@ -2687,19 +2681,8 @@ static int launch_res(const ConvArgs& a, hipStream_t st) {
   const int64_t M = (int64_t)a.B * a.H * a.W;
   const int nz = a.ksplit > 1 ? a.ksplit : 1;
   dim3 g((unsigned)((M + 511) / 512), (unsigned)((a.N + 32 * BNT - 1) / (32 * BNT)), (unsigned)nz);
-  size_t lds = ((size_t)(512 + 2 * (a.W + 1)) + (size_t)9 * 32 * BNT) * 40 * 2;
-  const size_t epi_lds = epilogue_rows_lds(8, BNT, 512, a.H * a.W);
-  if (lds < epi_lds) lds = epi_lds;
-  CTDD_REQUIRE(lds <= 160 * 1024, CTDD_ERANGE, "resident conv: %zu bytes of LDS", lds);
-  static bool attr_done[16] = {};
-  ensure_lds_ceiling((const void*)k_conv_res<BNT>, attr_done);
-  hipLaunchKernelGGL((k_conv_res<BNT>), g, dim3(512), lds, st, a);
-  if (int rc = finish_launch("k_conv_res")) return rc;
-  if (nz > 1) {
-    hipLaunchKernelGGL(k_conv_finish, dim3((a.N + 31) / 32, a.B), dim3(256), 0, st, a);
-    return finish_launch("k_conv_finish");
-  }
-  return CTDD_OK;
+  const size_t lds = ((size_t)(512 + 2 * (a.W + 1)) + (size_t)9 * 32 * BNT) * 40 * 2;
+  return launch_slab<k_conv_res<BNT>, 8, BNT, 512>("k_conv_res", "resident conv", a, g, lds, a.H * a.W, st);
 }
 
 extern "C" int ctdd_unet_conv_res(const void* args_, int bnt, void* stream) {
@@ -2729,23 +2712,11 @@ extern "C" int ctdd_unet_conv_res(const void* args_, int bnt, void* stream) {
 
 template <int BNT, int NBUF, int NW>
 static int launch_ring(const ConvArgs& a, hipStream_t st) {
-  constexpr int BMP = NW * 64, SP = (BMP + 2 * 34 + 31) / 32;
+  using G = RingS1<BNT, NBUF, NW>;
   const int64_t M = (int64_t)a.B * a.H * a.W;
   const int nz = a.ksplit > 1 ? a.ksplit : 1;
-  dim3 g((unsigned)((M + BMP - 1) / BMP), (unsigned)((a.N + 32 * BNT - 1) / (32 * BNT)), (unsigned)nz);
-  size_t lds = (size_t)NBUF * (SP * 1024 + 9 * 32 * BNT * 32);
-  const size_t epi_lds = epilogue_rows_lds(NW, BNT, BMP, a.H * a.W);
-  if (lds < epi_lds) lds = epi_lds;
-  CTDD_REQUIRE(lds <= 160 * 1024, CTDD_ERANGE, "ring conv: %zu bytes of LDS", lds);
-  static bool attr_done[16] = {};
-  ensure_lds_ceiling((const void*)k_conv_ring<BNT, NBUF, NW>, attr_done);
-  hipLaunchKernelGGL((k_conv_ring<BNT, NBUF, NW>), g, dim3(NW * 64), lds, st, a);
-  if (int rc = finish_launch("k_conv_ring")) return rc;
-  if (nz > 1) {
-    hipLaunchKernelGGL(k_conv_finish, dim3((a.N + 31) / 32, a.B), dim3(256), 0, st, a);
-    return finish_launch("k_conv_finish");
-  }
-  return CTDD_OK;
+  dim3 g((unsigned)((M + G::BMP - 1) / G::BMP), (unsigned)((a.N + G::BN - 1) / G::BN), (unsigned)nz);
+  return launch_ring_geom<k_conv_ring<BNT, NBUF, NW>, G>("k_conv_ring", "ring conv", a, g, a.H * a.W, st);
 }
 
 extern "C" int ctdd_unet_conv_ring(const void* args_, int bnt, void* stream) {
@@ -2779,18 +2750,11 @@ extern "C" int ctdd_unet_conv_ring(const void* args_, int bnt, void* stream) {
 
 template <int BNT>
 static int launch_ring_up(const ConvArgs& a, hipStream_t st) {
-  constexpr int NBUF = 3, BMP = 512, SP = (BMP + 2 * 34 + 31) / 32;
-  const int HW = a.Hin * a.Win;
+  using G = RingUp<BNT, 3>;
+  const int HW = a.Hin * a.Win;                                  // the tiles are of source pixels
   const int64_t M = (int64_t)a.B * HW;
-  dim3 g((unsigned)((M + BMP - 1) / BMP), (unsigned)(4 * (a.N / (32 * BNT))));
-  size_t lds = (size_t)NBUF * (SP * 1024 + 4 * 32 * BNT * 32);
-  const size_t epi_lds = epilogue_rows_lds(8, BNT, BMP, HW);
-  if (lds < epi_lds) lds = epi_lds;
-  CTDD_REQUIRE(lds <= 160 * 1024, CTDD_ERANGE, "upsample-phase conv: %zu bytes of LDS", lds);
-  static bool attr_done[16] = {};
-  ensure_lds_ceiling((const void*)k_conv_ring_up<BNT, NBUF>, attr_done);
-  hipLaunchKernelGGL((k_conv_ring_up<BNT, NBUF>), g, dim3(512), lds, st, a);
-  return finish_launch("k_conv_ring_up");
+  dim3 g((unsigned)((M + G::BMP - 1) / G::BMP), (unsigned)(4 * (a.N / G::BN)));
+  return launch_ring_geom<k_conv_ring_up<BNT, 3>, G>("k_conv_ring_up", "upsample-phase conv", a, g, HW, st);
 }
 
 extern "C" int ctdd_unet_conv_up_phases(const void* args_, int f32, void* stream) {
