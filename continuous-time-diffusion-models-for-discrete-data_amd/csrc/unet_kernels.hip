@@ -107,6 +107,12 @@ __device__ inline void tile_stats_flush(const ConvArgs& a, const TileStats& ts) 
   }
 }
 
+// SMALL: a grid of fewer than 32 pixels per sample with B > 1 (2x2, 3x3, ...; 16 pixels tile a 32-row slice exactly and stay on
+// the two-sample code).  A 32-row tile then spans up to 32 samples, so every row looks up its own sample p / HW for the per-sample
+// bias, the logits row and the statistics; a lane's rows ascend with r, so its sums run per sample and go to LDS when the sample
+// changes.  A template argument, chosen by launch_conv, and not a branch: compiled into the one kernel, this path took the
+// 32-column tiles from four or five waves per SIMD to two and put the 96- and 128-column tiles' accumulators in scratch.
+template <bool SMALL = false>
 __device__ inline void conv_epilogue_tile(const ConvArgs& a, const f32x16& acc, int64_t wrow0, int n, int g,
                                           int64_t M, int HW, const TileStats& ts) {
   const bool ncol = n < a.N;
@@ -118,8 +124,47 @@ __device__ inline void conv_epilogue_tile(const ConvArgs& a, const f32x16& acc, 
     }
     return;
   }
+  if constexpr (SMALL) {
+    if (!ncol) return;
+    const float bv = a.bias ? a.bias[n] : 0.0f;
+    const int S = a.logits_C > 0 ? a.N / a.logits_C : 1;
+    const int lch = a.logits_C > 0 ? n / S : 0, ls = a.logits_C > 0 ? n % S : 0;
+    const int b0 = (int)(wrow0 / HW);
+    const unsigned rem0 = (unsigned)(wrow0 - (int64_t)b0 * HW);        // < HW < 32
+    double s = 0.0, q = 0.0;
+    int bs = -1;                                                        // sample of the running sums
+    auto put = [&]() {
+      if (ts.lds && bs >= 0) {
+        double* st = ts.lds + ((size_t)(bs - ts.b0) * ts.BN + (n - ts.n0)) * 2;
+        atomicAdd(st, s);
+        atomicAdd(st + 1, q);
+      }
+    };
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int j = (r & 3) + 8 * (r >> 2) + 4 * g;
+      const int64_t p = wrow0 + j;
+      if (p < M) {
+        const unsigned db = (rem0 + (unsigned)j) / (unsigned)HW;
+        const int b = b0 + (int)db, px = (int)(rem0 + (unsigned)j - db * (unsigned)HW);
+        float v = acc[r] + bv + (a.tbias ? a.tbias[(size_t)b * a.tb_stride + n] : 0.0f);
+        if (a.act == 1) v = fmaxf(v, 0.0f);
+        else if (a.act == 2) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+        const size_t o = (size_t)p * a.N + n;
+        if (a.res_f32) v += a.res_f32[o];
+        else if (a.res_bf16) v += from_bf16(a.res_bf16[o]);
+        const size_t oo = a.logits_C > 0 ? (((size_t)b * a.logits_C + lch) * HW + px) * S + ls : o;
+        if (a.out_f32) a.out_f32[oo] = v;
+        if (a.out_hi) a.out_hi[oo] = to_bf16(v);
+        if (b != bs) { put(); bs = b; s = 0.0; q = 0.0; }
+        s += v; q += (double)v * v;
+      }
+    }
+    put();
+    return;
+  }
   const int b_first = (int)((wrow0 < M ? wrow0 : M - 1) / HW);
-  const int64_t next_sample = (int64_t)(b_first + 1) * HW;   // a 32-row tile spans at most two samples (HW >= 32 or B small)
+  const int64_t next_sample = (int64_t)(b_first + 1) * HW;   // a 32-row tile spans at most two samples (HW >= 32, HW == 16 or B == 1)
   const float bv = (a.bias && ncol) ? a.bias[n] : 0.0f;
   const float tb0 = (a.tbias && ncol) ? a.tbias[(size_t)b_first * a.tb_stride + n] : 0.0f;
   const float tb1 = (a.tbias && ncol && b_first + 1 < a.B) ? a.tbias[(size_t)(b_first + 1) * a.tb_stride + n] : 0.0f;
@@ -422,7 +467,7 @@ struct ChunkIter {
   }
 };
 
-template <int BK, int BNT, bool F32>
+template <int BK, int BNT, bool F32, bool SMALL = false>      // SMALL: the epilogue for grids of < 32 pixels per sample (conv_epilogue_tile)
 __global__ __launch_bounds__(256) void k_conv_igemm(const ConvArgs a) {
   constexpr int BN = 32 * BNT;
   constexpr int ESZ = F32 ? 4 : 2;            // element bytes
@@ -595,7 +640,7 @@ __global__ __launch_bounds__(256) void k_conv_igemm(const ConvArgs a) {
   // ---- epilogue.  lane: column n = n0 + 32 t + li ; register r: row 32*wave + (r&3) + 8*(r>>2) + 4*g
   const TileStats ts = tile_stats_begin(a, smem, m0, BM, n0, BN, M, HW);
 #pragma unroll
-  for (int t = 0; t < BNT; ++t) conv_epilogue_tile(a, acc[t], m0 + wave * 32, n0 + 32 * t + li, g, M, HW, ts);
+  for (int t = 0; t < BNT; ++t) conv_epilogue_tile<SMALL>(a, acc[t], m0 + wave * 32, n0 + 32 * t + li, g, M, HW, ts);
   tile_stats_flush(a, ts);
 }
 
@@ -2524,6 +2569,14 @@ __global__ __launch_bounds__(256) void k_logistic_head(const LogisticArgs a) {
 using namespace ctdd;
 
 // ============================================================================ C ABI
+template <int BK, int BNT, bool F32, bool SMALL>
+static int launch_igemm(const ConvArgs& a, dim3 g, size_t lds, hipStream_t st) {
+  static bool attr_done[16] = {};
+  ensure_lds_ceiling((const void*)k_conv_igemm<BK, BNT, F32, SMALL>, attr_done);
+  hipLaunchKernelGGL((k_conv_igemm<BK, BNT, F32, SMALL>), g, dim3(256), lds, st, a);
+  return finish_launch("k_conv_igemm");
+}
+
 template <int BK, int BNT, bool F32>
 static int launch_conv(const ConvArgs& a, hipStream_t st) {
   constexpr int ESZ = F32 ? 4 : 2;
@@ -2531,12 +2584,12 @@ static int launch_conv(const ConvArgs& a, hipStream_t st) {
   size_t lds = (size_t)(BM + 32 * BNT) * LDK * ESZ;
   const size_t stats_lds = (size_t)tile_stats_samples(BM, a.H * a.W) * 32 * BNT * 16;
   if (lds < stats_lds) lds = stats_lds;
+  CTDD_REQUIRE(lds <= 160 * 1024, CTDD_ERANGE, "generic conv: %zu bytes of LDS (H*W=%d on %d-column tiles)", lds, a.H * a.W, 32 * BNT);
   const int64_t M = (int64_t)a.B * a.H * a.W;
   dim3 g((unsigned)((M + BM - 1) / BM), (unsigned)((a.N + 32 * BNT - 1) / (32 * BNT)));
-  static bool attr_done[16] = {};
-  ensure_lds_ceiling((const void*)k_conv_igemm<BK, BNT, F32>, attr_done);
-  hipLaunchKernelGGL((k_conv_igemm<BK, BNT, F32>), g, dim3(256), lds, st, a);
-  return finish_launch("k_conv_igemm");
+  // fewer than 32 pixels per sample (other than 16), B > 1: a 32-row tile spans more than two samples -- the per-row epilogue
+  if (!((int64_t)a.H * a.W >= 32 || a.H * a.W == 16 || a.B == 1)) return launch_igemm<BK, BNT, F32, true>(a, g, lds, st);
+  return launch_igemm<BK, BNT, F32, false>(a, g, lds, st);
 }
 
 // Launch of a slab kernel with the row-major epilogue: KERNEL (one ceiling flag array per instantiation) on NW waves per

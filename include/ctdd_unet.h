@@ -43,7 +43,10 @@ typedef struct {
  * Ktot = 9 C, ksplit <= 1, H*W >= 32 or == 16 or B == 1, no logits layout / activation / out_lo, 16-byte aligned
  * tensors, 4*B*H*W < 2^31.  Every other call runs on the generic gather kernel as before; the results of the two
  * differ by the order of the fp32 sums only.  CTDD_CONV_S2_OLD=1 in the environment (read once per process) keeps
- * the generic kernel for those calls too. */
+ * the generic kernel for those calls too.
+ * The generic kernel takes any grid: with fewer than 32 pixels per sample (other than 16) and B > 1 each output row
+ * looks up its own sample for tbias, the logits layout and the statistics.  CTDD_ERANGE where the statistics of one
+ * 128-row tile (ceil(128 / (H*W)) + 1 samples x 32 bnt columns x 16 bytes) exceed the 160 KiB of LDS. */
 int ctdd_unet_conv(const void* conv_args, int bk, int bnt, int f32, void* stream);
 /* bf16 throughput kernel for stride-1 3x3 / 1x1 segments: the input slab of a pixel tile is staged in
  * LDS once per channel chunk and shared by the nine taps; bk in {48,64,32,16}, wm = rows per wave */

@@ -92,6 +92,56 @@ def test_engine_matches_module_mnist():
     model.train()
 
 
+def _small_level_net(size, seed=0, **model_over):
+    """config_tauUnet_mnist shrunk to ch 32 / 64 / 64, one ResBlock per level, on size x size data: three levels, the deepest of
+    (size / 4)^2 pixels.  Weights re-drawn as in _mnist_model, biases too (the per-sample time projection then differs per channel)."""
+    import lib.models.models  # noqa: F401
+    import lib.models.model_utils as mu
+    from config.mnist_config.config_tauUnet_mnist import get_config
+    cfg = get_config()
+    cfg.data.image_size, cfg.data.shape = size, [1, size, size]
+    cfg.model.update(ch=32, ch_mult=[1, 2, 2], num_res_blocks=1, concat_dim=size * size)
+    cfg.model.update(model_over)
+    torch.manual_seed(seed)
+    model = mu.create_model(cfg, torch.device("cuda"))
+    g = torch.Generator(device="cuda").manual_seed(seed + 1)
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if p.dim() > 1:
+                p.copy_(torch.randn(p.shape, generator=g, device="cuda") / (p[0].numel() ** 0.5))
+            elif name.endswith("bias"):
+                p.copy_(0.1 * torch.randn(p.shape, generator=g, device="cuda"))
+    model.init_ema()
+    return cfg, model
+
+
+@pytest.mark.parametrize("size", [8, 12])
+def test_engine_matches_module_small_deepest_level(size):
+    """Levels 8 / 4 / 2 and 12 / 6 / 3 at batch 5: the deepest level's convolutions have 4 or 9 pixels per sample, so a 32-row
+    accumulator tile of the generic convolution kernel spans up to eight samples.  Every sample has its own time: a per-sample
+    bias, a statistic or a logits row filed under the wrong sample shows.  The bars of test_engine_matches_module_mnist."""
+    from ctdd.unet_engine import UNetEngine
+    cfg, model = _small_level_net(size)
+    model.eval()
+    B, D = 5, size * size
+    x = torch.randint(0, 256, (B, D), device="cuda", generator=torch.Generator(device="cuda").manual_seed(size))
+    t = torch.tensor([0.03, 0.27, 0.5, 0.74, 0.99], device="cuda")
+    with torch.no_grad():
+        cfg.model.engine = "torch"
+        ref = model(x, t).cpu()
+        out = UNetEngine(model, precision="fp32")(x.view(B, 1, size, size), t).cpu()
+        fast = UNetEngine(model, precision="bf16")(x.view(B, 1, size, size), t).cpu()
+    assert ref.shape == out.shape == fast.shape == (B, D, 256)
+    scale = ref.abs().max().item()
+    e32, e16 = (out - ref).abs().max().item(), (fast - ref).abs().max().item()
+    print(f"{size}x{size} net, batch {B}: scale {scale:.3f}, fp32 error {e32:.3e} (bar {2e-4 * max(scale, 1.0):.3e}), "
+          f"bf16 error {e16:.3e} (bar {5e-2 * scale:.3e})")
+    assert scale > 0.5
+    assert e32 < 2e-4 * max(scale, 1.0)
+    assert e16 < 5e-2 * scale
+    model.train()
+
+
 def _mnist_model(seed=0, **model_over):
     import lib.models.models  # noqa: F401
     import lib.models.model_utils as mu

@@ -370,6 +370,27 @@ def test_parameter_gradients_mnist_size(precision, tol):
     print(f"mnist-size parameter gradients, {precision}: worst relative error {worst:.2e}")
 
 
+@pytest.mark.parametrize("size", [8, 12])
+def test_parameter_gradients_small_deepest_level(size):
+    """The three-level ch 32 / 64 / 64 net of test_gpu_unet on 8x8 (levels 8, 4, 2) and 12x12 (12, 6, 3) data, batch 5, one time
+    per sample: forward, data-gradient and weight-gradient kernels on grids of 4 and 9 pixels per sample.  fp32 mode, the 1e-4 bar."""
+    from test_gpu_unet import _small_level_net
+    cfg, model = _small_level_net(size, dropout=0.0, engine_precision="fp32")
+    B, D = 5, size * size
+    g = torch.Generator(device="cuda").manual_seed(size)
+    x = torch.randint(0, 256, (B, D), generator=g, device="cuda")
+    t = torch.tensor([0.03, 0.27, 0.5, 0.74, 0.99], device="cuda")
+    weight = torch.randn((B, D, 256), generator=g, device="cuda")
+    lr, gr = _grads(model, cfg, x, t, weight, "torch")
+    la, ga = _grads(model, cfg, x, t, weight, "hip")
+    assert getattr(model._engine, "_train_plans", None)
+    e = (la - lr).abs().max().item()
+    print(f"{size}x{size} net: training-plan logits error {e:.3e} of scale {lr.abs().max().item():.3f}")
+    assert e < 2e-4 * max(lr.abs().max().item(), 1.0)
+    worst = _compare(ga, gr, 1e-4, (size, "fp32"))
+    print(f"{size}x{size} net parameter gradients, fp32: worst relative error {worst:.2e}")
+
+
 def test_train_step_through_the_engine_matches_torch_step():
     """Standard.step (zero_grad -> CT-ELBO -> backward -> clip -> Adam -> EMA) with the network on the training plan against
     the same step on torch autograd ops: same loss, same updated weights (fp32 mode, dropout off)."""
