@@ -12,6 +12,8 @@
 // and optionally + nll_scale * CE(l, x0):  (p[j] - onehot(x0)[j]).  The objective is
 // scale * sum_rows loss + nll_scale * sum_rows -ll[x0]; rows' values go to a fp64 buffer summed by a
 // second launch (one scalar, no atomics on a single address).  One wave per row, lanes stride over s.
+// Under a per-sample mask of free rows (ctdd_crm_loss_masked / _ll_masked: inpainting training) both sums run over the free rows and
+// a held row's wave writes its zeros and leaves (k_crm_rows<true>).
 #include "common.hpp"
 
 namespace ctdd {
@@ -23,6 +25,8 @@ struct CrmArgs {
   float* grad; double* row_loss;
   int ll_in;     // `logits` already holds ll_all = log p_t(. | x^{\d}) (reverse_prob / reverse_logscale logit types, from
                  // ctdd_logprob): no log-softmax, grad = d loss / d ll_all (ctdd_logprob_bwd chains it to the logits)
+  const uint8_t* free_mask;   // (B,D) or null (k_crm_rows<true> only): a row with a zero byte is HELD -- its gradient row and its
+                 // row loss are written as zeros and nothing of it is read
 };
 
 __device__ inline float lwave_sum(float v) {
@@ -42,6 +46,7 @@ __device__ inline void log1mexp_h(float y, float& f, float& h) {
   else { const float e = expf(y); f = log1pf(-e); h = e / (1.0f - e); }
 }
 
+template <bool MASKED = false>     // MASKED: a.free_mask is set (the unmasked instantiation carries none of its branches)
 __global__ __launch_bounds__(256) void k_crm_rows(const CrmArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -49,6 +54,11 @@ __global__ __launch_bounds__(256) void k_crm_rows(const CrmArgs a) {
   const int S = a.S, b = (int)(row / a.D);
   const float* l = a.logits + (size_t)row * S;
   float* gr = a.grad + (size_t)row * S;
+  if (MASKED && !a.free_mask[row]) {                    // held row (the whole wave): its zeros only
+    for (int s = lane; s < S; s += 64) gr[s] = 0.0f;
+    if (lane == 0) a.row_loss[row] = 0.0;
+    return;
+  }
   const int x = min(max(a.xt[row], 0), S - 1);
   const int x0 = a.x0 ? min(max(a.x0[row], 0), S - 1) : -1;
   float L = 0.0f;
@@ -134,6 +144,17 @@ __global__ __launch_bounds__(256) void k_sum_rows(const double* __restrict__ v, 
 
 using namespace ctdd;
 
+// the row pass (its MASKED instantiation under a mask) and the sum of the rows' values
+static int crm_launch(const CrmArgs& a, float* out_loss, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)((a.rows + 3) / 4));
+  if (a.free_mask) hipLaunchKernelGGL(k_crm_rows<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_crm_rows<false>, grid, dim3(256), 0, st, a);
+  if (int rc = finish_launch("k_crm_rows")) return rc;
+  hipLaunchKernelGGL(k_sum_rows, dim3(1), dim3(256), 0, st, (const double*)a.row_loss, a.rows, out_loss);
+  return finish_launch("k_sum_rows");
+}
+
 extern "C" int ctdd_crm_loss(const float* logits, const int32_t* xt, const int32_t* x0, const float* qt0, int B, int D, int S,
                              int loss_type, float scale, float nll_scale, float* grad_logits, double* row_scratch,
                              float* out_loss, void* stream) {
@@ -141,12 +162,20 @@ extern "C" int ctdd_crm_loss(const float* logits, const int32_t* xt, const int32
   CTDD_REQUIRE(B > 0 && D > 0 && S >= 2, CTDD_EINVAL, "crm loss: B=%d D=%d S=%d", B, D, S);
   CTDD_REQUIRE(loss_type >= 0 && loss_type <= 2, CTDD_EINVAL, "crm loss: loss_type %d (0 rm, 1 mle, 2 elbo)", loss_type);
   CTDD_REQUIRE(loss_type != 2 || qt0, CTDD_EINVAL, "crm loss: elbo needs q_{t|0}");
-  CrmArgs a = {logits, xt, x0, qt0, (int64_t)B * D, D, S, loss_type, scale, nll_scale, grad_logits, row_scratch, 0};
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_crm_rows, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, st, a);
-  if (int rc = finish_launch("k_crm_rows")) return rc;
-  hipLaunchKernelGGL(k_sum_rows, dim3(1), dim3(256), 0, st, (const double*)row_scratch, a.rows, out_loss);
-  return finish_launch("k_sum_rows");
+  CrmArgs a = {logits, xt, x0, qt0, (int64_t)B * D, D, S, loss_type, scale, nll_scale, grad_logits, row_scratch, 0, nullptr};
+  return crm_launch(a, out_loss, stream);
+}
+// K12 under a per-sample mask of free rows: held rows add nothing to either sum and get an exact-zero gradient row
+extern "C" int ctdd_crm_loss_masked(const float* logits, const int32_t* xt, const int32_t* x0, const uint8_t* free_mask, const float* qt0,
+                                    int B, int D, int S, int loss_type, float scale, float nll_scale, float* grad_logits,
+                                    double* row_scratch, float* out_loss, void* stream) {
+  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "crm loss masked: null mask");
+  CTDD_REQUIRE(logits && xt && grad_logits && row_scratch && out_loss, CTDD_EINVAL, "crm loss masked: null buffer");
+  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2, CTDD_EINVAL, "crm loss masked: B=%d D=%d S=%d", B, D, S);
+  CTDD_REQUIRE(loss_type >= 0 && loss_type <= 2, CTDD_EINVAL, "crm loss masked: loss_type %d (0 rm, 1 mle, 2 elbo)", loss_type);
+  CTDD_REQUIRE(loss_type != 2 || qt0, CTDD_EINVAL, "crm loss masked: elbo needs q_{t|0}");
+  CrmArgs a = {logits, xt, x0, qt0, (int64_t)B * D, D, S, loss_type, scale, nll_scale, grad_logits, row_scratch, 0, free_mask};
+  return crm_launch(a, out_loss, stream);
 }
 
 // the same objective on ll_all (reverse_prob / reverse_logscale logit types): value and d loss / d ll_all
@@ -155,12 +184,19 @@ extern "C" int ctdd_crm_loss_ll(const float* ll_all, const int32_t* xt, const fl
   CTDD_REQUIRE(ll_all && xt && grad_ll && row_scratch && out_loss, CTDD_EINVAL, "crm loss (ll): null buffer");
   CTDD_REQUIRE(B > 0 && D > 0 && S >= 2, CTDD_EINVAL, "crm loss (ll): B=%d D=%d S=%d", B, D, S);
   CTDD_REQUIRE(loss_type >= 0 && loss_type <= 2 && (loss_type != 2 || qt0), CTDD_EINVAL, "crm loss (ll): loss_type %d / elbo needs q_{t|0}", loss_type);
-  CrmArgs a = {ll_all, xt, nullptr, qt0, (int64_t)B * D, D, S, loss_type, scale, 0.0f, grad_ll, row_scratch, 1};
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_crm_rows, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, st, a);
-  if (int rc = finish_launch("k_crm_rows")) return rc;
-  hipLaunchKernelGGL(k_sum_rows, dim3(1), dim3(256), 0, st, (const double*)row_scratch, a.rows, out_loss);
-  return finish_launch("k_sum_rows");
+  CrmArgs a = {ll_all, xt, nullptr, qt0, (int64_t)B * D, D, S, loss_type, scale, 0.0f, grad_ll, row_scratch, 1, nullptr};
+  return crm_launch(a, out_loss, stream);
+}
+// ... under a mask: a held row's d loss / d ll_all is an exact-zero row, which ctdd_logprob_bwd turns into a zero logit-gradient row
+extern "C" int ctdd_crm_loss_ll_masked(const float* ll_all, const int32_t* xt, const uint8_t* free_mask, const float* qt0, int B, int D,
+                                       int S, int loss_type, float scale, float* grad_ll, double* row_scratch, float* out_loss,
+                                       void* stream) {
+  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "crm loss masked (ll): null mask");
+  CTDD_REQUIRE(ll_all && xt && grad_ll && row_scratch && out_loss, CTDD_EINVAL, "crm loss masked (ll): null buffer");
+  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2, CTDD_EINVAL, "crm loss masked (ll): B=%d D=%d S=%d", B, D, S);
+  CTDD_REQUIRE(loss_type >= 0 && loss_type <= 2 && (loss_type != 2 || qt0), CTDD_EINVAL, "crm loss masked (ll): loss_type %d / elbo needs q_{t|0}", loss_type);
+  CrmArgs a = {ll_all, xt, nullptr, qt0, (int64_t)B * D, D, S, loss_type, scale, 0.0f, grad_ll, row_scratch, 1, free_mask};
+  return crm_launch(a, out_loss, stream);
 }
 
 // ================================================================== K11: tauLDR CT-ELBO, value + d/dlogits
@@ -972,10 +1008,18 @@ static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_
 // One wave per row; forward rows -> per-sample normalisers (k_elbo_reduce) -> backward rows.
 namespace ctdd {
 
+template <bool MASKED = false>     // MASKED: a.free_mask is set (the unmasked instantiation carries none of its branches)
 __global__ __launch_bounds__(256) void k_selbo_fwd(const ElboArgs a, const int32_t* __restrict__ regx) {
   const int lane = threadIdx.x & 63, S = a.S, D = a.D;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (int64_t)a.B * D) return;
+  if (MASKED && !a.free_mask[row]) {                    // held row (the whole wave): out of every sum over dimensions
+    if (lane == 0) {
+      double* dst = a.rows + (size_t)row * 4;
+      dst[0] = 0.0; dst[1] = 0.0; dst[2] = 0.0; dst[3] = 0.0;
+    }
+    return;
+  }
   const int b = (int)(row / D);
   const float* l = a.logits + (size_t)row * S;
   const float* q = a.q + (size_t)b * S * S;
@@ -1010,10 +1054,16 @@ __global__ __launch_bounds__(256) void k_selbo_fwd(const ElboArgs a, const int32
   }
 }
 
+template <bool MASKED = false>
 __global__ __launch_bounds__(256) void k_selbo_bwd(const ElboArgs a, const int32_t* __restrict__ regx) {
   const int lane = threadIdx.x & 63, S = a.S, D = a.D;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (int64_t)a.B * D) return;
+  if (MASKED && !a.free_mask[row]) {                    // held row: a zero gradient row
+    float* gz = a.grad + (size_t)row * S;
+    for (int s = lane; s < S; s += 64) gz[s] = 0.0f;
+    return;
+  }
   const int b = (int)(row / D);
   const float* l = a.logits + (size_t)row * S;
   const float* q = a.q + (size_t)b * S * S;
@@ -1054,7 +1104,7 @@ __global__ __launch_bounds__(256) void k_selbo_bwd(const ElboArgs a, const int32
 
 static int score_elbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x, const float* qt0,
                            const float* rate, int B, int D, int S, float eps, float nll_scale, void* scratch, float* grad_logits,
-                           float* out_loss, int ll_in, void* stream);
+                           float* out_loss, int ll_in, void* stream, const uint8_t* free_mask = nullptr);
 extern "C" int ctdd_score_elbo_loss(const float* logits, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x,
                                     const float* qt0, const float* rate, int B, int D, int S, float eps, float nll_scale,
                                     void* scratch, float* grad_logits, float* out_loss, void* stream) {
@@ -1066,9 +1116,24 @@ extern "C" int ctdd_score_elbo_loss_ll(const float* ll_all, const int32_t* x0, c
                                        void* scratch, float* grad_ll, float* out_loss, void* stream) {
   return score_elbo_impl(ll_all, x0, x_tilde, reg_x, qt0, rate, B, D, S, eps, nll_scale, scratch, grad_ll, out_loss, 1, stream);
 }
+// ScoreElbo under a per-sample mask of free rows (free (B,D) uint8, non-zero = free): every sum over dimensions -- base_sum / Z, the
+// normaliser, the signal term, the regulariser, the -ll[x~] term -- runs over the sample's free rows; held rows get an exact-zero
+// gradient row; a sample without a free row adds zero (k_elbo_sample_sums sets its normaliser to 1)
+extern "C" int ctdd_score_elbo_loss_masked(const float* logits, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x,
+                                           const uint8_t* free_mask, const float* qt0, const float* rate, int B, int D, int S, float eps,
+                                           float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream) {
+  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "score-elbo masked: null mask");
+  return score_elbo_impl(logits, x0, x_tilde, reg_x, qt0, rate, B, D, S, eps, nll_scale, scratch, grad_logits, out_loss, 0, stream, free_mask);
+}
+extern "C" int ctdd_score_elbo_loss_ll_masked(const float* ll_all, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x,
+                                              const uint8_t* free_mask, const float* qt0, const float* rate, int B, int D, int S, float eps,
+                                              float nll_scale, void* scratch, float* grad_ll, float* out_loss, void* stream) {
+  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "score-elbo masked (ll): null mask");
+  return score_elbo_impl(ll_all, x0, x_tilde, reg_x, qt0, rate, B, D, S, eps, nll_scale, scratch, grad_ll, out_loss, 1, stream, free_mask);
+}
 static int score_elbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x, const float* qt0,
                            const float* rate, int B, int D, int S, float eps, float nll_scale, void* scratch, float* grad_logits,
-                           float* out_loss, int ll_in, void* stream) {
+                           float* out_loss, int ll_in, void* stream, const uint8_t* free_mask) {
   CTDD_REQUIRE(logits && x0 && x_tilde && reg_x && qt0 && rate && scratch && grad_logits && out_loss, CTDD_EINVAL, "score-elbo: null buffer");
   CTDD_REQUIRE(B > 0 && D > 0 && S >= 2 && S <= 256, CTDD_ERANGE, "score-elbo: B=%d D=%d S=%d (S <= 256)", B, D, S);
   auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
@@ -1076,7 +1141,7 @@ static int score_elbo_impl(const float* logits, const int32_t* x0, const int32_t
   ElboArgs a;
   a.logits = logits; a.x0 = x0; a.xt = x_tilde; a.q = qt0; a.qT = qt0; a.R = rate;
   a.B = B; a.D = D; a.S = S; a.eps = eps; a.elbo_scale = 1.0f; a.nll_scale = nll_scale; a.reg_scale = 1.0f;
-  a.Dl = D; a.doff = 0; a.free_mask = nullptr;
+  a.Dl = D; a.doff = 0; a.free_mask = free_mask;
   a.Atab = (float*)sp; sp += al((int64_t)B * S * S * 4);
   a.u = (float*)sp; sp += al((int64_t)B * D * S * 4);
   a.rows = (double*)sp; sp += al((int64_t)B * D * 32);
@@ -1089,13 +1154,16 @@ static int score_elbo_impl(const float* logits, const int32_t* x0, const int32_t
   const int64_t rows = (int64_t)B * D;
   hipLaunchKernelGGL(k_elbo_atab, dim3(1, B), dim3(256), 0, st, a);          // (first column block only: base_sum; its A rows are unused scratch)
   if (int rc = finish_launch("k_elbo_atab")) return rc;
-  hipLaunchKernelGGL(k_selbo_fwd, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, reg_x);
+  const dim3 wg((unsigned)((rows + 3) / 4));
+  if (free_mask) hipLaunchKernelGGL(k_selbo_fwd<true>, wg, dim3(256), 0, st, a, reg_x);
+  else hipLaunchKernelGGL(k_selbo_fwd<false>, wg, dim3(256), 0, st, a, reg_x);
   if (int rc = finish_launch("k_selbo_fwd")) return rc;
   hipLaunchKernelGGL(k_elbo_sample_sums, dim3(B), dim3(256), 0, st, a, sums);
   if (int rc = finish_launch("k_elbo_sample_sums")) return rc;
   hipLaunchKernelGGL(k_elbo_reduce, dim3(1), dim3(256), 0, st, a, (const double*)sums);
   if (int rc = finish_launch("k_elbo_reduce")) return rc;
-  hipLaunchKernelGGL(k_selbo_bwd, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, reg_x);
+  if (free_mask) hipLaunchKernelGGL(k_selbo_bwd<true>, wg, dim3(256), 0, st, a, reg_x);
+  else hipLaunchKernelGGL(k_selbo_bwd<false>, wg, dim3(256), 0, st, a, reg_x);
   return finish_launch("k_selbo_bwd");
 }
 

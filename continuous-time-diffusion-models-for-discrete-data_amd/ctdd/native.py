@@ -72,6 +72,10 @@ _SIGS = {
     "ctdd_crm_loss_ll": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P], _I),
     "ctdd_score_elbo_loss_ll": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_logprob_bwd": ([_I, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P], _I),
+    "ctdd_crm_loss_masked": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
+    "ctdd_crm_loss_ll_masked": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P], _I),
+    "ctdd_score_elbo_loss_masked": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
+    "ctdd_score_elbo_loss_ll_masked": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P], _I),
     "ctdd_opt_chunk_elems": ([], _I),
     "ctdd_adam_ema_step": ([_P, _P, _I, _F, _F, _F, _F, _I64, _F, _F, _P, _P], _I),
     "ctdd_grad_sumsq": ([_P, _P, _I, _P, _I, _P], _I),
@@ -639,6 +643,83 @@ def ctelbo_loss_masked(logits, x0, x_tilde, free, qt0, qt0T, rate, eps, sig_scal
                                        B, D, S, float(eps), float(sig_scale), float(reg_scale), float(nll_scale),
                                        _ptr(scratch), _ptr(grad, torch.float32, "grad_out"), _ptr(out), _stream()), "ctdd_ctelbo_loss_masked")
     return out[0], grad
+
+
+def _seq_masked_operands(what, logits, free, states, tables, grad_out):
+    """Host checks shared by the four masked sequence objectives: logits (B, D, S), `states` (B, D) each, `tables` (B, S, S) each
+    (None skipped), free a bool (B, D) tensor on the logits' device.  Returns (B, D, S, free pointer, gradient buffer)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise CtddError(f"{what}: logits {tuple(getattr(logits, 'shape', ()))}, expected (B, D, S)")
+    B, D, S = logits.shape
+    for name, x in states:
+        if x is not None and tuple(x.shape) != (B, D):
+            raise CtddError(f"{what}: {name} {tuple(x.shape)} against logits {tuple(logits.shape)}")
+    for name, tab in tables:
+        if tab is not None and tuple(tab.shape) != (B, S, S):
+            raise CtddError(f"{what}: {name} {tuple(tab.shape)}, expected {(B, S, S)}")
+    if not isinstance(free, torch.Tensor) or free.dtype != torch.bool:
+        raise CtddError(f"{what}: free must be a bool tensor, got {getattr(free, 'dtype', type(free))}")
+    if free.device != logits.device:
+        raise CtddError(f"{what}: free on {free.device}, logits on {logits.device}")
+    fp = _free_mask(free, B, D, what)
+    grad = torch.empty_like(logits) if grad_out is None else grad_out
+    if grad.shape != logits.shape:
+        raise CtddError(f"{what}: grad_out {tuple(grad.shape)} against logits {tuple(logits.shape)}")
+    return B, D, S, fp, grad
+
+
+_CRM_TYPES = {"rm": 0, "mle": 1, "elbo": 2}
+
+
+def crm_loss_masked(logits, xt, x0, free, qt0, loss_type, scale, nll_scale, grad_out=None):
+    """K12 on the free rows (`free` (B, D) bool; logits (B, D, S) read in place, xt / x0 full shape):
+    scale * sum_free loss_bd + nll_scale * sum_free CE(logits_bd, x0_bd) (x0 None: no CE term).  Returns (loss scalar tensor,
+    d loss / d logits): full shape, exact zeros on held rows, every element written by the call (`grad_out`: into this buffer)."""
+    B, D, S, fp, grad = _seq_masked_operands("crm_loss_masked", logits, free, (("xt", xt), ("x0", x0)), (("qt0", qt0),), grad_out)
+    rows = torch.empty((B * D,), dtype=torch.float64, device=logits.device)
+    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    _check(load().ctdd_crm_loss_masked(_ptr(logits, f32, "logits"), _ptr(xt, i32, "xt"), _ptr(x0, i32, "x0"), fp, _ptr(qt0, f32, "qt0"),
+                                       B, D, S, _CRM_TYPES[loss_type], float(scale), float(nll_scale), _ptr(grad, f32, "grad_out"),
+                                       _ptr(rows), _ptr(out), _stream()), "ctdd_crm_loss_masked")
+    _count("ctdd_crm_loss_masked")
+    return out[0], grad
+
+
+def crm_loss_ll_masked(ll_all, xt, free, qt0, loss_type, scale, grad_out=None):
+    """K12 on ll_all (reverse logit types) over the free rows: (loss scalar tensor, d loss / d ll_all), zero rows where held."""
+    B, D, S, fp, grad = _seq_masked_operands("crm_loss_ll_masked", ll_all, free, (("xt", xt),), (("qt0", qt0),), grad_out)
+    rows = torch.empty((B * D,), dtype=torch.float64, device=ll_all.device)
+    out = torch.empty((1,), dtype=torch.float32, device=ll_all.device)
+    _check(load().ctdd_crm_loss_ll_masked(_ptr(ll_all, f32, "ll_all"), _ptr(xt, i32, "xt"), fp, _ptr(qt0, f32, "qt0"), B, D, S,
+                                          _CRM_TYPES[loss_type], float(scale), _ptr(grad, f32, "grad_out"), _ptr(rows), _ptr(out),
+                                          _stream()), "ctdd_crm_loss_ll_masked")
+    _count("ctdd_crm_loss_ll_masked")
+    return out[0], grad
+
+
+def _score_elbo_masked(name, logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out):
+    B, D, S, fp, grad = _seq_masked_operands(name[5:], logits, free, (("x0", x0), ("x_tilde", x_tilde), ("reg_x", reg_x)),
+                                             (("qt0", qt0), ("rate", rate)), grad_out)
+    lib = load()
+    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits.device)
+    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    _check(getattr(lib, name)(_ptr(logits, f32, "logits"), _ptr(x0, i32, "x0"), _ptr(x_tilde, i32, "x_tilde"), _ptr(reg_x, i32, "reg_x"), fp,
+                              _ptr(qt0, f32, "qt0"), _ptr(rate, f32, "rate"), B, D, S, float(eps), float(nll_scale), _ptr(scratch),
+                              _ptr(grad, f32, "grad_out"), _ptr(out), _stream()), name)
+    _count(name)
+    return out[0], grad
+
+
+def score_elbo_loss_masked(logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out=None):
+    """ScoreElbo (direct logits) with every sum over dimensions restricted to the free rows of each sample (`free` (B, D) bool;
+    everything else full shape; nll_scale = nll_weight / B).  Returns (loss scalar tensor, d loss / d logits): exact zeros on held
+    rows, every element written by the call (`grad_out`: into this buffer).  A sample without a free row adds zero."""
+    return _score_elbo_masked("ctdd_score_elbo_loss_masked", logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out)
+
+
+def score_elbo_loss_ll_masked(ll_all, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out=None):
+    """The same on ll_all (reverse logit types): (loss scalar tensor, d loss / d ll_all), zero rows where held."""
+    return _score_elbo_masked("ctdd_score_elbo_loss_ll_masked", ll_all, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out)
 
 
 # ---------------------------------------------------------------- S = 256 fast path

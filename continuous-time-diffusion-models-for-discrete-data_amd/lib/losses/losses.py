@@ -1,6 +1,7 @@
 """Training losses behind the reference's registry names (lib/losses/losses.py): CTElbo 12-287,
 NLL 1504-1778, CTElboLambda 1783-2058, CondCTElbo 547-781, CatRM 786-890, CatRMNLL 1135-1242,
-NLLOriginal 1049-1103, ScoreElbo 1246-1500.
+NLLOriginal 1049-1103, ScoreElbo 1246-1500; and the inpainting objectives that have no counterpart there: InpaintCTElbo,
+InpaintCatRM, InpaintScoreElbo (the CT-ELBO, CatRM / CatRMNLL and ScoreElbo of a per-sample set of free entries, lib/losses/masks.py).
 
 Every loss = forward noising x0 -> x_t (and, for the ELBO family, the one-jump neighbour x~) followed
 by an objective on the network's logits.  Noising runs in the HIP kernels K1/K2/K3 (per-sample
@@ -295,6 +296,45 @@ def _ct_elbo_terms_masked(logits_reg, logits_sig, x0, reg_x, x_tilde, free, qt0,
     return torch.mean(sig) + torch.mean(reg_term)
 
 
+def _free_rows(name, cfg, minibatch):
+    """The inpainting objectives' minibatch and mask: (x0 (B, D) int64, free (B, D) bool on x0's device, n_free).  The mask is
+    drawn (or taken from the _FIXED_NOISE hook) and counted on the host; shape and config errors are ValueErrors before any
+    device work."""
+    import lib.losses.masks as masks
+    minibatch = _flatten(minibatch)
+    D = cfg.model.concat_dim
+    if minibatch.dim() != 2 or minibatch.shape[1] != D or minibatch.shape[0] < 1:
+        raise ValueError(f"{name}: minibatch of shape {tuple(minibatch.shape)}, model.concat_dim = {D}")
+    B = int(minibatch.shape[0])
+    if _FIXED_NOISE is not None and "free" in _FIXED_NOISE:
+        masks.check_mask_config(cfg, D)
+        free_host = torch.as_tensor(_FIXED_NOISE["free"]).cpu()
+        if free_host.dtype != torch.bool or tuple(free_host.shape) != (B, D):
+            raise ValueError(f"{name}: pinned free mask {free_host.dtype} {tuple(free_host.shape)}, expected bool {(B, D)}")
+    else:
+        free_host = masks.sample_free(cfg, B, D)
+    n_free = int(free_host.sum())                                  # on the host: the cross-entropy weight is a plain float
+    x0 = minibatch.long()
+    # the step's one upload of the mask: from pinned memory, asynchronous -- a pageable copy would make the host wait for the device
+    free = free_host.pin_memory().to(x0.device, non_blocking=True) if x0.is_cuda else free_host
+    return x0, free, n_free
+
+
+def _noise_masked(model, x0, free, ts, with_tilde):
+    """Tables and full-shape int64 x_t, x~ (None unless with_tilde): held entries of both are x0 bit for bit."""
+    if _FIXED_NOISE is not None:
+        qt0, qT, rate, _ = model.process.tables(ts, want_qt0=True, want_qt0T=True, want_rate=True)
+        pin = lambda k: torch.where(free, _FIXED_NOISE[k].to(x0.device).long(), x0)
+        return qt0, qT, rate, pin("x_t"), pin("x_tilde") if with_tilde else None
+    qt0, qT, rate, probs = model.process.tables(ts, want_qt0=True, want_qt0T=True, want_rate=True, want_noise_probs=True)
+    x0i = x0.to(torch.int32).contiguous()
+    x_t = torch.where(free, native.noise_categorical(probs, x0i, seed=_seed()), x0i)
+    if not with_tilde:
+        return qt0, qT, rate, x_t.long(), None
+    _, _, x_tilde = native.xtilde_sample_masked(rate, x_t, free, seed=_seed())
+    return qt0, qT, rate, x_t.long(), x_tilde.long()
+
+
 @losses_utils.register_loss
 class InpaintCTElbo:
     """CT-ELBO of a per-sample set of free entries given the held ones: what a model must be trained with for the samplers'
@@ -316,37 +356,13 @@ class InpaintCTElbo:
         self.mask = cfg.loss.mask
 
     def _noise(self, model, x0, free, ts):
-        """Tables and full-shape int64 x_t, x~: held entries of both are x0 bit for bit."""
-        if _FIXED_NOISE is not None:
-            qt0, qT, rate, _ = model.process.tables(ts, want_qt0=True, want_qt0T=True, want_rate=True)
-            pin = lambda k: torch.where(free, _FIXED_NOISE[k].to(x0.device).long(), x0)
-            return qt0, qT, rate, pin("x_t"), pin("x_tilde")
-        qt0, qT, rate, probs = model.process.tables(ts, want_qt0=True, want_qt0T=True, want_rate=True, want_noise_probs=True)
-        x0i = x0.to(torch.int32).contiguous()
-        x_t = torch.where(free, native.noise_categorical(probs, x0i, seed=_seed()), x0i)
-        _, _, x_tilde = native.xtilde_sample_masked(rate, x_t, free, seed=_seed())
-        return qt0, qT, rate, x_t.long(), x_tilde.long()
+        return _noise_masked(model, x0, free, ts, True)
 
     def calc_loss(self, minibatch, state=None, label=None):
-        import lib.losses.masks as masks
         state, minibatch = _unpack(minibatch, state)
-        minibatch = _flatten(minibatch)
-        D = self.cfg.model.concat_dim
-        if minibatch.dim() != 2 or minibatch.shape[1] != D or minibatch.shape[0] < 1:
-            raise ValueError(f"InpaintCTElbo: minibatch of shape {tuple(minibatch.shape)}, model.concat_dim = {D}")
-        B = int(minibatch.shape[0])
-        if _FIXED_NOISE is not None and "free" in _FIXED_NOISE:
-            masks.check_mask_config(self.cfg, D)
-            free_host = torch.as_tensor(_FIXED_NOISE["free"]).cpu()
-            if free_host.dtype != torch.bool or tuple(free_host.shape) != (B, D):
-                raise ValueError(f"InpaintCTElbo: pinned free mask {free_host.dtype} {tuple(free_host.shape)}, expected bool {(B, D)}")
-        else:
-            free_host = masks.sample_free(self.cfg, B, D)
-        n_free = int(free_host.sum())                                  # on the host: the cross-entropy weight is a plain float
+        x0, free, n_free = _free_rows("InpaintCTElbo", self.cfg, minibatch)
+        B = int(x0.shape[0])
         model = state["model"]
-        x0 = minibatch.long()
-        # the step's one upload of the mask: from pinned memory, asynchronous -- a pageable copy would make the host wait for the device
-        free = free_host.pin_memory().to(x0.device, non_blocking=True) if x0.is_cuda else free_host
         ts = _draw_ts(B, model.device, self.min_time, 1.0)
         qt0, qT, rate, x_t, x_tilde = self._noise(model, x0, free, ts)
         eps, nll_scale = float(self.ratio_eps), float(self.nll_weight) / max(n_free, 1)
@@ -602,3 +618,204 @@ class ScoreElbo:
         sig_norm = torch.sum(outer_rate * q_x0 / (Z * q_x0_xt), dim=(1, 2))
         neg_elbo = torch.mean(-outer / sig_norm) + torch.mean(reg_term)
         return neg_elbo + self.nll_weight * (torch.sum(-ll_xt) / B)
+
+
+# ---------------------------------------------------------------- inpainting objectives of the sequence (SDDM) models
+class _CrmMaskedFn(torch.autograd.Function):
+    """K12 on the free rows (ctdd_crm_loss_masked), direct logits: the CE term rides in the same launch."""
+
+    @staticmethod
+    def forward(ctx, logits, xt, x0, free, qt0, loss_type, scale, nll_scale):
+        i32 = lambda t: None if t is None else t.to(torch.int32).contiguous()
+        val, grad = native.crm_loss_masked(logits.detach().float().contiguous(), i32(xt), i32(x0), free,
+                                           None if qt0 is None else qt0.float().contiguous(), loss_type, scale, nll_scale)
+        ctx.save_for_backward(grad)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 7
+
+
+class _CrmRevMaskedFn(torch.autograd.Function):
+    """The CRM objectives on the free rows for the reverse logit types: ctdd_logprob -> ctdd_crm_loss_ll_masked -> ctdd_logprob_bwd
+    (a zero d/d ll_all row comes out as a zero logit-gradient row).  The cross-entropy term is on the raw logits: with x0 given
+    it is one more ctdd_crm_loss_masked pass (loss_type rm, scale 0)."""
+
+    @staticmethod
+    def forward(ctx, logits, xt, x0, free, qt0, qt0T, logit_type, loss_type, scale, nll_scale):
+        lg = logits.detach().float().contiguous()
+        xti = xt.to(torch.int32).contiguous()
+        tidx = torch.arange(lg.shape[0], dtype=torch.int32, device=lg.device)
+        ll_all, _ = native.logprob(lg, xti, qt0, logit_type, tidx, qt0T=qt0T)
+        val, dll = native.crm_loss_ll_masked(ll_all, xti, free, qt0 if loss_type == "elbo" else None, loss_type, scale)
+        grad, _ = native.logprob_bwd(logit_type, lg, qt0, qt0T, dll, ll_all=ll_all)
+        if x0 is not None:
+            ce, grad_ce = native.crm_loss_masked(lg, xti, x0.to(torch.int32).contiguous(), free, None, "rm", 0.0, nll_scale)
+            val, grad = val + ce, grad.add_(grad_ce)
+        ctx.save_for_backward(grad)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 9
+
+
+class _ScoreElboMaskedFn(torch.autograd.Function):
+    """ScoreElbo on the free rows (ctdd_score_elbo_loss_masked), direct logits."""
+
+    @staticmethod
+    def forward(ctx, logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale):
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        val, grad = native.score_elbo_loss_masked(logits.detach().float().contiguous(), i32(x0), i32(x_tilde), i32(reg_x), free,
+                                                  qt0.contiguous(), rate.contiguous(), eps, nll_scale)
+        ctx.save_for_backward(grad)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 8
+
+
+class _ScoreElboRevMaskedFn(torch.autograd.Function):
+    """ScoreElbo on the free rows for the reverse logit types (the same three-launch chain around ctdd_score_elbo_loss_ll_masked)."""
+
+    @staticmethod
+    def forward(ctx, logits, x0, x_tilde, reg_x, free, qt0, qt0T, rate, logit_type, eps, nll_scale):
+        lg = logits.detach().float().contiguous()
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        tidx = torch.arange(lg.shape[0], dtype=torch.int32, device=lg.device)
+        ll_all, _ = native.logprob(lg, i32(x_tilde), qt0, logit_type, tidx, qt0T=qt0T)
+        val, dll = native.score_elbo_loss_ll_masked(ll_all, i32(x0), i32(x_tilde), i32(reg_x), free, qt0, rate.contiguous(), eps, nll_scale)
+        grad, _ = native.logprob_bwd(logit_type, lg, qt0, qt0T, dll, ll_all=ll_all)
+        ctx.save_for_backward(grad)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 10
+
+
+def _crm_terms_masked(cfg, model, logits, x_t, ts, x0, free, nll_scale):
+    """(1 - ce_coeff)/B * sum_free crm_bd + nll_scale * sum_free CE(logits_bd, x0_bd) in plain torch: full-shape operands, the sums
+    over the free rows (`free` (B, D) bool) only."""
+    ll_all, ll_xt = get_logprob_with_logits(cfg, model, x_t, ts, logits)
+    per_row = _crm_loss(cfg, model, x_t, ts, ll_all, ll_xt)
+    out = torch.where(free, per_row, torch.zeros_like(per_row)).sum() * ((1.0 - cfg.loss.ce_coeff) / x_t.shape[0])
+    if nll_scale:
+        ce = F.cross_entropy(logits.permute(0, 2, 1), x0, reduction="none")
+        out = out + nll_scale * torch.where(free, ce, torch.zeros_like(ce)).sum()
+    return out
+
+
+def _score_elbo_terms_masked(cfg, model, logits, x0, reg_x, x_tilde, ts, free, qt0, rate, eps, nll_weight):
+    """ScoreElbo with every sum over dimensions restricted to the sample's free rows: per sample the objective of its free rows
+    alone; a sample without a free row contributes zero.  Full-shape operands."""
+    B = x0.shape[0]
+    n = torch.arange(B, device=x0.device).view(B, 1)
+    rT = rate.transpose(1, 2)
+    rows = lambda v: torch.where(free, v, torch.zeros_like(v)).sum(1)         # (B, D) -> (B): the free rows only
+    ll_all, ll_xt = get_logprob_with_logits(cfg, model, x_tilde, ts, logits)
+    d = ll_all - ll_xt.unsqueeze(-1)
+    reg_term = rows(torch.sum(torch.exp(d) * _masked_rows(rT, reg_x), dim=2))
+    outer_rate = _masked_rows(rT, x_tilde)
+    q_x0 = qt0[n, x0]
+    q_x0_xt = torch.gather(q_x0, -1, x_tilde.unsqueeze(-1)) + eps
+    outer = rows(torch.sum(outer_rate * (q_x0 / q_x0_xt) * d, dim=2))
+    row_sums = -torch.diagonal(rate, dim1=1, dim2=2)
+    base_tmp = row_sums[n, x_tilde]
+    Z = rows(base_tmp).view(B, 1, 1) - base_tmp.unsqueeze(-1) + row_sums.unsqueeze(1)
+    Z = torch.where(free.unsqueeze(-1), Z, torch.ones_like(Z))                # (a held row's Z is not a normaliser of anything)
+    sig_norm = rows(torch.sum(outer_rate * q_x0 / (Z * q_x0_xt), dim=2))
+    some = free.any(dim=1)
+    sig = torch.where(some, -outer / torch.where(some, sig_norm, torch.ones_like(sig_norm)), torch.zeros_like(outer))
+    return torch.mean(sig) + torch.mean(reg_term) + nll_weight * (rows(-ll_xt).sum() / B)
+
+
+def _fused_reverse(cfg, logits):
+    return (cfg.loss.logit_type in ("reverse_prob", "reverse_logscale") and logits.is_cuda and logits.shape[-1] <= 256
+            and getattr(cfg.loss, "fused", True))
+
+
+@losses_utils.register_loss
+class InpaintCatRM:
+    """Categorical ratio matching of a per-sample set of free entries given the held ones: what a hollow / masked transformer must
+    be trained with for `inpaint(model, x_known, mask)` of the CRM samplers.  cfg.loss.mask names the mask distribution
+    (lib/losses/masks.py); loss_type rm / mle / elbo, logit_type, ce_coeff are CatRM's, nll_weight (default 0) CatRMNLL's.
+
+    With free set F_b of sample b and n_free = sum_b |F_b|:  x_t = x0 on held entries, ~ q_{t|0} on free ones;  the network sees
+    the full state (held values, not the mask);  t ~ U(min_time, 1) clamped to 0.99999;
+      loss = (1 - ce_coeff)/B * sum_b sum_{d in F_b} crm_bd + nll_weight * (sum_b sum_{d in F_b} CE(l_bd, x0_bd)) / n_free.
+    With an all-free mask this is CatRM (nll_weight = 0) or CatRMNLL's objective."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.min_time = cfg.loss.min_time
+        self.nll_weight = getattr(cfg.loss, "nll_weight", 0.0) or 0.0
+        self.mask = cfg.loss.mask
+
+    def calc_loss(self, minibatch, state=None, label=None):
+        state, minibatch = _unpack(minibatch, state)
+        cfg = self.cfg
+        if cfg.loss.loss_type not in ("rm", "mle", "elbo"):
+            raise ValueError(f"InpaintCatRM: loss.loss_type must be rm, mle or elbo, got {cfg.loss.loss_type!r}")
+        if cfg.loss.logit_type not in native.LOGIT_TYPES:
+            raise ValueError(f"InpaintCatRM: unknown loss.logit_type {cfg.loss.logit_type!r}")
+        x0, free, n_free = _free_rows("InpaintCatRM", cfg, minibatch)
+        B = int(x0.shape[0])
+        model = state["model"]
+        ts = torch.clamp(_draw_ts(B, model.device, self.min_time, 1.0), max=0.99999)
+        qt0, qT, _, x_t, _ = _noise_masked(model, x0, free, ts, False)
+        logits = model(x_t, ts)
+        scale, nll_scale = (1.0 - cfg.loss.ce_coeff) / B, float(self.nll_weight) / max(n_free, 1)
+        x0_ce = x0 if nll_scale else None
+        if cfg.loss.logit_type == "direct" and logits.is_cuda and getattr(cfg.loss, "fused", True):
+            return _CrmMaskedFn.apply(logits, x_t, x0_ce, free, qt0 if cfg.loss.loss_type == "elbo" else None, cfg.loss.loss_type,
+                                      scale, nll_scale)
+        if _fused_reverse(cfg, logits):
+            return _CrmRevMaskedFn.apply(logits, x_t, x0_ce, free, qt0.contiguous(), qT, cfg.loss.logit_type, cfg.loss.loss_type,
+                                         scale, nll_scale)
+        return _crm_terms_masked(cfg, model, logits, x_t, ts, x0, free, nll_scale)      # (CPU, S > 256, cfg.loss.fused = False)
+
+
+@losses_utils.register_loss
+class InpaintScoreElbo:
+    """ScoreElbo of a per-sample set of free entries given the held ones (cfg.loss.mask: lib/losses/masks.py; the other fields
+    are ScoreElbo's).  x_t = x0 on held entries, ~ q_{t|0} on free ones;  x~ moves one free entry of x_t, chosen with probability
+    rs[x_t^d] / sum_{d' in F_b} rs[x_t^d'];  reg_x = x~ with one forward pass and x_t with two, logits = model(reg_x, ts);
+      loss = (1/B) sum_b (-outer_b / norm_b + reg_b) + (nll_weight/B) sum_b sum_{d in F_b} -ll_xt_bd
+    with reg, outer, norm and the base sum inside Z over F_b only; a sample without a free row contributes zero.  With an all-free
+    mask this is ScoreElbo."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.ratio_eps = cfg.loss.eps_ratio
+        self.nll_weight = cfg.loss.nll_weight
+        self.min_time = cfg.loss.min_time
+        self.one_forward_pass = cfg.loss.one_forward_pass
+        self.mask = cfg.loss.mask
+
+    def calc_loss(self, minibatch, state=None, label=None):
+        state, minibatch = _unpack(minibatch, state)
+        cfg = self.cfg
+        if cfg.loss.logit_type not in native.LOGIT_TYPES:
+            raise ValueError(f"InpaintScoreElbo: unknown loss.logit_type {cfg.loss.logit_type!r}")
+        x0, free, _ = _free_rows("InpaintScoreElbo", cfg, minibatch)
+        B = int(x0.shape[0])
+        model = state["model"]
+        eps = float(self.ratio_eps)
+        ts = torch.clamp(_draw_ts(B, model.device, self.min_time, 1.0), max=0.99999)
+        qt0, qT, rate, x_t, x_tilde = _noise_masked(model, x0, free, ts, True)
+        reg_x = x_tilde if self.one_forward_pass else x_t
+        logits = model(reg_x, ts)
+        fused = logits.is_cuda and logits.shape[-1] <= 256 and getattr(cfg.loss, "fused", True)
+        if cfg.loss.logit_type == "direct" and fused:
+            return _ScoreElboMaskedFn.apply(logits, x0, x_tilde, reg_x, free, qt0, rate, eps, float(self.nll_weight) / B)
+        if _fused_reverse(cfg, logits):
+            return _ScoreElboRevMaskedFn.apply(logits, x0, x_tilde, reg_x, free, qt0.contiguous(), qT, rate, cfg.loss.logit_type, eps,
+                                               float(self.nll_weight) / B)
+        return _score_elbo_terms_masked(cfg, model, logits, x0, reg_x, x_tilde, ts, free, qt0, rate, eps, self.nll_weight)

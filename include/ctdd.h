@@ -338,6 +338,31 @@ int ctdd_logprob_bwd(int logit_type, const float* logits, const float* qt0, cons
                      const int32_t* x0, float nll_scale, int B, int D, int S, float* grad_logits, double* ce_rows,
                      float* out_ce, void* stream);
 
+/* ---- K12 / ScoreElbo under a per-sample mask of free rows (inpainting training of the sequence models: InpaintCatRM,
+ * InpaintScoreElbo).  Each entry is its unmasked sibling plus free (B,D) uint8, non-zero = free; every other operand keeps its
+ * full shape and meaning.  Held rows are left out of every sum over rows or dimensions; their gradient rows are exact zeros,
+ * written by the call (every element of the gradient buffer is written; the logits are never written); a held row's wave
+ * returns before any exp, log or table read.  A free row's arithmetic is the unmasked kernel's.
+ *   ctdd_crm_loss_masked      out_loss = scale * sum_{(b,d) free} loss_bd + nll_scale * sum_{(b,d) free} -log_softmax(logits)[x0]
+ *   ctdd_crm_loss_ll_masked   the first sum on ll_all; grad_ll = d out_loss / d ll_all (zero rows stay zero rows through
+ *                             ctdd_logprob_bwd / ctdd_logprob_rp_bwd_mfma)
+ *   ctdd_score_elbo_loss_masked / _ll_masked
+ *                             out_loss = mean_b(-sig_b / norm_b) + mean_b(reg_b) + nll_scale * sum_{(b,d) free} -ll[x~], with sig_b,
+ *                             norm_b, reg_b and the base_sum inside Z summed over the free rows of sample b; a sample without a
+ *                             free row adds zero.  S <= 256; scratch: ctdd_ctelbo_scratch_bytes(B,D,S).
+ * A null free, B, D or S out of range and elbo without qt0 are refused before any launch. */
+int ctdd_crm_loss_masked(const float* logits, const int32_t* xt, const int32_t* x0, const uint8_t* free, const float* qt0,
+                         int B, int D, int S, int loss_type, float scale, float nll_scale, float* grad_logits,
+                         double* row_scratch, float* out_loss, void* stream);
+int ctdd_crm_loss_ll_masked(const float* ll_all, const int32_t* xt, const uint8_t* free, const float* qt0, int B, int D, int S,
+                            int loss_type, float scale, float* grad_ll, double* row_scratch, float* out_loss, void* stream);
+int ctdd_score_elbo_loss_masked(const float* logits, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x,
+                                const uint8_t* free, const float* qt0, const float* rate, int B, int D, int S, float eps,
+                                float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream);
+int ctdd_score_elbo_loss_ll_masked(const float* ll_all, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x,
+                                   const uint8_t* free, const float* qt0, const float* rate, int B, int D, int S, float eps,
+                                   float nll_scale, void* scratch, float* grad_ll, float* out_loss, void* stream);
+
 /* ---- K28: clip_grad_norm_ + Adam.step + EMA update over all parameter tensors in two launches
  * (lib/training/training.py:17-40, lib/models/models.py:745-758, torch.optim.Adam single-tensor formulas).
  * tensors: device array of ctdd_opt_tensor; chunks: device array of ctdd_opt_chunk covering every tensor in
