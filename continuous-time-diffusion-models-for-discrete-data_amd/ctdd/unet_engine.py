@@ -85,6 +85,7 @@ def _lib():
                            ("ctdd_unet_time", [_P, _P, _P, _I, _P, _P]), ("ctdd_unet_time_uniform", [_P, _P, _P, _I, _P, _P]),
                            ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_resblock_small", [_P, _I, _P]),
                            ("ctdd_unet_resblock_mid", [_P, _I, _P]), ("ctdd_unet_conv_rows", [_P, _I, _P]),
+                           ("ctdd_unet_conv_rows_head", [_P, _I, _P]),
                            ("ctdd_unet_logistic_head", [_P, _P])):
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argt, _I
@@ -194,6 +195,29 @@ def conv_rows_covers(H, W, cs, rcs, cout, G, residual=False):
     channels (<= 384 per concatenation), groups dividing the GroupNorm channels, 1x1 segments or a residual but not both."""
     return bool(H >= 1 and 1 <= W <= 28 and cout == 96 and 1 <= len(cs) <= 2 and len(rcs) <= 2 and all(c > 0 and c % 32 == 0 for c in [*cs, *rcs])
                 and sum(cs) <= 384 and sum(rcs) <= 384 and G > 0 and sum(cs) % G == 0 and not (rcs and residual))
+
+
+def pack_conv_rows_head_weights(w, C1):
+    """ctdd_unet_conv_rows_head's [N][9 C1] matrix: zero-padded to 96 ceil(N / 96) rows, then pack_row_tile_weights in two streams per
+    96-channel pass (pass p reads streams 2 p and 2 p + 1, which lie one after the other).  Returned as [96 passes][9 C1]."""
+    N, passes = w.shape[0], -(-w.shape[0] // 96)
+    wp = torch.zeros((96 * passes, w.shape[1]), dtype=w.dtype, device=w.device)
+    wp[:N] = w
+    return pack_row_tile_weights(wp, [C1], [], 2 * passes)
+
+
+# default of cfg.model.head_rows_min_wgs (UNetEngine._runs_head_rows): the grid of ctdd_unet_conv_rows_head (one workgroup per sample
+# and band of 14 rows) from which the one launch replaces the head's ctdd_unet_gn_apply + ctdd_unet_conv_ring pair.  Graph replay of
+# one MNIST plan, pair | one launch (tools/conv_table.py, twice per side from batch 64 on; DESIGN.md section 5): batch 16 (32
+# workgroups) 1154 | 1188 us, batch 32 (64) 1234 | 1265 us, batch 64 (128) 1360-1364 | 1362-1371 us, batch 96 (192) 1527-1528 |
+# 1503-1508 us, batch 128 (256) 1558-1563 | 1519-1522 us: the smallest measured grid at which the one launch wins
+HEAD_ROWS_MIN_WGS = 192
+
+
+def conv_rows_head_covers(H, W, C1, N, G):
+    """Shapes ctdd_unet_conv_rows_head takes (csrc/unet_head_kernels.hip): rows of <= 28 pixels, one GroupNorm source of 32, 64 or 96
+    channels whose groups divide it, 32 .. 576 output channels in multiples of 32."""
+    return bool(H >= 1 and 1 <= W <= 28 and C1 in (32, 64, 96) and G > 0 and C1 % G == 0 and 32 <= N <= 576 and N % 32 == 0)
 
 
 def fold_upsample_weights(w):
@@ -498,6 +522,25 @@ class _PlanBuilder:
         self.launch(lib.ctdd_unet_conv_rows, C.byref(a), 0, label=f"{Hc}x{Wc} K={Ktot} N={N} gn+conv rows C={cs} raw={rcs}",
                     flops=2 * B * Hc * Wc * N * Ktot)
 
+    def conv_rows_head(self, src, norm, oc, logits):
+        """GroupNorm `norm` + Swish of `src` and the output convolution `oc` into the bf16 (B, H W, N) `logits` as ONE
+        ctdd_unet_conv_rows_head launch: the head's gn_apply + conv pair without the activated tensor."""
+        eng, B = self.eng, self.B
+        N, C1 = oc.weight.shape[0], src.C
+        a = _ConvRowsArgs()
+        a.s1_bf16, a.C1 = ptr(src.hi), C1
+        self.stats_views.append((a, src.stats, "st1"))
+        g, b_ = norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()
+        a.gamma, a.beta, a.G, a.eps = ptr(g), ptr(b_), norm.num_groups, norm.eps
+        w, _ = eng._pack(pack_conv_rows_head_weights(eng._w2d([(oc.weight, 0)], [(None, C1, SEG_3x3)]), C1))
+        bias = oc.bias.detach().float().contiguous()
+        a.w, a.bias, a.out_bf16 = ptr(w), ptr(bias), ptr(logits)
+        a.B, a.H, a.W, a.N = B, src.H, src.W, N
+        self.keep.extend([g, b_, w, bias, a])
+        # (flops: the unpadded N; the channels past N that the last pass computes are not the network's)
+        self.launch(self.lib.ctdd_unet_conv_rows_head, C.byref(a), 0, label=f"{src.H}x{src.W} K={9 * C1} N={N} gn+conv rows head C={[C1]}",
+                    flops=2 * B * src.H * src.W * N * 9 * C1)
+
     def conv2_operands(self, rb, a2, srcs):
         """conv2 of a ResBlock as ONE K-segmented convolution: the 3x3 segment on the activated tensor `a2` (None where the kernel
         makes it itself) and, for a block with a linear skip, a 1x1 segment on each raw source.  Returns segs, wsrc, the bias
@@ -728,7 +771,6 @@ class _PlanBuilder:
         """Output GroupNorm + convolution into st.logits (logistic_pars: into st.net_out, then the logistic head)."""
         eng, tc, B, st, m, net, dev, (Cin, H0, W0) = self.eng, self.tc, self.B, self.st, self.m, self.net, self.dev, self.shape
         S = net.S
-        ao = self.gn_apply([cur], net.out[0], True, net.out[0].eps, cur.H * cur.W)
         oc = net.out[2]
         n_out = oc.weight.shape[0]
         D = Cin * H0 * W0
@@ -737,6 +779,13 @@ class _PlanBuilder:
         ldt = torch.bfloat16 if logits_bf16 and not (logistic and (tc is not None or eng.precise or S % 4)) else torch.float32
         st.logits = logits_out if logits_out is not None else torch.empty((B, D, S), dtype=ldt, device=dev)
         assert st.logits.dtype == ldt
+        # the S-channel logits of a one-channel image are exactly [pixel][N]: GroupNorm + convolution as ONE ctdd_unet_conv_rows_head
+        # launch (csrc/unet_head_kernels.hip); cfg.model.head_rows = 0 keeps the pair
+        if (not logistic and Cin == 1 and ldt == torch.bfloat16 and cur.stats is not None
+                and eng._runs_head_rows(B, cur.H, cur.W, cur.C, n_out, net.out[0].num_groups, tc is not None)):
+            self.conv_rows_head(cur, net.out[0], oc, st.logits)
+            return
+        ao = self.gn_apply([cur], net.out[0], True, net.out[0].eps, cur.H * cur.W)
         if logistic:
             st.net_out = torch.empty((B * H0 * W0, n_out), dtype=torch.float32, device=dev)
             self.conv([(ao, ao.C, SEG_3x3)], [(oc.weight, 0)],
@@ -868,6 +917,15 @@ class UNetEngine:
         return bool(not training and not self.precise and int(getattr(m, "conv_rows", 1))
                     and conv_rows_covers(Hc, Wc, cs, rcs, cout, G, residual)
                     and B * -(-Hc // 14) >= int(getattr(m, "conv_rows_min_wgs", CONV_ROWS_MIN_WGS)))
+
+    def _runs_head_rows(self, B, Hc, Wc, C1, N, G, training):
+        """Whether the output head's GroupNorm + convolution pair runs as ONE ctdd_unet_conv_rows_head launch: bf16 inference only,
+        cfg.model.conv_rows and cfg.model.head_rows (both default on), a shape the kernel takes, and at least
+        cfg.model.head_rows_min_wgs workgroups (one per sample and band of 14 rows)."""
+        m = self.cfg.model
+        return bool(not training and not self.precise and int(getattr(m, "conv_rows", 1)) and int(getattr(m, "head_rows", 1))
+                    and conv_rows_head_covers(Hc, Wc, C1, N, G)
+                    and B * -(-Hc // 14) >= int(getattr(m, "head_rows_min_wgs", HEAD_ROWS_MIN_WGS)))
 
     def _onepass_gn_covers(self, B, training):
         """Whether ctdd_unet_gn_onepass has a slab for every GroupNorm launch a one-pass plan would hold at its small levels (the

@@ -145,6 +145,19 @@ typedef struct {
  * for tile = 0, 1, 2: the fragment of tap (dy, dx) on that block (27 (C1 + C2) / 32 fragments); then for each raw source, for each
  * 32-channel block of it, for tile = 0, 1, 2: the fragment of the 1x1 segment (3 (RC1 + RC2) / 32 fragments).  Nothing is padded. */
 int ctdd_unet_conv_rows(const void* conv_rows_args, int f32, void* stream);
+/* The output head of such a level on the same argument struct (csrc/unet_head_kernels.hip): GroupNorm + Swish + 3x3 convolution
+ * into N output channels in one launch,
+ *   out[b][y][x][0..N) = bf16(conv3x3(bf16(swish(GN(s1)))) + bias)
+ * the ctdd_unet_gn_apply + ctdd_unet_conv_ring pair without the activated tensor in memory, the rounding points of the pair.  One
+ * workgroup per (sample, band of 14 output rows) fills the slab of ctdd_unet_conv_rows once and runs ceil(N / 96) passes of 96
+ * output channels over it; the output row pitch is N elements and a pass writes channels [96 p, min(96 p + 96, N)) of a pixel.
+ * 1 <= W <= 28, any H, one GroupNorm source with statistics and C1 = 32, 64 or 96, G divides C1, N a multiple of 32 with
+ * 32 <= N <= 576, C2 = RC1 = RC2 = 0, res_bf16, tbias and out_stats null, 16-byte aligned tensors, f32 must be 0.  Anything else:
+ * CTDD_ERANGE / CTDD_EINVAL, nothing launched.
+ * Weights (ctdd/unet_engine.py: pack_conv_rows_head_weights): the [N][9 C1] matrix zero-padded to 96 ceil(N / 96) rows, in
+ * 2 ceil(N / 96) streams of ctdd_unet_conv_rows' order (stream s: output channels [48 s, 48 s + 48), 27 C1 / 32 fragments), one after
+ * the other: pass p reads streams 2 p and 2 p + 1.  Channels >= N are computed and never stored. */
+int ctdd_unet_conv_rows_head(const void* conv_rows_args, int f32, void* stream);
 
 typedef struct {
   const float* t; int B, ch, tdim;

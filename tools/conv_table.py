@@ -1,7 +1,11 @@
 """Per-launch table of the U-Net inference plan (one sub-batch plan as the sampler loop replays it): label, microseconds when the
 launch runs alone (HIP events, 5 repetitions), matrix TFLOP/s, share of the summed time.
 
-    python tools/conv_table.py [--batch 128] [--config mnist|cifar10]
+    python tools/conv_table.py [--batch 128] [--config mnist|cifar10] [--model-opt knob=value ...]
+
+--model-opt sets integer cfg.model knobs: head_rows=0 keeps the output head's ctdd_unet_gn_apply + ctdd_unet_conv_ring pair instead
+of the ctdd_unet_conv_rows_head step, head_rows_min_wgs=1 / conv_rows_min_wgs=1 take the grid-size rules out of the way below their
+default thresholds, conv_rows=0 keeps every 28x28 pair.
 """
 import argparse
 import os

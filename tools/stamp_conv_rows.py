@@ -1,6 +1,7 @@
-"""Phase durations of k_conv_rows (csrc/unet_rows_kernels.hip) from the stamps build (tools/build_conv_stamps.sh, -DCTDD_ROWS_STAMPS:
-thread 0 of every workgroup leaves s_memtime at the phase boundaries in the buffer passed as out_stats; the statistics are off in
-that build).  Printed as raw s_memtime ticks (shader cycles), mean / min / max over the workgroups of the third launch.
+"""Phase durations of k_conv_rows (csrc/unet_rows_kernels.hip) and k_conv_rows_head (csrc/unet_head_kernels.hip) from the stamps build
+(tools/build_conv_stamps.sh, -DCTDD_ROWS_STAMPS: thread 0 of every workgroup leaves s_memtime at the phase boundaries in the buffer
+passed as out_stats; the statistics are off in that build).  Printed as raw s_memtime ticks (shader cycles), mean / min / max over
+the workgroups of the third launch.
 
     bash tools/build_conv_stamps.sh && python tools/stamp_conv_rows.py [--batch 128]
 """
@@ -54,15 +55,48 @@ def run(lib, B, cs, rcs, res):
         print(f"   {nm:36s} mean {float(dur[:, i].mean()):8.0f}  min {float(dur[:, i].min()):8.0f}  max {float(dur[:, i].max()):8.0f}")
 
 
+def run_head(lib, B, C1, N):
+    """k_conv_rows_head at 28x28: [workgroups][16] stamps: entry, prologue, fill, then per pass its K loop and its epilogue / store."""
+    H = W = 28
+    M, K, npass = B * H * W, 9 * C1, -(-N // 96)
+    rn = lambda *s: torch.randn(s, device="cuda")
+    x = rn(M, C1).to(torch.bfloat16)
+    xd = x.double().view(B, H * W, -1)
+    st = torch.stack([xd.sum(1), (xd * xd).sum(1)], -1).contiguous()
+    w = ue.pack_conv_rows_head_weights((rn(N, K) / K ** 0.5).to(torch.bfloat16), C1)
+    gamma, beta, bias = torch.ones(C1, device="cuda"), torch.zeros(C1, device="cuda"), torch.zeros(N, device="cuda")
+    out = torch.empty((M, N), dtype=torch.bfloat16, device="cuda")
+    nwg = B * 2
+    buf = torch.zeros((nwg, 16), dtype=torch.int64, device="cuda")
+    a = ue._ConvRowsArgs()
+    a.s1_bf16, a.st1, a.C1 = x.data_ptr(), st.data_ptr(), C1
+    a.gamma, a.beta, a.G, a.eps, a.w, a.bias = gamma.data_ptr(), beta.data_ptr(), 32, 1e-5, w.data_ptr(), bias.data_ptr()
+    a.out_bf16, a.out_stats, a.B, a.H, a.W, a.N = out.data_ptr(), buf.data_ptr(), B, H, W, N
+    st_ = torch.cuda.current_stream().cuda_stream
+    for _ in range(3):
+        assert lib.ctdd_unet_conv_rows_head(C.byref(a), 0, st_) == 0, lib.ctdd_last_error().decode()
+    torch.cuda.synchronize()
+    d = buf.cpu().double()
+    nst = 3 + 2 * npass
+    dur = d[:, 1:nst] - d[:, 0:nst - 1]
+    names = ["prologue (zero fill, scale/shift)", "fill"] + [f"pass {p} {what}" for p in range(npass) for what in ("K loop", "epilogue + store")]
+    print(f"head B={B} 28x28 C1={C1} N={N}: {nwg} workgroups, per workgroup {float((d[:, nst - 1] - d[:, 0]).mean()):.0f} cycles")
+    for i, nm in enumerate(names):
+        print(f"   {nm:36s} mean {float(dur[:, i].mean()):8.0f}  min {float(dur[:, i].min()):8.0f}  max {float(dur[:, i].max()):8.0f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
     a = ap.parse_args()
     lib = C.CDLL(os.path.join(_R, "continuous-time-diffusion-models-for-discrete-data_amd", "librows_stamps.so"))
-    lib.ctdd_unet_conv_rows.argtypes, lib.ctdd_unet_conv_rows.restype = [C.c_void_p, C.c_int, C.c_void_p], C.c_int
+    for fn in (lib.ctdd_unet_conv_rows, lib.ctdd_unet_conv_rows_head):
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_int, C.c_void_p], C.c_int
     lib.ctdd_last_error.restype = C.c_char_p
     for cs, rcs, res in (([96], [], False), ([96], [], True), ([96, 96], [], False), ([192, 96], [], False), ([96], [96, 96], False)):
         run(lib, a.batch, cs, rcs, res)
+    for C1, N in ((96, 256), (96, 96)):
+        run_head(lib, a.batch, C1, N)
 
 
 if __name__ == "__main__":
