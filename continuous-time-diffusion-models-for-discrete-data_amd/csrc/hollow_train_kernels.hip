@@ -946,7 +946,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
       for (int r = 0; r < 16; r += 2) {
         const float p0 = __expf(sacc[r] - msafe), p1 = __expf(sacc[r + 1] - msafe);
         rs += p0 + p1;
-        pw[r >> 1] = ht_pack2((keep >> r) & 1u ? p0 * inv_keep : 0.0f, (keep >> (r + 1)) & 1u ? p1 * inv_keep : 0.0f);
+        // (the common factor 1 / (1 - p) joins the fp32 epilogue: folded into the bf16 operand its rounding -- 4/3 -> 1.3359 --
+        //  biased out, and with it D_i = dO.O, against the backward's fp32 rescale of dP)
+        pw[r >> 1] = ht_pack2((keep >> r) & 1u ? p0 : 0.0f, (keep >> (r + 1)) & 1u ? p1 : 0.0f);
       }
       rs += __shfl_xor(rs, 32, WAVE);
       l = l * corr + rs;
@@ -969,7 +971,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
   }
   if (!qok) return;
   if (!BWD && kh == 0) { st[0] = m; st[1] = l; }
-  const float f = BWD ? a.scale : 1.0f / l;
+  const float f = BWD ? a.scale : inv_keep / l;
   const size_t oo = BWD ? (size_t)b * a.dq_bs + (size_t)i * a.dq_rs + h * HD : ((size_t)b * a.Tq + i) * a.out_rs + h * HD;
   float* o32 = BWD ? a.dq : a.out;
   unsigned short* o16 = BWD ? a.dq_bf16 : a.out_bf16;
@@ -1092,7 +1094,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         const bool ok = (okm >> (r + e)) & 1u;
         const float pr = ok ? __expf(sacc[r + e] - Sm[il]) * Sl[il] : 0.0f;
         const bool kp = (keep >> (r + e)) & 1u;
-        p[e] = kp ? pr * inv_keep : 0.0f;
+        p[e] = kp ? pr : 0.0f;                                                  // (dV's 1 / (1 - p) in the fp32 epilogue, as the forward's)
         ds[e] = pr * ((kp ? pacc[r + e] * inv_keep : 0.0f) - Sd[il]);
       }
       pw[r >> 1] = ht_pack2(p[0], p[1]);
@@ -1113,7 +1115,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int d0 = 8 * r4 + 4 * kh;
     if (d0 < HD) {
       const float4 kv = make_float4(kacc[4 * r4], kacc[4 * r4 + 1], kacc[4 * r4 + 2], kacc[4 * r4 + 3]);
-      const float4 vv = make_float4(vacc[4 * r4], vacc[4 * r4 + 1], vacc[4 * r4 + 2], vacc[4 * r4 + 3]);
+      const float4 vv = make_float4(vacc[4 * r4] * inv_keep, vacc[4 * r4 + 1] * inv_keep, vacc[4 * r4 + 2] * inv_keep, vacc[4 * r4 + 3] * inv_keep);
       if (a.dk) *(float4*)(a.dk + ok_ + d0) = kv;
       if (a.dv) *(float4*)(a.dv + ov + d0) = vv;
       if (a.dk_bf16) *(uint2*)(a.dk_bf16 + ok_ + d0) = make_uint2(ht_pack2(kv.x, kv.y), ht_pack2(kv.z, kv.w));
@@ -1304,7 +1306,9 @@ extern "C" int ctdd_hollow_layernorm_bwd(const void* args_, void* stream) {
   else { HD_DISPATCH_(KERNEL, false, GRIDX) }
 static int attn_check(const AttnTrainArgs& a) {
   CTDD_REQUIRE(a.q && a.k && a.v && a.out && a.stats, CTDD_EINVAL, "attention (training): null buffer");
-  CTDD_REQUIRE(a.mode >= 0 && a.mode <= 3 && (a.mode != 2 || a.Tk == 2 * a.Tq + 1), CTDD_EINVAL, "attention (training): mode %d Tq=%d Tk=%d", a.mode, a.Tq, a.Tk);
+  CTDD_REQUIRE(a.mode >= 0 && a.mode <= 3 && a.Tq > 0 && a.Tk > 0 && (a.mode != 2 || a.Tk == 2 * a.Tq + 1) && (a.mode >= 2 || a.Tk == a.Tq),
+               CTDD_EINVAL, "attention (training): mode %d Tq=%d Tk=%d", a.mode, a.Tq, a.Tk);     // (the inference launchers' shape rules)
+  CTDD_REQUIRE(a.B > 0 && a.H > 0, CTDD_EINVAL, "attention (training): B=%d H=%d", a.B, a.H);
   CTDD_REQUIRE(a.drop_p >= 0.0f && a.drop_p < 1.0f && (a.drop_p == 0.0f || a.rng), CTDD_EINVAL, "attention (training): dropout %g", (double)a.drop_p);
   return CTDD_OK;
 }

@@ -33,7 +33,8 @@ int ctdd_hollow_layernorm_bwd(const void* ln_bwd_args, void* stream);
  * forward with dropout on the probabilities (nn.MultiheadAttention's attention dropout), `stats` [B][H][Tq][4] receives the
  * softmax row maximum and sum; backward (two launches, no atomics: dQ per query, dK / dV per key, scores recomputed).
  * mode 0 causal, 1 anti-causal, 2 readout (Tk == 2 Tq + 1), 3 unmasked (every key j < Tk for every query i < Tq, Tq and Tk
- * independent: the single-stream transformers' encoder); any other mode returns CTDD_EINVAL and launches nothing. */
+ * independent: the single-stream transformers' encoder); any other mode, a non-positive B, H, Tq or Tk, and Tk != Tq in the
+ * modes 0 / 1 return CTDD_EINVAL and launch nothing. */
 typedef struct {
   const float* q; const float* k; const float* v; int64_t q_bs, k_bs, v_bs; int q_rs, k_rs, v_rs;
   int B, Tq, Tk, H, hd, mode; float scale; float* out; int out_rs; float* stats;
