@@ -68,6 +68,11 @@ class _AttnArgs(C.Structure):
     _fields_ = [("qkv", _P), ("B", _I), ("T", _I), ("C", _I), ("heads", _I), ("out_hi", _P), ("out_f32", _P)]
 
 
+class _AttnBlockArgs(C.Structure):
+    _fields_ = [("an_bf16", _P), ("x_bf16", _P), ("w_qkv", _P), ("b_qkv", _P), ("w_proj", _P), ("b_proj", _P), ("B", _I), ("T", _I),
+                ("C", _I), ("heads", _I), ("out_bf16", _P)]
+
+
 class _LogisticArgs(C.Structure):
     _fields_ = [("net", _P), ("x0", _P), ("B", _I), ("C", _I), ("HW", _I), ("S", _I), ("fix", _I), ("out", _P), ("fast", _I), ("out_bf16", _P)]
 
@@ -83,7 +88,8 @@ def _lib():
                            ("ctdd_unet_conv_up_phases", [_P, _I, _P]), ("ctdd_unet_upsample2x", [_P, _I, _I, _I, _I, _P, _P]), ("ctdd_unet_first_conv", [_P, _P]),
                            ("ctdd_unet_gn_apply", [_P, _P]), ("ctdd_unet_gn_onepass", [_P, _I, _I, _P]), ("ctdd_unet_channel_stats", [_P, _I, _I, _I, _P, _P]),
                            ("ctdd_unet_time", [_P, _P, _P, _I, _P, _P]), ("ctdd_unet_time_uniform", [_P, _P, _P, _I, _P, _P]),
-                           ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_resblock_small", [_P, _I, _P]),
+                           ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_attention_block", [_P, _I, _P]),
+                           ("ctdd_unet_resblock_small", [_P, _I, _P]),
                            ("ctdd_unet_resblock_mid", [_P, _I, _P]), ("ctdd_unet_conv_rows", [_P, _I, _P]),
                            ("ctdd_unet_conv_rows_head", [_P, _I, _P]),
                            ("ctdd_unet_logistic_head", [_P, _P])):
@@ -135,6 +141,21 @@ def pack_resblock_weights(w2d):
     N, K = w2d.shape
     assert N == 192 and K % 64 == 0
     return w2d.reshape(4, 3, 16, K // 64, 2, 4, 8).permute(0, 3, 1, 4, 5, 2, 6).contiguous().reshape(N, K)
+
+
+def attention_block_covers(T, Cn, heads):
+    """Shapes ctdd_unet_attention_block holds (csrc/unet_attn_kernels.hip): a sample of <= 64 tokens, 192 channels in 8 heads (the
+    heads' fp32 [q | k | v] regions of 64 tokens fill 152 KiB of the CU's 160 KiB of LDS)."""
+    return bool(1 <= T <= 64 and Cn == 192 and heads == 8)
+
+
+def pack_attention_weights(w2d):
+    """[N][C] (N % 64 == 0, C % 32 == 0: the qkv or proj matrix of the attention block) -> the fragment order ctdd_unet_attention_block
+    streams (include/ctdd_unet.h): [wave][k step][tile][q][i][8], wave w holding output channels [N / 4 w, N / 4 (w + 1)), so that every
+    wave-instruction of the weight stream reads 1 KiB of consecutive bytes."""
+    N, K = w2d.shape
+    assert N % 64 == 0 and K % 32 == 0
+    return w2d.reshape(4, N // 64, 16, K // 32, 4, 8).permute(0, 3, 1, 4, 2, 5).contiguous().reshape(N, K)
 
 
 def resblock_mid_covers(H, W, cs, cout, G1, G2):
@@ -635,6 +656,11 @@ class _PlanBuilder:
         T = x.H * x.W
         an = self.gn_apply([x], att.norm, False, att.norm.eps, T)
         Cx = x.C
+        # bf16 inference behind a one-pass GroupNorm: qkv, softmax and proj as ONE ctdd_unet_attention_block launch
+        # (csrc/unet_attn_kernels.hip: one workgroup per sample, qkv and the attention output stay in LDS);
+        # cfg.model.attention_fused = 0 keeps the three launches below
+        if self.onepass_gn and T <= self.no_stats_hw and self.eng._fuses_attention(att, T, Cx, tc is not None):
+            return self.attention_fused(att, x, an)
         qkv = torch.empty((B * T, 3 * Cx), dtype=torch.float32, device=self.dev)
         self.keep.append(qkv)
         self.conv([(an, Cx, SEG_1x1)], [(att.qkv.weight, 0)],
@@ -650,6 +676,21 @@ class _PlanBuilder:
         y = _Tensor(self, x.H, x.W, Cx)
         self.conv([(ao, Cx, SEG_1x1)], [(att.proj_out.weight, 0)],
                   att.proj_out.bias.detach().float().contiguous(), Cx, x.H, x.W, x.H, x.W, y, res=x, bias_params=[att.proj_out.bias])
+        return y
+
+    def attention_fused(self, att, x, an):
+        """The block behind its GroupNorm as ONE ctdd_unet_attention_block launch: the two 1x1 matrices in the kernel's fragment order."""
+        eng, B, T, Cx = self.eng, self.B, x.H * x.W, x.C
+        y = _Tensor(self, x.H, x.W, Cx)
+        (wq, _), (wp, _) = (eng._pack(pack_attention_weights(w.detach().float().reshape(w.shape[0], Cx))) for w in (att.qkv.weight, att.proj_out.weight))
+        bq, bp = att.qkv.bias.detach().float().contiguous(), att.proj_out.bias.detach().float().contiguous()
+        a = _AttnBlockArgs()
+        a.an_bf16, a.x_bf16, a.w_qkv, a.b_qkv, a.w_proj, a.b_proj = ptr(an.hi), ptr(x.hi), ptr(wq), ptr(bq), ptr(wp), ptr(bp)
+        a.B, a.T, a.C, a.heads, a.out_bf16 = B, T, Cx, att.num_heads, ptr(y.hi)
+        self.keep.extend([wq, bq, wp, bp, a])
+        # (flops: the two convolutions the launch replaces)
+        self.launch(self.lib.ctdd_unet_attention_block, C.byref(a), 0, label=f"{x.H}x{x.W} attention block C={Cx} heads={att.num_heads}",
+                    flops=2 * B * T * Cx * (3 * Cx + Cx))
         return y
 
     def time(self, uniform_t):
@@ -908,6 +949,12 @@ class UNetEngine:
                     and Hc * Wc <= self._onepass_max_hw()
                     and not resblock_small_covers(Hc, Wc, cs, rb.conv1.weight.shape[0], rb.norm1.num_groups, rb.norm2.num_groups)
                     and resblock_mid_covers(Hc, Wc, cs, rb.conv1.weight.shape[0], rb.norm1.num_groups, rb.norm2.num_groups))
+
+    def _fuses_attention(self, att, T, Cn, training):
+        """Whether a plan with one-pass GroupNorm runs the attention block's qkv, softmax and proj as ONE ctdd_unet_attention_block
+        launch: bf16 inference only (training records the fp32 qkv), cfg.model.attention_fused (default on), a shape the kernel holds."""
+        return bool(not training and not self.precise and int(getattr(self.cfg.model, "attention_fused", 1))
+                    and attention_block_covers(T, Cn, att.num_heads))
 
     def _runs_conv_rows(self, B, Hc, Wc, cs, rcs, cout, G, residual, training):
         """Whether a GroupNorm + convolution pair of the four-launch ResBlock runs as ONE ctdd_unet_conv_rows launch: bf16 inference

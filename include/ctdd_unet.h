@@ -174,6 +174,25 @@ int ctdd_unet_time_uniform(const void* time_args, const float* proj_w, const flo
 typedef struct { const float* qkv; int B, T, C, heads; void* out_hi; float* out_f32; } ctdd_attn_args;
 int ctdd_unet_attention(const void* attn_args, void* stream);              /* unet.py:176-200 */
 
+typedef struct {
+  const void* an_bf16; const void* x_bf16;          /* [B][T][C] bf16: the block's GroupNorm output (ctdd_unet_gn_onepass) and its raw input (the residual) */
+  const void* w_qkv; const float* b_qkv;            /* [3 C][C] bf16 in fragment order (below), [3 C] fp32; output channels in the reference's order, [q | k | v] per head */
+  const void* w_proj; const float* b_proj;          /* [C][C] bf16 in fragment order, [C] fp32 */
+  int B, T, C, heads; void* out_bf16;               /* [B][T][C] bf16 */
+} ctdd_attn_block_args;
+/* The mid-block self-attention behind its GroupNorm (unet.py:152-200) in one launch, bf16 (csrc/unet_attn_kernels.hip):
+ *   qkv = an Wqkv^T + b_qkv (fp32) -> per head softmax((q s)(k s)^T) v, s = (C / heads)^-1/4 (fp32) -> ao (bf16)
+ *   out = bf16(ao Wproj^T + b_proj + x)
+ * one workgroup per sample, qkv and ao never leave the CU; the rounding points of the three launches it replaces (ctdd_unet_conv_patch
+ * into fp32, ctdd_unet_attention, ctdd_unet_conv_patch with a residual), the fp32 sums in another order (accumulators start from the
+ * bias) and the softmax's exponential as the hardware exp2 of (s - max) log2 e.  C = 192 in 8 heads, T <= 64,
+ * 16-byte aligned tensors, f32 must be 0.  Anything else (fp32 mode, other channel or head counts, a head width that is not a multiple
+ * of 4, T > 64: the LDS image would pass 160 KiB): CTDD_ERANGE / CTDD_EINVAL, nothing launched.
+ * Weights (ctdd/unet_engine.py: pack_attention_weights): element (n, k) of an [N][C] matrix, N = 4 waves x NT tiles x 16 (NT = 9 for
+ * qkv, 3 for proj), n = 16 (NT wave + tile) + i, k = 32 step + 8 q + e, is at ((((wave * C / 32 + step) * NT + tile) * 4 + q) * 16 + i) * 8 + e:
+ * a stream per wave, each wave-instruction reading 1 KiB of consecutive bytes. */
+int ctdd_unet_attention_block(const void* attn_block_args, int f32, void* stream);
+
 typedef struct { const float* net; const float* x0; int B, C, HW, S, fix; float* out;
                  int fast;   /* 1: hardware exp2/log2 forms (bf16 engine mode) */
                  void* out_bf16;   /* or null; fast mode, S % 4 == 0: the (B, D, S) logits in bf16 instead of `out` (the sampler

@@ -44,6 +44,9 @@ def _model(config):
     # and the 28x28 GroupNorm + convolution pairs as two launches each (cfg.model.conv_rows = 0); the plans with
     # ctdd_unet_conv_rows are pinned by tests/test_gpu_conv_rows.py
     cfg.model.conv_rows = 0
+    # and the mid attention block as qkv convolution + ctdd_unet_attention + proj convolution (cfg.model.attention_fused = 0); the
+    # plans with ctdd_unet_attention_block are pinned by tests/test_gpu_attention_fused.py
+    cfg.model.attention_fused = 0
     torch.manual_seed(0)
     return mu.create_model(cfg, torch.device("cuda"))
 
