@@ -55,3 +55,12 @@ def encoder(c, name, embed_dim, num_layers, mlp_dim, concat_dim, S, num_output_f
                    transformer_norm_type="prenorm", mlp_dim=mlp_dim, out_dim=S, readout_dim=S,
                    num_output_ffresiduals=num_output_ffresiduals, qkv_dim=embed_dim, ema_decay=0.9999, time_scale_factor=1000,
                    log_prob="cat", Q_sigma=20.0, engine_train="torch")
+
+
+def d3pm_model(c, S, T, transition_mat_type, start, stop, hybrid_coeff, is_img, fused):
+    """cfg.model fields of lib.d3pm.make_diffusion.  d3pm_fused: objective and sampler step on the kernels of csrc/d3pm.hip
+    (False: the torch-op formulation on the device).  A config sets it True only where tools/time_d3pm.py saw every fused run
+    beat every torch-op run at that config's shape."""
+    c.model.update(type="linear", start=start, stop=stop, num_timesteps=T, model_prediction="x_start",
+                   transition_mat_type=transition_mat_type, transition_bands=None, loss_type="hybrid", hybrid_coeff=hybrid_coeff,
+                   model_output="logits", num_pixel_vals=S, device=c.device, is_img=is_img, d3pm_fused=fused)

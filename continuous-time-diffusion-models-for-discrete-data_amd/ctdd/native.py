@@ -80,6 +80,9 @@ _SIGS = {
     "ctdd_adam_ema_step": ([_P, _P, _I, _F, _F, _F, _F, _I64, _F, _F, _P, _P], _I),
     "ctdd_grad_sumsq": ([_P, _P, _I, _P, _I, _P], _I),
     "ctdd_adam_ema_apply": ([_P, _P, _I, _F, _F, _F, _F, _I64, _F, _F, _P, _P], _I),
+    "ctdd_d3pm_scratch_bytes": ([_I, _I, _I], _I64),
+    "ctdd_d3pm_loss": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P], _I),
+    "ctdd_d3pm_step": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _U64, _U64, _P, _P, _P, _P], _I),
 }
 UNET_EXPORTS = ("ctdd_unet_conv", "ctdd_unet_conv_patch", "ctdd_unet_conv_res", "ctdd_unet_conv_ring", "ctdd_unet_conv_up_phases", "ctdd_unet_upsample2x", "ctdd_unet_first_conv", "ctdd_unet_gn_apply", "ctdd_unet_gn_onepass", "ctdd_unet_channel_stats",
                 "ctdd_unet_time", "ctdd_unet_time_uniform", "ctdd_unet_attention", "ctdd_unet_logistic_head", "ctdd_unet_resblock_small",
@@ -591,6 +594,54 @@ def ctelbo_loss(logits, x0, x_tilde, qt0, qt0T, rate, eps, elbo_scale, nll_scale
     else:
         _check(lib.ctdd_ctelbo_loss_terms(*head, float(elbo_scale), float(reg_scale), *tail), "ctdd_ctelbo_loss_terms")
     return out[0], grad
+
+
+def d3pm_loss(logits, x0, xt, t, qprev, qprevT, q1T, eps, vb_scale, ce_scale, want_grad=True):
+    """D3PM objective (csrc/d3pm.hip): (loss, vb, ce) per sample, each (B,), in bits per dimension, and d loss_b / d logits[b]
+    (B, D, S) (None without `want_grad`).  Tables per sample (B, S, S): Qbar_{t-1}, its transpose, Q_t^T."""
+    if logits.dim() != 3:
+        raise CtddError(f"d3pm_loss: logits {tuple(logits.shape)}, expected (B, D, S)")
+    B, D, S = logits.shape
+    if tuple(x0.shape) != (B, D) or tuple(xt.shape) != (B, D) or tuple(t.shape) != (B,):
+        raise CtddError(f"d3pm_loss: x0 {tuple(x0.shape)} / xt {tuple(xt.shape)} / t {tuple(t.shape)} against logits {tuple(logits.shape)}")
+    for name, tab in (("qprev", qprev), ("qprevT", qprevT), ("q1T", q1T)):
+        if tuple(tab.shape) != (B, S, S):
+            raise CtddError(f"d3pm_loss: {name} {tuple(tab.shape)}, expected {(B, S, S)}")
+    lib = load()
+    dev = logits.device
+    scratch = torch.empty((int(lib.ctdd_d3pm_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=dev)
+    grad = torch.empty_like(logits) if want_grad else None
+    out = torch.empty((3, B), dtype=f32, device=dev)
+    _count("ctdd_d3pm_loss")
+    _check(lib.ctdd_d3pm_loss(_ptr(logits, f32, "logits"), _ptr(x0, i32, "x0"), _ptr(xt, i32, "xt"), _ptr(t, i32, "t"),
+                              _ptr(qprev, f32, "qprev"), _ptr(qprevT, f32, "qprevT"), _ptr(q1T, f32, "q1T"), B, D, S, float(eps),
+                              float(vb_scale), float(ce_scale), _ptr(scratch), _ptr(grad), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                              _stream()), "ctdd_d3pm_loss")
+    return out[0], out[1], out[2], grad
+
+
+def d3pm_step(logits, x, qprev, qprevT, q1T, t, eps, noise=None, seed=0, offset=0, want_logits=False):
+    """One D3PM ancestral step at one `t` for the whole batch (csrc/d3pm.hip): x_{t-1} (N, D) int32 [, the model logits].
+    Tables (S, S): Qbar_{max(t-1, 0)}, its transpose, Q_t^T.  noise (N, D, S) uniforms, or None for the rows' Philox streams."""
+    if logits.dim() != 3:
+        raise CtddError(f"d3pm_step: logits {tuple(logits.shape)}, expected (N, D, S)")
+    N, D, S = logits.shape
+    if tuple(x.shape) != (N, D):
+        raise CtddError(f"d3pm_step: x {tuple(x.shape)} against logits {tuple(logits.shape)}")
+    for name, tab in (("qprev", qprev), ("qprevT", qprevT), ("q1T", q1T)):
+        if tuple(tab.shape) != (S, S):
+            raise CtddError(f"d3pm_step: {name} {tuple(tab.shape)}, expected {(S, S)}")
+    if noise is not None and tuple(noise.shape) != (N, D, S):
+        raise CtddError(f"d3pm_step: noise {tuple(noise.shape)}, expected {(N, D, S)}")
+    dev = logits.device
+    scratch = torch.empty((2, N, D, S), dtype=f32, device=dev) if S % 32 == 0 and int(t) != 0 else None
+    out = torch.empty((N, D), dtype=i32, device=dev)
+    model = torch.empty((N, D, S), dtype=f32, device=dev) if want_logits else None
+    _count("ctdd_d3pm_step")
+    _check(load().ctdd_d3pm_step(_ptr(logits, f32, "logits"), _ptr(x, i32, "x"), _ptr(qprev, f32, "qprev"), _ptr(qprevT, f32, "qprevT"),
+                                 _ptr(q1T, f32, "q1T"), int(t), N, D, S, float(eps), _ptr(noise, f32, "noise"), int(seed), int(offset),
+                                 _ptr(scratch), _ptr(out), _ptr(model), _stream()), "ctdd_d3pm_step")
+    return (out, model) if want_logits else out
 
 
 def ctelbo_loss_window(logits_full, x0, x_tilde, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale, d_off, grad_out=None):

@@ -819,3 +819,20 @@ class InpaintScoreElbo:
             return _ScoreElboRevMaskedFn.apply(logits, x0, x_tilde, reg_x, free, qt0.contiguous(), qT, rate, cfg.loss.logit_type, eps,
                                                float(self.nll_weight) / B)
         return _score_elbo_terms_masked(cfg, model, logits, x0, reg_x, x_tilde, ts, free, qt0, rate, eps, self.nll_weight)
+
+
+class d3pm_loss:
+    """D3PM baseline objective (reference losses.py:1107-1130): a plain class, not registered -- the scripts build it as
+    `d3pm_loss(cfg, make_diffusion(cfg.model))`.  One uniform integer step per sample, then the mean of
+    CategoricalDiffusion.training_losses (lib/d3pm.py: ctdd_d3pm_loss on a GPU, torch ops on the CPU)."""
+
+    def __init__(self, cfg, diffusion):
+        self.cfg = cfg
+        self.diffusion = diffusion
+        self.device = cfg.device
+        self.num_timesteps = cfg.model.num_timesteps
+
+    def calc_loss(self, minibatch, state):
+        model = state["model"]
+        t = torch.randint(low=0, high=self.num_timesteps, size=(minibatch.shape[0],)).to(minibatch.device)
+        return self.diffusion.training_losses(model, minibatch, t).mean()

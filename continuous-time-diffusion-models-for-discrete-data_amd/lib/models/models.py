@@ -427,15 +427,17 @@ class EMA:
 
 
 def _compose(name, net_cls, rate_cls, doc):
-    """Build `class name(EMA, net_cls, rate_cls)` with the reference's init order and register it."""
+    """Build `class name(EMA, net_cls, rate_cls)` with the reference's init order and register it (rate_cls None: no CTMC)."""
 
     def __init__(self, cfg, device, rank=None):
         EMA.__init__(self, cfg)
         net_cls.__init__(self, cfg, device, rank)
-        rate_cls.__init__(self, cfg, device)
+        if rate_cls is not None:
+            rate_cls.__init__(self, cfg, device)
         self.init_ema()
 
-    cls = type(name, (EMA, net_cls, rate_cls), {"__init__": __init__, "__doc__": doc})
+    bases = (EMA, net_cls) + ((rate_cls,) if rate_cls is not None else ())
+    cls = type(name, bases, {"__init__": __init__, "__doc__": doc})
     return model_utils.register_model(cls)
 
 
@@ -454,3 +456,5 @@ UniVarBertEMA = _compose("UniVarBertEMA", BertMLPRes, UniformVariantRate, "x0-pr
 UniformBertEMA = _compose("UniformBertEMA", BertMLPRes, UniformRate, "x0-prediction transformer, uniform CTMC")
 UniVarMaskedEMA = _compose("UniVarMaskedEMA", MaskedModel, UniformVariantRate, "masked transformer, time-warped uniform CTMC")
 UniformMaskedEMA = _compose("UniformMaskedEMA", MaskedModel, UniformRate, "masked transformer, uniform CTMC")
+# the D3PM baseline's network (models.py:1044-1050): no rate class, its forward process is lib.d3pm.CategoricalDiffusion
+UniBertD3PM = _compose("UniBertD3PM", BertMLPRes, None, "x0-prediction transformer of the D3PM baseline (no CTMC)")
