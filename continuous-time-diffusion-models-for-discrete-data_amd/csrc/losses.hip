@@ -156,48 +156,47 @@ static int crm_launch(const CrmArgs& a, float* out_loss, void* stream) {
   return finish_launch("k_sum_rows");
 }
 
+// the argument checks shared by the four ctdd_crm_loss* entry points (`what` prefixes the messages), then the launch
+static int crm_checked(const char* what, const CrmArgs& a, int B, bool masked, float* out_loss, void* stream) {
+  CTDD_REQUIRE(!masked || a.free_mask, CTDD_EINVAL, "%s: null mask", what);
+  CTDD_REQUIRE(a.logits && a.xt && a.grad && a.row_loss && out_loss, CTDD_EINVAL, "%s: null buffer", what);
+  CTDD_REQUIRE(B > 0 && a.D > 0 && a.S >= 2, CTDD_EINVAL, "%s: B=%d D=%d S=%d", what, B, a.D, a.S);
+  const bool type_ok = a.loss_type >= 0 && a.loss_type <= 2, q_ok = a.loss_type != 2 || a.qt0;
+  if (a.ll_in) {
+    CTDD_REQUIRE(type_ok && q_ok, CTDD_EINVAL, "%s: loss_type %d / elbo needs q_{t|0}", what, a.loss_type);
+  } else {
+    CTDD_REQUIRE(type_ok, CTDD_EINVAL, "%s: loss_type %d (0 rm, 1 mle, 2 elbo)", what, a.loss_type);
+    CTDD_REQUIRE(q_ok, CTDD_EINVAL, "%s: elbo needs q_{t|0}", what);
+  }
+  return crm_launch(a, out_loss, stream);
+}
+
 extern "C" int ctdd_crm_loss(const float* logits, const int32_t* xt, const int32_t* x0, const float* qt0, int B, int D, int S,
                              int loss_type, float scale, float nll_scale, float* grad_logits, double* row_scratch,
                              float* out_loss, void* stream) {
-  CTDD_REQUIRE(logits && xt && grad_logits && row_scratch && out_loss, CTDD_EINVAL, "crm loss: null buffer");
-  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2, CTDD_EINVAL, "crm loss: B=%d D=%d S=%d", B, D, S);
-  CTDD_REQUIRE(loss_type >= 0 && loss_type <= 2, CTDD_EINVAL, "crm loss: loss_type %d (0 rm, 1 mle, 2 elbo)", loss_type);
-  CTDD_REQUIRE(loss_type != 2 || qt0, CTDD_EINVAL, "crm loss: elbo needs q_{t|0}");
   CrmArgs a = {logits, xt, x0, qt0, (int64_t)B * D, D, S, loss_type, scale, nll_scale, grad_logits, row_scratch, 0, nullptr};
-  return crm_launch(a, out_loss, stream);
+  return crm_checked("crm loss", a, B, false, out_loss, stream);
 }
 // K12 under a per-sample mask of free rows: held rows add nothing to either sum and get an exact-zero gradient row
 extern "C" int ctdd_crm_loss_masked(const float* logits, const int32_t* xt, const int32_t* x0, const uint8_t* free_mask, const float* qt0,
                                     int B, int D, int S, int loss_type, float scale, float nll_scale, float* grad_logits,
                                     double* row_scratch, float* out_loss, void* stream) {
-  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "crm loss masked: null mask");
-  CTDD_REQUIRE(logits && xt && grad_logits && row_scratch && out_loss, CTDD_EINVAL, "crm loss masked: null buffer");
-  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2, CTDD_EINVAL, "crm loss masked: B=%d D=%d S=%d", B, D, S);
-  CTDD_REQUIRE(loss_type >= 0 && loss_type <= 2, CTDD_EINVAL, "crm loss masked: loss_type %d (0 rm, 1 mle, 2 elbo)", loss_type);
-  CTDD_REQUIRE(loss_type != 2 || qt0, CTDD_EINVAL, "crm loss masked: elbo needs q_{t|0}");
   CrmArgs a = {logits, xt, x0, qt0, (int64_t)B * D, D, S, loss_type, scale, nll_scale, grad_logits, row_scratch, 0, free_mask};
-  return crm_launch(a, out_loss, stream);
+  return crm_checked("crm loss masked", a, B, true, out_loss, stream);
 }
 
 // the same objective on ll_all (reverse_prob / reverse_logscale logit types): value and d loss / d ll_all
 extern "C" int ctdd_crm_loss_ll(const float* ll_all, const int32_t* xt, const float* qt0, int B, int D, int S, int loss_type, float scale,
                                 float* grad_ll, double* row_scratch, float* out_loss, void* stream) {
-  CTDD_REQUIRE(ll_all && xt && grad_ll && row_scratch && out_loss, CTDD_EINVAL, "crm loss (ll): null buffer");
-  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2, CTDD_EINVAL, "crm loss (ll): B=%d D=%d S=%d", B, D, S);
-  CTDD_REQUIRE(loss_type >= 0 && loss_type <= 2 && (loss_type != 2 || qt0), CTDD_EINVAL, "crm loss (ll): loss_type %d / elbo needs q_{t|0}", loss_type);
   CrmArgs a = {ll_all, xt, nullptr, qt0, (int64_t)B * D, D, S, loss_type, scale, 0.0f, grad_ll, row_scratch, 1, nullptr};
-  return crm_launch(a, out_loss, stream);
+  return crm_checked("crm loss (ll)", a, B, false, out_loss, stream);
 }
 // ... under a mask: a held row's d loss / d ll_all is an exact-zero row, which ctdd_logprob_bwd turns into a zero logit-gradient row
 extern "C" int ctdd_crm_loss_ll_masked(const float* ll_all, const int32_t* xt, const uint8_t* free_mask, const float* qt0, int B, int D,
                                        int S, int loss_type, float scale, float* grad_ll, double* row_scratch, float* out_loss,
                                        void* stream) {
-  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "crm loss masked (ll): null mask");
-  CTDD_REQUIRE(ll_all && xt && grad_ll && row_scratch && out_loss, CTDD_EINVAL, "crm loss masked (ll): null buffer");
-  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2, CTDD_EINVAL, "crm loss masked (ll): B=%d D=%d S=%d", B, D, S);
-  CTDD_REQUIRE(loss_type >= 0 && loss_type <= 2 && (loss_type != 2 || qt0), CTDD_EINVAL, "crm loss masked (ll): loss_type %d / elbo needs q_{t|0}", loss_type);
   CrmArgs a = {ll_all, xt, nullptr, qt0, (int64_t)B * D, D, S, loss_type, scale, 0.0f, grad_ll, row_scratch, 1, free_mask};
-  return crm_launch(a, out_loss, stream);
+  return crm_checked("crm loss masked (ll)", a, B, true, out_loss, stream);
 }
 
 // ================================================================== K11: tauLDR CT-ELBO, value + d/dlogits
@@ -771,63 +770,40 @@ __global__ __launch_bounds__(256) void k_elbo_zero_held(const ElboArgs a) {
 
 }  // namespace ctdd
 
+// The ELBO kernels' scratch, stated once: Atab (B,S,S) f32 | u (B,D,S) f32 | rows (B*D,4) f64 | base_sum (B) f32 | cb (B) f32 |
+// sums (B,4) f64 | RT (B,S,S) f32, each 256-byte aligned.  Points `a` and `sums` into `scratch`; returns the byte count.
+static int64_t elbo_scratch_layout(ElboArgs& a, double*& sums, void* scratch, int B, int D, int S) {
+  const uintptr_t base = (uintptr_t)scratch;
+  uintptr_t p = base;
+  auto take = [&p](int64_t bytes) { const uintptr_t at = p; p += (uintptr_t)((bytes + 255) / 256 * 256); return at; };
+  a.Atab = (float*)take((int64_t)B * S * S * 4);
+  a.u = (float*)take((int64_t)B * D * S * 4);
+  a.rows = (double*)take((int64_t)B * D * 32);
+  a.base_sum = (float*)take((int64_t)B * 4);
+  a.cb = (float*)take((int64_t)B * 4);
+  sums = (double*)take((int64_t)B * 32);
+  a.RT = (float*)take((int64_t)B * S * S * 4);
+  return (int64_t)(p - base);
+}
 extern "C" int64_t ctdd_ctelbo_scratch_bytes(int B, int D, int S) {
-  // Atab (B,S,S) f32 | u (B,D,S) f32 | rows (B*D,4) f64 | base_sum (B) f32 | cb (B) f32 | sums (B,4) f64 | RT (B,S,S) f32   (each 256-B aligned)
-  auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-  return 2 * al((int64_t)B * S * S * 4) + al((int64_t)B * D * S * 4) + al((int64_t)B * D * 32) + 2 * al((int64_t)B * 4) + al((int64_t)B * 32);
+  ElboArgs a;
+  double* sums;
+  return elbo_scratch_layout(a, sums, nullptr, B, D, S);
 }
 
 static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
                        const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
                        float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream,
-                       const uint8_t* free_mask = nullptr);
-extern "C" int ctdd_ctelbo_loss(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
-                                const float* rate, int B, int D, int S, float eps, float elbo_scale, float nll_scale,
-                                void* scratch, float* grad_logits, float* out_loss, void* stream) {
-  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, elbo_scale, elbo_scale, nll_scale, scratch, grad_logits, out_loss,
-                     stream);
-}
-extern "C" int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
-                                      const float* rate, int B, int D, int S, float eps, float sig_scale, float reg_scale, float nll_scale,
-                                      void* scratch, float* grad_logits, float* out_loss, void* stream) {
-  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss, stream);
-}
-// K11 on rows [d_off, d_off + D) of (B, Dl, S) logits, read in place; the full-shape gradient is written in place, zeros outside the window
-extern "C" int ctdd_ctelbo_loss_window(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
-                                       const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
-                                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream) {
-  CTDD_REQUIRE(d_off >= 0 && D >= 1 && Dl >= D && d_off <= Dl - D, CTDD_ERANGE, "ct-elbo window: rows [%d, %d + %d) of Dl=%d", d_off, d_off, D, Dl);
-  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, Dl, d_off, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss,
-                     stream);
-}
-// K11 under a per-sample mask of free rows: logits, x0, x_tilde, grad_logits full shape; held rows get an exact-zero gradient row
-extern "C" int ctdd_ctelbo_loss_masked(const float* logits, const int32_t* x0, const int32_t* x_tilde, const uint8_t* free_mask,
-                                       const float* qt0, const float* qt0T, const float* rate, int B, int D, int S, float eps,
-                                       float sig_scale, float reg_scale, float nll_scale, void* scratch, float* grad_logits,
-                                       float* out_loss, void* stream) {
-  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "ct-elbo masked: null mask");
-  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss,
-                     stream, free_mask);
-}
-static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
-                       const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
-                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream, const uint8_t* free_mask) {
+                       const uint8_t* free_mask = nullptr) {
   const float elbo_scale = sig_scale;
   CTDD_REQUIRE(logits && x0 && x_tilde && qt0 && qt0T && rate && scratch && grad_logits && out_loss, CTDD_EINVAL, "ct-elbo: null buffer");
   CTDD_REQUIRE(B > 0 && D > 0 && S >= 2 && S <= 256, CTDD_ERANGE, "ct-elbo: B=%d D=%d S=%d (S <= 256)", B, D, S);
-  auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-  unsigned char* sp = (unsigned char*)scratch;
   ElboArgs a;
   a.logits = logits; a.x0 = x0; a.xt = x_tilde; a.q = qt0; a.qT = qt0T; a.R = rate;
   a.B = B; a.D = D; a.S = S; a.eps = eps; a.elbo_scale = elbo_scale; a.nll_scale = nll_scale; a.reg_scale = reg_scale;
   a.Dl = Dl; a.doff = d_off; a.free_mask = free_mask;
-  a.Atab = (float*)sp; sp += al((int64_t)B * S * S * 4);
-  a.u = (float*)sp; sp += al((int64_t)B * D * S * 4);
-  a.rows = (double*)sp; sp += al((int64_t)B * D * 32);
-  a.base_sum = (float*)sp; sp += al((int64_t)B * 4);
-  a.cb = (float*)sp; sp += al((int64_t)B * 4);
-  double* sums = (double*)sp; sp += al((int64_t)B * 32);
-  a.RT = (float*)sp;
+  double* sums;
+  elbo_scratch_layout(a, sums, scratch, B, D, S);
   a.grad = grad_logits; a.out_loss = out_loss; a.ll_in = 0;
   hipStream_t st = (hipStream_t)stream;
   const dim3 rg((D + LRB - 1) / LRB, B), gg((D + 127) / 128, B);
@@ -908,6 +884,34 @@ static int ctelbo_impl(const float* logits, const int32_t* x0, const int32_t* x_
   }
   ELBO_ROWS(k_elbo_bwd, 0, rg);
   return finish_launch("k_elbo_bwd");
+}
+extern "C" int ctdd_ctelbo_loss(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
+                                const float* rate, int B, int D, int S, float eps, float elbo_scale, float nll_scale,
+                                void* scratch, float* grad_logits, float* out_loss, void* stream) {
+  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, elbo_scale, elbo_scale, nll_scale, scratch, grad_logits, out_loss,
+                     stream);
+}
+extern "C" int ctdd_ctelbo_loss_terms(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
+                                      const float* rate, int B, int D, int S, float eps, float sig_scale, float reg_scale, float nll_scale,
+                                      void* scratch, float* grad_logits, float* out_loss, void* stream) {
+  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss, stream);
+}
+// K11 on rows [d_off, d_off + D) of (B, Dl, S) logits, read in place; the full-shape gradient is written in place, zeros outside the window
+extern "C" int ctdd_ctelbo_loss_window(const float* logits, const int32_t* x0, const int32_t* x_tilde, const float* qt0, const float* qt0T,
+                                       const float* rate, int B, int D, int S, int Dl, int d_off, float eps, float sig_scale, float reg_scale,
+                                       float nll_scale, void* scratch, float* grad_logits, float* out_loss, void* stream) {
+  CTDD_REQUIRE(d_off >= 0 && D >= 1 && Dl >= D && d_off <= Dl - D, CTDD_ERANGE, "ct-elbo window: rows [%d, %d + %d) of Dl=%d", d_off, d_off, D, Dl);
+  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, Dl, d_off, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss,
+                     stream);
+}
+// K11 under a per-sample mask of free rows: logits, x0, x_tilde, grad_logits full shape; held rows get an exact-zero gradient row
+extern "C" int ctdd_ctelbo_loss_masked(const float* logits, const int32_t* x0, const int32_t* x_tilde, const uint8_t* free_mask,
+                                       const float* qt0, const float* qt0T, const float* rate, int B, int D, int S, float eps,
+                                       float sig_scale, float reg_scale, float nll_scale, void* scratch, float* grad_logits,
+                                       float* out_loss, void* stream) {
+  CTDD_REQUIRE(free_mask, CTDD_EINVAL, "ct-elbo masked: null mask");
+  return ctelbo_impl(logits, x0, x_tilde, qt0, qt0T, rate, B, D, S, D, 0, eps, sig_scale, reg_scale, nll_scale, scratch, grad_logits, out_loss,
+                     stream, free_mask);
 }
 
 // ================================================================== K12b: ScoreElbo (direct logits), value + d/dlogits
@@ -1017,7 +1021,33 @@ __global__ __launch_bounds__(256) void k_selbo_bwd(const ElboArgs a, const int32
 
 static int score_elbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x, const float* qt0,
                            const float* rate, int B, int D, int S, float eps, float nll_scale, void* scratch, float* grad_logits,
-                           float* out_loss, int ll_in, void* stream, const uint8_t* free_mask = nullptr);
+                           float* out_loss, int ll_in, void* stream, const uint8_t* free_mask = nullptr) {
+  CTDD_REQUIRE(logits && x0 && x_tilde && reg_x && qt0 && rate && scratch && grad_logits && out_loss, CTDD_EINVAL, "score-elbo: null buffer");
+  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2 && S <= 256, CTDD_ERANGE, "score-elbo: B=%d D=%d S=%d (S <= 256)", B, D, S);
+  ElboArgs a;
+  a.logits = logits; a.x0 = x0; a.xt = x_tilde; a.q = qt0; a.qT = qt0; a.R = rate;
+  a.B = B; a.D = D; a.S = S; a.eps = eps; a.elbo_scale = 1.0f; a.nll_scale = nll_scale; a.reg_scale = 1.0f;
+  a.Dl = D; a.doff = 0; a.free_mask = free_mask;
+  double* sums;
+  elbo_scratch_layout(a, sums, scratch, B, D, S);
+  a.RT = nullptr;                                       // (k_elbo_atab runs its first column block only here)
+  a.grad = grad_logits; a.out_loss = out_loss; a.ll_in = ll_in;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t rows = (int64_t)B * D;
+  hipLaunchKernelGGL(k_elbo_atab, dim3(1, B), dim3(256), 0, st, a);          // (first column block only: base_sum; its A rows are unused scratch)
+  if (int rc = finish_launch("k_elbo_atab")) return rc;
+  const dim3 wg((unsigned)((rows + 3) / 4));
+  if (free_mask) hipLaunchKernelGGL(k_selbo_fwd<true>, wg, dim3(256), 0, st, a, reg_x);
+  else hipLaunchKernelGGL(k_selbo_fwd<false>, wg, dim3(256), 0, st, a, reg_x);
+  if (int rc = finish_launch("k_selbo_fwd")) return rc;
+  hipLaunchKernelGGL(k_elbo_sample_sums, dim3(B), dim3(256), 0, st, a, sums);
+  if (int rc = finish_launch("k_elbo_sample_sums")) return rc;
+  hipLaunchKernelGGL(k_elbo_reduce, dim3(1), dim3(256), 0, st, a, (const double*)sums);
+  if (int rc = finish_launch("k_elbo_reduce")) return rc;
+  if (free_mask) hipLaunchKernelGGL(k_selbo_bwd<true>, wg, dim3(256), 0, st, a, reg_x);
+  else hipLaunchKernelGGL(k_selbo_bwd<false>, wg, dim3(256), 0, st, a, reg_x);
+  return finish_launch("k_selbo_bwd");
+}
 extern "C" int ctdd_score_elbo_loss(const float* logits, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x,
                                     const float* qt0, const float* rate, int B, int D, int S, float eps, float nll_scale,
                                     void* scratch, float* grad_logits, float* out_loss, void* stream) {
@@ -1043,41 +1073,6 @@ extern "C" int ctdd_score_elbo_loss_ll_masked(const float* ll_all, const int32_t
                                               float nll_scale, void* scratch, float* grad_ll, float* out_loss, void* stream) {
   CTDD_REQUIRE(free_mask, CTDD_EINVAL, "score-elbo masked (ll): null mask");
   return score_elbo_impl(ll_all, x0, x_tilde, reg_x, qt0, rate, B, D, S, eps, nll_scale, scratch, grad_ll, out_loss, 1, stream, free_mask);
-}
-static int score_elbo_impl(const float* logits, const int32_t* x0, const int32_t* x_tilde, const int32_t* reg_x, const float* qt0,
-                           const float* rate, int B, int D, int S, float eps, float nll_scale, void* scratch, float* grad_logits,
-                           float* out_loss, int ll_in, void* stream, const uint8_t* free_mask) {
-  CTDD_REQUIRE(logits && x0 && x_tilde && reg_x && qt0 && rate && scratch && grad_logits && out_loss, CTDD_EINVAL, "score-elbo: null buffer");
-  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2 && S <= 256, CTDD_ERANGE, "score-elbo: B=%d D=%d S=%d (S <= 256)", B, D, S);
-  auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-  unsigned char* sp = (unsigned char*)scratch;          // same layout as ctdd_ctelbo_scratch_bytes
-  ElboArgs a;
-  a.logits = logits; a.x0 = x0; a.xt = x_tilde; a.q = qt0; a.qT = qt0; a.R = rate;
-  a.B = B; a.D = D; a.S = S; a.eps = eps; a.elbo_scale = 1.0f; a.nll_scale = nll_scale; a.reg_scale = 1.0f;
-  a.Dl = D; a.doff = 0; a.free_mask = free_mask;
-  a.Atab = (float*)sp; sp += al((int64_t)B * S * S * 4);
-  a.u = (float*)sp; sp += al((int64_t)B * D * S * 4);
-  a.rows = (double*)sp; sp += al((int64_t)B * D * 32);
-  a.base_sum = (float*)sp; sp += al((int64_t)B * 4);
-  a.cb = (float*)sp; sp += al((int64_t)B * 4);
-  double* sums = (double*)sp;
-  a.RT = nullptr;                                       // (k_elbo_atab runs its first column block only here)
-  a.grad = grad_logits; a.out_loss = out_loss; a.ll_in = ll_in;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t rows = (int64_t)B * D;
-  hipLaunchKernelGGL(k_elbo_atab, dim3(1, B), dim3(256), 0, st, a);          // (first column block only: base_sum; its A rows are unused scratch)
-  if (int rc = finish_launch("k_elbo_atab")) return rc;
-  const dim3 wg((unsigned)((rows + 3) / 4));
-  if (free_mask) hipLaunchKernelGGL(k_selbo_fwd<true>, wg, dim3(256), 0, st, a, reg_x);
-  else hipLaunchKernelGGL(k_selbo_fwd<false>, wg, dim3(256), 0, st, a, reg_x);
-  if (int rc = finish_launch("k_selbo_fwd")) return rc;
-  hipLaunchKernelGGL(k_elbo_sample_sums, dim3(B), dim3(256), 0, st, a, sums);
-  if (int rc = finish_launch("k_elbo_sample_sums")) return rc;
-  hipLaunchKernelGGL(k_elbo_reduce, dim3(1), dim3(256), 0, st, a, (const double*)sums);
-  if (int rc = finish_launch("k_elbo_reduce")) return rc;
-  if (free_mask) hipLaunchKernelGGL(k_selbo_bwd<true>, wg, dim3(256), 0, st, a, reg_x);
-  else hipLaunchKernelGGL(k_selbo_bwd<false>, wg, dim3(256), 0, st, a, reg_x);
-  return finish_launch("k_selbo_bwd");
 }
 
 // ================================================================== backward of get_logprob_with_logits for the reverse logit types

@@ -143,6 +143,12 @@ def _check(rc, what):
 
 f32, i32 = torch.float32, torch.int32
 
+LAUNCH_COUNTS = {}      # entry point -> calls (tests assert that an objective really ran through the HIP path)
+
+
+def _count(name):
+    LAUNCH_COUNTS[name] = LAUNCH_COUNTS.get(name, 0) + 1
+
 
 def rate_table(eigvecs, right, eigvals, base_rate, integral, beta, S, normalise, clamp_below=1e-8,
                want_qt0=True, want_qt0T=False, want_rate=False, want_noise_probs=False):
@@ -475,20 +481,6 @@ def philox_uniform(seed, offset, nrows, nblk, device):
     return out
 
 
-def crm_loss(logits, xt, x0, qt0, loss_type, scale, nll_scale):
-    """K12: (loss scalar tensor, d loss / d logits) for the CRM objectives with direct logits."""
-    B, D, S = logits.shape
-    grad = torch.empty_like(logits)
-    rows = torch.empty((B * D,), dtype=torch.float64, device=logits.device)
-    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
-    lt = {"rm": 0, "mle": 1, "elbo": 2}[loss_type]
-    _check(load().ctdd_crm_loss(_ptr(logits, torch.float32, "logits"), _ptr(xt, torch.int32, "xt"),
-                                _ptr(x0, torch.int32, "x0") if x0 is not None else None,
-                                _ptr(qt0, torch.float32, "qt0") if qt0 is not None else None, B, D, S, lt, float(scale),
-                                float(nll_scale), _ptr(grad), _ptr(rows), _ptr(out), _stream()), "ctdd_crm_loss")
-    return out[0], grad
-
-
 def dropout_seed():
     """Seed of a network's dropout stream: drawn from torch's CPU generator (reproducible under torch.manual_seed) and mixed with
     the data-parallel rank, so that ranks seeded alike still drop different units."""
@@ -500,42 +492,6 @@ def dropout_seed():
     except Exception:
         pass
     return seed
-
-
-LAUNCH_COUNTS = {}      # entry point -> calls (tests assert that an objective really ran through the HIP path)
-
-
-def _count(name):
-    LAUNCH_COUNTS[name] = LAUNCH_COUNTS.get(name, 0) + 1
-
-
-def crm_loss_ll(ll_all, xt, qt0, loss_type, scale):
-    """K12 on ll_all (reverse logit types): (loss scalar tensor, d loss / d ll_all)."""
-    B, D, S = ll_all.shape
-    grad = torch.empty_like(ll_all)
-    rows = torch.empty((B * D,), dtype=torch.float64, device=ll_all.device)
-    out = torch.empty((1,), dtype=torch.float32, device=ll_all.device)
-    lt = {"rm": 0, "mle": 1, "elbo": 2}[loss_type]
-    _check(load().ctdd_crm_loss_ll(_ptr(ll_all, torch.float32, "ll_all"), _ptr(xt, torch.int32, "xt"),
-                                   _ptr(qt0, torch.float32, "qt0") if qt0 is not None else None, B, D, S, lt, float(scale),
-                                   _ptr(grad), _ptr(rows), _ptr(out), _stream()), "ctdd_crm_loss_ll")
-    _count("ctdd_crm_loss_ll")
-    return out[0], grad
-
-
-def score_elbo_loss_ll(ll_all, x0, x_tilde, reg_x, qt0, rate, eps, nll_scale):
-    """ScoreElbo on ll_all (reverse logit types): (loss scalar tensor, d loss / d ll_all)."""
-    B, D, S = ll_all.shape
-    lib = load()
-    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=ll_all.device)
-    grad = torch.empty_like(ll_all)
-    out = torch.empty((1,), dtype=torch.float32, device=ll_all.device)
-    _check(lib.ctdd_score_elbo_loss_ll(_ptr(ll_all, torch.float32, "ll_all"), _ptr(x0, torch.int32, "x0"), _ptr(x_tilde, torch.int32, "x_tilde"),
-                                       _ptr(reg_x, torch.int32, "reg_x"), _ptr(qt0, torch.float32, "qt0"), _ptr(rate, torch.float32, "rate"),
-                                       B, D, S, float(eps), float(nll_scale), _ptr(scratch), _ptr(grad), _ptr(out), _stream()),
-           "ctdd_score_elbo_loss_ll")
-    _count("ctdd_score_elbo_loss_ll")
-    return out[0], grad
 
 
 def logprob_bwd(logit_type, logits, qt0, qt0T, dll, x0=None, nll_scale=0.0, ll_all=None):
@@ -560,40 +516,6 @@ def logprob_bwd(logit_type, logits, qt0, qt0T, dll, x0=None, nll_scale=0.0, ll_a
                                    _ptr(ce_rows) if ce_rows is not None else None, _ptr(out_ce), _stream()), "ctdd_logprob_bwd")
     _count("ctdd_logprob_bwd")
     return grad, out_ce[0]
-
-
-def score_elbo_loss(logits, x0, x_tilde, reg_x, qt0, rate, eps, nll_scale):
-    """(loss scalar tensor, d loss / d logits) of ScoreElbo with direct logits."""
-    B, D, S = logits.shape
-    lib = load()
-    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits.device)
-    grad = torch.empty_like(logits)
-    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
-    _check(lib.ctdd_score_elbo_loss(_ptr(logits, torch.float32, "logits"), _ptr(x0, torch.int32, "x0"), _ptr(x_tilde, torch.int32, "x_tilde"),
-                                    _ptr(reg_x, torch.int32, "reg_x"), _ptr(qt0, torch.float32, "qt0"), _ptr(rate, torch.float32, "rate"),
-                                    B, D, S, float(eps), float(nll_scale), _ptr(scratch), _ptr(grad), _ptr(out), _stream()),
-           "ctdd_score_elbo_loss")
-    return out[0], grad
-
-
-def ctelbo_loss(logits, x0, x_tilde, qt0, qt0T, rate, eps, elbo_scale, nll_scale, reg_scale=None):
-    """K11: (loss scalar tensor, d loss / d logits) of the tauLDR CT-ELBO.  `reg_scale` None: the one-forward-pass objective
-    (both ELBO terms weighted `elbo_scale`); otherwise the signal term is weighted `elbo_scale` and the regulariser
-    `reg_scale`, every term evaluated at the state passed as `x_tilde` (one half of the two-forward-pass objective)."""
-    B, D, S = logits.shape
-    lib = load()
-    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits.device)
-    grad = torch.empty_like(logits)
-    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
-    head = (_ptr(logits, torch.float32, "logits"), _ptr(x0, torch.int32, "x0"), _ptr(x_tilde, torch.int32, "x_tilde"),
-            _ptr(qt0, torch.float32, "qt0"), _ptr(qt0T, torch.float32, "qt0T"), _ptr(rate, torch.float32, "rate"), B, D, S, float(eps))
-    tail = (float(nll_scale), _ptr(scratch), _ptr(grad), _ptr(out), _stream())
-    _count("ctdd_ctelbo_loss" if reg_scale is None else "ctdd_ctelbo_loss_terms")
-    if reg_scale is None:
-        _check(lib.ctdd_ctelbo_loss(*head, float(elbo_scale), *tail), "ctdd_ctelbo_loss")
-    else:
-        _check(lib.ctdd_ctelbo_loss_terms(*head, float(elbo_scale), float(reg_scale), *tail), "ctdd_ctelbo_loss_terms")
-    return out[0], grad
 
 
 def d3pm_loss(logits, x0, xt, t, qprev, qprevT, q1T, eps, vb_scale, ce_scale, want_grad=True):
@@ -644,133 +566,166 @@ def d3pm_step(logits, x, qprev, qprevT, q1T, t, eps, noise=None, seed=0, offset=
     return (out, model) if want_logits else out
 
 
+# ---------------------------------------------------------------- the fused training objectives (csrc/losses.hip)
+# One routine per family -- CT-ELBO (K11), CRM (K12), ScoreElbo -- behind the public wrappers, which only name their ABI entry and pass
+# its optional parts: a mask of free rows, a row window, the ll_all form of the reverse logit types.
+_CRM_TYPES = {"rm": 0, "mle": 1, "elbo": 2}
+
+
+def _loss_operands(what, first, logits, states, tables, grad_out, width=None):
+    """Host checks shared by the objectives, on shapes alone (no copy, no synchronisation): `logits` (B, Dl, S), named `first` in
+    messages; `states` (B, D) each and `tables` (B, S, S) each as (name, tensor) pairs, None skipped; D = Dl unless `width` names
+    the operand whose second extent it is (the row window).  Returns (B, D, S, gradient buffer)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise CtddError(f"{what}: {first} {tuple(getattr(logits, 'shape', ()))}, expected (B, D, S)")
+    B, D, S = logits.shape
+    like = ""
+    if width is not None and width[1].dim() == 2:
+        D, like = int(width[1].shape[1]), f" (the window is {width[0]}'s, {tuple(width[1].shape)})"
+    for name, x in states:
+        if x is not None and tuple(x.shape) != (B, D):
+            raise CtddError(f"{what}: {name} {tuple(x.shape)}, expected {(B, D)}{like}")
+    for name, tab in tables:
+        if tab is not None and tuple(tab.shape) != (B, S, S):
+            raise CtddError(f"{what}: {name} {tuple(tab.shape)}, expected {(B, S, S)}")
+    grad = torch.empty_like(logits) if grad_out is None else grad_out
+    if grad.shape != logits.shape:
+        raise CtddError(f"{what}: grad_out {tuple(grad.shape)} against {first} {tuple(logits.shape)}")
+    return B, D, S, grad
+
+
+def _seq_free_mask(free, logits, B, D, what):
+    """_free_mask for the sequence objectives, which take a bool mask on the logits' device only."""
+    if not isinstance(free, torch.Tensor) or free.dtype != torch.bool:
+        raise CtddError(f"{what}: free must be a bool tensor, got {getattr(free, 'dtype', type(free))}")
+    if free.device != logits.device:
+        raise CtddError(f"{what}: free on {free.device}, logits on {logits.device}")
+    return _free_mask(free, B, D, what)
+
+
+def _ctelbo(name, logits, x0, x_tilde, qt0, qt0T, rate, eps, scales, nll_scale, free=None, d_off=None, grad_out=None):
+    """The four ctdd_ctelbo_loss* entries: `scales` the term weights the entry takes, `free` for _masked, `d_off` for _window."""
+    what = name[5:]
+    B, D, S, grad = _loss_operands(what, "logits", logits, (("x0", x0), ("x_tilde", x_tilde)), (("qt0", qt0), ("qt0T", qt0T), ("rate", rate)),
+                                   grad_out, width=None if d_off is None else ("x0", x0))
+    mask, window = (), ()
+    if name.endswith("_masked"):
+        mask = (_free_mask(free, B, D, what),)
+    if d_off is not None:
+        Dl = logits.shape[1]
+        if not (0 <= int(d_off) and D >= 1 and int(d_off) + D <= Dl):
+            raise CtddError(f"{what}: rows [{d_off}, {d_off} + {D}) of {Dl}")
+        window = (Dl, int(d_off))
+    head = (_ptr(logits, f32, "logits"), _ptr(x0, i32, "x0"), _ptr(x_tilde, i32, "x_tilde"), *mask, _ptr(qt0, f32, "qt0"),
+            _ptr(qt0T, f32, "qt0T"), _ptr(rate, f32, "rate"), B, D, S, *window, float(eps), *map(float, scales), float(nll_scale))
+    lib = load()
+    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits.device)
+    out = torch.empty((1,), dtype=f32, device=logits.device)
+    _check(getattr(lib, name)(*head, _ptr(scratch), _ptr(grad, f32, "grad_out"), _ptr(out), _stream()), name)
+    _count(name)                                   # (a call the library accepted)
+    return out[0], grad
+
+
+def _crm(name, logits, xt, x0, free, qt0, loss_type, scale, nll_scale, grad_out=None):
+    """The four ctdd_crm_loss* entries: the _ll ones take ll_all for the logits and have no x0 / nll_scale; `free` for _masked."""
+    what, ll = name[5:], "_loss_ll" in name
+    first = "ll_all" if ll else "logits"
+    B, D, S, grad = _loss_operands(what, first, logits, (("xt", xt), ("x0", x0)), (("qt0", qt0),), grad_out)
+    mask = (_seq_free_mask(free, logits, B, D, what),) if name.endswith("_masked") else ()
+    ce, nll = ((), ()) if ll else ((_ptr(x0, i32, "x0"),), (float(nll_scale),))
+    head = (_ptr(logits, f32, first), _ptr(xt, i32, "xt"), *ce, *mask, _ptr(qt0, f32, "qt0"), B, D, S, _CRM_TYPES[loss_type],
+            float(scale), *nll)
+    rows = torch.empty((B * D,), dtype=torch.float64, device=logits.device)
+    out = torch.empty((1,), dtype=f32, device=logits.device)
+    _check(getattr(load(), name)(*head, _ptr(grad, f32, "grad_out"), _ptr(rows), _ptr(out), _stream()), name)
+    _count(name)                                   # (a call the library accepted)
+    return out[0], grad
+
+
+def _score_elbo(name, logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out=None):
+    """The four ctdd_score_elbo_loss* entries: the _ll ones take ll_all for the logits; `free` for _masked."""
+    what, first = name[5:], "ll_all" if "_loss_ll" in name else "logits"
+    B, D, S, grad = _loss_operands(what, first, logits, (("x0", x0), ("x_tilde", x_tilde), ("reg_x", reg_x)),
+                                   (("qt0", qt0), ("rate", rate)), grad_out)
+    mask = (_seq_free_mask(free, logits, B, D, what),) if name.endswith("_masked") else ()
+    head = (_ptr(logits, f32, first), _ptr(x0, i32, "x0"), _ptr(x_tilde, i32, "x_tilde"), _ptr(reg_x, i32, "reg_x"), *mask,
+            _ptr(qt0, f32, "qt0"), _ptr(rate, f32, "rate"), B, D, S, float(eps), float(nll_scale))
+    lib = load()
+    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits.device)
+    out = torch.empty((1,), dtype=f32, device=logits.device)
+    _check(getattr(lib, name)(*head, _ptr(scratch), _ptr(grad, f32, "grad_out"), _ptr(out), _stream()), name)
+    _count(name)                                   # (a call the library accepted)
+    return out[0], grad
+
+
+def ctelbo_loss(logits, x0, x_tilde, qt0, qt0T, rate, eps, elbo_scale, nll_scale, reg_scale=None):
+    """K11: (loss scalar tensor, d loss / d logits) of the tauLDR CT-ELBO.  `reg_scale` None: the one-forward-pass objective
+    (both ELBO terms weighted `elbo_scale`); otherwise the signal term is weighted `elbo_scale` and the regulariser
+    `reg_scale`, every term evaluated at the state passed as `x_tilde` (one half of the two-forward-pass objective)."""
+    if reg_scale is None:
+        return _ctelbo("ctdd_ctelbo_loss", logits, x0, x_tilde, qt0, qt0T, rate, eps, (elbo_scale,), nll_scale)
+    return _ctelbo("ctdd_ctelbo_loss_terms", logits, x0, x_tilde, qt0, qt0T, rate, eps, (elbo_scale, reg_scale), nll_scale)
+
+
 def ctelbo_loss_window(logits_full, x0, x_tilde, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale, d_off, grad_out=None):
     """K11 on rows [d_off, d_off + D) of the (B, Dl, S) logits, read in place; x0 / x_tilde are the compact (B, D) window.
     Returns (loss scalar tensor, d loss / d logits_full): full shape, zeros on the rows outside the window, every element
     written by the call (`grad_out`: write into this (B, Dl, S) buffer instead of a fresh one).  Terms and weights as
     ctelbo_loss with `reg_scale` given."""
-    B, Dl, S = logits_full.shape
-    D = x0.shape[1]
-    if x0.shape != (B, D) or x_tilde.shape != (B, D):
-        raise CtddError(f"ctelbo_loss_window: x0 {tuple(x0.shape)} / x_tilde {tuple(x_tilde.shape)} against {B} samples")
-    if not (0 <= int(d_off) and D >= 1 and int(d_off) + D <= Dl):
-        raise CtddError(f"ctelbo_loss_window: rows [{d_off}, {d_off} + {D}) of {Dl}")
-    lib = load()
-    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits_full.device)
-    grad = torch.empty_like(logits_full) if grad_out is None else grad_out
-    if grad.shape != logits_full.shape:
-        raise CtddError(f"ctelbo_loss_window: grad_out {tuple(grad.shape)} against logits {tuple(logits_full.shape)}")
-    out = torch.empty((1,), dtype=torch.float32, device=logits_full.device)
-    _count("ctdd_ctelbo_loss_window")
-    _check(lib.ctdd_ctelbo_loss_window(_ptr(logits_full, torch.float32, "logits"), _ptr(x0, torch.int32, "x0"), _ptr(x_tilde, torch.int32, "x_tilde"),
-                                       _ptr(qt0, torch.float32, "qt0"), _ptr(qt0T, torch.float32, "qt0T"), _ptr(rate, torch.float32, "rate"),
-                                       B, D, S, Dl, int(d_off), float(eps), float(sig_scale), float(reg_scale), float(nll_scale),
-                                       _ptr(scratch), _ptr(grad, torch.float32, "grad_out"), _ptr(out), _stream()), "ctdd_ctelbo_loss_window")
-    return out[0], grad
+    return _ctelbo("ctdd_ctelbo_loss_window", logits_full, x0, x_tilde, qt0, qt0T, rate, eps, (sig_scale, reg_scale), nll_scale,
+                   d_off=d_off, grad_out=grad_out)
 
 
 def ctelbo_loss_masked(logits, x0, x_tilde, free, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale, grad_out=None):
     """K11 on the free rows of every sample (`free` (B, D) bool / uint8; logits (B, D, S) read in place, x0 / x_tilde full shape).
     Returns (loss scalar tensor, d loss / d logits): full shape, exact zeros on held rows, every element written by the call
     (`grad_out`: write into this buffer instead of a fresh one).  Terms and weights as ctelbo_loss with `reg_scale` given."""
-    if logits.dim() != 3:
-        raise CtddError(f"ctelbo_loss_masked: logits {tuple(logits.shape)}, expected (B, D, S)")
-    B, D, S = logits.shape
-    if tuple(x0.shape) != (B, D) or tuple(x_tilde.shape) != (B, D):
-        raise CtddError(f"ctelbo_loss_masked: x0 {tuple(x0.shape)} / x_tilde {tuple(x_tilde.shape)} against logits {tuple(logits.shape)}")
-    for name, tab in (("qt0", qt0), ("qt0T", qt0T), ("rate", rate)):
-        if tuple(tab.shape) != (B, S, S):
-            raise CtddError(f"ctelbo_loss_masked: {name} {tuple(tab.shape)}, expected {(B, S, S)}")
-    fp = _free_mask(free, B, D, "ctelbo_loss_masked")
-    lib = load()
-    grad = torch.empty_like(logits) if grad_out is None else grad_out
-    if grad.shape != logits.shape:
-        raise CtddError(f"ctelbo_loss_masked: grad_out {tuple(grad.shape)} against logits {tuple(logits.shape)}")
-    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits.device)
-    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
-    _count("ctdd_ctelbo_loss_masked")
-    _check(lib.ctdd_ctelbo_loss_masked(_ptr(logits, torch.float32, "logits"), _ptr(x0, torch.int32, "x0"), _ptr(x_tilde, torch.int32, "x_tilde"),
-                                       fp, _ptr(qt0, torch.float32, "qt0"), _ptr(qt0T, torch.float32, "qt0T"), _ptr(rate, torch.float32, "rate"),
-                                       B, D, S, float(eps), float(sig_scale), float(reg_scale), float(nll_scale),
-                                       _ptr(scratch), _ptr(grad, torch.float32, "grad_out"), _ptr(out), _stream()), "ctdd_ctelbo_loss_masked")
-    return out[0], grad
+    return _ctelbo("ctdd_ctelbo_loss_masked", logits, x0, x_tilde, qt0, qt0T, rate, eps, (sig_scale, reg_scale), nll_scale,
+                   free=free, grad_out=grad_out)
 
 
-def _seq_masked_operands(what, logits, free, states, tables, grad_out):
-    """Host checks shared by the four masked sequence objectives: logits (B, D, S), `states` (B, D) each, `tables` (B, S, S) each
-    (None skipped), free a bool (B, D) tensor on the logits' device.  Returns (B, D, S, free pointer, gradient buffer)."""
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
-        raise CtddError(f"{what}: logits {tuple(getattr(logits, 'shape', ()))}, expected (B, D, S)")
-    B, D, S = logits.shape
-    for name, x in states:
-        if x is not None and tuple(x.shape) != (B, D):
-            raise CtddError(f"{what}: {name} {tuple(x.shape)} against logits {tuple(logits.shape)}")
-    for name, tab in tables:
-        if tab is not None and tuple(tab.shape) != (B, S, S):
-            raise CtddError(f"{what}: {name} {tuple(tab.shape)}, expected {(B, S, S)}")
-    if not isinstance(free, torch.Tensor) or free.dtype != torch.bool:
-        raise CtddError(f"{what}: free must be a bool tensor, got {getattr(free, 'dtype', type(free))}")
-    if free.device != logits.device:
-        raise CtddError(f"{what}: free on {free.device}, logits on {logits.device}")
-    fp = _free_mask(free, B, D, what)
-    grad = torch.empty_like(logits) if grad_out is None else grad_out
-    if grad.shape != logits.shape:
-        raise CtddError(f"{what}: grad_out {tuple(grad.shape)} against logits {tuple(logits.shape)}")
-    return B, D, S, fp, grad
+def crm_loss(logits, xt, x0, qt0, loss_type, scale, nll_scale):
+    """K12: (loss scalar tensor, d loss / d logits) for the CRM objectives with direct logits."""
+    return _crm("ctdd_crm_loss", logits, xt, x0, None, qt0, loss_type, scale, nll_scale)
 
 
-_CRM_TYPES = {"rm": 0, "mle": 1, "elbo": 2}
+def crm_loss_ll(ll_all, xt, qt0, loss_type, scale):
+    """K12 on ll_all (reverse logit types): (loss scalar tensor, d loss / d ll_all)."""
+    return _crm("ctdd_crm_loss_ll", ll_all, xt, None, None, qt0, loss_type, scale, 0.0)
 
 
 def crm_loss_masked(logits, xt, x0, free, qt0, loss_type, scale, nll_scale, grad_out=None):
     """K12 on the free rows (`free` (B, D) bool; logits (B, D, S) read in place, xt / x0 full shape):
     scale * sum_free loss_bd + nll_scale * sum_free CE(logits_bd, x0_bd) (x0 None: no CE term).  Returns (loss scalar tensor,
     d loss / d logits): full shape, exact zeros on held rows, every element written by the call (`grad_out`: into this buffer)."""
-    B, D, S, fp, grad = _seq_masked_operands("crm_loss_masked", logits, free, (("xt", xt), ("x0", x0)), (("qt0", qt0),), grad_out)
-    rows = torch.empty((B * D,), dtype=torch.float64, device=logits.device)
-    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
-    _check(load().ctdd_crm_loss_masked(_ptr(logits, f32, "logits"), _ptr(xt, i32, "xt"), _ptr(x0, i32, "x0"), fp, _ptr(qt0, f32, "qt0"),
-                                       B, D, S, _CRM_TYPES[loss_type], float(scale), float(nll_scale), _ptr(grad, f32, "grad_out"),
-                                       _ptr(rows), _ptr(out), _stream()), "ctdd_crm_loss_masked")
-    _count("ctdd_crm_loss_masked")
-    return out[0], grad
+    return _crm("ctdd_crm_loss_masked", logits, xt, x0, free, qt0, loss_type, scale, nll_scale, grad_out)
 
 
 def crm_loss_ll_masked(ll_all, xt, free, qt0, loss_type, scale, grad_out=None):
     """K12 on ll_all (reverse logit types) over the free rows: (loss scalar tensor, d loss / d ll_all), zero rows where held."""
-    B, D, S, fp, grad = _seq_masked_operands("crm_loss_ll_masked", ll_all, free, (("xt", xt),), (("qt0", qt0),), grad_out)
-    rows = torch.empty((B * D,), dtype=torch.float64, device=ll_all.device)
-    out = torch.empty((1,), dtype=torch.float32, device=ll_all.device)
-    _check(load().ctdd_crm_loss_ll_masked(_ptr(ll_all, f32, "ll_all"), _ptr(xt, i32, "xt"), fp, _ptr(qt0, f32, "qt0"), B, D, S,
-                                          _CRM_TYPES[loss_type], float(scale), _ptr(grad, f32, "grad_out"), _ptr(rows), _ptr(out),
-                                          _stream()), "ctdd_crm_loss_ll_masked")
-    _count("ctdd_crm_loss_ll_masked")
-    return out[0], grad
+    return _crm("ctdd_crm_loss_ll_masked", ll_all, xt, None, free, qt0, loss_type, scale, 0.0, grad_out)
 
 
-def _score_elbo_masked(name, logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out):
-    B, D, S, fp, grad = _seq_masked_operands(name[5:], logits, free, (("x0", x0), ("x_tilde", x_tilde), ("reg_x", reg_x)),
-                                             (("qt0", qt0), ("rate", rate)), grad_out)
-    lib = load()
-    scratch = torch.empty((int(lib.ctdd_ctelbo_scratch_bytes(B, D, S)),), dtype=torch.uint8, device=logits.device)
-    out = torch.empty((1,), dtype=torch.float32, device=logits.device)
-    _check(getattr(lib, name)(_ptr(logits, f32, "logits"), _ptr(x0, i32, "x0"), _ptr(x_tilde, i32, "x_tilde"), _ptr(reg_x, i32, "reg_x"), fp,
-                              _ptr(qt0, f32, "qt0"), _ptr(rate, f32, "rate"), B, D, S, float(eps), float(nll_scale), _ptr(scratch),
-                              _ptr(grad, f32, "grad_out"), _ptr(out), _stream()), name)
-    _count(name)
-    return out[0], grad
+def score_elbo_loss(logits, x0, x_tilde, reg_x, qt0, rate, eps, nll_scale):
+    """(loss scalar tensor, d loss / d logits) of ScoreElbo with direct logits."""
+    return _score_elbo("ctdd_score_elbo_loss", logits, x0, x_tilde, reg_x, None, qt0, rate, eps, nll_scale)
+
+
+def score_elbo_loss_ll(ll_all, x0, x_tilde, reg_x, qt0, rate, eps, nll_scale):
+    """ScoreElbo on ll_all (reverse logit types): (loss scalar tensor, d loss / d ll_all)."""
+    return _score_elbo("ctdd_score_elbo_loss_ll", ll_all, x0, x_tilde, reg_x, None, qt0, rate, eps, nll_scale)
 
 
 def score_elbo_loss_masked(logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out=None):
     """ScoreElbo (direct logits) with every sum over dimensions restricted to the free rows of each sample (`free` (B, D) bool;
     everything else full shape; nll_scale = nll_weight / B).  Returns (loss scalar tensor, d loss / d logits): exact zeros on held
     rows, every element written by the call (`grad_out`: into this buffer).  A sample without a free row adds zero."""
-    return _score_elbo_masked("ctdd_score_elbo_loss_masked", logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out)
+    return _score_elbo("ctdd_score_elbo_loss_masked", logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out)
 
 
 def score_elbo_loss_ll_masked(ll_all, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out=None):
     """The same on ll_all (reverse logit types): (loss scalar tensor, d loss / d ll_all), zero rows where held."""
-    return _score_elbo_masked("ctdd_score_elbo_loss_ll_masked", ll_all, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out)
+    return _score_elbo("ctdd_score_elbo_loss_ll_masked", ll_all, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale, grad_out)
 
 
 # ---------------------------------------------------------------- S = 256 fast path

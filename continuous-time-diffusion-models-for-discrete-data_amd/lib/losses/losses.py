@@ -10,6 +10,10 @@ from torch's generator; the objectives are written as batched gathers and (B,D,S
 the device so autograd reaches the network (no index-vector construction, SURVEY 6: 63 % of the
 reference's CPU time there).  Both argument orders of the reference are accepted: the class-level
 `calc_loss(state, minibatch, label=None)` and the stale `calc_loss(minibatch, state)`.
+
+Every objective exists once, with the held rows optional: `free` (B, D) bool names the entries that are noised and carry the
+objective (None: all of them).  On a GPU value and logit-gradient come from the HIP kernels of csrc/losses.hip through one autograd
+wrapper, _HipValueGrad; the plain-torch restatements below them are the CPU / S > 256 / cfg.loss.fused = False path.
 """
 import torch
 import torch.nn as nn
@@ -48,69 +52,171 @@ def _draw_ts(B, device, lo, hi):
     return torch.rand((B,), device=device) * (hi - lo) + lo
 
 
-def _noise(model, x0, ts, with_tilde, want_T=False):
+def _noise(model, x0, ts, with_tilde, want_T=False, free=None):
     """x_t ~ q_{t|0}(.|x0) per dimension and optionally the one-jump neighbour x~ (losses.py:39-101).
-    Returns qt0, rate (B,S,S) and int64 x_t[, x~]; with want_T the transposed table q_{t|0}^T is appended."""
-    if _FIXED_NOISE is not None:
-        qt0, qT, rate, _ = model.process.tables(ts, want_qt0=True, want_qt0T=want_T, want_rate=True)
-        xt = _FIXED_NOISE["x_t"].to(x0.device).long()
-        out = (qt0, rate, xt, (_FIXED_NOISE["x_tilde"].to(x0.device).long() if with_tilde else None))
-        return out + (qT,) if want_T else out
-    qt0, qT, rate, probs = model.process.tables(ts, want_qt0=True, want_qt0T=want_T, want_rate=True, want_noise_probs=True)
+    Returns (qt0, qt0^T, rate, x_t, x~): tables (B,S,S), the transpose None unless want_T; int64 states, x~ None unless with_tilde.
+    Under a mask `free` the held entries of x_t and x~ are x0 bit for bit and x~ moves a free entry."""
+    fixed = _FIXED_NOISE is not None
+    qt0, qT, rate, probs = model.process.tables(ts, want_qt0=True, want_qt0T=want_T, want_rate=True, want_noise_probs=not fixed)
+    if fixed:
+        def pin(k):
+            x = _FIXED_NOISE[k].to(x0.device).long()
+            return x if free is None else torch.where(free, x, x0)
+        return qt0, qT, rate, pin("x_t"), pin("x_tilde") if with_tilde else None
     x0i = x0.to(torch.int32).contiguous()
     x_t = native.noise_categorical(probs, x0i, seed=_seed())
+    if free is not None:
+        x_t = torch.where(free, x_t, x0i)
     if not with_tilde:
-        out = (qt0, rate, x_t.long(), None)
-        return out + (qT,) if want_T else out
-    _, _, x_tilde = native.xtilde_sample(rate, x_t, seed=_seed())
-    out = (qt0, rate, x_t.long(), x_tilde.long())
-    return out + (qT,) if want_T else out
+        return qt0, qT, rate, x_t.long(), None
+    if free is None:
+        _, _, x_tilde = native.xtilde_sample(rate, x_t, seed=_seed())
+    else:
+        _, _, x_tilde = native.xtilde_sample_masked(rate, x_t, free, seed=_seed())
+    return qt0, qT, rate, x_t.long(), x_tilde.long()
 
 
-class _CtElboFn(torch.autograd.Function):
-    """K11 (csrc/losses.hip): CT-ELBO value and logit-gradient in HIP (one forward pass)."""
+def _tables_with_transpose(model, ts):
+    """(q_{t|0}, its transpose), each (B,S,S): the transpose straight out of K1 when the model carries a device process."""
+    pr = getattr(model, "process", None)
+    if pr is not None and hasattr(pr, "tables"):
+        qt0, qT, _, _ = pr.tables(ts, want_qt0=True, want_qt0T=True)
+        return qt0, qT
+    qt0 = model.transition(ts).float().contiguous()
+    return qt0, qt0.transpose(1, 2).contiguous()
+
+
+# ---------------------------------------------------------------- the HIP path: one autograd wrapper, one reverse-logit chain
+class _HipValueGrad(torch.autograd.Function):
+    """A value and its logit-gradient computed together by HIP (csrc/losses.hip).  `f` maps the detached fp32 contiguous logits to
+    (value, d value / d logits) and holds every other operand; the gradient is saved and scaled in backward."""
 
     @staticmethod
-    def forward(ctx, logits, x0, x_tilde, qt0, qt0T, rate, eps, elbo_scale, nll_scale, reg_scale=None):
-        val, grad = native.ctelbo_loss(logits.detach().float().contiguous(), x0.to(torch.int32).contiguous(),
-                                       x_tilde.to(torch.int32).contiguous(), qt0.contiguous(), qt0T.contiguous(),
-                                       rate.contiguous(), eps, elbo_scale, nll_scale, reg_scale)
+    def forward(ctx, logits, f):
+        val, grad = f(logits.detach().float().contiguous())
         ctx.save_for_backward(grad)
         return val
 
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 9
+        return grad * g, None
 
 
+def _i32(t):
+    return None if t is None else t.to(torch.int32).contiguous()
+
+
+def _fused(cfg, logits):
+    return logits.is_cuda and logits.shape[-1] <= 256 and getattr(cfg.loss, "fused", True)
+
+
+def _reverse_chain(lg, x, qt0, qT, logit_type, inner, x0=None, nll_scale=0.0):
+    """An objective on ll_all for logit_type reverse_prob / reverse_logscale in HIP: ctdd_logprob -> inner(ll_all) = (value,
+    d value / d ll_all) -> ctdd_logprob_bwd (a zero d/d ll_all row comes out as a zero logit-gradient row).  x0 given: CatRMNLL's
+    cross-entropy term nll_scale * sum -log_softmax(lg)[x0] on the raw logits rides in the last launch.  Returns (value, d/d lg)."""
+    tidx = torch.arange(lg.shape[0], dtype=torch.int32, device=lg.device)
+    ll_all, _ = native.logprob(lg, x, qt0, logit_type, tidx, qt0T=qT)
+    val, dll = inner(ll_all)
+    grad, ce = native.logprob_bwd(logit_type, lg, qt0, qT, dll, x0, nll_scale, ll_all=ll_all)
+    return (val if x0 is None else val + ce), grad
+
+
+# ---------------------------------------------------------------- the plain-torch restatements (free = None: every row)
 def _masked_rows(tab, x):
     """tab (B,S,S), x (B,D) -> tab[b, x_bd, :] with entry x_bd zeroed: (B,D,S)."""
     rows = tab[torch.arange(tab.shape[0], device=tab.device).view(-1, 1), x]
     return rows.scatter(-1, x.unsqueeze(-1), 0.0)
 
 
-def _ct_elbo_terms(logits_reg, logits_sig, x0, reg_x, x_tilde, qt0, rate, eps):
-    """Negative CT-ELBO of tauLDR (losses.py:106-278): mean(-sig/norm) + mean(reg)."""
+def _sum_d(v, free):
+    """(B, D) -> (B): the sum over the sample's free rows."""
+    return v.sum(1) if free is None else torch.where(free, v, torch.zeros_like(v)).sum(1)
+
+
+def _sum_ds(v, free):
+    """(B, D, S) -> (B): the sum over states and the sample's free rows."""
+    return torch.sum(v, dim=(1, 2)) if free is None else _sum_d(torch.sum(v, dim=2), free)
+
+
+def _signal_term(inner, x0, x_tilde, qt0, rate, eps, free):
+    """mean_b(-outer_b / norm_b) of the CT-ELBO (losses.py:190-278) for the log-ratio `inner` (B,D,S).  Under a mask the base sum
+    inside Z, outer and norm run over the sample's free rows; a sample without a free row contributes zero."""
     B = x0.shape[0]
     n = torch.arange(B, device=x0.device).view(B, 1)
+    outer_rate = _masked_rows(rate.transpose(1, 2), x_tilde)      # rate[b, s, x~], s != x~
+    q_x0 = qt0[n, x0]                                             # qt0[b, x0, s]
+    q_x0_xt = torch.gather(q_x0, -1, x_tilde.unsqueeze(-1)) + eps  # (B,D,1)
+    outer = _sum_ds(outer_rate * (q_x0 / q_x0_xt) * inner, free)
+    row_sums = -torch.diagonal(rate, dim1=1, dim2=2)              # (B,S)
+    base_tmp = row_sums[n, x_tilde]                               # (B,D)
+    Z = _sum_d(base_tmp, free).view(B, 1, 1) - base_tmp.unsqueeze(-1) + row_sums.unsqueeze(1)
+    if free is not None:
+        Z = torch.where(free.unsqueeze(-1), Z, torch.ones_like(Z))                # (a held row's Z is not a normaliser of anything)
+    sig_norm = _sum_ds(outer_rate * q_x0 / (Z * q_x0_xt), free)
+    if free is None:
+        return torch.mean(-outer / sig_norm)
+    some = free.any(dim=1)
+    return torch.mean(torch.where(some, -outer / torch.where(some, sig_norm, torch.ones_like(sig_norm)), torch.zeros_like(outer)))
+
+
+def _ct_elbo_terms(logits_reg, logits_sig, x0, reg_x, x_tilde, qt0, rate, eps, free=None):
+    """Negative CT-ELBO of tauLDR (losses.py:106-278): mean(-sig/norm) + mean(reg).  `free` (B, D) bool: every sum over dimensions
+    restricted to the sample's free rows -- per sample the negative CT-ELBO of its free rows alone.  Full-shape operands."""
+    n = torch.arange(x0.shape[0], device=x0.device).view(-1, 1)
     qT, rT = qt0.transpose(1, 2), rate.transpose(1, 2)            # qT[b,x,s0] = qt0[b,s0,x]; rT[b,x,s] = rate[b,s,x]
     p_reg = F.softmax(logits_reg, dim=2)
     reg_tmp = _masked_rows(rT, reg_x) @ qT                        # sum_s (mask*rate[s,x]) qt0[s0,s]
-    reg_term = torch.sum((p_reg / (qT[n, reg_x] + eps)) * reg_tmp, dim=(1, 2))
+    reg_term = _sum_ds((p_reg / (qT[n, reg_x] + eps)) * reg_tmp, free)
     p_sig = p_reg if logits_sig is logits_reg else F.softmax(logits_sig, dim=2)
     inner = torch.log((p_sig / (qT[n, x_tilde] + eps)) @ qt0 + eps)
-    outer_rate = _masked_rows(rT, x_tilde)                        # rate[b, s, x~], s != x~
-    q_x0 = qt0[n, x0]                                             # qt0[b, x0, s]
-    q_x0_xt = torch.gather(q_x0, -1, x_tilde.unsqueeze(-1)) + eps  # (B,D,1)
-    outer = torch.sum(outer_rate * (q_x0 / q_x0_xt) * inner, dim=(1, 2))
-    row_sums = -torch.diagonal(rate, dim1=1, dim2=2)              # (B,S)
-    base_tmp = row_sums[n, x_tilde]                               # (B,D)
-    Z = base_tmp.sum(1).view(B, 1, 1) - base_tmp.unsqueeze(-1) + row_sums.unsqueeze(1)
-    sig_norm = torch.sum(outer_rate * q_x0 / (Z * q_x0_xt), dim=(1, 2))
-    return torch.mean(-outer / sig_norm) + torch.mean(reg_term)
+    return _signal_term(inner, x0, x_tilde, qt0, rate, eps, free) + torch.mean(reg_term)
 
 
+def _score_elbo_terms(cfg, model, logits, x0, reg_x, x_tilde, ts, qt0, rate, eps, nll_weight, free=None):
+    """ScoreElbo (losses.py:1246-1500): the CT-ELBO with the ratios exp(ll_all - ll_xt) + nll_weight * sum(-ll_xt) / B; under a mask
+    every sum over dimensions runs over the sample's free rows."""
+    ll_all, ll_xt = get_logprob_with_logits(cfg, model, x_tilde, ts, logits)
+    d = ll_all - ll_xt.unsqueeze(-1)
+    reg_term = _sum_ds(torch.exp(d) * _masked_rows(rate.transpose(1, 2), reg_x), free)
+    neg_elbo = _signal_term(d, x0, x_tilde, qt0, rate, eps, free) + torch.mean(reg_term)
+    nll = torch.sum(-ll_xt) if free is None else _sum_d(-ll_xt, free).sum()
+    return neg_elbo + nll_weight * (nll / x0.shape[0])
+
+
+def _ce_term(logits, x0, nll_weight, nll_scale, free):
+    """nll_weight * mean CE(logits, x0); under a mask nll_scale * (the sum of CE over the free rows)."""
+    if free is None:
+        return nll_weight * F.cross_entropy(logits.permute(0, 2, 1), x0)
+    ce = F.cross_entropy(logits.permute(0, 2, 1), x0, reduction="none")
+    return nll_scale * torch.where(free, ce, torch.zeros_like(ce)).sum()
+
+
+def _free_rows(name, cfg, minibatch):
+    """The inpainting objectives' minibatch and mask: (x0 (B, D) int64, free (B, D) bool on x0's device, n_free).  The mask is
+    drawn (or taken from the _FIXED_NOISE hook) and counted on the host; shape and config errors are ValueErrors before any
+    device work."""
+    import lib.losses.masks as masks
+    minibatch = _flatten(minibatch)
+    D = cfg.model.concat_dim
+    if minibatch.dim() != 2 or minibatch.shape[1] != D or minibatch.shape[0] < 1:
+        raise ValueError(f"{name}: minibatch of shape {tuple(minibatch.shape)}, model.concat_dim = {D}")
+    B = int(minibatch.shape[0])
+    if _FIXED_NOISE is not None and "free" in _FIXED_NOISE:
+        masks.check_mask_config(cfg, D)
+        free_host = torch.as_tensor(_FIXED_NOISE["free"]).cpu()
+        if free_host.dtype != torch.bool or tuple(free_host.shape) != (B, D):
+            raise ValueError(f"{name}: pinned free mask {free_host.dtype} {tuple(free_host.shape)}, expected bool {(B, D)}")
+    else:
+        free_host = masks.sample_free(cfg, B, D)
+    n_free = int(free_host.sum())                                  # on the host: the cross-entropy weight is a plain float
+    x0 = minibatch.long()
+    # the step's one upload of the mask: from pinned memory, asynchronous -- a pageable copy would make the host wait for the device
+    free = free_host.pin_memory().to(x0.device, non_blocking=True) if x0.is_cuda else free_host
+    return x0, free, n_free
+
+
+# ---------------------------------------------------------------- the CT-ELBO family
 class _CTElboBase:
     def __init__(self, cfg):
         self.cfg = cfg
@@ -128,20 +234,20 @@ class _CTElboBase:
         x0 = _flatten(minibatch).long()
         B, D = x0.shape
         ts = _draw_ts(B, model.device, self.min_time, self.max_t)
-        qt0, rate, x_t, x_tilde, qT = _noise(model, x0, ts, True, want_T=True)
+        qt0, qT, rate, x_t, x_tilde = _noise(model, x0, ts, True, want_T=True)
         x_logits = model(x_t, ts)
-        fused = x_logits.is_cuda and x_logits.shape[-1] <= 256 and getattr(self.cfg.loss, "fused", True)
-        if self.one_forward_pass and fused:
-            return _CtElboFn.apply(x_logits, x0, x_tilde, qt0, qT, rate, float(self.ratio_eps), float(elbo_scale),
-                                   float(nll_coef) / (B * D))
-        if fused:
+        if _fused(self.cfg, x_logits):
+            eps, w, nll_scale = float(self.ratio_eps), float(elbo_scale), float(nll_coef) / (B * D)
+
+            def k11(logits, x, elbo_scale, nll_scale, reg_scale=None):
+                x0i, xi, tabs = _i32(x0), _i32(x), (qt0.contiguous(), qT.contiguous(), rate.contiguous())
+                return _HipValueGrad.apply(logits, lambda lg: native.ctelbo_loss(lg, x0i, xi, *tabs, eps, elbo_scale, nll_scale, reg_scale))
+            if self.one_forward_pass:
+                return k11(x_logits, x_tilde, w, nll_scale)
             # two forward passes (losses.py:150-158): the regulariser and the cross entropy see model(x_t) at reg_x = x_t,
             # the signal term sees model(x~) at x~  --  K11 once per network output with the other term's weight at zero
             logits_sig = model(x_tilde, ts)
-            eps, w = float(self.ratio_eps), float(elbo_scale)
-            reg = _CtElboFn.apply(x_logits, x0, x_t, qt0, qT, rate, eps, 0.0, float(nll_coef) / (B * D), w)
-            sig = _CtElboFn.apply(logits_sig, x0, x_tilde, qt0, qT, rate, eps, w, 0.0, 0.0)
-            return reg + sig
+            return k11(x_logits, x_t, 0.0, nll_scale, w) + k11(logits_sig, x_tilde, w, 0.0, 0.0)
         if self.one_forward_pass:
             logits_sig, reg_x = x_logits, x_tilde
         else:
@@ -181,26 +287,57 @@ class CTElboLambda(_CTElboBase):
         return self._total(state, minibatch, w, 1 - w)
 
 
-class _CtElboWindowFn(torch.autograd.Function):
-    """K11 on a window of rows (ctdd_ctelbo_loss_window): the network's full (B, Dl, S) logits are read in place, the gradient
-    comes back full-shape with zeros on the rows before `d_off`; x0 / x_tilde are the compact (B, Dl - d_off) free rows."""
+class _HeldCTElbo:
+    """The body CondCTElbo and InpaintCTElbo share: the CT-ELBO of the rows that are not held.  t ~ U(min_time, 1); the single
+    forward of one_forward_pass is at x~; with two passes the regulariser sees model(x_t) at reg_x = x_t and the signal term and
+    the cross entropy see model(x~).  A subclass's _held_rows(minibatch) describes the held rows as (prefix, x0, free, n_ce):
+    `prefix` (B, k) the held entries in front of the noised ones (k = 0 under a mask), x0 (B, d) the entries that are noised, `free`
+    (B, d) bool the ones among them that carry the objective (None: all), n_ce the number of rows in the cross-entropy mean.
+    On a GPU K11 reads the network's full (B, k + d, S) logits in place -- a row window (ctdd_ctelbo_loss_window) for a prefix, the
+    free rows (ctdd_ctelbo_loss_masked) for a mask -- and the gradient comes back full shape with zeros on the held rows."""
 
-    @staticmethod
-    def forward(ctx, logits_full, x0, x_tilde, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale, d_off):
-        i32 = lambda t: t.to(torch.int32).contiguous()
-        val, grad = native.ctelbo_loss_window(logits_full.detach().float().contiguous(), i32(x0), i32(x_tilde), qt0.contiguous(),
-                                              qt0T.contiguous(), rate.contiguous(), eps, sig_scale, reg_scale, nll_scale, d_off)
-        ctx.save_for_backward(grad)
-        return val
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.ratio_eps = cfg.loss.eps_ratio
+        self.nll_weight = cfg.loss.nll_weight
+        self.min_time = cfg.loss.min_time
+        self.one_forward_pass = cfg.loss.one_forward_pass
 
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 10
+    def calc_loss(self, minibatch, state=None, label=None):
+        state, minibatch = _unpack(minibatch, state)
+        prefix, x0, free, n_ce = self._held_rows(minibatch)
+        model = state["model"]
+        B, k = x0.shape[0], prefix.shape[1]
+        ts = _draw_ts(B, model.device, self.min_time, 1.0)
+        qt0, qT, rate, x_t, x_tilde = _noise(model, x0, ts, True, want_T=True, free=free)   # only the rows that are not held are noised
+        eps, nll_scale = float(self.ratio_eps), float(self.nll_weight) / n_ce
+        net = lambda x: model(torch.cat((prefix, x), dim=1) if k else x, ts)               # (B, k + d, S): the network sees held values
+        if self.one_forward_pass:
+            logits_sig = logits_reg = net(x_tilde)
+            reg_x = x_tilde
+        else:
+            logits_reg = net(x_t)
+            logits_sig = net(x_tilde)
+            reg_x = x_t
+        if _fused(self.cfg, logits_sig):
+            def k11(logits, x, sig_scale, reg_scale, nll_scale):
+                x0i, xi, tabs = _i32(x0), _i32(x), (qt0.contiguous(), qT.contiguous(), rate.contiguous())
+                if free is None:
+                    return _HipValueGrad.apply(logits, lambda lg: native.ctelbo_loss_window(lg, x0i, xi, *tabs, eps, sig_scale, reg_scale,
+                                                                                              nll_scale, k))
+                return _HipValueGrad.apply(logits, lambda lg: native.ctelbo_loss_masked(lg, x0i, xi, free, *tabs, eps, sig_scale, reg_scale,
+                                                                                          nll_scale))
+            if self.one_forward_pass:
+                return k11(logits_sig, x_tilde, 1.0, 1.0, nll_scale)
+            return k11(logits_reg, x_t, 0.0, 1.0, 0.0) + k11(logits_sig, x_tilde, 1.0, 0.0, nll_scale)
+        l_reg = logits_reg[:, k:, :] if k else logits_reg                                  # (S > 256, cfg.loss.fused = False)
+        l_sig = l_reg if self.one_forward_pass else logits_sig[:, k:, :] if k else logits_sig
+        neg_elbo = _ct_elbo_terms(l_reg, l_sig, x0, reg_x, x_tilde, qt0, rate, self.ratio_eps, free)
+        return neg_elbo + _ce_term(l_sig, x0, self.nll_weight, nll_scale, free)
 
 
 @losses_utils.register_loss
-class CondCTElbo:
+class CondCTElbo(_HeldCTElbo):
     """CT-ELBO of the free rows given a held prefix (losses.py:547-781): the first `condition_dim` entries of every sample are the
     conditioner, passed to the network unnoised; rows condition_dim .. D-1 are noised and carry the objective.  What the
     conditional samplers (ConditionalTauLeaping / ConditionalPCTauLeaping) assume the model was trained with.
@@ -209,134 +346,23 @@ class CondCTElbo:
     passes the cross entropy is on the second (x~) forward's logits (665, 777-779)."""
 
     def __init__(self, cfg):
-        self.cfg = cfg
-        self.ratio_eps = cfg.loss.eps_ratio
-        self.nll_weight = cfg.loss.nll_weight
-        self.min_time = cfg.loss.min_time
-        self.one_forward_pass = cfg.loss.one_forward_pass
+        super().__init__(cfg)
         self.condition_dim = cfg.loss.condition_dim
         self.cross_ent = nn.CrossEntropyLoss()
 
-    def calc_loss(self, minibatch, state=None, label=None):
-        state, minibatch = _unpack(minibatch, state)
+    def _held_rows(self, minibatch):
         minibatch = _flatten(minibatch)
         D, k = self.cfg.model.concat_dim, self.condition_dim
         if not (isinstance(k, int) and 0 < k < D):
             raise ValueError(f"CondCTElbo: loss.condition_dim must be an integer in (0, {D}), got {k!r}")
         if minibatch.dim() != 2 or minibatch.shape[1] != D:
             raise ValueError(f"CondCTElbo: minibatch of shape {tuple(minibatch.shape)}, model.concat_dim = {D}")
-        model = state["model"]
         x0_full = minibatch.long()
-        B, d = x0_full.shape[0], D - k
-        conditioner, data = x0_full[:, :k], x0_full[:, k:].contiguous()
-        ts = _draw_ts(B, model.device, self.min_time, 1.0)
-        qt0, rate, x_t, x_tilde, qT = _noise(model, data, ts, True, want_T=True)          # (B, d): only the free rows are noised
-        eps, nll_coef = float(self.ratio_eps), float(self.nll_weight)
-        if self.one_forward_pass:
-            logits_sig = logits_reg = model(torch.cat((conditioner, x_tilde), dim=1), ts)   # (B, D, S)
-            reg_x = x_tilde
-        else:
-            logits_reg = model(torch.cat((conditioner, x_t), dim=1), ts)
-            logits_sig = model(torch.cat((conditioner, x_tilde), dim=1), ts)
-            reg_x = x_t
-        fused = logits_sig.is_cuda and logits_sig.shape[-1] <= 256 and getattr(self.cfg.loss, "fused", True)
-        if fused and self.one_forward_pass:
-            return _CtElboWindowFn.apply(logits_sig, data, x_tilde, qt0, qT, rate, eps, 1.0, 1.0, nll_coef / (B * d), k)
-        if fused:
-            reg = _CtElboWindowFn.apply(logits_reg, data, x_t, qt0, qT, rate, eps, 0.0, 1.0, 0.0, k)
-            sig = _CtElboWindowFn.apply(logits_sig, data, x_tilde, qt0, qT, rate, eps, 1.0, 0.0, nll_coef / (B * d), k)
-            return reg + sig
-        l_reg = logits_reg[:, k:, :]                                                       # (S > 256, cfg.loss.fused = False)
-        l_sig = l_reg if self.one_forward_pass else logits_sig[:, k:, :]
-        neg_elbo = _ct_elbo_terms(l_reg, l_sig, data, reg_x, x_tilde, qt0, rate, self.ratio_eps)
-        return neg_elbo + self.nll_weight * self.cross_ent(l_sig.permute(0, 2, 1), data)
-
-
-class _CtElboMaskedFn(torch.autograd.Function):
-    """K11 on a per-sample set of free rows (ctdd_ctelbo_loss_masked): the network's (B, D, S) logits are read in place, x0 /
-    x_tilde are full shape, the gradient comes back full shape with exact zeros on the held rows."""
-
-    @staticmethod
-    def forward(ctx, logits, x0, x_tilde, free, qt0, qt0T, rate, eps, sig_scale, reg_scale, nll_scale):
-        i32 = lambda t: t.to(torch.int32).contiguous()
-        val, grad = native.ctelbo_loss_masked(logits.detach().float().contiguous(), i32(x0), i32(x_tilde), free, qt0.contiguous(),
-                                              qt0T.contiguous(), rate.contiguous(), eps, sig_scale, reg_scale, nll_scale)
-        ctx.save_for_backward(grad)
-        return val
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 10
-
-
-def _ct_elbo_terms_masked(logits_reg, logits_sig, x0, reg_x, x_tilde, free, qt0, rate, eps):
-    """_ct_elbo_terms with every sum over dimensions restricted to the sample's free rows (`free` (B, D) bool): per sample the
-    negative CT-ELBO of its free rows alone; a sample without a free row contributes zero.  Full-shape operands."""
-    B = x0.shape[0]
-    n = torch.arange(B, device=x0.device).view(B, 1)
-    qT, rT = qt0.transpose(1, 2), rate.transpose(1, 2)
-    rows = lambda v: torch.where(free, v, torch.zeros_like(v)).sum(1)         # (B, D) -> (B): the free rows only
-    p_reg = F.softmax(logits_reg, dim=2)
-    reg_tmp = _masked_rows(rT, reg_x) @ qT
-    reg_term = rows(torch.sum((p_reg / (qT[n, reg_x] + eps)) * reg_tmp, dim=2))
-    p_sig = p_reg if logits_sig is logits_reg else F.softmax(logits_sig, dim=2)
-    inner = torch.log((p_sig / (qT[n, x_tilde] + eps)) @ qt0 + eps)
-    outer_rate = _masked_rows(rT, x_tilde)
-    q_x0 = qt0[n, x0]
-    q_x0_xt = torch.gather(q_x0, -1, x_tilde.unsqueeze(-1)) + eps
-    outer = rows(torch.sum(outer_rate * (q_x0 / q_x0_xt) * inner, dim=2))
-    row_sums = -torch.diagonal(rate, dim1=1, dim2=2)
-    base_tmp = row_sums[n, x_tilde]
-    Z = rows(base_tmp).view(B, 1, 1) - base_tmp.unsqueeze(-1) + row_sums.unsqueeze(1)
-    Z = torch.where(free.unsqueeze(-1), Z, torch.ones_like(Z))                # (a held row's Z is not a normaliser of anything)
-    sig_norm = rows(torch.sum(outer_rate * q_x0 / (Z * q_x0_xt), dim=2))
-    some = free.any(dim=1)
-    sig = torch.where(some, -outer / torch.where(some, sig_norm, torch.ones_like(sig_norm)), torch.zeros_like(outer))
-    return torch.mean(sig) + torch.mean(reg_term)
-
-
-def _free_rows(name, cfg, minibatch):
-    """The inpainting objectives' minibatch and mask: (x0 (B, D) int64, free (B, D) bool on x0's device, n_free).  The mask is
-    drawn (or taken from the _FIXED_NOISE hook) and counted on the host; shape and config errors are ValueErrors before any
-    device work."""
-    import lib.losses.masks as masks
-    minibatch = _flatten(minibatch)
-    D = cfg.model.concat_dim
-    if minibatch.dim() != 2 or minibatch.shape[1] != D or minibatch.shape[0] < 1:
-        raise ValueError(f"{name}: minibatch of shape {tuple(minibatch.shape)}, model.concat_dim = {D}")
-    B = int(minibatch.shape[0])
-    if _FIXED_NOISE is not None and "free" in _FIXED_NOISE:
-        masks.check_mask_config(cfg, D)
-        free_host = torch.as_tensor(_FIXED_NOISE["free"]).cpu()
-        if free_host.dtype != torch.bool or tuple(free_host.shape) != (B, D):
-            raise ValueError(f"{name}: pinned free mask {free_host.dtype} {tuple(free_host.shape)}, expected bool {(B, D)}")
-    else:
-        free_host = masks.sample_free(cfg, B, D)
-    n_free = int(free_host.sum())                                  # on the host: the cross-entropy weight is a plain float
-    x0 = minibatch.long()
-    # the step's one upload of the mask: from pinned memory, asynchronous -- a pageable copy would make the host wait for the device
-    free = free_host.pin_memory().to(x0.device, non_blocking=True) if x0.is_cuda else free_host
-    return x0, free, n_free
-
-
-def _noise_masked(model, x0, free, ts, with_tilde):
-    """Tables and full-shape int64 x_t, x~ (None unless with_tilde): held entries of both are x0 bit for bit."""
-    if _FIXED_NOISE is not None:
-        qt0, qT, rate, _ = model.process.tables(ts, want_qt0=True, want_qt0T=True, want_rate=True)
-        pin = lambda k: torch.where(free, _FIXED_NOISE[k].to(x0.device).long(), x0)
-        return qt0, qT, rate, pin("x_t"), pin("x_tilde") if with_tilde else None
-    qt0, qT, rate, probs = model.process.tables(ts, want_qt0=True, want_qt0T=True, want_rate=True, want_noise_probs=True)
-    x0i = x0.to(torch.int32).contiguous()
-    x_t = torch.where(free, native.noise_categorical(probs, x0i, seed=_seed()), x0i)
-    if not with_tilde:
-        return qt0, qT, rate, x_t.long(), None
-    _, _, x_tilde = native.xtilde_sample_masked(rate, x_t, free, seed=_seed())
-    return qt0, qT, rate, x_t.long(), x_tilde.long()
+        return x0_full[:, :k], x0_full[:, k:].contiguous(), None, x0_full.shape[0] * (D - k)
 
 
 @losses_utils.register_loss
-class InpaintCTElbo:
+class InpaintCTElbo(_HeldCTElbo):
     """CT-ELBO of a per-sample set of free entries given the held ones: what a model must be trained with for the samplers'
     `inpaint(model, x_known, mask)` under masks that are not a prefix.  cfg.loss.mask names the mask distribution
     (lib/losses/masks.py: prefix / bernoulli / half / box / mixture); the other fields are CondCTElbo's, and so are its
@@ -348,43 +374,15 @@ class InpaintCTElbo:
     where neg_elbo_b is the negative CT-ELBO of sample b on its free rows alone.  With mask = "prefix" this is CondCTElbo."""
 
     def __init__(self, cfg):
-        self.cfg = cfg
-        self.ratio_eps = cfg.loss.eps_ratio
-        self.nll_weight = cfg.loss.nll_weight
-        self.min_time = cfg.loss.min_time
-        self.one_forward_pass = cfg.loss.one_forward_pass
+        super().__init__(cfg)
         self.mask = cfg.loss.mask
 
-    def _noise(self, model, x0, free, ts):
-        return _noise_masked(model, x0, free, ts, True)
-
-    def calc_loss(self, minibatch, state=None, label=None):
-        state, minibatch = _unpack(minibatch, state)
+    def _held_rows(self, minibatch):
         x0, free, n_free = _free_rows("InpaintCTElbo", self.cfg, minibatch)
-        B = int(x0.shape[0])
-        model = state["model"]
-        ts = _draw_ts(B, model.device, self.min_time, 1.0)
-        qt0, qT, rate, x_t, x_tilde = self._noise(model, x0, free, ts)
-        eps, nll_scale = float(self.ratio_eps), float(self.nll_weight) / max(n_free, 1)
-        if self.one_forward_pass:                                      # (B, D, S): the network sees held values, not the mask
-            logits_sig = logits_reg = model(x_tilde, ts)
-            reg_x = x_tilde
-        else:
-            logits_reg = model(x_t, ts)
-            logits_sig = model(x_tilde, ts)
-            reg_x = x_t
-        fused = logits_sig.is_cuda and logits_sig.shape[-1] <= 256 and getattr(self.cfg.loss, "fused", True)
-        if fused and self.one_forward_pass:
-            return _CtElboMaskedFn.apply(logits_sig, x0, x_tilde, free, qt0, qT, rate, eps, 1.0, 1.0, nll_scale)
-        if fused:
-            reg = _CtElboMaskedFn.apply(logits_reg, x0, x_t, free, qt0, qT, rate, eps, 0.0, 1.0, 0.0)
-            sig = _CtElboMaskedFn.apply(logits_sig, x0, x_tilde, free, qt0, qT, rate, eps, 1.0, 0.0, nll_scale)
-            return reg + sig
-        neg_elbo = _ct_elbo_terms_masked(logits_reg, logits_sig, x0, reg_x, x_tilde, free, qt0, rate, self.ratio_eps)
-        ce = F.cross_entropy(logits_sig.permute(0, 2, 1), x0, reduction="none")
-        return neg_elbo + nll_scale * torch.where(free, ce, torch.zeros_like(ce)).sum()
+        return x0[:, :0], x0, free, max(n_free, 1)
 
 
+# ---------------------------------------------------------------- categorical ratio matching
 def _crm_loss(cfg, model, xt, t, ll_all, ll_xt):
     """Categorical ratio matching objectives (losses.py:794-836): rm / mle / elbo, per (b,d)."""
     S = cfg.data.S
@@ -404,109 +402,61 @@ def _crm_loss(cfg, model, xt, t, ll_all, ll_xt):
     raise ValueError("Unknown loss_type: %s" % lt)
 
 
-class _ScoreElboFn(torch.autograd.Function):
-    """ScoreElbo value and logit-gradient in HIP (csrc/losses.hip), direct logits."""
+def _crm_reverse(logits, xt, x0, free, qt0, qT, logit_type, loss_type, scale, nll_scale):
+    """The CRM objectives for logit_type reverse_prob / reverse_logscale in HIP: ctdd_logprob -> K12 on ll_all -> ctdd_logprob_bwd.
+    The cross-entropy term (x0 given) is on the raw logits: without a mask it rides in the last launch, under a mask `free` it
+    is one more ctdd_crm_loss_masked pass (loss_type rm, scale 0)."""
+    xti, x0i, q_elbo = _i32(xt), _i32(x0), qt0 if loss_type == "elbo" else None
 
-    @staticmethod
-    def forward(ctx, logits, x0, x_tilde, reg_x, qt0, rate, eps, nll_scale):
-        i32 = lambda t: t.to(torch.int32).contiguous()
-        val, grad = native.score_elbo_loss(logits.detach().float().contiguous(), i32(x0), i32(x_tilde), i32(reg_x), qt0.contiguous(),
-                                           rate.contiguous(), eps, nll_scale)
-        ctx.save_for_backward(grad)
-        return val
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 7
-
-
-class _CrmLossFn(torch.autograd.Function):
-    """K12 (csrc/losses.hip): value and logit-gradient of the CRM objective in one HIP pass."""
-
-    @staticmethod
-    def forward(ctx, logits, xt, x0, qt0, loss_type, scale, nll_scale):
-        val, grad = native.crm_loss(logits.detach().float().contiguous(), xt.to(torch.int32).contiguous(),
-                                    None if x0 is None else x0.to(torch.int32).contiguous(),
-                                    None if qt0 is None else qt0.float().contiguous(), loss_type, scale, nll_scale)
-        ctx.save_for_backward(grad)
-        return val
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None, None, None, None, None
+    def f(lg):
+        if free is None:
+            return _reverse_chain(lg, xti, qt0, qT, logit_type, lambda ll_all: native.crm_loss_ll(ll_all, xti, q_elbo, loss_type, scale),
+                                  x0i, nll_scale)
+        val, grad = _reverse_chain(lg, xti, qt0, qT, logit_type,
+                                   lambda ll_all: native.crm_loss_ll_masked(ll_all, xti, free, q_elbo, loss_type, scale))
+        if x0i is not None:
+            ce, grad_ce = native.crm_loss_masked(lg, xti, x0i, free, None, "rm", 0.0, nll_scale)
+            val, grad = val + ce, grad.add_(grad_ce)
+        return val, grad
+    return _HipValueGrad.apply(logits, f)
 
 
-def _tables_with_transpose(model, ts):
-    """(q_{t|0}, its transpose), each (B,S,S): the transpose straight out of K1 when the model carries a device process."""
-    pr = getattr(model, "process", None)
-    if pr is not None and hasattr(pr, "tables"):
-        qt0, qT, _, _ = pr.tables(ts, want_qt0=True, want_qt0T=True)
-        return qt0, qT
-    qt0 = model.transition(ts).float().contiguous()
-    return qt0, qt0.transpose(1, 2).contiguous()
-
-
-class _CrmRevFn(torch.autograd.Function):
-    """CRM objectives for logit_type reverse_prob / reverse_logscale in HIP: ctdd_logprob -> K12 on ll_all -> ctdd_logprob_bwd
-    (+ CatRMNLL's cross-entropy term on the raw logits inside the last launch)."""
-
-    @staticmethod
-    def forward(ctx, logits, xt, x0, qt0, qt0T, logit_type, loss_type, scale, nll_scale):
-        lg = logits.detach().float().contiguous()
-        xti = xt.to(torch.int32).contiguous()
-        tidx = torch.arange(lg.shape[0], dtype=torch.int32, device=lg.device)
-        ll_all, _ = native.logprob(lg, xti, qt0, logit_type, tidx, qt0T=qt0T)
-        val, dll = native.crm_loss_ll(ll_all, xti, qt0 if loss_type == "elbo" else None, loss_type, scale)
-        grad, ce = native.logprob_bwd(logit_type, lg, qt0, qt0T, dll, None if x0 is None else x0.to(torch.int32).contiguous(), nll_scale,
-                                      ll_all=ll_all)
-        ctx.save_for_backward(grad)
-        return val if x0 is None else val + ce
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 8
-
-
-class _ScoreElboRevFn(torch.autograd.Function):
-    """ScoreElbo for the reverse logit types in HIP (same three-launch chain)."""
-
-    @staticmethod
-    def forward(ctx, logits, x0, x_tilde, reg_x, qt0, qt0T, rate, logit_type, eps, nll_scale):
-        lg = logits.detach().float().contiguous()
-        i32 = lambda t: t.to(torch.int32).contiguous()
-        tidx = torch.arange(lg.shape[0], dtype=torch.int32, device=lg.device)
-        ll_all, _ = native.logprob(lg, i32(x_tilde), qt0, logit_type, tidx, qt0T=qt0T)
-        val, dll = native.score_elbo_loss_ll(ll_all, i32(x0), i32(x_tilde), i32(reg_x), qt0, rate.contiguous(), eps, nll_scale)
-        grad, _ = native.logprob_bwd(logit_type, lg, qt0, qt0T, dll, ll_all=ll_all)
-        ctx.save_for_backward(grad)
-        return val
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 9
-
-
-def _crm_objective(cfg, model, logits, xt, ts, x0, nll_weight):
-    """sum(loss_bd) (1 - ce_coeff) / B [+ nll_weight * CE(logits, x0)]; direct logits on a GPU run in K12."""
+def _crm_objective(cfg, model, logits, xt, ts, x0, nll_weight, free=None, n_free=None, tables=None):
+    """sum(loss_bd) (1 - ce_coeff) / B [+ nll_weight * CE(logits, x0)]; direct logits on a GPU run in K12.  `free` (B, D) bool with
+    its count n_free: the sums run over the free rows and the cross entropy is their mean; `tables` = (q_{t|0}, its transpose)
+    where the caller holds them already."""
     B, D = xt.shape
+    kind, lt = cfg.loss.logit_type, cfg.loss.loss_type
     scale = (1.0 - cfg.loss.ce_coeff) / B
-    if cfg.loss.logit_type == "direct" and logits.is_cuda:
-        qt0 = model.transition(ts) if cfg.loss.loss_type == "elbo" else None
-        return _CrmLossFn.apply(logits, xt, x0 if nll_weight else None, qt0, cfg.loss.loss_type, scale,
-                                float(nll_weight) / (B * D) if nll_weight else 0.0)
-    if logits.is_cuda and cfg.loss.logit_type in ("reverse_prob", "reverse_logscale") and logits.shape[-1] <= 256 and getattr(cfg.loss, "fused", True):
-        qt0, qT = _tables_with_transpose(model, ts)
-        return _CrmRevFn.apply(logits, xt, x0 if nll_weight else None, qt0, qT, cfg.loss.logit_type, cfg.loss.loss_type, scale,
-                               float(nll_weight) / (B * D) if nll_weight else 0.0)
+    nll_scale = float(nll_weight) / (B * D if free is None else max(n_free, 1)) if nll_weight else 0.0
+    x0_ce = x0 if nll_weight else None
+    # (without a mask the direct kernel runs whatever cfg.loss.fused says, as it always has)
+    if kind == "direct" and logits.is_cuda and (free is None or getattr(cfg.loss, "fused", True)):
+        qt0 = None
+        if lt == "elbo":
+            qt0 = (model.transition(ts) if tables is None else tables[0]).float().contiguous()
+        xti, x0i, mask = _i32(xt), _i32(x0_ce), () if free is None else (free,)
+        k12 = native.crm_loss if free is None else native.crm_loss_masked
+        return _HipValueGrad.apply(logits, lambda lg: k12(lg, xti, x0i, *mask, qt0, lt, scale, nll_scale))
+    if kind in ("reverse_prob", "reverse_logscale") and _fused(cfg, logits):
+        qt0, qT = _tables_with_transpose(model, ts) if tables is None else tables
+        return _crm_reverse(logits, xt, x0_ce, free, qt0.contiguous(), qT, kind, lt, scale, nll_scale)
     ll_all, ll_xt = get_logprob_with_logits(cfg, model, xt, ts, logits)      # (cfg.device == "cpu", S > 256, cfg.loss.fused = False)
-    out = torch.sum(_crm_loss(cfg, model, xt, ts, ll_all, ll_xt)) * scale
+    per_row = _crm_loss(cfg, model, xt, ts, ll_all, ll_xt)
+    out = (torch.sum(per_row) if free is None else torch.where(free, per_row, torch.zeros_like(per_row)).sum()) * scale
     if nll_weight:
-        out = out + nll_weight * F.cross_entropy(logits.permute(0, 2, 1), x0)
+        out = out + _ce_term(logits, x0, nll_weight, nll_scale, free)
     return out
+
+
+# The masked restatements under the names and argument orders tests/test_inpaint_seq_loss_cpu.py holds to the oracle: nothing of their
+# own, the functions above with `free` given (the cross-entropy weight arrives as nll_scale = nll_weight / n_free).
+def _crm_terms_masked(cfg, model, logits, x_t, ts, x0, free, nll_scale):
+    return _crm_objective(cfg, model, logits, x_t, ts, x0, nll_scale, free, n_free=1)
+
+
+def _score_elbo_terms_masked(cfg, model, logits, x0, reg_x, x_tilde, ts, free, qt0, rate, eps, nll_weight):
+    return _score_elbo_terms(cfg, model, logits, x0, reg_x, x_tilde, ts, qt0, rate, eps, nll_weight, free)
 
 
 class _CRMBase:
@@ -527,7 +477,7 @@ class _CRMBase:
         ts = _draw_ts(B, model.device, self.min_time, self.t_hi)
         if self.clamp_t:
             ts = torch.clamp(ts, max=0.99999)
-        _, _, xt, _ = _noise(model, x0, ts, False)
+        xt = _noise(model, x0, ts, False)[3]
         return model, x0, ts, xt
 
 
@@ -575,173 +525,6 @@ class NLLOriginal(_CRMBase):
 
 
 @losses_utils.register_loss
-class ScoreElbo:
-    """CT-ELBO evaluated with SDDM ratios exp(ll_all - ll_xt) + nll_weight * mean(-ll_xt)
-    (losses.py:1246-1500)."""
-
-    def __init__(self, cfg):
-        self.cfg = cfg
-        self.ratio_eps = cfg.loss.eps_ratio
-        self.nll_weight = cfg.loss.nll_weight
-        self.min_time = cfg.loss.min_time
-        self.one_forward_pass = cfg.loss.one_forward_pass
-
-    def calc_loss(self, minibatch, state=None, label=None):
-        state, minibatch = _unpack(minibatch, state)
-        model = state["model"]
-        x0 = _flatten(minibatch).long()
-        B = x0.shape[0]
-        eps = self.ratio_eps
-        ts = torch.clamp(_draw_ts(B, model.device, self.min_time, 1.0), max=0.99999)
-        qt0, rate, x_t, x_tilde = _noise(model, x0, ts, True)
-        reg_x = x_tilde if self.one_forward_pass else x_t
-        logits = model(reg_x, ts)
-        if self.cfg.loss.logit_type == "direct" and logits.is_cuda and logits.shape[-1] <= 256 and getattr(self.cfg.loss, "fused", True):
-            return _ScoreElboFn.apply(logits, x0, x_tilde, reg_x, qt0, rate, float(eps), float(self.nll_weight) / B)
-        if (self.cfg.loss.logit_type in ("reverse_prob", "reverse_logscale") and logits.is_cuda and logits.shape[-1] <= 256
-                and getattr(self.cfg.loss, "fused", True)):
-            _, qT = _tables_with_transpose(model, ts)
-            return _ScoreElboRevFn.apply(logits, x0, x_tilde, reg_x, qt0.contiguous(), qT, rate, self.cfg.loss.logit_type, float(eps),
-                                         float(self.nll_weight) / B)
-        n = torch.arange(B, device=x0.device).view(B, 1)
-        rT = rate.transpose(1, 2)
-        ll_all, ll_xt = get_logprob_with_logits(self.cfg, model, x_tilde, ts, logits)
-        d = ll_all - ll_xt.unsqueeze(-1)
-        reg_term = torch.sum(torch.exp(d) * _masked_rows(rT, reg_x), dim=(1, 2))
-        outer_rate = _masked_rows(rT, x_tilde)
-        q_x0 = qt0[n, x0]
-        q_x0_xt = torch.gather(q_x0, -1, x_tilde.unsqueeze(-1)) + eps
-        outer = torch.sum(outer_rate * (q_x0 / q_x0_xt) * d, dim=(1, 2))
-        row_sums = -torch.diagonal(rate, dim1=1, dim2=2)
-        base_tmp = row_sums[n, x_tilde]
-        Z = base_tmp.sum(1).view(B, 1, 1) - base_tmp.unsqueeze(-1) + row_sums.unsqueeze(1)
-        sig_norm = torch.sum(outer_rate * q_x0 / (Z * q_x0_xt), dim=(1, 2))
-        neg_elbo = torch.mean(-outer / sig_norm) + torch.mean(reg_term)
-        return neg_elbo + self.nll_weight * (torch.sum(-ll_xt) / B)
-
-
-# ---------------------------------------------------------------- inpainting objectives of the sequence (SDDM) models
-class _CrmMaskedFn(torch.autograd.Function):
-    """K12 on the free rows (ctdd_crm_loss_masked), direct logits: the CE term rides in the same launch."""
-
-    @staticmethod
-    def forward(ctx, logits, xt, x0, free, qt0, loss_type, scale, nll_scale):
-        i32 = lambda t: None if t is None else t.to(torch.int32).contiguous()
-        val, grad = native.crm_loss_masked(logits.detach().float().contiguous(), i32(xt), i32(x0), free,
-                                           None if qt0 is None else qt0.float().contiguous(), loss_type, scale, nll_scale)
-        ctx.save_for_backward(grad)
-        return val
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 7
-
-
-class _CrmRevMaskedFn(torch.autograd.Function):
-    """The CRM objectives on the free rows for the reverse logit types: ctdd_logprob -> ctdd_crm_loss_ll_masked -> ctdd_logprob_bwd
-    (a zero d/d ll_all row comes out as a zero logit-gradient row).  The cross-entropy term is on the raw logits: with x0 given
-    it is one more ctdd_crm_loss_masked pass (loss_type rm, scale 0)."""
-
-    @staticmethod
-    def forward(ctx, logits, xt, x0, free, qt0, qt0T, logit_type, loss_type, scale, nll_scale):
-        lg = logits.detach().float().contiguous()
-        xti = xt.to(torch.int32).contiguous()
-        tidx = torch.arange(lg.shape[0], dtype=torch.int32, device=lg.device)
-        ll_all, _ = native.logprob(lg, xti, qt0, logit_type, tidx, qt0T=qt0T)
-        val, dll = native.crm_loss_ll_masked(ll_all, xti, free, qt0 if loss_type == "elbo" else None, loss_type, scale)
-        grad, _ = native.logprob_bwd(logit_type, lg, qt0, qt0T, dll, ll_all=ll_all)
-        if x0 is not None:
-            ce, grad_ce = native.crm_loss_masked(lg, xti, x0.to(torch.int32).contiguous(), free, None, "rm", 0.0, nll_scale)
-            val, grad = val + ce, grad.add_(grad_ce)
-        ctx.save_for_backward(grad)
-        return val
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 9
-
-
-class _ScoreElboMaskedFn(torch.autograd.Function):
-    """ScoreElbo on the free rows (ctdd_score_elbo_loss_masked), direct logits."""
-
-    @staticmethod
-    def forward(ctx, logits, x0, x_tilde, reg_x, free, qt0, rate, eps, nll_scale):
-        i32 = lambda t: t.to(torch.int32).contiguous()
-        val, grad = native.score_elbo_loss_masked(logits.detach().float().contiguous(), i32(x0), i32(x_tilde), i32(reg_x), free,
-                                                  qt0.contiguous(), rate.contiguous(), eps, nll_scale)
-        ctx.save_for_backward(grad)
-        return val
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 8
-
-
-class _ScoreElboRevMaskedFn(torch.autograd.Function):
-    """ScoreElbo on the free rows for the reverse logit types (the same three-launch chain around ctdd_score_elbo_loss_ll_masked)."""
-
-    @staticmethod
-    def forward(ctx, logits, x0, x_tilde, reg_x, free, qt0, qt0T, rate, logit_type, eps, nll_scale):
-        lg = logits.detach().float().contiguous()
-        i32 = lambda t: t.to(torch.int32).contiguous()
-        tidx = torch.arange(lg.shape[0], dtype=torch.int32, device=lg.device)
-        ll_all, _ = native.logprob(lg, i32(x_tilde), qt0, logit_type, tidx, qt0T=qt0T)
-        val, dll = native.score_elbo_loss_ll_masked(ll_all, i32(x0), i32(x_tilde), i32(reg_x), free, qt0, rate.contiguous(), eps, nll_scale)
-        grad, _ = native.logprob_bwd(logit_type, lg, qt0, qt0T, dll, ll_all=ll_all)
-        ctx.save_for_backward(grad)
-        return val
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 10
-
-
-def _crm_terms_masked(cfg, model, logits, x_t, ts, x0, free, nll_scale):
-    """(1 - ce_coeff)/B * sum_free crm_bd + nll_scale * sum_free CE(logits_bd, x0_bd) in plain torch: full-shape operands, the sums
-    over the free rows (`free` (B, D) bool) only."""
-    ll_all, ll_xt = get_logprob_with_logits(cfg, model, x_t, ts, logits)
-    per_row = _crm_loss(cfg, model, x_t, ts, ll_all, ll_xt)
-    out = torch.where(free, per_row, torch.zeros_like(per_row)).sum() * ((1.0 - cfg.loss.ce_coeff) / x_t.shape[0])
-    if nll_scale:
-        ce = F.cross_entropy(logits.permute(0, 2, 1), x0, reduction="none")
-        out = out + nll_scale * torch.where(free, ce, torch.zeros_like(ce)).sum()
-    return out
-
-
-def _score_elbo_terms_masked(cfg, model, logits, x0, reg_x, x_tilde, ts, free, qt0, rate, eps, nll_weight):
-    """ScoreElbo with every sum over dimensions restricted to the sample's free rows: per sample the objective of its free rows
-    alone; a sample without a free row contributes zero.  Full-shape operands."""
-    B = x0.shape[0]
-    n = torch.arange(B, device=x0.device).view(B, 1)
-    rT = rate.transpose(1, 2)
-    rows = lambda v: torch.where(free, v, torch.zeros_like(v)).sum(1)         # (B, D) -> (B): the free rows only
-    ll_all, ll_xt = get_logprob_with_logits(cfg, model, x_tilde, ts, logits)
-    d = ll_all - ll_xt.unsqueeze(-1)
-    reg_term = rows(torch.sum(torch.exp(d) * _masked_rows(rT, reg_x), dim=2))
-    outer_rate = _masked_rows(rT, x_tilde)
-    q_x0 = qt0[n, x0]
-    q_x0_xt = torch.gather(q_x0, -1, x_tilde.unsqueeze(-1)) + eps
-    outer = rows(torch.sum(outer_rate * (q_x0 / q_x0_xt) * d, dim=2))
-    row_sums = -torch.diagonal(rate, dim1=1, dim2=2)
-    base_tmp = row_sums[n, x_tilde]
-    Z = rows(base_tmp).view(B, 1, 1) - base_tmp.unsqueeze(-1) + row_sums.unsqueeze(1)
-    Z = torch.where(free.unsqueeze(-1), Z, torch.ones_like(Z))                # (a held row's Z is not a normaliser of anything)
-    sig_norm = rows(torch.sum(outer_rate * q_x0 / (Z * q_x0_xt), dim=2))
-    some = free.any(dim=1)
-    sig = torch.where(some, -outer / torch.where(some, sig_norm, torch.ones_like(sig_norm)), torch.zeros_like(outer))
-    return torch.mean(sig) + torch.mean(reg_term) + nll_weight * (rows(-ll_xt).sum() / B)
-
-
-def _fused_reverse(cfg, logits):
-    return (cfg.loss.logit_type in ("reverse_prob", "reverse_logscale") and logits.is_cuda and logits.shape[-1] <= 256
-            and getattr(cfg.loss, "fused", True))
-
-
-@losses_utils.register_loss
 class InpaintCatRM:
     """Categorical ratio matching of a per-sample set of free entries given the held ones: what a hollow / masked transformer must
     be trained with for `inpaint(model, x_known, mask)` of the CRM samplers.  cfg.loss.mask names the mask distribution
@@ -766,24 +549,57 @@ class InpaintCatRM:
         if cfg.loss.logit_type not in native.LOGIT_TYPES:
             raise ValueError(f"InpaintCatRM: unknown loss.logit_type {cfg.loss.logit_type!r}")
         x0, free, n_free = _free_rows("InpaintCatRM", cfg, minibatch)
-        B = int(x0.shape[0])
         model = state["model"]
-        ts = torch.clamp(_draw_ts(B, model.device, self.min_time, 1.0), max=0.99999)
-        qt0, qT, _, x_t, _ = _noise_masked(model, x0, free, ts, False)
+        ts = torch.clamp(_draw_ts(int(x0.shape[0]), model.device, self.min_time, 1.0), max=0.99999)
+        qt0, qT, _, x_t, _ = _noise(model, x0, ts, False, want_T=True, free=free)
         logits = model(x_t, ts)
-        scale, nll_scale = (1.0 - cfg.loss.ce_coeff) / B, float(self.nll_weight) / max(n_free, 1)
-        x0_ce = x0 if nll_scale else None
-        if cfg.loss.logit_type == "direct" and logits.is_cuda and getattr(cfg.loss, "fused", True):
-            return _CrmMaskedFn.apply(logits, x_t, x0_ce, free, qt0 if cfg.loss.loss_type == "elbo" else None, cfg.loss.loss_type,
-                                      scale, nll_scale)
-        if _fused_reverse(cfg, logits):
-            return _CrmRevMaskedFn.apply(logits, x_t, x0_ce, free, qt0.contiguous(), qT, cfg.loss.logit_type, cfg.loss.loss_type,
-                                         scale, nll_scale)
-        return _crm_terms_masked(cfg, model, logits, x_t, ts, x0, free, nll_scale)      # (CPU, S > 256, cfg.loss.fused = False)
+        return _crm_objective(cfg, model, logits, x_t, ts, x0, self.nll_weight, free, n_free, tables=(qt0, qT))
+
+
+# ---------------------------------------------------------------- ScoreElbo
+@losses_utils.register_loss
+class ScoreElbo:
+    """CT-ELBO evaluated with SDDM ratios exp(ll_all - ll_xt) + nll_weight * mean(-ll_xt)
+    (losses.py:1246-1500)."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.ratio_eps = cfg.loss.eps_ratio
+        self.nll_weight = cfg.loss.nll_weight
+        self.min_time = cfg.loss.min_time
+        self.one_forward_pass = cfg.loss.one_forward_pass
+
+    def _rows(self, minibatch):
+        """(x0 (B, D) int64, the mask of its free entries or None)."""
+        return _flatten(minibatch).long(), None
+
+    def calc_loss(self, minibatch, state=None, label=None):
+        state, minibatch = _unpack(minibatch, state)
+        x0, free = self._rows(minibatch)
+        cfg, model = self.cfg, state["model"]
+        B, kind = x0.shape[0], cfg.loss.logit_type
+        eps, nll_scale = float(self.ratio_eps), float(self.nll_weight) / B
+        ts = torch.clamp(_draw_ts(B, model.device, self.min_time, 1.0), max=0.99999)
+        qt0, qT, rate, x_t, x_tilde = _noise(model, x0, ts, True, want_T=free is not None, free=free)
+        reg_x = x_tilde if self.one_forward_pass else x_t
+        logits = model(reg_x, ts)
+        if kind in native.LOGIT_TYPES and _fused(cfg, logits):
+            if kind != "direct" and free is None:                  # (the unmasked noising asks for no transpose: only this chain reads it)
+                qT = _tables_with_transpose(model, ts)[1]
+            mask = () if free is None else (free,)
+
+            def f(lg):
+                ops = (_i32(x0), _i32(x_tilde), _i32(reg_x), *mask, qt0.contiguous(), rate.contiguous())
+                if kind == "direct":
+                    return (native.score_elbo_loss if free is None else native.score_elbo_loss_masked)(lg, *ops, eps, nll_scale)
+                k = native.score_elbo_loss_ll if free is None else native.score_elbo_loss_ll_masked
+                return _reverse_chain(lg, ops[1], ops[-2], qT, kind, lambda ll_all: k(ll_all, *ops, eps, nll_scale))
+            return _HipValueGrad.apply(logits, f)
+        return _score_elbo_terms(cfg, model, logits, x0, reg_x, x_tilde, ts, qt0, rate, self.ratio_eps, self.nll_weight, free)
 
 
 @losses_utils.register_loss
-class InpaintScoreElbo:
+class InpaintScoreElbo(ScoreElbo):
     """ScoreElbo of a per-sample set of free entries given the held ones (cfg.loss.mask: lib/losses/masks.py; the other fields
     are ScoreElbo's).  x_t = x0 on held entries, ~ q_{t|0} on free ones;  x~ moves one free entry of x_t, chosen with probability
     rs[x_t^d] / sum_{d' in F_b} rs[x_t^d'];  reg_x = x~ with one forward pass and x_t with two, logits = model(reg_x, ts);
@@ -792,33 +608,13 @@ class InpaintScoreElbo:
     mask this is ScoreElbo."""
 
     def __init__(self, cfg):
-        self.cfg = cfg
-        self.ratio_eps = cfg.loss.eps_ratio
-        self.nll_weight = cfg.loss.nll_weight
-        self.min_time = cfg.loss.min_time
-        self.one_forward_pass = cfg.loss.one_forward_pass
+        super().__init__(cfg)
         self.mask = cfg.loss.mask
 
-    def calc_loss(self, minibatch, state=None, label=None):
-        state, minibatch = _unpack(minibatch, state)
-        cfg = self.cfg
-        if cfg.loss.logit_type not in native.LOGIT_TYPES:
-            raise ValueError(f"InpaintScoreElbo: unknown loss.logit_type {cfg.loss.logit_type!r}")
-        x0, free, _ = _free_rows("InpaintScoreElbo", cfg, minibatch)
-        B = int(x0.shape[0])
-        model = state["model"]
-        eps = float(self.ratio_eps)
-        ts = torch.clamp(_draw_ts(B, model.device, self.min_time, 1.0), max=0.99999)
-        qt0, qT, rate, x_t, x_tilde = _noise_masked(model, x0, free, ts, True)
-        reg_x = x_tilde if self.one_forward_pass else x_t
-        logits = model(reg_x, ts)
-        fused = logits.is_cuda and logits.shape[-1] <= 256 and getattr(cfg.loss, "fused", True)
-        if cfg.loss.logit_type == "direct" and fused:
-            return _ScoreElboMaskedFn.apply(logits, x0, x_tilde, reg_x, free, qt0, rate, eps, float(self.nll_weight) / B)
-        if _fused_reverse(cfg, logits):
-            return _ScoreElboRevMaskedFn.apply(logits, x0, x_tilde, reg_x, free, qt0.contiguous(), qT, rate, cfg.loss.logit_type, eps,
-                                               float(self.nll_weight) / B)
-        return _score_elbo_terms_masked(cfg, model, logits, x0, reg_x, x_tilde, ts, free, qt0, rate, eps, self.nll_weight)
+    def _rows(self, minibatch):
+        if self.cfg.loss.logit_type not in native.LOGIT_TYPES:
+            raise ValueError(f"InpaintScoreElbo: unknown loss.logit_type {self.cfg.loss.logit_type!r}")
+        return _free_rows("InpaintScoreElbo", self.cfg, minibatch)[:2]
 
 
 class d3pm_loss:

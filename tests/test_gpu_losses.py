@@ -177,7 +177,7 @@ def test_crm_reverse_logit_types_match_oracle_formulas(S, D, logit_type, loss_ty
     wgrad, = torch.autograd.grad(want, lo)
     lg = logits.cuda().requires_grad_(True)
     q = qt0.cuda()
-    val = L._CrmRevFn.apply(lg, xt.cuda(), x0.cuda(), q, q.transpose(1, 2).contiguous(), logit_type, loss_type, scale, nllw / (B * D))
+    val = L._crm_reverse(lg, xt.cuda(), x0.cuda(), None, q, q.transpose(1, 2).contiguous(), logit_type, loss_type, scale, nllw / (B * D))
     grad, = torch.autograd.grad(val, lg)
     np.testing.assert_allclose(val.item(), want.item(), rtol=3e-5)
     np.testing.assert_allclose(grad.cpu().numpy(), wgrad.numpy(), rtol=5e-4, atol=1e-6 * wgrad.abs().max().item() + 1e-9)
@@ -260,3 +260,69 @@ def test_ctelbo_term_weights_compose_the_two_pass_objective(S, D, B):
     v2, d2 = native.ctelbo_loss(lb.detach(), x0.int(), x_tilde.int(), qt0, qT, rate, eps, w, nllw / (B * D), reg_scale=w)
     np.testing.assert_allclose(v1.item(), v2.item(), rtol=1e-6)
     assert (d1 - d2).abs().max().item() <= 1e-6 * d1.abs().max().item()
+
+
+class _LeafLogits:
+    """model(x, t) = shared + own[i] + one_hot(x) / 2 on the i-th call: leaves that tell the network outputs of one step apart."""
+
+    def __init__(self, B, D, S):
+        from ctdd.process import DeviceForwardProcess
+        self.process = DeviceForwardProcess("uniform", S, "cuda", rate_const=1.7, t_func="sqrt_cos")
+        self.device, self.S, self.calls = torch.device("cuda"), S, 0
+        self.shared = torch.randn(B, D, S, generator=torch.Generator().manual_seed(B * D * S)).cuda().requires_grad_()
+        self.own = [torch.zeros(B, D, S, device="cuda", requires_grad=True) for _ in range(2)]
+
+    def __call__(self, x, t):
+        self.calls += 1
+        return self.shared + self.own[self.calls - 1] + 0.5 * torch.nn.functional.one_hot(x, self.S)
+
+    def transition(self, t):
+        return self.process.transition(t)
+
+    def rate(self, t):
+        return self.process.rate(t)
+
+
+# objective -> (config fields, the entry point that must have run, its launches per step)
+_WRAPPED = {"ctelbo": (dict(loss="CTElbo", one_forward_pass=True), "ctdd_ctelbo_loss", 1),
+            "ctelbo_two_pass": (dict(loss="CTElbo", one_forward_pass=False), "ctdd_ctelbo_loss_terms", 2),
+            "crm": (dict(loss="CatRMNLL", logit_type="reverse_prob", loss_type="mle"), "ctdd_crm_loss_ll", 1),
+            "score_elbo": (dict(loss="ScoreElbo", logit_type="direct", one_forward_pass=True), "ctdd_score_elbo_loss", 1)}
+
+
+@pytest.mark.parametrize("B,D,S", [(2, 5, 3), (2, 9, 32)])       # below a wave, rows no multiple of 4 or 8; the matrix-instruction path
+@pytest.mark.parametrize("objective", list(_WRAPPED))
+def test_the_one_autograd_wrapper_scales_and_accumulates(objective, B, D, S):
+    """_HipValueGrad.backward on one objective of each family: the gradient of 3 * loss is exactly 3 * (the gradient of loss), and
+    with two applications in one graph (the two-pass CT-ELBO) the shared leaf gets exactly the sum of the two outputs' gradients."""
+    import lib.losses.losses as L
+    import lib.losses.losses_utils as lu
+    from ctdd import native
+    fields, entry, launches = _WRAPPED[objective]
+    m = dict(S=S, D=D, eps_ratio=1e-9, nll_weight=0.3, min_time=0.01, one_forward_pass=True, logit_type="direct", loss_type="rm",
+             ce_coeff=0.2, max_t=0.95, n_iters=10)
+    m.update(fields)
+    gen = torch.Generator().manual_seed(S + D)
+    x0, x_t = torch.randint(0, S, (B, D), generator=gen).cuda(), torch.randint(0, S, (B, D), generator=gen).cuda()
+    x_tilde = x_t.clone()
+    x_tilde[:, D - 1] = (x_tilde[:, D - 1] + 1) % S
+    model = _LeafLogits(B, D, S)
+    L._FIXED_NOISE = {"ts": torch.rand(B, generator=gen) * 0.8 + 0.1, "x_t": x_t, "x_tilde": x_tilde}
+    before = native.LAUNCH_COUNTS.get(entry, 0)
+    try:
+        state = {"model": model, "n_iter": 3}
+        loss = lu.get_loss(_cfg(m)).calc_loss(x0, state) if m["loss"] in ("CatRMNLL", "ScoreElbo") else lu.get_loss(_cfg(m)).calc_loss(state, x0)
+    finally:
+        L._FIXED_NOISE = None
+    assert native.LAUNCH_COUNTS.get(entry, 0) - before == launches and model.calls == launches
+    leaves = (model.shared,) + tuple(model.own[:launches])
+    g1 = torch.autograd.grad(loss, leaves, retain_graph=True)
+    g3 = torch.autograd.grad(loss * 3.0, leaves)
+    for a, b in zip(g1[1:], g3[1:]):
+        assert torch.isfinite(a).all() and a.abs().max() > 0
+        assert torch.equal(b, a * 3.0)
+    if launches == 1:
+        assert torch.equal(g1[0], g1[1]) and torch.equal(g3[0], g1[0] * 3.0)
+    else:
+        assert not torch.equal(g1[1], g1[2])
+        assert torch.equal(g1[0], g1[1] + g1[2]) and torch.equal(g3[0], g3[1] + g3[2])

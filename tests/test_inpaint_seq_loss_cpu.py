@@ -4,6 +4,7 @@
 2. with an all-free mask the classes are CatRM / CatRMNLL / ScoreElbo;
 3. shape and config errors are ValueErrors raised before the model is touched;
 4. the two inpainting configs build and register; the four masked entry points are declared, bound and exported."""
+import inspect
 import os
 import re
 
@@ -209,8 +210,13 @@ def test_registry_and_entry_points():
     for name in ("crm_loss_masked", "crm_loss_ll_masked", "score_elbo_loss_masked", "score_elbo_loss_ll_masked"):
         assert re.search(r"^int\s+ctdd_" + name + r"\s*\(", hdr, flags=re.M), name
         assert "ctdd_" + name in native.EXPORTS and callable(getattr(native, name))
-    for fn in (L._CrmMaskedFn, L._CrmRevMaskedFn, L._ScoreElboMaskedFn, L._ScoreElboRevMaskedFn):
-        assert issubclass(fn, torch.autograd.Function)
+    # one autograd wrapper for every fused objective, and the inpainting losses reach it through the bodies they share
+    fns = [v for v in vars(L).values() if isinstance(v, type) and issubclass(v, torch.autograd.Function)]
+    assert fns == [L._HipValueGrad]
+    assert L.InpaintScoreElbo.calc_loss is L.ScoreElbo.calc_loss and L.InpaintCTElbo.calc_loss is L.CondCTElbo.calc_loss
+    for body in (L.ScoreElbo.calc_loss, L.CondCTElbo.calc_loss, L._crm_objective, L._crm_reverse):
+        assert "_HipValueGrad.apply(" in inspect.getsource(body), body
+    assert "_crm_objective(" in inspect.getsource(L.InpaintCatRM.calc_loss)
 
 
 @pytest.mark.parametrize("which", ["maze", "synthetic"])
