@@ -1,0 +1,312 @@
+// absorb.hip -- absorbing-state ("masked") diffusion: forward noising (ctdd_absorb_noise), the negative ELBO with its logit
+// gradient (ctdd_absorb_elbo_loss) and one reverse step (ctdd_absorb_step).  include/ctdd_absorb.h states the formulas and the
+// Philox counter layouts.
+//
+// Loss and step are row softmaxes over a row that fits in registers.  A row is owned by a group of LPR lanes of one wave, lane j of
+// the group holding the PER consecutive states PER j .. PER j + PER - 1 (float4 loads when S % 4 == 0); 64 / LPR rows per wave,
+// four waves per workgroup:
+//   S <= 4: LPR 1 (64 rows a wave)   S <= 16: LPR 4 (16)   S <= 64: LPR 16 (4)   S <= 256 / 512 / 1024: LPR 64, PER 4 / 8 / 16 (1)
+// Every reduction and the inverse-CDF scan are shuffles inside the group.  A row is read once (maximum, sum, scan and gradient
+// come from the registers) and not at all where nothing depends on it: rows without a term in the loss, rows that are not masked or
+// do not unmask in the step.  The loss sum and the step's counter take one atomic per workgroup.
+#include "common.hpp"
+#include "../../include/ctdd_absorb.h"
+
+namespace ctdd {
+
+constexpr int AWV = 4;        // waves per workgroup
+
+template <int LPR>
+__device__ inline float grp_max(float v) {
+#pragma unroll
+  for (int m = LPR / 2; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, WAVE));
+  return v;
+}
+template <int LPR>
+__device__ inline float grp_sum(float v) {
+#pragma unroll
+  for (int m = LPR / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
+  return v;
+}
+template <int LPR>
+__device__ inline int grp_sum_i(int v) {
+#pragma unroll
+  for (int m = LPR / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
+  return v;
+}
+
+// the lane's PER states of one row, -inf past S and at the mask state; nothing is read unless `need`
+template <int PER>
+__device__ inline void absorb_load(const float* __restrict__ src, int S, int s0, int mask_state, bool vec, bool need, float (&v)[PER]) {
+#pragma unroll
+  for (int k = 0; k < PER; ++k) v[k] = -INFINITY;
+  if (!need) return;
+  if (vec) {                                                    // S % 4 == 0 and a 16-byte aligned base: a float4 is inside the row or past it
+#pragma unroll
+    for (int q = 0; q < PER / 4; ++q) {
+      const int s = s0 + 4 * q;
+      if (s < S) {
+        const float4 t = *reinterpret_cast<const float4*>(src + s);
+        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if (s0 + k < S) v[k] = src[s0 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < PER; ++k)
+    if (s0 + k == mask_state) v[k] = -INFINITY;
+}
+
+template <int PER>
+__device__ inline void absorb_store(float* __restrict__ dst, int S, int s0, bool vec, const float (&g)[PER]) {
+  if (vec) {
+#pragma unroll
+    for (int q = 0; q < PER / 4; ++q) {
+      const int s = s0 + 4 * q;
+      if (s < S) *reinterpret_cast<float4*>(dst + s) = make_float4(g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if (s0 + k < S) dst[s0 + k] = g[k];
+  }
+}
+
+// ---------------------------------------------------------------- noising: thread i owns the entries 4 i .. 4 i + 3 (one Philox block)
+__global__ __launch_bounds__(256) void k_absorb_noise(const int32_t* __restrict__ x0, const float* __restrict__ alpha, int64_t n, int D,
+                                                      int mask_state, uint64_t seed, uint64_t offset, int32_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t e0 = i * 4;
+  if (e0 >= n) return;
+  const u4 r = philox_row(seed, offset, (uint64_t)i, 0u);
+  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int64_t e = e0 + c;
+    if (e < n) out[e] = u01(w[c]) >= alpha[e / D] ? mask_state : x0[e];
+  }
+}
+
+// ---------------------------------------------------------------- negative ELBO + logit gradient
+struct AbsorbLossArgs {
+  const float* logits;
+  const int32_t *x0, *xt;
+  const float* w;
+  float nll_scale, inv_B;
+  int64_t rows;
+  int D, S, mask_state;
+  int vec;
+  double* acc;                // scratch: the fp64 sum of the call ...
+  unsigned int* done;         // ... and the number of workgroups that have added to it
+  float* out_loss;
+  float* grad;
+};
+
+template <int LPR, int PER>
+__global__ __launch_bounds__(64 * AWV) void k_absorb_loss(const AbsorbLossArgs a) {
+  __shared__ double red[AWV];
+  constexpr int RPW = WAVE / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane % LPR, s0 = j * PER, S = a.S, m = a.mask_state;
+  const int64_t row = ((int64_t)blockIdx.x * AWV + wave) * RPW + lane / LPR;
+  const bool in = row < a.rows;
+  float wt = 0.0f;
+  int x0 = -1;
+  if (in) {
+    x0 = a.x0[row];
+    if (x0 != m && x0 >= 0 && x0 < S) {
+      wt = a.nll_scale;
+      if (a.xt[row] == m) wt += a.w[row / a.D] * a.inv_B;
+    }
+  }
+  const bool need = wt != 0.0f;                                 // uniform over the row's group
+  float v[PER], e[PER];
+  absorb_load<PER>(a.logits + (size_t)(in ? row : 0) * S, S, s0, m, a.vec, need, v);
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) mx = fmaxf(mx, v[k]);
+  mx = grp_max<LPR>(mx);
+  if (!(mx > -INFINITY)) mx = 0.0f;                             // rows that were not read
+  float z = 0.0f, lx = 0.0f;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    e[k] = expf(v[k] - mx);                                     // exp(-inf) = 0: the mask state and the states past S
+    z += e[k];
+    if (s0 + k == x0) lx = v[k] - mx;
+  }
+  z = grp_sum<LPR>(z);
+  lx = grp_sum<LPR>(lx);
+  if (in && a.grad) {
+    float g[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) g[k] = need ? wt * (e[k] / z - (s0 + k == x0 ? 1.0f : 0.0f)) : 0.0f;
+    absorb_store<PER>(a.grad + (size_t)row * S, S, s0, a.vec, g);
+  }
+  double t = (need && j == 0) ? (double)wt * (double)(logf(z) - lx) : 0.0;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o, WAVE);
+  if (lane == 0) red[wave] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+#pragma unroll
+    for (int i = 0; i < AWV; ++i) tot += red[i];
+    atomicAdd(a.acc, tot);                                      // (device scope: performed where every XCD sees it)
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the sum's add has completed before the ticket is drawn
+    if (atomicAdd(a.done, 1u) == gridDim.x - 1) {               // the last workgroup: round once, leave the scratch zeroed
+      __threadfence();
+      const double sum = atomicAdd(a.acc, 0.0);
+      a.out_loss[0] += (float)sum;
+      atomicExch((unsigned long long*)a.acc, 0ull);
+      atomicExch(a.done, 0u);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- one reverse step
+struct AbsorbStepArgs {
+  const float* logits;
+  const int32_t* x;
+  int64_t rows;
+  int S, mask_state;
+  int vec;
+  float p;
+  uint32_t flags;
+  uint64_t seed, offset;
+  int32_t* out_x;
+  int32_t* changed;
+};
+
+template <int LPR, int PER>
+__global__ __launch_bounds__(64 * AWV) void k_absorb_step(const AbsorbStepArgs a) {
+  __shared__ int red[AWV];
+  constexpr int RPW = WAVE / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane % LPR, s0 = j * PER, S = a.S, m = a.mask_state;
+  const int64_t row = ((int64_t)blockIdx.x * AWV + wave) * RPW + lane / LPR;
+  const bool in = row < a.rows, greedy = (a.flags & CTDD_ABSORB_ARGMAX) != 0;
+  const int xo = in ? a.x[row] : 0;
+  bool need = in && xo == m;
+  float u1 = 0.0f;
+  if (need && !greedy) {
+    const u4 r = philox_row(a.seed, a.offset, (uint64_t)row, 0u);
+    need = u01(r.x) < a.p;
+    u1 = u01(r.y);
+  }
+  float v[PER];
+  absorb_load<PER>(a.logits + (size_t)(in ? row : 0) * S, S, s0, m, a.vec, need, v);
+  float mx = -INFINITY;
+  int bi = S;                                                   // the lane's first index of its maximum
+#pragma unroll
+  for (int k = 0; k < PER; ++k)
+    if (s0 + k < S && s0 + k != m && (bi == S || v[k] > mx)) { mx = v[k]; bi = s0 + k; }
+  int pick;
+  if (greedy) {
+#pragma unroll
+    for (int o = LPR / 2; o >= 1; o >>= 1) {                    // lowest index on ties
+      const float ov = __shfl_xor(mx, o, WAVE);
+      const int oi = __shfl_xor(bi, o, WAVE);
+      if (oi < S && (bi >= S || ov > mx || (ov == mx && oi < bi))) { mx = ov; bi = oi; }
+    }
+    pick = bi;
+  } else {
+    mx = grp_max<LPR>(mx);
+    if (!(mx > -INFINITY)) mx = 0.0f;
+    float c[PER], run = 0.0f;                                   // inclusive running sums of the lane's weights
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { run += expf(v[k] - mx); c[k] = run; }
+    float inc = run;                                            // inclusive scan of the lanes' totals over the group
+#pragma unroll
+    for (int o = 1; o < LPR; o <<= 1) {
+      const float up = __shfl_up(inc, o, LPR);
+      if (j >= o) inc += up;
+    }
+    const float before = inc - run;
+    const float total = __shfl(inc, LPR - 1, LPR);
+    const float target = u1 * total;
+    int cnt = 0;                                                // states whose running sum is <= target: the pick is their number
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if (s0 + k < S && before + c[k] <= target) ++cnt;
+    pick = grp_sum_i<LPR>(cnt);
+  }
+  if (pick >= S || pick == m || pick < 0) pick = (m == S - 1) ? S - 2 : S - 1;   // target == total after rounding: the last real state
+  const bool left = need;
+  if (in && j == 0) a.out_x[row] = left ? pick : xo;
+  if (a.changed) {
+    int n = (left && j == 0) ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o, WAVE);
+    if (lane == 0) red[wave] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int tot = 0;
+#pragma unroll
+      for (int i = 0; i < AWV; ++i) tot += red[i];
+      if (tot) atomicAdd(a.changed, tot);
+    }
+  }
+}
+
+// (LPR, PER) of a row width; rows per workgroup = AWV * 64 / LPR
+#define ABSORB_SHAPE(S, CALL)                                                       \
+  if ((S) <= 4) { constexpr int LPR = 1, PER = 4; CALL; }                           \
+  else if ((S) <= 16) { constexpr int LPR = 4, PER = 4; CALL; }                     \
+  else if ((S) <= 64) { constexpr int LPR = 16, PER = 4; CALL; }                    \
+  else if ((S) <= 256) { constexpr int LPR = 64, PER = 4; CALL; }                   \
+  else if ((S) <= 512) { constexpr int LPR = 64, PER = 8; CALL; }                   \
+  else { constexpr int LPR = 64, PER = 16; CALL; }
+
+static inline int absorb_lpr(int S) { return S <= 4 ? 1 : S <= 16 ? 4 : S <= 64 ? 16 : 64; }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace ctdd
+
+using namespace ctdd;
+
+extern "C" int ctdd_absorb_noise(const int32_t* x0, const float* alpha, int B, int D, int mask_state, uint64_t seed, uint64_t offset,
+                                 int32_t* out_xt, void* stream) {
+  CTDD_REQUIRE(x0 && alpha && out_xt, CTDD_EINVAL, "absorb noise: null buffer");
+  CTDD_REQUIRE(B > 0 && D > 0 && mask_state >= 0, CTDD_ERANGE, "absorb noise: B=%d D=%d mask_state=%d", B, D, mask_state);
+  const int64_t n = (int64_t)B * D, threads = (n + 3) / 4;
+  const int64_t blocks = (threads + 255) / 256;
+  CTDD_REQUIRE(blocks <= INT32_MAX, CTDD_ERANGE, "absorb noise: B D = %lld entries", (long long)n);
+  hipLaunchKernelGGL(k_absorb_noise, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x0, alpha, n, D, mask_state, seed, offset,
+                     out_xt);
+  return finish_launch("k_absorb_noise");
+}
+
+extern "C" int64_t ctdd_absorb_scratch_bytes(void) { return 16; }
+
+extern "C" int ctdd_absorb_elbo_loss(const float* logits, const int32_t* x0, const int32_t* xt, const float* w, float nll_scale, int B,
+                                     int D, int S, int mask_state, void* scratch, float* out_loss, float* grad_logits, void* stream) {
+  CTDD_REQUIRE(logits && x0 && xt && w && scratch && out_loss, CTDD_EINVAL, "absorb loss: null buffer");
+  CTDD_REQUIRE(B > 0 && D > 0 && S >= 2 && S <= CTDD_MAX_S && mask_state >= 0 && mask_state < S, CTDD_ERANGE,
+               "absorb loss: B=%d D=%d S=%d mask_state=%d (2 <= S <= %d, 0 <= mask_state < S)", B, D, S, mask_state, CTDD_MAX_S);
+  const int64_t rows = (int64_t)B * D;
+  const int rpb = AWV * WAVE / absorb_lpr(S);
+  const int64_t blocks = (rows + rpb - 1) / rpb;
+  CTDD_REQUIRE(blocks <= INT32_MAX, CTDD_ERANGE, "absorb loss: B D = %lld rows", (long long)rows);
+  const int vec = S % 4 == 0 && aligned16(logits) && (!grad_logits || aligned16(grad_logits));
+  AbsorbLossArgs a = {logits, x0, xt, w, nll_scale, 1.0f / (float)B, rows, D, S, mask_state, vec,
+                      (double*)scratch, (unsigned int*)((char*)scratch + 8), out_loss, grad_logits};
+  ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_loss<LPR, PER>), dim3((unsigned)blocks), dim3(64 * AWV), 0, (hipStream_t)stream, a));
+  return finish_launch("k_absorb_loss");
+}
+
+extern "C" int ctdd_absorb_step(const float* logits, const int32_t* x, int N, int D, int S, int mask_state, float p_unmask, uint32_t flags,
+                                uint64_t seed, uint64_t offset, int32_t* out_x, int32_t* out_changed, void* stream) {
+  CTDD_REQUIRE(logits && x && out_x, CTDD_EINVAL, "absorb step: null buffer");
+  CTDD_REQUIRE(N > 0 && D > 0 && S >= 2 && S <= CTDD_MAX_S && mask_state >= 0 && mask_state < S, CTDD_ERANGE,
+               "absorb step: N=%d D=%d S=%d mask_state=%d (2 <= S <= %d, 0 <= mask_state < S)", N, D, S, mask_state, CTDD_MAX_S);
+  CTDD_REQUIRE((flags & ~CTDD_ABSORB_ARGMAX) == 0, CTDD_EINVAL, "absorb step: unknown flags %u", flags);
+  const int64_t rows = (int64_t)N * D;
+  const int rpb = AWV * WAVE / absorb_lpr(S);
+  const int64_t blocks = (rows + rpb - 1) / rpb;
+  CTDD_REQUIRE(blocks <= INT32_MAX, CTDD_ERANGE, "absorb step: N D = %lld rows", (long long)rows);
+  AbsorbStepArgs a = {logits, x, rows, S, mask_state, S % 4 == 0 && aligned16(logits), p_unmask, flags, seed, offset, out_x, out_changed};
+  ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_step<LPR, PER>), dim3((unsigned)blocks), dim3(64 * AWV), 0, (hipStream_t)stream, a));
+  return finish_launch("k_absorb_step");
+}

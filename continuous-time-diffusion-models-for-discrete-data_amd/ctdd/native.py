@@ -83,6 +83,10 @@ _SIGS = {
     "ctdd_d3pm_scratch_bytes": ([_I, _I, _I], _I64),
     "ctdd_d3pm_loss": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P], _I),
     "ctdd_d3pm_step": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _U64, _U64, _P, _P, _P, _P], _I),
+    "ctdd_absorb_noise": ([_P, _P, _I, _I, _I, _U64, _U64, _P, _P], _I),
+    "ctdd_absorb_scratch_bytes": ([], _I64),
+    "ctdd_absorb_elbo_loss": ([_P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+    "ctdd_absorb_step": ([_P, _P, _I, _I, _I, _I, _F, _U32, _U64, _U64, _P, _P, _P], _I),
 }
 UNET_EXPORTS = ("ctdd_unet_conv", "ctdd_unet_conv_patch", "ctdd_unet_conv_res", "ctdd_unet_conv_ring", "ctdd_unet_conv_up_phases", "ctdd_unet_upsample2x", "ctdd_unet_first_conv", "ctdd_unet_gn_apply", "ctdd_unet_gn_onepass", "ctdd_unet_channel_stats",
                 "ctdd_unet_time", "ctdd_unet_time_uniform", "ctdd_unet_attention", "ctdd_unet_logistic_head", "ctdd_unet_resblock_small",
@@ -564,6 +568,65 @@ def d3pm_step(logits, x, qprev, qprevT, q1T, t, eps, noise=None, seed=0, offset=
                                  _ptr(q1T, f32, "q1T"), int(t), N, D, S, float(eps), _ptr(noise, f32, "noise"), int(seed), int(offset),
                                  _ptr(scratch), _ptr(out), _ptr(model), _stream()), "ctdd_d3pm_step")
     return (out, model) if want_logits else out
+
+
+# ---------------------------------------------------------------- absorbing-state diffusion (csrc/absorb.hip, include/ctdd_absorb.h)
+ABSORB_ARGMAX = 1
+ABSORB_MAX_S = 1024          # CTDD_MAX_S
+
+
+def _absorb_shapes(what, logits, states):
+    """(B, D, S) of fp32 logits (B, D, S) against int32 states (B, D) each, given as (name, tensor) pairs."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise CtddError(f"{what}: logits {tuple(getattr(logits, 'shape', ()))}, expected (B, D, S)")
+    B, D, S = (int(v) for v in logits.shape)
+    for name, x in states:
+        if not isinstance(x, torch.Tensor) or tuple(x.shape) != (B, D):
+            raise CtddError(f"{what}: {name} {tuple(getattr(x, 'shape', ()))} against logits {tuple(logits.shape)}")
+    return B, D, S
+
+
+def absorb_noise(x0, alpha, mask_state, seed=0, offset=0):
+    """x_t (B, D) int32: entry (b, d) is mask_state iff its Philox uniform is >= alpha[b], else x0 (ctdd_absorb_noise)."""
+    if not isinstance(x0, torch.Tensor) or x0.dim() != 2 or not isinstance(alpha, torch.Tensor) or tuple(alpha.shape) != (x0.shape[0],):
+        raise CtddError(f"absorb_noise: x0 {tuple(getattr(x0, 'shape', ()))} / alpha {tuple(getattr(alpha, 'shape', ()))}, expected (B, D) / (B,)")
+    B, D = (int(v) for v in x0.shape)
+    out = torch.empty_like(x0) if x0.is_cuda else None
+    _count("ctdd_absorb_noise")
+    _check(load().ctdd_absorb_noise(_ptr(x0, i32, "x0"), _ptr(alpha, f32, "alpha"), B, D, int(mask_state), int(seed), int(offset), _ptr(out),
+                                    _stream()), "ctdd_absorb_noise")
+    return out
+
+
+def absorb_elbo_loss(logits, x0, xt, w, nll_scale, mask_state, want_grad=True):
+    """(value (0-d fp32), d value / d logits (B, D, S) or None): the absorbing-state negative ELBO
+    (1/B) sum_b w[b] sum_{d masked} -lp[x0] + nll_scale sum_{rows} -lp[x0] with the softmax over s != mask_state."""
+    B, D, S = _absorb_shapes("absorb_elbo_loss", logits, (("x0", x0), ("xt", xt)))
+    if not isinstance(w, torch.Tensor) or tuple(w.shape) != (B,):
+        raise CtddError(f"absorb_elbo_loss: w {tuple(getattr(w, 'shape', ()))}, expected {(B,)}")
+    ptrs = (_ptr(logits, f32, "logits"), _ptr(x0, i32, "x0"), _ptr(xt, i32, "xt"), _ptr(w, f32, "w"))
+    lib, dev = load(), logits.device
+    scratch = torch.zeros((int(lib.ctdd_absorb_scratch_bytes()),), dtype=torch.uint8, device=dev)
+    out = torch.zeros((1,), dtype=f32, device=dev)
+    grad = torch.empty_like(logits) if want_grad else None
+    _count("ctdd_absorb_elbo_loss")
+    _check(lib.ctdd_absorb_elbo_loss(*ptrs, float(nll_scale), B, D, S, int(mask_state), _ptr(scratch), _ptr(out), _ptr(grad), _stream()),
+           "ctdd_absorb_elbo_loss")
+    return out[0], grad
+
+
+def absorb_step(logits, x, mask_state, p_unmask, flags=0, seed=0, offset=0, out=None, changed=None):
+    """One reverse step (ctdd_absorb_step): rows of x (N, D) int32 at mask_state unmask with probability p_unmask to a draw from
+    the softmax over s != mask_state (flags = ABSORB_ARGMAX: all of them, to its argmax); the others are copied through.
+    changed: int32[1] device counter of the rows that left the mask state, incremented."""
+    N, D, S = _absorb_shapes("absorb_step", logits, (("x", x),))
+    ptrs = (_ptr(logits, f32, "logits"), _ptr(x, i32, "x"))
+    if out is None:
+        out = torch.empty_like(x)
+    _count("ctdd_absorb_step")
+    _check(load().ctdd_absorb_step(*ptrs, N, D, S, int(mask_state), float(p_unmask), int(flags), int(seed), int(offset), _ptr(out, i32, "out"),
+                                   _ptr(changed, i32, "changed"), _stream()), "ctdd_absorb_step")
+    return out
 
 
 # ---------------------------------------------------------------- the fused training objectives (csrc/losses.hip)

@@ -1,7 +1,8 @@
 """Device-resident CTMC forward process: eigendecomposition on the host at construction (numpy
 float64, exactly as lib/models/forward_model.py does), per-t tables by the K1 HIP kernel.
 
-One object serves the four reference processes; `lib.models.forward_model` wraps it with the
+One object serves the four reference processes and the absorbing-state one (closed-form eigensystem, plus the scalars
+alpha / elbo_weight / unmask_prob that its own objective and sampler run on); `lib.models.forward_model` wraps it with the
 reference's class / attribute names."""
 import math
 
@@ -48,8 +49,34 @@ def birth_death_rate_matrix(S):
     return R - np.diag(np.sum(R, axis=1))
 
 
+def absorbing_rate_matrix(S, rate_const, mask_state):
+    """Every state jumps to `mask_state` at rate_const; the mask state's row is zero."""
+    R = np.zeros((S, S))
+    R[:, mask_state] = rate_const
+    R -= rate_const * np.eye(S)
+    R[mask_state, :] = 0.0
+    return R
+
+
+def absorbing_eigensystem(S, rate_const, mask_state):
+    """(eigenvalues, V, W = V^-1) of absorbing_rate_matrix in closed form: V = I + (1 - e_m) e_m^T, W = I - (1 - e_m) e_m^T,
+    eigenvalue 0 at index m and -rate_const elsewhere (an (S - 1)-fold eigenvalue: no numerical eigensolver)."""
+    col = np.ones(S)
+    col[mask_state] = 0.0
+    V, W = np.eye(S), np.eye(S)
+    V[:, mask_state] += col
+    W[:, mask_state] -= col
+    lam = np.full(S, -float(rate_const))
+    lam[mask_state] = 0.0
+    return lam, V, W
+
+
+ABSORBING_T_FUNCS = ("loglinear", "log_sqr", "sqrt_cos", "log")
+UNMASK_RULES = ("ancestral", "euler", "tauleap")
+
+
 class DeviceForwardProcess:
-    KINDS = ("gaussian", "uniform", "univar", "birthdeath")
+    KINDS = ("gaussian", "uniform", "univar", "birthdeath", "absorbing")
 
     def __init__(self, kind, S, device, **p):
         if kind not in self.KINDS:
@@ -59,6 +86,16 @@ class DeviceForwardProcess:
             R = gaussian_target_rate_matrix(S, p["rate_sigma"], p["Q_sigma"])
             lam, V = np.linalg.eig(R)
             W = np.linalg.inv(V)
+        elif kind == "absorbing":
+            m = self.mask_state = int(p["mask_state"])
+            if not 0 <= m < self.S or self.S < 2:
+                raise ValueError(f"absorbing process: mask_state {m} outside [0, S = {self.S})")
+            if p["t_func"] not in ABSORBING_T_FUNCS:
+                raise ValueError("Unknown t_func %s" % p["t_func"])
+            if p["t_func"] == "loglinear" and float(p["rate_const"]) != 1.0:
+                raise ValueError(f"absorbing process: t_func 'loglinear' takes rate_const = 1, got {p['rate_const']!r}")
+            R = absorbing_rate_matrix(self.S, p["rate_const"], m)
+            lam, V, W = absorbing_eigensystem(self.S, p["rate_const"], m)
         else:
             R = {"uniform": lambda: uniform_rate_matrix(S, p["rate_const"]),
                  "univar": lambda: uniform_rate_matrix(S, p["rate_const"]),
@@ -73,6 +110,10 @@ class DeviceForwardProcess:
     # ---- scalar schedules; t is a float32 tensor (any device) -> same device
     def integral(self, t):
         k, p = self.kind, self.p
+        if k == "absorbing" and p["t_func"] == "loglinear":
+            return -torch.log(1 - (1 - p["alpha_eps"]) * t)
+        if k == "absorbing":
+            k = "univar"                             # log_sqr / sqrt_cos / log: the time-warped uniform process's schedules
         if k == "gaussian" or (k == "univar" and p["t_func"] == "log"):
             return p["time_base"] * (p["time_exp"] ** t) - p["time_base"]
         if k == "uniform":
@@ -88,6 +129,10 @@ class DeviceForwardProcess:
 
     def beta(self, t):
         k, p = self.kind, self.p
+        if k == "absorbing" and p["t_func"] == "loglinear":
+            return (1 - p["alpha_eps"]) / (1 - (1 - p["alpha_eps"]) * t)
+        if k == "absorbing":
+            k = "univar"
         if k == "gaussian" or (k == "univar" and p["t_func"] == "log"):
             return p["time_base"] * math.log(p["time_exp"]) * (p["time_exp"] ** t)
         if k == "uniform":
@@ -107,7 +152,7 @@ class DeviceForwardProcess:
         c = self.integral(t)
         if t_from is not None:
             c = c - self.integral(t_from)
-        elif self.kind == "univar":                  # transition(t) = transit_between(0,t) (:202-204)
+        elif self.kind in ("univar", "absorbing"):   # transition(t) = transit_between(0,t) (:202-204)
             c = c - self.integral(torch.zeros_like(t))
         return c
 
@@ -146,3 +191,40 @@ class DeviceForwardProcess:
         """rate(t)[b, y, :] without materialising (B,S,S): beta(t) * base_rate[y]."""
         b = self._dev(self.beta(t)).view(-1, *([1] * y.dim()))
         return self.base_rate[y.long()] * b
+
+    # ---- absorbing-state scalars; t a float tensor on any device -> same device (the kernels of csrc/absorb.hip take these, no table)
+    def _absorbing(self, what):
+        if self.kind != "absorbing":
+            raise ValueError(f"{what} is defined for the absorbing process only (this one is {self.kind!r})")
+
+    def alpha(self, t):
+        """exp(-c(t)): the probability that an entry is still unmasked at t.  c(t) = rate_const (I(t) - I(0))."""
+        self._absorbing("alpha")
+        if self.p["t_func"] == "loglinear":
+            return 1 - (1 - self.p["alpha_eps"]) * t
+        return torch.exp(-self.p["rate_const"] * self.exponent(t))
+
+    def elbo_weight(self, t):
+        """c'(t) alpha_t / (1 - alpha_t) with c' = rate_const beta(t): the weight of the masked cross entropy in the negative ELBO
+        (1 / t for loglinear, where rate_const = 1)."""
+        self._absorbing("elbo_weight")
+        if self.p["t_func"] == "loglinear":
+            return 1 / t
+        a = self.alpha(t)
+        return self.p["rate_const"] * self.beta(t) * a / (1 - a)
+
+    def unmask_prob(self, t, h, rule="ancestral"):
+        """Probability that a masked entry unmasks in the reverse step t -> t - h.  ancestral: (a(t-h) - a(t)) / (1 - a(t)), the
+        exact posterior for a fixed p_theta (1 at t - h = 0); euler: min(1, h elbo_weight(t)); tauleap: lam exp(-lam) with
+        lam = h elbo_weight(t), exactly one Poisson event (several are rejected, as TauL does for non-ordinal data)."""
+        self._absorbing("unmask_prob")
+        t = torch.as_tensor(t)
+        if rule == "ancestral":
+            a = self.alpha(t)
+            return (self.alpha(t - h) - a) / (1 - a)
+        lam = h * self.elbo_weight(t)
+        if rule == "euler":
+            return torch.clamp(lam, max=1.0)
+        if rule == "tauleap":
+            return lam * torch.exp(-lam)
+        raise ValueError(f"unknown unmasking rule {rule!r}: one of {UNMASK_RULES}")

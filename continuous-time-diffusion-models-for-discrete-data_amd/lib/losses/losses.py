@@ -1,7 +1,8 @@
 """Training losses behind the reference's registry names (lib/losses/losses.py): CTElbo 12-287,
 NLL 1504-1778, CTElboLambda 1783-2058, CondCTElbo 547-781, CatRM 786-890, CatRMNLL 1135-1242,
 NLLOriginal 1049-1103, ScoreElbo 1246-1500; and the inpainting objectives that have no counterpart there: InpaintCTElbo,
-InpaintCatRM, InpaintScoreElbo (the CT-ELBO, CatRM / CatRMNLL and ScoreElbo of a per-sample set of free entries, lib/losses/masks.py).
+InpaintCatRM, InpaintScoreElbo (the CT-ELBO, CatRM / CatRMNLL and ScoreElbo of a per-sample set of free entries, lib/losses/masks.py),
+and AbsorbingElbo (the absorbing-state process's negative ELBO, on its own kernels: csrc/absorb.hip).
 
 Every loss = forward noising x0 -> x_t (and, for the ELBO family, the one-jump neighbour x~) followed
 by an objective on the network's logits.  Noising runs in the HIP kernels K1/K2/K3 (per-sample
@@ -57,6 +58,9 @@ def _noise(model, x0, ts, with_tilde, want_T=False, free=None):
     Returns (qt0, qt0^T, rate, x_t, x~): tables (B,S,S), the transpose None unless want_T; int64 states, x~ None unless with_tilde.
     Under a mask `free` the held entries of x_t and x~ are x0 bit for bit and x~ moves a free entry."""
     fixed = _FIXED_NOISE is not None
+    if getattr(model.process, "kind", None) == "absorbing":
+        # (the one-jump neighbour is undefined at the all-mask state; nothing here has been checked on a zero rate row)
+        raise ValueError("this objective runs the general S x S path, which does not cover the absorbing process: use AbsorbingElbo")
     qt0, qT, rate, probs = model.process.tables(ts, want_qt0=True, want_qt0T=want_T, want_rate=True, want_noise_probs=not fixed)
     if fixed:
         def pin(k):
@@ -615,6 +619,60 @@ class InpaintScoreElbo(ScoreElbo):
         if self.cfg.loss.logit_type not in native.LOGIT_TYPES:
             raise ValueError(f"InpaintScoreElbo: unknown loss.logit_type {self.cfg.loss.logit_type!r}")
         return _free_rows("InpaintScoreElbo", self.cfg, minibatch)[:2]
+
+
+# ---------------------------------------------------------------- absorbing-state diffusion
+def _absorbing_elbo_terms(logits, x0, x_t, w, nll_scale, mask_state):
+    """(1/B) sum_b w_b sum_{d: x_t = m, x0 != m} -lp[x0] + nll_scale sum_{x0 != m} -lp[x0], lp the log-softmax over the states
+    s != m: the plain-torch statement of ctdd_absorb_elbo_loss (include/ctdd_absorb.h), in the logits' dtype."""
+    B, m = x0.shape[0], int(mask_state)
+    real = torch.arange(logits.shape[-1], device=logits.device) != m
+    lp = F.log_softmax(logits.masked_fill(~real, float("-inf")), dim=-1)
+    has = x0 != m
+    nlp = -torch.gather(lp, -1, torch.where(has, x0, torch.full_like(x0, (m + 1) % logits.shape[-1])).unsqueeze(-1)).squeeze(-1)
+    nlp = torch.where(has, nlp, torch.zeros_like(nlp))
+    masked = torch.where(x_t == m, nlp, torch.zeros_like(nlp))
+    return (w.to(nlp.dtype) * masked.sum(1)).sum() / B + nll_scale * nlp.sum()
+
+
+@losses_utils.register_loss
+class AbsorbingElbo:
+    """Negative ELBO of the absorbing-state ("masked") process (lib.models.forward_model.AbsorbingRate), a weighted masked cross
+    entropy:  t ~ U(min_time, max_t);  every entry of x_t is the mask state with probability 1 - alpha_t, else x0;  one forward at
+    x_t;  loss = (1/B) sum_b w(t_b) sum_{d masked} -log p_theta(x0_d | x_t) + nll_weight * mean CE(logits, x0), with
+    w = beta alpha / (1 - alpha) and every softmax over the states other than the mask.  On a GPU noising, value and logit
+    gradient are the kernels of csrc/absorb.hip (no table, no contraction); cfg.loss.fused = False or a CPU model: torch ops."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.nll_weight = getattr(cfg.loss, "nll_weight", 0.0) or 0.0
+        self.min_time = cfg.loss.min_time
+        self.max_t = cfg.training.max_t
+
+    def calc_loss(self, state, minibatch, label=None):
+        state, minibatch = _unpack(state, minibatch)
+        model = state["model"]
+        pr = getattr(model, "process", None)
+        if getattr(pr, "kind", None) != "absorbing":
+            raise ValueError("AbsorbingElbo needs a model on the absorbing process (AbsorbingRate, e.g. AbsorbingBertEMA)")
+        m = pr.mask_state
+        x0 = _flatten(minibatch).long()
+        B, D = x0.shape
+        ts = _draw_ts(B, model.device, self.min_time, self.max_t)
+        w = pr.elbo_weight(ts).float().contiguous()
+        nll_scale = float(self.nll_weight) / (B * D)
+        on_gpu = x0.is_cuda and getattr(self.cfg.loss, "fused", True)
+        if _FIXED_NOISE is not None:
+            x_t = _FIXED_NOISE["x_t"].to(x0.device).long()
+        elif on_gpu:
+            x_t = native.absorb_noise(_i32(x0), pr.alpha(ts).float().contiguous(), m, seed=_seed()).long()
+        else:
+            x_t = torch.where(torch.rand(x0.shape, device=x0.device) >= pr.alpha(ts).view(B, 1), torch.full_like(x0, m), x0)
+        logits = model(x_t, ts)
+        if on_gpu and logits.is_cuda and logits.shape[-1] <= native.ABSORB_MAX_S:
+            x0i, xti = _i32(x0), _i32(x_t)
+            return _HipValueGrad.apply(logits, lambda lg: native.absorb_elbo_loss(lg, x0i, xti, w, nll_scale, m))
+        return _absorbing_elbo_terms(logits, x0, x_t, w, nll_scale, m)
 
 
 class d3pm_loss:

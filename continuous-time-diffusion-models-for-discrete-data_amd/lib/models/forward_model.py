@@ -73,6 +73,37 @@ class UniformVariantRate(_ProcessMixin):
         self.rate_matrix = self.process.base_rate
 
 
+class AbsorbingRate(_ProcessMixin):
+    """Absorbing-state ("masked") process, not in the reference: every state jumps to cfg.model.mask_state (default S - 1;
+    cfg.data.S counts it) at rate rate_const * beta(t) and stays there.  cfg.model.t_func: "loglinear" (default; alpha_t =
+    1 - (1 - alpha_eps) t, rate_const must be 1) or the time-warped uniform process's "log_sqr" / "sqrt_cos" / "log".
+    alpha(t), elbo_weight(t), unmask_prob(t, h, rule) are the scalars AbsorbingElbo and AbsorbingLeap run on; the tables
+    (transition, rate, ...) come from the closed-form eigensystem and are for users' own code."""
+
+    def __init__(self, cfg, device):
+        m = cfg.model
+        self.rate_const = getattr(m, "rate_const", 1.0)
+        self.t_func = getattr(m, "t_func", "loglinear")
+        self.alpha_eps = getattr(m, "alpha_eps", 1e-3)
+        mask_state = getattr(m, "mask_state", None)
+        self.mask_state = int(cfg.data.S) - 1 if mask_state is None else int(mask_state)
+        kw = dict(rate_const=self.rate_const, t_func=self.t_func, alpha_eps=self.alpha_eps, mask_state=self.mask_state)
+        if self.t_func == "log":
+            self.time_base, self.time_exp = m.time_base, m.time_exp
+            kw.update(time_base=self.time_base, time_exp=self.time_exp)
+        self._init_process("absorbing", cfg, device, **kw)
+        self.rate_matrix = self.base_rate = self.process.base_rate
+
+    def alpha(self, t):
+        return self.process.alpha(t)
+
+    def elbo_weight(self, t):
+        return self.process.elbo_weight(t)
+
+    def unmask_prob(self, t, h, rule="ancestral"):
+        return self.process.unmask_prob(t, h, rule)
+
+
 class BirthDeathForwardBase(_ProcessMixin):
     """forward_model.py:9-75."""
 

@@ -13,7 +13,7 @@ import torch.nn.functional as F
 from torch.nn.parallel import DistributedDataParallel as DDP
 
 import lib.models.model_utils as model_utils
-from lib.models.forward_model import GaussianTargetRate, UniformRate, UniformVariantRate, BirthDeathForwardBase  # noqa: F401
+from lib.models.forward_model import GaussianTargetRate, UniformRate, UniformVariantRate, BirthDeathForwardBase, AbsorbingRate  # noqa: F401
 from lib.networks import unet
 
 
@@ -456,5 +456,7 @@ UniVarBertEMA = _compose("UniVarBertEMA", BertMLPRes, UniformVariantRate, "x0-pr
 UniformBertEMA = _compose("UniformBertEMA", BertMLPRes, UniformRate, "x0-prediction transformer, uniform CTMC")
 UniVarMaskedEMA = _compose("UniVarMaskedEMA", MaskedModel, UniformVariantRate, "masked transformer, time-warped uniform CTMC")
 UniformMaskedEMA = _compose("UniformMaskedEMA", MaskedModel, UniformRate, "masked transformer, uniform CTMC")
+# absorbing-state ("masked") diffusion on the x0-prediction transformer (AbsorbingElbo / AbsorbingLeap; not in the reference)
+AbsorbingBertEMA = _compose("AbsorbingBertEMA", BertMLPRes, AbsorbingRate, "x0-prediction transformer, absorbing-state CTMC")
 # the D3PM baseline's network (models.py:1044-1050): no rate class, its forward process is lib.d3pm.CategoricalDiffusion
 UniBertD3PM = _compose("UniBertD3PM", BertMLPRes, None, "x0-prediction transformer of the D3PM baseline (no CTMC)")

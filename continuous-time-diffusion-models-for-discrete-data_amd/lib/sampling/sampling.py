@@ -1,7 +1,8 @@
 """Samplers behind the reference's registry names (lib/sampling/sampling.py): TauL 82-234,
 LBJF 238-356, MidPointTauL 360-526, PCTauL 530-646, ConditionalTauLeaping 649-758,
 ConditionalPCTauLeaping 761-905, ExactSampling 975-1061; ConditionalLBJF, ConditionalMidPointTauL and
-ConditionalExactSampling (not in the reference) hold entries the way its two conditional samplers do.
+ConditionalExactSampling (not in the reference) hold entries the way its two conditional samplers do; AbsorbingLeap (not in the
+reference either) is the absorbing-state process's sampler, on its own step kernel.
 
 Same constructor `(cfg)`, same `sample(model, N)` return shapes; the per-step work is one fused
 libctdd launch (reverse rates -> jump draw -> state update) on int32 device state.  Differences
@@ -23,9 +24,14 @@ from lib.models.models import borrow_engine_output
 _CTELBO_LOSSES = ("CTElbo", "NLL", "CTElboLambda")
 
 
-def get_initial_samples(N, D, device, S, initial_dist, initial_dist_std=None, seed=None):
+def get_initial_samples(N, D, device, S, initial_dist, initial_dist_std=None, seed=None, mask_state=None):
     """sampling.py:14-28.  Returns int64 (N,D) on `device` (uniform randint, or the discretised
-    Gaussian centred at S//2 drawn by inverse CDF on the device)."""
+    Gaussian centred at S//2 drawn by inverse CDF on the device; "absorbing": every entry at mask_state, default S - 1)."""
+    if initial_dist == "absorbing":
+        m = S - 1 if mask_state is None else int(mask_state)
+        if not 0 <= m < S:
+            raise ValueError(f"mask_state {m} outside [0, S = {S})")
+        return torch.full((N, D), m, dtype=torch.int64, device=device)
     if seed is None:
         seed = _fresh_seed()
     if initial_dist == "uniform":
@@ -50,8 +56,15 @@ def _branch(cfg):
     return native.BRANCH_CTELBO if cfg.loss.name in _CTELBO_LOSSES else native.BRANCH_CRM
 
 
+def _refuse_absorbing(model):
+    """The general S x S samplers have not been checked on a rate matrix with a zero row: an absorbing model goes to AbsorbingLeap."""
+    if getattr(getattr(model, "process", None), "kind", None) == "absorbing":
+        raise ValueError("this sampler runs the general S x S path, which does not cover the absorbing process: use AbsorbingLeap")
+
+
 def get_reverse_rates(model, logits, x, t_ones, cfg, N, D, S):
     """sampling.py:31-78: (reverse_rates, ratio), both (N,D,S); own state not zeroed."""
+    _refuse_absorbing(model)
     branch = _branch(cfg)
     lt = getattr(cfg.loss, "logit_type", "direct") if branch == native.BRANCH_CRM else "direct"
     need_q = branch == native.BRANCH_CTELBO or lt != "direct"
@@ -94,6 +107,7 @@ class _GridSampler:
         return t32, qt0, pr.beta(t32).tolist()
 
     def _initial(self, model, N, key, std):
+        _refuse_absorbing(model)                     # (every loop of this family starts here)
         return get_initial_samples(N, self.D, model.device, self.S, self.initial_dist, std, seed=key).to(torch.int32)
 
     def _final_argmax(self, model, x, N):
@@ -768,6 +782,7 @@ def lbjf_corrector_step(cfg, model, xt, t, h, N, device, xt_target=None, seed=No
     with torch.no_grad():
         logits = model(xt.long(), t_ones).float().contiguous()
     lt = getattr(cfg.loss, "logit_type", "direct")
+    _refuse_absorbing(model)
     pr = model.process
     q = pr.tables(t32, want_qt0=True)[0][0] if lt != "direct" else None
     beta = float(pr.beta(t32)[0])
@@ -798,3 +813,73 @@ def lbjf_corrector_step(cfg, model, xt, t, h, N, device, xt_target=None, seed=No
 for _alias, _cls in (("TauLeaping", TauL), ("ElboTauL", TauL), ("CRMTauL", TauL), ("LBJFSampling", LBJF),
                      ("CRMLBJF", LBJF), ("ElboLBJF", LBJF), ("CRMebmLBJF", LBJF), ("PCTauLeaping", PCTauL)):
     sampling_utils.register_alias(_alias, _cls)
+
+
+@sampling_utils.register_sampler
+class AbsorbingLeap(_Conditioned):
+    """Reverse sampler of the absorbing-state ("masked") process (lib.models.forward_model.AbsorbingRate; not in the reference).
+    Unmasked entries never move; per step a masked entry unmasks with one scalar probability and then takes a state drawn from
+    the network's softmax over the states other than the mask: one network forward and one ctdd_absorb_step launch
+    (csrc/absorb.hip) per step, no table, no Poisson draw, no host sync inside the loop.
+
+    cfg.sampler.rule: "ancestral" (default; (a(t-h) - a(t)) / (1 - a(t)), the exact posterior for a fixed network), "euler"
+    (min(1, h w(t))) or "tauleap" (lam exp(-lam), lam = h w(t)) -- AbsorbingRate.unmask_prob.  num_steps and min_t as in TauL: the
+    grid is linspace(max_t, min_t, num_steps) followed by 0; after the loop one forward at min_t assigns every entry that is
+    still masked its argmax.  `sample(model, N)` starts from the all-mask state and returns (x int (N, D), changed per step / N);
+    `inpaint(model, x_known, mask)` (mask True = held, as in the conditional samplers) starts the held entries at their known
+    value, which is all it takes: they are not masked, so no step touches them."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.D = cfg.model.concat_dim
+        self.S = cfg.data.S
+        s = cfg.sampler
+        self.num_steps, self.min_t, self.max_t = s.num_steps, s.min_t, cfg.training.max_t
+        self.rule = getattr(s, "rule", "ancestral")
+        from ctdd.process import UNMASK_RULES
+        if self.rule not in UNMASK_RULES:
+            raise ValueError(f"sampler.rule must be one of {UNMASK_RULES}, got {self.rule!r}")
+        self.seed = None              # set to an int for a fixed Philox key
+        self.rank_stream = 0          # added to the key by the multi-GPU driver (ctdd/distributed.py)
+
+    _key = _GridSampler._key
+
+    @staticmethod
+    def _process(model):
+        pr = getattr(model, "process", None)
+        if getattr(pr, "kind", None) != "absorbing":
+            raise ValueError("AbsorbingLeap needs a model on the absorbing process (AbsorbingRate, e.g. AbsorbingBertEMA)")
+        return pr
+
+    def sample(self, model, N):
+        m = self._process(model).mask_state
+        x = torch.full((int(N), self.D), m, dtype=torch.int32, device=torch.device(model.device))
+        return self._loop(model, x)
+
+    def inpaint(self, model, x_known, mask):
+        m = self._process(model).mask_state
+        N, xk, held = self._held(x_known, mask)
+        if bool((xk[held] == m).any()):
+            raise ValueError(f"x_known: a held entry is the mask state {m}")
+        if bool(held.all()):
+            return xk.numpy().astype(int)
+        dev = torch.device(model.device)
+        x = torch.where(held.to(dev), xk.to(dev), torch.full((), m, dtype=torch.int32, device=dev))
+        return self._loop(model, x.contiguous())[0]
+
+    def _loop(self, model, x):
+        pr = self._process(model)
+        m, N, dev, key = pr.mask_state, x.shape[0], x.device, self._key()
+        ts = np.concatenate((np.linspace(self.max_t, self.min_t, self.num_steps), np.array([0])))
+        t64 = torch.from_numpy(ts)
+        # every step's unmasking probability on the host, before the loop (fp64 schedules; the network sees the fp32 times)
+        p = torch.clamp(pr.unmask_prob(t64[:-1], t64[:-1] - t64[1:], self.rule), 0.0, 1.0).tolist()
+        t32 = t64[:-1].to(torch.float32)
+        changed = torch.zeros(self.num_steps + 1, dtype=torch.int32, device=dev)
+        with torch.no_grad(), borrow_engine_output(model, bf16_logits=False, uniform_time=True):
+            for i in range(self.num_steps):
+                logits = _GridSampler._net_logits(model, x, _GridSampler._t_ones(t32, i, N, dev))
+                x = native.absorb_step(logits, x, m, p[i], 0, key, i, changed=changed[i:i + 1])
+            logits = _GridSampler._net_logits(model, x, torch.full((N,), float(np.float32(self.min_t)), device=dev))
+            x = native.absorb_step(logits, x, m, 1.0, native.ABSORB_ARGMAX, key, self.num_steps, changed=changed[self.num_steps:])
+        return x.cpu().numpy().astype(int), (changed[:self.num_steps].cpu().numpy() / N).tolist()

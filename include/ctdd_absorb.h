@@ -1,0 +1,58 @@
+/* ctdd_absorb.h -- C ABI of the absorbing-state ("masked") diffusion kernels (csrc/absorb.hip): forward noising, the negative
+ * ELBO with its logit gradient, and one reverse (unmasking) step.  Conventions as in ctdd.h: device pointers, row-major, int status
+ * (CTDD_OK == 0, message through ctdd_last_error), `stream` a hipStream_t.  Logits fp32 (B, D, S) contiguous, states int32,
+ * 2 <= S <= CTDD_MAX_S (S counts the mask state: S = 2 is one real state plus the mask), 0 <= mask_state < S.
+ *
+ * The process: with alpha_t = exp(-c(t)) the probability that an entry is still unmasked at t, an entry of x_t is mask_state with
+ * probability 1 - alpha_t and x0 otherwise, independently.  No S x S table enters any of the three kernels.
+ *
+ * Softmax excluding the mask state (every softmax below): over the states s != m = mask_state only.  l[m] takes no part in the
+ * row maximum, its weight is exactly 0 and its gradient entry is exactly 0:
+ *   mx = max_{s != m} l[s],  e[s] = exp(l[s] - mx) (e[m] = 0),  z = sum_s e[s],  lp[s] = (l[s] - mx) - log z.
+ * Rows are packed 64, 16, 4 or 1 to a wave (S <= 4, 16, 64, above); every row is read once, and not at all where it carries no
+ * term (loss) or does not move (step). */
+#ifndef CTDD_ABSORB_H
+#define CTDD_ABSORB_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define CTDD_ABSORB_ARGMAX 1u   /* ctdd_absorb_step: every masked row takes argmax_{s != m} l[s] (lowest index on ties), no draw */
+
+/* x_t[b][d] = mask_state iff u >= alpha[b], else x0[b][d].   x0, out_xt (B, D); alpha (B,) on the device.
+ * u: one Philox uniform per entry.  Entry e = b D + d reads component (e & 3) of the block Philox(key = seed,
+ * counter = (row = e >> 2, offset, draw = 0)), mapped to (0, 1) as ctdd_philox_uniform does: the uniforms of the call are
+ * ctdd_philox_uniform(seed, offset, ceil(B D / 4), 1) read in row-major order. */
+int ctdd_absorb_noise(const int32_t* x0, const float* alpha, int B, int D, int mask_state, uint64_t seed, uint64_t offset,
+                      int32_t* out_xt, void* stream);
+
+/* Bytes of `scratch` for ctdd_absorb_elbo_loss.  The caller zeroes it once; a call leaves it zeroed. */
+int64_t ctdd_absorb_scratch_bytes(void);
+
+/* Negative ELBO (a weighted masked cross entropy) and d loss / d logits.   x0, xt (B, D); w (B,) on the device.
+ *   loss = (1/B) sum_b w[b] sum_{d: xt[b][d] == m, x0[b][d] != m} -lp[b][d][x0]  +  nll_scale sum_{(b,d): x0 != m} -lp[b][d][x0]
+ * Row (b, d) has the weight wt = [xt == m] w[b] / B + nll_scale if x0 != m (and x0 in [0, S)), else 0:
+ *   grad[b][d][s] = wt (e[s] / z - [s == x0]);   a row with wt == 0 is not read and its gradient row is exact zeros.
+ * *out_loss += loss (row terms are summed in fp64: one fp64 atomic per workgroup into `scratch`, the last workgroup rounds once).
+ * grad_logits (B, D, S) is written full shape, or NULL (value only). */
+int ctdd_absorb_elbo_loss(const float* logits, const int32_t* x0, const int32_t* xt, const float* w, float nll_scale, int B, int D,
+                          int S, int mask_state, void* scratch, float* out_loss, float* grad_logits, void* stream);
+
+/* One reverse step for N D rows.   logits (N, D, S), x, out_x (N, D).
+ *   x != m: out_x = x, bit for bit; the row's logits are not read.
+ *   x == m: the row r = n D + d reads ONE block Philox(key = seed, counter = (row = r, offset, draw = 0)):
+ *     component 0: u0 -- the row unmasks iff u0 < p_unmask (else out_x = m; the logits are not read);
+ *     component 1: u1 -- the new state, by inverse CDF over the weights e[s] of the softmax excluding the mask state:
+ *                  the first s whose running sum e[0] + .. + e[s] exceeds u1 z.  Never m.
+ *   flags & CTDD_ABSORB_ARGMAX: every masked row takes argmax_{s != m} l[s], lowest index on ties; no draw, p_unmask unused.
+ * out_changed (int32[1] or NULL) += the number of rows that left the mask state (one atomic per workgroup). */
+int ctdd_absorb_step(const float* logits, const int32_t* x, int N, int D, int S, int mask_state, float p_unmask, uint32_t flags,
+                     uint64_t seed, uint64_t offset, int32_t* out_x, int32_t* out_changed, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
