@@ -9,6 +9,8 @@
 //
 // Reference semantics: lib/sampling/sampling.py:31-78 (rates), 119-160 (tau-leap), 278-293
 // (LBJF), 417-453 (midpoint); lib/models/model_utils.py:30-60 (log-probs).
+#include <type_traits>
+
 #include "draw.hpp"
 
 namespace ctdd {
@@ -801,20 +803,17 @@ __global__ __launch_bounds__(256) void k_rows_small(const StepArgs a) {
 
 template <int S>
 static void launch_small_mode(const StepArgs& a, dim3 g, hipStream_t st) {
-  if (a.rows) {                 // row-list launch (small_rows_ok admits no MODE_RATES here)
+  auto go = [&](auto rows) {     // full launch, or the row list (small_rows_ok admits no MODE_RATES there: that kernel does not exist)
+    constexpr bool ROWS = decltype(rows)::value;
     switch (a.mode) {
-      case MODE_TAULEAP: hipLaunchKernelGGL((k_rows_small<S, MODE_TAULEAP, true>), g, dim3(256), 0, st, a); break;
-      case MODE_LBJF: hipLaunchKernelGGL((k_rows_small<S, MODE_LBJF, true>), g, dim3(256), 0, st, a); break;
-      default: hipLaunchKernelGGL((k_rows_small<S, MODE_MIDPOINT, true>), g, dim3(256), 0, st, a); break;
+      case MODE_RATES: if constexpr (!ROWS) hipLaunchKernelGGL((k_rows_small<S, MODE_RATES, ROWS>), g, dim3(256), 0, st, a); break;
+      case MODE_TAULEAP: hipLaunchKernelGGL((k_rows_small<S, MODE_TAULEAP, ROWS>), g, dim3(256), 0, st, a); break;
+      case MODE_LBJF: hipLaunchKernelGGL((k_rows_small<S, MODE_LBJF, ROWS>), g, dim3(256), 0, st, a); break;
+      default: hipLaunchKernelGGL((k_rows_small<S, MODE_MIDPOINT, ROWS>), g, dim3(256), 0, st, a); break;
     }
-    return;
-  }
-  switch (a.mode) {
-    case MODE_RATES: hipLaunchKernelGGL((k_rows_small<S, MODE_RATES>), g, dim3(256), 0, st, a); break;
-    case MODE_TAULEAP: hipLaunchKernelGGL((k_rows_small<S, MODE_TAULEAP>), g, dim3(256), 0, st, a); break;
-    case MODE_LBJF: hipLaunchKernelGGL((k_rows_small<S, MODE_LBJF>), g, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_rows_small<S, MODE_MIDPOINT>), g, dim3(256), 0, st, a); break;
-  }
+  };
+  if (a.rows) go(std::true_type{});
+  else go(std::false_type{});
 }
 // the fused steps with ONE table for the launch, rates not precomputed, 16-byte aligned buffers
 static bool small_rows_ok(const StepArgs& a) {
@@ -856,21 +855,18 @@ static int launch_rows(const StepArgs& a0, void* stream) {
   CTDD_REQUIRE(grid > 0 && grid < (1ll << 31), CTDD_ERANGE, "rows out of range: %lld", (long long)R);
   hipStream_t st = (hipStream_t)stream;
   dim3 g((unsigned)grid), b(256);
-  if (a.rows) {                 // row-list launch (tau-leap, LBJF, midpoint, exact and the pre_rates tails): the same kernels
-                                // with the ROWS indirection
-    if (ept_need <= 1) hipLaunchKernelGGL((k_rows<1, true>), g, b, 0, st, a);
-    else if (ept_need <= 2) hipLaunchKernelGGL((k_rows<2, true>), g, b, 0, st, a);
-    else if (ept_need <= 4) hipLaunchKernelGGL((k_rows<4, true>), g, b, 0, st, a);
-    else if (ept_need <= 8) hipLaunchKernelGGL((k_rows<8, true>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((k_rows<16, true>), g, b, 0, st, a);
-    return finish_launch("k_rows (row list)");
-  }
-  if (ept_need <= 1) hipLaunchKernelGGL(k_rows<1>, g, b, 0, st, a);
-  else if (ept_need <= 2) hipLaunchKernelGGL(k_rows<2>, g, b, 0, st, a);
-  else if (ept_need <= 4) hipLaunchKernelGGL(k_rows<4>, g, b, 0, st, a);
-  else if (ept_need <= 8) hipLaunchKernelGGL(k_rows<8>, g, b, 0, st, a);
-  else hipLaunchKernelGGL(k_rows<16>, g, b, 0, st, a);
-  return finish_launch("k_rows");
+  auto go = [&](auto rows) {     // row list (tau-leap, LBJF, midpoint, exact and the pre_rates tails): the same kernels with the
+                                 // ROWS indirection
+    constexpr bool ROWS = decltype(rows)::value;
+    if (ept_need <= 1) hipLaunchKernelGGL((k_rows<1, ROWS>), g, b, 0, st, a);
+    else if (ept_need <= 2) hipLaunchKernelGGL((k_rows<2, ROWS>), g, b, 0, st, a);
+    else if (ept_need <= 4) hipLaunchKernelGGL((k_rows<4, ROWS>), g, b, 0, st, a);
+    else if (ept_need <= 8) hipLaunchKernelGGL((k_rows<8, ROWS>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((k_rows<16, ROWS>), g, b, 0, st, a);
+  };
+  if (a.rows) go(std::true_type{});
+  else go(std::false_type{});
+  return finish_launch(a.rows ? "k_rows (row list)" : "k_rows");
 }
 
 static int check_common(const void* logits, const void* x, int N, int D, int S) {
@@ -901,12 +897,22 @@ static int check_row_list(const int32_t* out_x, const int32_t* x, const int32_t*
   return *status == CTDD_OK && n_rows > 0;
 }
 
+// The tail of every step family below, after its input checks: the output / row-list checks, then the launch.  listed = the call
+// came through the family's ctdd_*_rows entry (a null list is refused there, not taken for a full launch); else every row is stepped.
+static int launch_step(StepArgs& a, bool listed, const int32_t* rows, int n_rows, void* stream) {
+  if (listed) {
+    int st;
+    if (!check_row_list(a.out_x, a.x, rows, n_rows, a.N, a.D, &st)) return st;
+    a.rows = rows; a.n_rows = n_rows;
+  } else {
+    CTDD_REQUIRE(a.out_x, CTDD_EINVAL, "null output");
+  }
+  return launch_rows(a, stream);
+}
+
 }  // namespace ctdd
 
 using namespace ctdd;
-
-// steps_s256.hip: fast path, returns 1 when it handled the call
-namespace ctdd { int try_s256(const StepArgs& a, void* stream, int* status); }
 
 extern "C" int ctdd_logprob(const float* logits, const int32_t* x, const float* qt0, const int32_t* tidx,
                             int logit_type, int N, int D, int S, float* out_ll_all, float* out_ll_xt,
@@ -932,8 +938,6 @@ extern "C" int ctdd_reverse_rates(int branch, int logit_type, const float* logit
   a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = rate; a.tidx = tidx; a.beta = 1.0f; a.eps = eps;
   a.N = N; a.D = D; a.S = S; a.branch = branch; a.logit_type = logit_type; a.mode = MODE_RATES;
   a.out_a = out_rates; a.out_b = out_ratio;
-  int st;
-  if (try_s256(a, stream, &st)) return st;
   return launch_rows(a, stream);
 }
 
@@ -949,44 +953,101 @@ extern "C" int ctdd_tauleap_draw(const float* rates, const int32_t* x, const int
   return launch_rows(a, stream);
 }
 
-extern "C" int ctdd_tauleap_step(int branch, int logit_type, const float* logits, const int32_t* x,
-                                 const int32_t* x_base, const float* qt0, const float* base_rate,
-                                 float beta, float eps, float h, uint32_t flags, uint64_t seed,
-                                 uint64_t offset, int N, int D, int S, int32_t* out_x,
-                                 int32_t* out_changed, void* stream) {
+/* The step families.  Each exists once: the plain entry steps every row, its _rows twin (include/ctdd.h, the contract above
+ * ctdd_tauleap_step_rows) runs the same kernels and draws on the listed rows only -- row v of the launch is row rows[v]; E,
+ * out_probs and rates stay (N*D, S) and are indexed by the listed row; unlisted rows of out_x are not written, so it must not
+ * alias x. */
+static int tauleap_step(int branch, int logit_type, const float* logits, const int32_t* x, const int32_t* x_base, const float* qt0,
+                        const float* base_rate, float beta, float eps, float h, uint32_t flags, uint64_t seed, uint64_t offset,
+                        int N, int D, int S, bool listed, const int32_t* rows, int n_rows, int32_t* out_x, int32_t* out_changed,
+                        void* stream) {
   if (int rc = check_common(logits, x, N, D, S)) return rc;
   if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
-  CTDD_REQUIRE(out_x, CTDD_EINVAL, "null output");
   StepArgs a{};
   a.logits = logits; a.x = x; a.x_base = x_base; a.qt0 = qt0; a.rate = base_rate; a.beta = beta;
   a.eps = eps; a.h = h; a.flags = flags; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
   a.branch = branch; a.logit_type = logit_type; a.mode = MODE_TAULEAP;
   a.out_x = out_x; a.out_changed = out_changed;
-  int st;
-  if (try_s256(a, stream, &st)) return st;
-  return launch_rows(a, stream);
+  return launch_step(a, listed, rows, n_rows, stream);
 }
 
-/* The tau-leap step on the listed rows only (include/ctdd.h): same kernels and draws as ctdd_tauleap_step, row v of the
- * launch is row rows[v]; unlisted rows of out_x are not written, so out_x must not alias x. */
+static int lbjf_step(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0, const float* base_rate,
+                     float beta, float eps, float h, uint32_t flags, const float* E, uint64_t seed, uint64_t offset, int N, int D,
+                     int S, bool listed, const int32_t* rows, int n_rows, int32_t* out_x, float* out_probs, int32_t* out_changed,
+                     void* stream) {
+  if (int rc = check_common(logits, x, N, D, S)) return rc;
+  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
+  StepArgs a{};
+  a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = base_rate; a.beta = beta; a.eps = eps; a.h = h;
+  a.flags = flags; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
+  a.branch = branch; a.logit_type = logit_type; a.mode = MODE_LBJF;
+  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed;
+  return launch_step(a, listed, rows, n_rows, stream);
+}
+
+static int midpoint_predict(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
+                            const float* base_rate, float beta, float eps, float h, int N, int D, int S, bool listed,
+                            const int32_t* rows, int n_rows, int32_t* out_x, void* stream) {
+  if (int rc = check_common(logits, x, N, D, S)) return rc;
+  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
+  StepArgs a{};
+  a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = base_rate; a.beta = beta; a.eps = eps;
+  a.h = (float)(0.5 * (double)h);   // 0.5*h evaluated in double, then cast (sampling.py:437-439)
+  a.N = N; a.D = D; a.S = S; a.branch = branch; a.logit_type = logit_type; a.mode = MODE_MIDPOINT;
+  a.out_x = out_x;
+  return launch_step(a, listed, rows, n_rows, stream);
+}
+
+static int exact_step(const float* logits, const int32_t* x, const float* q_lo, const float* q_step, const float* E, uint64_t seed,
+                      uint64_t offset, int N, int D, int S, bool listed, const int32_t* rows, int n_rows, int32_t* out_x,
+                      float* out_probs, int32_t* out_changed, void* stream) {
+  if (int rc = check_common(logits, x, N, D, S)) return rc;
+  CTDD_REQUIRE(q_lo && q_step, CTDD_EINVAL, "exact step: null table");
+  StepArgs a{};
+  a.logits = logits; a.x = x; a.qt0 = q_lo; a.rate = q_step; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
+  a.branch = CTDD_BRANCH_CRM; a.logit_type = CTDD_LOGIT_DIRECT; a.mode = MODE_EXACT;
+  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed;
+  return launch_step(a, listed, rows, n_rows, stream);
+}
+
+/* LBJF / midpoint tails on reverse rates that are already computed and masked (rates (N,D,S): the out_rates of
+ * ctdd_tauleap_step_s256) -- the S = 256 samplers get their S x S contraction from the matrix-core kernel this way. */
+static int lbjf_from_rates(const float* rates, const int32_t* x, float h, const float* E, uint64_t seed, uint64_t offset, int N,
+                           int D, int S, bool listed, const int32_t* rows, int n_rows, int32_t* out_x, float* out_probs,
+                           int32_t* out_changed, void* stream) {
+  if (int rc = check_common(rates, x, N, D, S)) return rc;
+  StepArgs a{};
+  a.logits = rates; a.x = x; a.h = h; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
+  a.mode = MODE_LBJF; a.pre_rates = 1;
+  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed;
+  return launch_step(a, listed, rows, n_rows, stream);
+}
+
+static int midpoint_from_rates(const float* rates, const int32_t* x, float h, int N, int D, int S, bool listed, const int32_t* rows,
+                               int n_rows, int32_t* out_x, void* stream) {
+  if (int rc = check_common(rates, x, N, D, S)) return rc;
+  StepArgs a{};
+  a.logits = rates; a.x = x; a.h = (float)(0.5 * (double)h); a.N = N; a.D = D; a.S = S;
+  a.mode = MODE_MIDPOINT; a.pre_rates = 1;
+  a.out_x = out_x;
+  return launch_step(a, listed, rows, n_rows, stream);
+}
+
+extern "C" int ctdd_tauleap_step(int branch, int logit_type, const float* logits, const int32_t* x,
+                                 const int32_t* x_base, const float* qt0, const float* base_rate,
+                                 float beta, float eps, float h, uint32_t flags, uint64_t seed,
+                                 uint64_t offset, int N, int D, int S, int32_t* out_x,
+                                 int32_t* out_changed, void* stream) {
+  return tauleap_step(branch, logit_type, logits, x, x_base, qt0, base_rate, beta, eps, h, flags, seed, offset, N, D, S, false,
+                      nullptr, 0, out_x, out_changed, stream);
+}
 extern "C" int ctdd_tauleap_step_rows(int branch, int logit_type, const float* logits, const int32_t* x,
                                       const int32_t* x_base, const float* qt0, const float* base_rate,
                                       float beta, float eps, float h, uint32_t flags, uint64_t seed,
                                       uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
                                       int32_t* out_x, int32_t* out_changed, void* stream) {
-  if (int rc = check_common(logits, x, N, D, S)) return rc;
-  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
-  CTDD_REQUIRE(out_x, CTDD_EINVAL, "null output");
-  CTDD_REQUIRE(out_x != x, CTDD_EINVAL, "out_x must not alias x (unlisted rows are not written)");
-  CTDD_REQUIRE(n_rows >= 0 && (int64_t)n_rows <= (int64_t)N * D, CTDD_ERANGE, "n_rows=%d outside [0, N*D]", n_rows);
-  if (n_rows == 0) return CTDD_OK;
-  CTDD_REQUIRE(rows, CTDD_EINVAL, "null row list");
-  StepArgs a{};
-  a.logits = logits; a.x = x; a.x_base = x_base; a.qt0 = qt0; a.rate = base_rate; a.beta = beta;
-  a.eps = eps; a.h = h; a.flags = flags; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
-  a.branch = branch; a.logit_type = logit_type; a.mode = MODE_TAULEAP;
-  a.out_x = out_x; a.out_changed = out_changed; a.rows = rows; a.n_rows = n_rows;
-  return launch_rows(a, stream);
+  return tauleap_step(branch, logit_type, logits, x, x_base, qt0, base_rate, beta, eps, h, flags, seed, offset, N, D, S, true,
+                      rows, n_rows, out_x, out_changed, stream);
 }
 
 extern "C" int ctdd_lbjf_step(int branch, int logit_type, const float* logits, const int32_t* x,
@@ -994,136 +1055,54 @@ extern "C" int ctdd_lbjf_step(int branch, int logit_type, const float* logits, c
                               uint32_t flags, const float* E, uint64_t seed, uint64_t offset,
                               int N, int D, int S, int32_t* out_x, float* out_probs,
                               int32_t* out_changed, void* stream) {
-  if (int rc = check_common(logits, x, N, D, S)) return rc;
-  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
-  CTDD_REQUIRE(out_x, CTDD_EINVAL, "null output");
-  StepArgs a{};
-  a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = base_rate; a.beta = beta; a.eps = eps; a.h = h;
-  a.flags = flags; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
-  a.branch = branch; a.logit_type = logit_type; a.mode = MODE_LBJF;
-  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed;
-  return launch_rows(a, stream);
+  return lbjf_step(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, E, seed, offset, N, D, S, false, nullptr, 0,
+                   out_x, out_probs, out_changed, stream);
+}
+extern "C" int ctdd_lbjf_step_rows(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
+                                   const float* base_rate, float beta, float eps, float h, uint32_t flags, const float* E,
+                                   uint64_t seed, uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
+                                   int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream) {
+  return lbjf_step(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, E, seed, offset, N, D, S, true, rows, n_rows,
+                   out_x, out_probs, out_changed, stream);
 }
 
 extern "C" int ctdd_midpoint_predict(int branch, int logit_type, const float* logits, const int32_t* x,
                                      const float* qt0, const float* base_rate, float beta, float eps,
                                      float h, int N, int D, int S, int32_t* out_x, void* stream) {
-  if (int rc = check_common(logits, x, N, D, S)) return rc;
-  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
-  CTDD_REQUIRE(out_x, CTDD_EINVAL, "null output");
-  StepArgs a{};
-  a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = base_rate; a.beta = beta; a.eps = eps;
-  a.h = (float)(0.5 * (double)h);   // 0.5*h evaluated in double, then cast (sampling.py:437-439)
-  a.N = N; a.D = D; a.S = S; a.branch = branch; a.logit_type = logit_type; a.mode = MODE_MIDPOINT;
-  a.out_x = out_x;
-  return launch_rows(a, stream);
+  return midpoint_predict(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, N, D, S, false, nullptr, 0, out_x, stream);
+}
+extern "C" int ctdd_midpoint_predict_rows(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
+                                          const float* base_rate, float beta, float eps, float h, int N, int D, int S,
+                                          const int32_t* rows, int n_rows, int32_t* out_x, void* stream) {
+  return midpoint_predict(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, N, D, S, true, rows, n_rows, out_x, stream);
 }
 
 extern "C" int ctdd_exact_step(const float* logits, const int32_t* x, const float* q_lo, const float* q_step, const float* E,
                                uint64_t seed, uint64_t offset, int N, int D, int S, int32_t* out_x, float* out_probs,
                                int32_t* out_changed, void* stream) {
-  if (int rc = check_common(logits, x, N, D, S)) return rc;
-  CTDD_REQUIRE(q_lo && q_step && out_x, CTDD_EINVAL, "exact step: null table / output");
-  StepArgs a{};
-  a.logits = logits; a.x = x; a.qt0 = q_lo; a.rate = q_step; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
-  a.branch = CTDD_BRANCH_CRM; a.logit_type = CTDD_LOGIT_DIRECT; a.mode = MODE_EXACT;
-  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed;
-  return launch_rows(a, stream);
+  return exact_step(logits, x, q_lo, q_step, E, seed, offset, N, D, S, false, nullptr, 0, out_x, out_probs, out_changed, stream);
+}
+extern "C" int ctdd_exact_step_rows(const float* logits, const int32_t* x, const float* q_lo, const float* q_step, const float* E,
+                                    uint64_t seed, uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
+                                    int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream) {
+  return exact_step(logits, x, q_lo, q_step, E, seed, offset, N, D, S, true, rows, n_rows, out_x, out_probs, out_changed, stream);
 }
 
-/* LBJF / midpoint tails on reverse rates that are already computed and masked (rates (N,D,S): the out_rates of
- * ctdd_tauleap_step_s256) -- the S = 256 samplers get their S x S contraction from the matrix-core kernel this way. */
 extern "C" int ctdd_lbjf_from_rates(const float* rates, const int32_t* x, float h, const float* E, uint64_t seed, uint64_t offset,
                                     int N, int D, int S, int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream) {
-  if (int rc = check_common(rates, x, N, D, S)) return rc;
-  CTDD_REQUIRE(out_x, CTDD_EINVAL, "null output");
-  StepArgs a{};
-  a.logits = rates; a.x = x; a.h = h; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
-  a.mode = MODE_LBJF; a.pre_rates = 1;
-  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed;
-  return launch_rows(a, stream);
+  return lbjf_from_rates(rates, x, h, E, seed, offset, N, D, S, false, nullptr, 0, out_x, out_probs, out_changed, stream);
+}
+extern "C" int ctdd_lbjf_from_rates_rows(const float* rates, const int32_t* x, float h, const float* E, uint64_t seed,
+                                         uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows, int32_t* out_x,
+                                         float* out_probs, int32_t* out_changed, void* stream) {
+  return lbjf_from_rates(rates, x, h, E, seed, offset, N, D, S, true, rows, n_rows, out_x, out_probs, out_changed, stream);
 }
 
 extern "C" int ctdd_midpoint_from_rates(const float* rates, const int32_t* x, float h, int N, int D, int S, int32_t* out_x,
                                         void* stream) {
-  if (int rc = check_common(rates, x, N, D, S)) return rc;
-  CTDD_REQUIRE(out_x, CTDD_EINVAL, "null output");
-  StepArgs a{};
-  a.logits = rates; a.x = x; a.h = (float)(0.5 * (double)h); a.N = N; a.D = D; a.S = S;
-  a.mode = MODE_MIDPOINT; a.pre_rates = 1;
-  a.out_x = out_x;
-  return launch_rows(a, stream);
+  return midpoint_from_rates(rates, x, h, N, D, S, false, nullptr, 0, out_x, stream);
 }
-
-/* The LBJF, midpoint-predictor and exact steps and the two pre_rates tails on the listed rows only (include/ctdd.h, the
- * contract above ctdd_tauleap_step_rows): the full entry point's StepArgs plus the row list; E and out_probs stay (N*D, S)
- * and are indexed by the listed row. */
-extern "C" int ctdd_lbjf_step_rows(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
-                                   const float* base_rate, float beta, float eps, float h, uint32_t flags, const float* E,
-                                   uint64_t seed, uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
-                                   int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream) {
-  if (int rc = check_common(logits, x, N, D, S)) return rc;
-  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
-  int st;
-  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
-  StepArgs a{};
-  a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = base_rate; a.beta = beta; a.eps = eps; a.h = h;
-  a.flags = flags; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
-  a.branch = branch; a.logit_type = logit_type; a.mode = MODE_LBJF;
-  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed; a.rows = rows; a.n_rows = n_rows;
-  return launch_rows(a, stream);
-}
-
-extern "C" int ctdd_midpoint_predict_rows(int branch, int logit_type, const float* logits, const int32_t* x, const float* qt0,
-                                          const float* base_rate, float beta, float eps, float h, int N, int D, int S,
-                                          const int32_t* rows, int n_rows, int32_t* out_x, void* stream) {
-  if (int rc = check_common(logits, x, N, D, S)) return rc;
-  if (int rc = check_branch(branch, logit_type, qt0, base_rate)) return rc;
-  int st;
-  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
-  StepArgs a{};
-  a.logits = logits; a.x = x; a.qt0 = qt0; a.rate = base_rate; a.beta = beta; a.eps = eps;
-  a.h = (float)(0.5 * (double)h);   // as ctdd_midpoint_predict
-  a.N = N; a.D = D; a.S = S; a.branch = branch; a.logit_type = logit_type; a.mode = MODE_MIDPOINT;
-  a.out_x = out_x; a.rows = rows; a.n_rows = n_rows;
-  return launch_rows(a, stream);
-}
-
-extern "C" int ctdd_exact_step_rows(const float* logits, const int32_t* x, const float* q_lo, const float* q_step, const float* E,
-                                    uint64_t seed, uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows,
-                                    int32_t* out_x, float* out_probs, int32_t* out_changed, void* stream) {
-  if (int rc = check_common(logits, x, N, D, S)) return rc;
-  CTDD_REQUIRE(q_lo && q_step, CTDD_EINVAL, "exact step: null table");
-  int st;
-  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
-  StepArgs a{};
-  a.logits = logits; a.x = x; a.qt0 = q_lo; a.rate = q_step; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
-  a.branch = CTDD_BRANCH_CRM; a.logit_type = CTDD_LOGIT_DIRECT; a.mode = MODE_EXACT;
-  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed; a.rows = rows; a.n_rows = n_rows;
-  return launch_rows(a, stream);
-}
-
-extern "C" int ctdd_lbjf_from_rates_rows(const float* rates, const int32_t* x, float h, const float* E, uint64_t seed,
-                                         uint64_t offset, int N, int D, int S, const int32_t* rows, int n_rows, int32_t* out_x,
-                                         float* out_probs, int32_t* out_changed, void* stream) {
-  if (int rc = check_common(rates, x, N, D, S)) return rc;
-  int st;
-  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
-  StepArgs a{};
-  a.logits = rates; a.x = x; a.h = h; a.E = E; a.seed = seed; a.offset = offset; a.N = N; a.D = D; a.S = S;
-  a.mode = MODE_LBJF; a.pre_rates = 1;
-  a.out_x = out_x; a.out_a = out_probs; a.out_changed = out_changed; a.rows = rows; a.n_rows = n_rows;
-  return launch_rows(a, stream);
-}
-
 extern "C" int ctdd_midpoint_from_rates_rows(const float* rates, const int32_t* x, float h, int N, int D, int S,
                                              const int32_t* rows, int n_rows, int32_t* out_x, void* stream) {
-  if (int rc = check_common(rates, x, N, D, S)) return rc;
-  int st;
-  if (!check_row_list(out_x, x, rows, n_rows, N, D, &st)) return st;
-  StepArgs a{};
-  a.logits = rates; a.x = x; a.h = (float)(0.5 * (double)h); a.N = N; a.D = D; a.S = S;
-  a.mode = MODE_MIDPOINT; a.pre_rates = 1;
-  a.out_x = out_x; a.rows = rows; a.n_rows = n_rows;
-  return launch_rows(a, stream);
+  return midpoint_from_rates(rates, x, h, N, D, S, true, rows, n_rows, out_x, stream);
 }

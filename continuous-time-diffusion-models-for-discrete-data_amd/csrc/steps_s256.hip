@@ -558,8 +558,3 @@ extern "C" int ctdd_tauleap_step_s256_rows(const void* logits, const int32_t* x,
   return tauleap_s256(logits, x, x_base, step_tables, RT0, R0, beta, h, flags, seed, offset, N, D, rows, n_rows, out_rates, out_x,
                       out_changed, stream);
 }
-
-namespace ctdd {
-struct StepArgs;
-int try_s256(const StepArgs&, void*, int*) { return 0; }   // plain entry points keep the generic kernel
-}  // namespace ctdd

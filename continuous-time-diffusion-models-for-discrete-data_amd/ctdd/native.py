@@ -277,19 +277,10 @@ def tauleap_draw(rates, x, h, is_ordinal, seed, offset, x_base=None, changed=Non
     return out
 
 
-def tauleap_step(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, seed, offset,
-                 x_base=None, out=None, changed=None):
-    N, D, S = logits.shape
-    if out is None:
-        out = torch.empty((N, D), dtype=i32, device=x.device)
-    rc = load().ctdd_tauleap_step(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
-                                  _ptr(x_base, i32, "x_base"), _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"),
-                                  float(beta), float(eps), float(h), int(flags), seed, offset, N, D, S,
-                                  _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_tauleap_step")
-    return out
-
-
+# ---------------------------------------------------------------- the sampler steps: one binding per family, row list optional
+# `rows` None: every row is stepped and `out` is fresh.  `rows` given (ascending, distinct int32 indices into the N*D rows, on the
+# device): the `_rows` entry of the family runs the same kernels on those rows only -- listed rows bit-identical to the full
+# launch's, unlisted rows of `out` / `probs` / `rates` not written (so `out` must not alias x; its default is a copy of x).
 def _row_list(rows, N, D):
     if rows.dim() != 1:
         raise CtddError(f"rows: expected a 1-D int32 tensor, got shape {tuple(rows.shape)}")
@@ -309,158 +300,156 @@ def _prefilled(out, x, N, D):
     return out
 
 
+def _step_entry(name, rows, out, x, N, D, want_x=True):
+    """-> (C entry, its (rows, n_rows) arguments -- they follow the shape integers in every `_rows` signature --, output state)."""
+    rl = () if rows is None else _row_list(rows, N, D)
+    if not want_x:
+        out = None
+    elif rows is not None:
+        out = _prefilled(out, x, N, D)
+    elif out is None:
+        out = torch.empty((N, D), dtype=i32, device=x.device)
+    return name if rows is None else name + "_rows", rl, out
+
+
+def _buffer(want, buf, like, what):
+    """A full-size f32 output (`probs`, `rates`): `buf` when given, else a fresh uninitialised tensor; None when not wanted."""
+    if not want:
+        return None
+    if buf is None:
+        return torch.empty(like.shape, dtype=f32, device=like.device)
+    if tuple(buf.shape) != tuple(like.shape):
+        raise CtddError(f"{what}: expected shape {tuple(like.shape)}, got {tuple(buf.shape)}")
+    return buf
+
+
+def _launched(rc, name):
+    _check(rc, name)
+    _count(name)
+
+
+def _tauleap(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, seed, offset, rows=None, x_base=None, out=None,
+             changed=None):
+    N, D, S = logits.shape
+    name, rl, out = _step_entry("ctdd_tauleap_step", rows, out, x, N, D)
+    _launched(getattr(load(), name)(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
+                                    _ptr(x_base, i32, "x_base"), _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"),
+                                    float(beta), float(eps), float(h), int(flags), seed, offset, N, D, S, *rl,
+                                    _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream()), name)
+    return out
+
+
+def _lbjf(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows=None, flags=0, E=None, seed=0, offset=0, out=None,
+          want_probs=False, probs=None, changed=None):
+    N, D, S = logits.shape
+    name, rl, out = _step_entry("ctdd_lbjf_step", rows, out, x, N, D)
+    probs = _buffer(want_probs, probs, logits, "probs")
+    _launched(getattr(load(), name)(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
+                                    _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"), float(beta), float(eps), float(h),
+                                    int(flags), _ptr(E, f32, "E"), seed, offset, N, D, S, *rl, _ptr(out, i32, "out"),
+                                    _ptr(probs, f32, "probs"), _ptr(changed, i32, "changed"), _stream()), name)
+    return (out, probs) if want_probs else out
+
+
+def _exact(logits, x, q_lo, q_step, rows=None, E=None, seed=0, offset=0, out=None, want_probs=False, probs=None, changed=None):
+    N, D, S = logits.shape
+    name, rl, out = _step_entry("ctdd_exact_step", rows, out, x, N, D)
+    probs = _buffer(want_probs, probs, logits, "probs")
+    _launched(getattr(load(), name)(_ptr(logits, f32, "logits"), _ptr(x, i32, "x"), _ptr(q_lo, f32, "q_lo"),
+                                    _ptr(q_step, f32, "q_step"), _ptr(E, f32, "E"), seed, offset, N, D, S, *rl,
+                                    _ptr(out, i32, "out"), _ptr(probs, f32, "probs"), _ptr(changed, i32, "changed"), _stream()), name)
+    return (out, probs) if want_probs else out
+
+
+def _midpoint(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows=None, out=None):
+    N, D, S = logits.shape
+    name, rl, out = _step_entry("ctdd_midpoint_predict", rows, out, x, N, D)
+    _launched(getattr(load(), name)(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
+                                    _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"), float(beta), float(eps), float(h),
+                                    N, D, S, *rl, _ptr(out, i32, "out"), _stream()), name)
+    return out
+
+
+def _lbjf_rates(rates, x, h, rows=None, E=None, seed=0, offset=0, out=None, want_probs=False, probs=None, changed=None):
+    N, D, S = rates.shape
+    name, rl, out = _step_entry("ctdd_lbjf_from_rates", rows, out, x, N, D)
+    probs = _buffer(want_probs, probs, rates, "probs")
+    _launched(getattr(load(), name)(_ptr(rates, f32, "rates"), _ptr(x, i32, "x"), float(h), _ptr(E, f32, "E"), seed, offset,
+                                    N, D, S, *rl, _ptr(out, i32, "out"), _ptr(probs, f32, "probs"),
+                                    _ptr(changed, i32, "changed"), _stream()), name)
+    return (out, probs) if want_probs else out
+
+
+def _midpoint_rates(rates, x, h, rows=None, out=None):
+    N, D, S = rates.shape
+    name, rl, out = _step_entry("ctdd_midpoint_from_rates", rows, out, x, N, D)
+    _launched(getattr(load(), name)(_ptr(rates, f32, "rates"), _ptr(x, i32, "x"), float(h), N, D, S, *rl, _ptr(out, i32, "out"),
+                                    _stream()), name)
+    return out
+
+
+# The public names keep their positional signatures (`rows` sits where each C signature's callers expect it).
+def tauleap_step(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, seed, offset,
+                 x_base=None, out=None, changed=None):
+    return _tauleap(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, seed, offset, None, x_base, out, changed)
+
+
 def tauleap_step_rows(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, seed, offset, rows,
                       x_base=None, out=None, changed=None):
-    """tauleap_step on the rows listed in `rows` (ascending, distinct int32 indices into the N*D rows, on the device): listed
-    rows of the result are bit-identical to the full step's, the others are `out` as given (default: a copy of x)."""
-    N, D, S = logits.shape
-    rp, nr = _row_list(rows, N, D)
-    out = _prefilled(out, x, N, D)
-    rc = load().ctdd_tauleap_step_rows(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
-                                       _ptr(x_base, i32, "x_base"), _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"),
-                                       float(beta), float(eps), float(h), int(flags), seed, offset, N, D, S, rp, nr,
-                                       _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_tauleap_step_rows")
-    _count("ctdd_tauleap_step_rows")
-    return out
+    """tauleap_step on the listed rows: the other rows of the result are `out` as given (default: a copy of x)."""
+    return _tauleap(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags, seed, offset, rows, x_base, out, changed)
 
 
 def lbjf_step(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, flags=0, E=None, seed=0, offset=0,
               want_probs=False, changed=None):
-    N, D, S = logits.shape
-    out = torch.empty((N, D), dtype=i32, device=x.device)
-    probs = torch.empty_like(logits) if want_probs else None
-    rc = load().ctdd_lbjf_step(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
-                               _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"), float(beta), float(eps),
-                               float(h), int(flags), _ptr(E, f32, "E"), seed, offset, N, D, S, _ptr(out), _ptr(probs),
-                               _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_lbjf_step")
-    return (out, probs) if want_probs else out
+    return _lbjf(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, None, flags, E, seed, offset, None, want_probs, None, changed)
+
+
+def lbjf_step_rows(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows, flags=0, E=None, seed=0, offset=0,
+                   out=None, want_probs=False, probs=None, changed=None):
+    """lbjf_step on the listed rows: the other rows of the state / probabilities are `out` / `probs` as given (default: a copy of
+    x / uninitialised).  E, when given, is the full (N*D, S) noise: a listed row reads its own row of it."""
+    return _lbjf(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows, flags, E, seed, offset, out, want_probs, probs, changed)
 
 
 def exact_step(logits, x, q_lo, q_step, E=None, seed=0, offset=0, want_probs=False, changed=None):
     """ExactSampling step: x_new ~ Categorical((softmax(logits) @ q_lo) * q_step[:, x]) per dimension (K5-style contraction +
     exponential race in one launch)."""
-    N, D, S = logits.shape
-    out = torch.empty((N, D), dtype=i32, device=x.device)
-    probs = torch.empty_like(logits) if want_probs else None
-    rc = load().ctdd_exact_step(_ptr(logits, f32, "logits"), _ptr(x, i32, "x"), _ptr(q_lo, f32, "q_lo"), _ptr(q_step, f32, "q_step"),
-                                _ptr(E, f32, "E"), seed, offset, N, D, S, _ptr(out), _ptr(probs), _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_exact_step")
-    return (out, probs) if want_probs else out
+    return _exact(logits, x, q_lo, q_step, None, E, seed, offset, None, want_probs, None, changed)
+
+
+def exact_step_rows(logits, x, q_lo, q_step, rows, E=None, seed=0, offset=0, out=None, want_probs=False, probs=None, changed=None):
+    """exact_step on the listed rows (see lbjf_step_rows)."""
+    return _exact(logits, x, q_lo, q_step, rows, E, seed, offset, out, want_probs, probs, changed)
 
 
 def midpoint_predict(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h):
-    N, D, S = logits.shape
-    out = torch.empty((N, D), dtype=i32, device=x.device)
-    rc = load().ctdd_midpoint_predict(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
-                                      _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"), float(beta),
-                                      float(eps), float(h), N, D, S, _ptr(out), _stream())
-    _check(rc, "ctdd_midpoint_predict")
-    return out
+    return _midpoint(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h)
+
+
+def midpoint_predict_rows(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows, out=None):
+    """midpoint_predict on the listed rows: every other row of the result is `out` as given (default: a copy of x, i.e. x' = x)."""
+    return _midpoint(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows, out)
 
 
 def lbjf_from_rates(rates, x, h, E=None, seed=0, offset=0, want_probs=False, changed=None):
     """LBJF posterior + draw on masked reverse rates (N, D, S) that are already computed (tauleap_step_s256(want_rates=True))."""
-    N, D, S = rates.shape
-    out = torch.empty((N, D), dtype=i32, device=x.device)
-    probs = torch.empty_like(rates) if want_probs else None
-    rc = load().ctdd_lbjf_from_rates(_ptr(rates, f32, "rates"), _ptr(x, i32, "x"), float(h), _ptr(E, f32, "E"), seed, offset,
-                                     N, D, S, _ptr(out), _ptr(probs), _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_lbjf_from_rates")
-    return (out, probs) if want_probs else out
-
-
-def midpoint_from_rates(rates, x, h):
-    N, D, S = rates.shape
-    out = torch.empty((N, D), dtype=i32, device=x.device)
-    rc = load().ctdd_midpoint_from_rates(_ptr(rates, f32, "rates"), _ptr(x, i32, "x"), float(h), N, D, S, _ptr(out), _stream())
-    _check(rc, "ctdd_midpoint_from_rates")
-    return out
-
-
-def _rows_probs(want_probs, probs, like):
-    """out_probs of a row-list step: `probs` (full size, unlisted rows untouched) when given, else a fresh uninitialised tensor."""
-    if not want_probs:
-        return None
-    if probs is None:
-        return torch.empty(like.shape, dtype=f32, device=like.device)
-    if tuple(probs.shape) != tuple(like.shape):
-        raise CtddError(f"probs: expected shape {tuple(like.shape)}, got {tuple(probs.shape)}")
-    return probs
-
-
-def lbjf_step_rows(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows, flags=0, E=None, seed=0, offset=0,
-                   out=None, want_probs=False, probs=None, changed=None):
-    """lbjf_step on the rows listed in `rows` (see tauleap_step_rows): listed rows of the state and of the probabilities are
-    bit-identical to the full step's, the others are `out` / `probs` as given (default: a copy of x / uninitialised).  E, when
-    given, is the full (N*D, S) noise: a listed row reads its own row of it."""
-    N, D, S = logits.shape
-    rp, nr = _row_list(rows, N, D)
-    out = _prefilled(out, x, N, D)
-    probs = _rows_probs(want_probs, probs, logits)
-    rc = load().ctdd_lbjf_step_rows(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
-                                    _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"), float(beta), float(eps),
-                                    float(h), int(flags), _ptr(E, f32, "E"), seed, offset, N, D, S, rp, nr, _ptr(out, i32, "out"),
-                                    _ptr(probs, f32, "probs"), _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_lbjf_step_rows")
-    _count("ctdd_lbjf_step_rows")
-    return (out, probs) if want_probs else out
-
-
-def exact_step_rows(logits, x, q_lo, q_step, rows, E=None, seed=0, offset=0, out=None, want_probs=False, probs=None, changed=None):
-    """exact_step on the rows listed in `rows` (see lbjf_step_rows)."""
-    N, D, S = logits.shape
-    rp, nr = _row_list(rows, N, D)
-    out = _prefilled(out, x, N, D)
-    probs = _rows_probs(want_probs, probs, logits)
-    rc = load().ctdd_exact_step_rows(_ptr(logits, f32, "logits"), _ptr(x, i32, "x"), _ptr(q_lo, f32, "q_lo"), _ptr(q_step, f32, "q_step"),
-                                     _ptr(E, f32, "E"), seed, offset, N, D, S, rp, nr, _ptr(out, i32, "out"), _ptr(probs, f32, "probs"),
-                                     _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_exact_step_rows")
-    _count("ctdd_exact_step_rows")
-    return (out, probs) if want_probs else out
-
-
-def midpoint_predict_rows(branch, logit_type, logits, x, qt0, base_rate, beta, eps, h, rows, out=None):
-    """midpoint_predict on the rows listed in `rows`: x' of a listed row is the full launch's, every other row of the result is
-    `out` as given (default: a copy of x, i.e. x' = x on the unlisted rows)."""
-    N, D, S = logits.shape
-    rp, nr = _row_list(rows, N, D)
-    out = _prefilled(out, x, N, D)
-    rc = load().ctdd_midpoint_predict_rows(branch, LOGIT_TYPES[logit_type], _ptr(logits, f32, "logits"), _ptr(x, i32, "x"),
-                                           _ptr(qt0, f32, "qt0"), _ptr(base_rate, f32, "base_rate"), float(beta),
-                                           float(eps), float(h), N, D, S, rp, nr, _ptr(out, i32, "out"), _stream())
-    _check(rc, "ctdd_midpoint_predict_rows")
-    _count("ctdd_midpoint_predict_rows")
-    return out
+    return _lbjf_rates(rates, x, h, None, E, seed, offset, None, want_probs, None, changed)
 
 
 def lbjf_from_rates_rows(rates, x, h, rows, E=None, seed=0, offset=0, out=None, want_probs=False, probs=None, changed=None):
-    """lbjf_from_rates on the rows listed in `rows`: `rates` (N, D, S) is read at the listed rows only (what
+    """lbjf_from_rates on the listed rows: `rates` (N, D, S) is read at the listed rows only (what
     tauleap_step_s256_rows(want_rates=True) wrote there)."""
-    N, D, S = rates.shape
-    rp, nr = _row_list(rows, N, D)
-    out = _prefilled(out, x, N, D)
-    probs = _rows_probs(want_probs, probs, rates)
-    rc = load().ctdd_lbjf_from_rates_rows(_ptr(rates, f32, "rates"), _ptr(x, i32, "x"), float(h), _ptr(E, f32, "E"), seed, offset,
-                                          N, D, S, rp, nr, _ptr(out, i32, "out"), _ptr(probs, f32, "probs"),
-                                          _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_lbjf_from_rates_rows")
-    _count("ctdd_lbjf_from_rates_rows")
-    return (out, probs) if want_probs else out
+    return _lbjf_rates(rates, x, h, rows, E, seed, offset, out, want_probs, probs, changed)
+
+
+def midpoint_from_rates(rates, x, h):
+    return _midpoint_rates(rates, x, h)
 
 
 def midpoint_from_rates_rows(rates, x, h, rows, out=None):
-    """midpoint_from_rates on the rows listed in `rows` (see midpoint_predict_rows, lbjf_from_rates_rows)."""
-    N, D, S = rates.shape
-    rp, nr = _row_list(rows, N, D)
-    out = _prefilled(out, x, N, D)
-    rc = load().ctdd_midpoint_from_rates_rows(_ptr(rates, f32, "rates"), _ptr(x, i32, "x"), float(h), N, D, S, rp, nr,
-                                              _ptr(out, i32, "out"), _stream())
-    _check(rc, "ctdd_midpoint_from_rates_rows")
-    _count("ctdd_midpoint_from_rates_rows")
-    return out
+    """midpoint_from_rates on the listed rows (see midpoint_predict_rows, lbjf_from_rates_rows)."""
+    return _midpoint_rates(rates, x, h, rows, out)
 
 
 def argmax(logits):
@@ -822,53 +811,37 @@ class S256Tables:
         return self.steps.data_ptr() + i * self.block
 
 
+def _tauleap_s256(logits, x, tables, i, beta, h, flags, seed, offset, rows=None, x_base=None, out=None, changed=None,
+                  want_rates=False, rates=None, want_x=True):
+    """The S = 256 member of the step families above (same `rows` contract).  want_rates: also the masked reverse rates, into
+    `rates` (N, D, 256) f32 when given, else into a fresh uninitialised tensor.  want_x=False (with want_rates): the rates only --
+    no draw, no state, the returned state is None (the first half of an S = 256 LBJF / midpoint step)."""
+    N, D, S = logits.shape
+    name = "ctdd_tauleap_step_s256" if rows is None else "ctdd_tauleap_step_s256_rows"
+    if S != 256:
+        raise CtddError(f"{name[5:]} needs S == 256")
+    if not want_x and not want_rates:
+        raise CtddError(f"{name[5:]}: want_x=False needs want_rates=True")
+    name, rl, out = _step_entry("ctdd_tauleap_step_s256", rows, out, x, N, D, want_x)
+    rates = _buffer(want_rates, rates, logits, "rates")
+    bf16_logits = logits.dtype == torch.bfloat16             # (the bf16 U-Net engine's output): bf16 step only
+    if bf16_logits and not tables.bf16:
+        raise CtddError(f"{name[5:]}: bf16 logits need S256Tables(..., bf16=True)")
+    flags = (int(flags) | (STEP_CRM if tables.crm else 0) | (STEP_BF16 if tables.bf16 else 0)
+             | (STEP_LOGITS_BF16 if bf16_logits else 0))
+    _launched(getattr(load(), name)(_ptr(logits, torch.bfloat16 if bf16_logits else f32, "logits"), _ptr(x, i32, "x"),
+                                    _ptr(x_base, i32, "x_base"), tables.step_ptr(i), _ptr(tables.RT0), _ptr(tables.R0),
+                                    float(beta), float(h), flags, seed, offset, N, D, *rl, _ptr(rates, f32, "rates"),
+                                    _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream()), name)
+    return (out, rates) if want_rates else out
+
+
 def tauleap_step_s256(logits, x, tables, i, beta, h, flags, seed, offset, x_base=None, out=None, changed=None,
                       want_rates=False, want_x=True):
-    N, D, S = logits.shape
-    if S != 256:
-        raise CtddError("tauleap_step_s256 needs S == 256")
-    rates = torch.empty(logits.shape, dtype=f32, device=logits.device) if want_rates else None
-    if want_x and out is None:
-        out = torch.empty((N, D), dtype=i32, device=x.device)
-    lflag = 0
-    if logits.dtype == torch.bfloat16:                       # bf16 logits (the bf16 U-Net engine's output): bf16 step only
-        if not tables.bf16:
-            raise CtddError("tauleap_step_s256: bf16 logits need S256Tables(..., bf16=True)")
-        lflag = STEP_LOGITS_BF16
-    rc = load().ctdd_tauleap_step_s256(_ptr(logits, torch.bfloat16 if lflag else f32, "logits"), _ptr(x, i32, "x"), _ptr(x_base, i32, "x_base"),
-                                       tables.step_ptr(i), _ptr(tables.RT0), _ptr(tables.R0), float(beta), float(h),
-                                       int(flags) | (STEP_CRM if tables.crm else 0) | (STEP_BF16 if tables.bf16 else 0) | lflag, seed, offset, N, D, _ptr(rates), _ptr(out, i32, "out") if want_x else None,
-                                       _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_tauleap_step_s256")
-    return (out, rates) if want_rates else out
+    return _tauleap_s256(logits, x, tables, i, beta, h, flags, seed, offset, None, x_base, out, changed, want_rates, None, want_x)
 
 
 def tauleap_step_s256_rows(logits, x, tables, i, beta, h, flags, seed, offset, rows, x_base=None, out=None, changed=None,
                            want_rates=False, rates=None, want_x=True):
-    """tauleap_step_s256 on the rows listed in `rows` (see tauleap_step_rows).  want_rates: also the masked reverse rates of the
-    listed rows, into `rates` (N, D, 256) f32 when given (unlisted rows untouched), else into a fresh uninitialised tensor.
-    want_x=False (with want_rates): the listed rows' rates only -- no draw, no state, the returned state is None (the first
-    half of an S = 256 LBJF / midpoint step, as tauleap_step_s256(want_rates=True, want_x=False) is of the full one)."""
-    N, D, S = logits.shape
-    if S != 256:
-        raise CtddError("tauleap_step_s256_rows needs S == 256")
-    if not want_x and not want_rates:
-        raise CtddError("tauleap_step_s256_rows: want_x=False needs want_rates=True")
-    rp, nr = _row_list(rows, N, D)
-    out = _prefilled(out, x, N, D) if want_x else None
-    if want_rates and rates is None:
-        rates = torch.empty(logits.shape, dtype=f32, device=logits.device)
-    lflag = 0
-    if logits.dtype == torch.bfloat16:
-        if not tables.bf16:
-            raise CtddError("tauleap_step_s256_rows: bf16 logits need S256Tables(..., bf16=True)")
-        lflag = STEP_LOGITS_BF16
-    rc = load().ctdd_tauleap_step_s256_rows(_ptr(logits, torch.bfloat16 if lflag else f32, "logits"), _ptr(x, i32, "x"),
-                                            _ptr(x_base, i32, "x_base"), tables.step_ptr(i), _ptr(tables.RT0), _ptr(tables.R0),
-                                            float(beta), float(h),
-                                            int(flags) | (STEP_CRM if tables.crm else 0) | (STEP_BF16 if tables.bf16 else 0) | lflag,
-                                            seed, offset, N, D, rp, nr, _ptr(rates, f32, "rates") if want_rates else None,
-                                            _ptr(out, i32, "out") if want_x else None, _ptr(changed, i32, "changed"), _stream())
-    _check(rc, "ctdd_tauleap_step_s256_rows")
-    _count("ctdd_tauleap_step_s256_rows")
-    return (out, rates) if want_rates else out
+    """tauleap_step_s256 on the listed rows (see tauleap_step_rows); `rates`: unlisted rows untouched."""
+    return _tauleap_s256(logits, x, tables, i, beta, h, flags, seed, offset, rows, x_base, out, changed, want_rates, rates, want_x)

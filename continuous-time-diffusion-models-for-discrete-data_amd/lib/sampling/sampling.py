@@ -157,42 +157,74 @@ class _GridSampler:
             raise ValueError(f"sampler.step_precision must be 'auto', 'bf16' or 'fp32', got {mode!r}")
         return mode == "bf16"
 
-    def _leap(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, x_base=None, changed=None):
+    # -- the steps.  rows None: every row moves; an int32 device tensor of row indices into the N*D rows: only those do, and the
+    # other rows of the returned state are those of x (the `_rows` entries of the same kernels, see ctdd/native.py)
+    def _leap(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, x_base=None, changed=None, rows=None):
         """One fused reverse-rate / jump / update launch (MFMA path when prepared, else generic)."""
         if fast is not None:
-            return native.tauleap_step_s256(logits, x, fast, i, beta, h, flags, key, offset, x_base=x_base,
-                                            changed=changed)
-        return native.tauleap_step(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta,
-                                   self.eps_ratio, h, flags, key, offset, x_base=x_base, changed=changed)
+            return native._tauleap_s256(logits, x, fast, i, beta, h, flags, key, offset, rows, x_base=x_base, changed=changed)
+        return native._tauleap(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta, self.eps_ratio, h,
+                               flags, key, offset, rows, x_base=x_base, changed=changed)
 
-    def _leap_rows(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, rows, changed=None, x_base=None):
-        """_leap on the listed rows only (int32 device tensor of row indices into the N*D rows); the other rows of the returned
-        state are those of x."""
+    def _lbjf(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, changed=None, rows=None, rates=None):
+        """One Euler / LBJF step; at S = 256 the reverse rates come from the matrix-core kernel (into `rates` (N, D, 256) when
+        given: the buffer a row-list sampler allocates once per call), the posterior and the categorical draw run on them."""
         if fast is not None:
-            return native.tauleap_step_s256_rows(logits, x, fast, i, beta, h, flags, key, offset, rows, x_base=x_base,
-                                                 changed=changed)
-        return native.tauleap_step_rows(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta,
-                                        self.eps_ratio, h, flags, key, offset, rows, x_base=x_base, changed=changed)
+            _, rates = native._tauleap_s256(logits, x, fast, i, beta, h, flags & native.STEP_CORRECTOR, key, offset, rows,
+                                            want_rates=True, rates=rates, want_x=False)
+            return native._lbjf_rates(rates, x, h, rows, None, key, offset, changed=changed)
+        return native._lbjf(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta, self.eps_ratio, h, rows,
+                            flags, None, key, offset, changed=changed)
 
-    def _lbjf(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, changed=None):
-        """One Euler / LBJF step; at S = 256 the reverse rates come from the matrix-core kernel, the posterior and the
-        categorical draw run on them."""
+    def _midpoint_predict(self, model, logits, x, q_i, fast, i, beta, h, key, rows=None, rates=None):
+        """The deterministic half-step drift x' of midpoint tau-leaping (x' = x on unlisted rows); S = 256 as in _lbjf."""
         if fast is not None:
-            _, rates = native.tauleap_step_s256(logits, x, fast, i, beta, h, flags & native.STEP_CORRECTOR, key, offset,
-                                                want_rates=True, want_x=False)
-            return native.lbjf_from_rates(rates, x, h, None, key, offset, changed=changed)
-        return native.lbjf_step(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta, self.eps_ratio,
-                                h, flags, None, key, offset, changed=changed)
+            _, rates = native._tauleap_s256(logits, x, fast, i, beta, float(np.float32(h)), 0, key, 0, rows, want_rates=True,
+                                            rates=rates, want_x=False)
+            return native._midpoint_rates(rates, x, h, rows)
+        return native._midpoint(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta, self.eps_ratio, h, rows)
 
-    def _lbjf_rows(self, model, logits, x, q_i, fast, i, beta, h, flags, key, offset, rows, rates=None, changed=None):
-        """_lbjf on the listed rows only; the other rows of the returned state are those of x.  `rates`: the (N, D, 256) buffer
-        the S = 256 pair passes the listed rows' rates through (allocated once per call by the sampler)."""
-        if fast is not None:
-            native.tauleap_step_s256_rows(logits, x, fast, i, beta, h, flags & native.STEP_CORRECTOR, key, offset, rows,
-                                          want_rates=True, rates=rates, want_x=False)
-            return native.lbjf_from_rates_rows(rates, x, h, rows, None, key, offset, changed=changed)
-        return native.lbjf_step_rows(self.branch, self.logit_type, logits, x, q_i, model.process.base_rate, beta, self.eps_ratio,
-                                     h, rows, flags, None, key, offset, changed=changed)
+    def _grid(self):
+        """linspace(max_t, min_t, num_steps) followed by 0."""
+        return np.concatenate((np.linspace(self.max_t, self.min_t, self.num_steps), np.array([0])))
+
+    def _pc_loop(self, model, N, std, flags, held=None):
+        """The predictor-corrector tau-leaping loop of PCTauL and ConditionalPCTauLeaping: h = 1 / num_steps, grid
+        linspace(1.0, min_t + h, num_steps) walked over ts[:-1], correctors at t - h once t <= corrector_entry_time, argmax at
+        min_t.  std: of the initial draw; held as in LBJF._loop.  Returns the (N, D) int array."""
+        s = self.cfg.sampler
+        dev = torch.device(model.device)
+        key = self._key()
+        with torch.no_grad(), self._borrow(model):
+            x = self._initial(model, N, key, std)
+            rows = None
+            if held is not None:
+                xk, m, rows = held
+                x = torch.where(m, xk, x)
+            h0 = 1.0 / s.num_steps
+            ts = np.linspace(1.0, s.min_t + h0, s.num_steps)
+            pr = model.process
+            t32, qt0, betas = self._tables(model, ts)
+            fast = self._fast_tables(model, qt0)
+            sub = 1 + max(int(s.num_corrector_steps), 0)
+            for i, t in enumerate(ts[:-1]):
+                h = ts[i] - ts[i + 1]
+                logits = self._net_logits(model, x, self._t_ones(t32, i, N, dev), fast)
+                x = self._leap(model, logits, x, qt0[i], fast, i, betas[i], float(np.float32(h)), flags, key, i * sub, rows=rows)
+                if t <= s.corrector_entry_time:
+                    tc = torch.tensor([t - h], dtype=torch.float64).to(torch.float32)
+                    qc = pr.tables(tc, want_qt0=True)[0][0]
+                    bc = float(pr.beta(tc)[0])
+                    t_c = torch.full((N,), float(tc[0]), device=dev)
+                    fast_c = self._fast_tables(model, qc.unsqueeze(0)) if fast is not None else None
+                    for c in range(s.num_corrector_steps):
+                        logits = self._net_logits(model, x, t_c, fast_c)
+                        x = self._leap(model, logits, x, qc, fast_c, 0, bc, float(np.float32(s.corrector_step_size_multiplier * h)),
+                                       flags | native.STEP_CORRECTOR, key, i * sub + 1 + c, rows=rows)
+            x = self._final_argmax(model, x, N)
+            if held is not None:
+                x = torch.where(m, xk, x)
+            return x.cpu().numpy().astype(int)
 
     @staticmethod
     def _t_ones(t32, i, N, device):
@@ -225,12 +257,18 @@ class TauL(_GridSampler):
         p = int(p)
         return p if (unet and p > 1 and N % p == 0 and N // p >= 32) else 1
 
-    def begin(self, model, N, pipeline=None):
+    def begin(self, model, N, pipeline=None, held=None):
+        """held = (x_known int32, mask bool, free-row lists: one per sub-batch and relative to it), all on the device
+        (ConditionalTauLeaping): the held entries are scattered in after the initial draw and every launch moves the listed rows only."""
         dev = torch.device(model.device)
         st = type("TauLState", (), {})()
         st.model, st.N, st.dev, st.key = model, N, dev, self._key()
         st.x = self._initial(model, N, st.key, self.cfg.model.Q_sigma)
-        st.ts = np.concatenate((np.linspace(self.max_t, self.min_t, self.num_steps), np.array([0])))
+        st.rows = None
+        if held is not None:
+            xk, m, st.rows = held
+            st.x = torch.where(m, xk, st.x)
+        st.ts = self._grid()
         st.t32, st.qt0, st.betas = self._tables(model, st.ts[:-1])
         st.fast = self._fast_tables(model, st.qt0)
         # the grid's times are known here: the U-Net engine computes every step's time-projection row in one launch and the
@@ -291,12 +329,14 @@ class TauL(_GridSampler):
         # (with the time table the plans never read the times: a stride-0 view of the grid value instead of a fill launch per step)
         t_ones = st.t_dev[i].expand(N) if st.temb is not None else self._t_ones(st.t32, i, N, st.dev)
         q_i = st.qt0[i] if st.qt0 is not None else None
+        rows = st.rows[part] if st.rows is not None else None
         logits = self._net_logits(model, x, t_ones, st.fast)
-        x = self._leap(model, logits, x, q_i, st.fast, i, st.betas[i], h, st.flags, key, i * st.sub, changed=changed)
+        x = self._leap(model, logits, x, q_i, st.fast, i, st.betas[i], h, st.flags, key, i * st.sub, changed=changed, rows=rows)
         if t <= self.corrector_entry_time:
             for c in range(self.num_corrector_steps):
                 logits = self._net_logits(model, x, t_ones, st.fast)
-                x = self._leap(model, logits, x, q_i, st.fast, i, st.betas[i], h, st.flags | native.STEP_CORRECTOR, key, i * st.sub + 1 + c)
+                x = self._leap(model, logits, x, q_i, st.fast, i, st.betas[i], h, st.flags | native.STEP_CORRECTOR, key, i * st.sub + 1 + c,
+                               rows=rows)
         return x
 
     def finish(self, st):
@@ -335,28 +375,28 @@ class LBJF(_GridSampler):
         key = self._key()
         with torch.no_grad(), self._borrow(model):
             x = self._initial(model, N, key, self.cfg.model.Q_sigma)
-            ts = np.concatenate((np.linspace(self.max_t, self.min_t, self.num_steps), np.array([0])))
+            ts = self._grid()
             t32, qt0, betas = self._tables(model, ts[:-1])
             changed = torch.zeros(self.num_steps, dtype=torch.int32, device=dev)
             fast = self._fast_tables(model, qt0)
             sub = 1 + max(int(self.num_corrector_steps), 0)
-            if held is None:
-                step = self._lbjf
-            else:
+            rows = rates = None
+            if held is not None:
                 xk, m, rows = held
                 x = torch.where(m, xk, x)
                 rates = torch.empty((N, self.D, self.S), dtype=torch.float32, device=dev) if fast is not None else None
-                step = lambda *a, **kw: self._lbjf_rows(*a, rows, rates=rates, **kw)
             for i, t in enumerate(ts[:-1]):
                 h = float(np.float32(ts[i] - ts[i + 1]))
                 t_ones = self._t_ones(t32, i, N, dev)
                 q_i = qt0[i] if qt0 is not None else None
                 logits = self._net_logits(model, x, t_ones, fast)
-                x = step(model, logits, x, q_i, fast, i, betas[i], h, 0, key, i * sub, changed=changed[i:i + 1])
+                x = self._lbjf(model, logits, x, q_i, fast, i, betas[i], h, 0, key, i * sub, changed=changed[i:i + 1], rows=rows,
+                               rates=rates)
                 if t <= self.corrector_entry_time:
                     for c in range(self.num_corrector_steps):
                         logits = self._net_logits(model, x, t_ones, fast)
-                        x = step(model, logits, x, q_i, fast, i, betas[i], h, native.STEP_CORRECTOR, key, i * sub + 1 + c)
+                        x = self._lbjf(model, logits, x, q_i, fast, i, betas[i], h, native.STEP_CORRECTOR, key, i * sub + 1 + c,
+                                       rows=rows, rates=rates)
             if self.loss_name == "CTElbo":
                 x = self._final_argmax(model, x, N)
             if held is not None:
@@ -380,6 +420,15 @@ class MidPointTauL(_GridSampler):
     def sample(self, model, N):
         return self._loop(model, N)
 
+    def _times(self):
+        """(h, the times of the full steps): max_t, max_t - h, ... while the half step stays above min_t."""
+        h = (self.max_t - self.min_t) / self.num_steps
+        full, t = [], self.max_t
+        while t - 0.5 * h > self.min_t:
+            full.append(t)
+            t = t - h
+        return h, full
+
     def _loop(self, model, N, held=None):
         """The sampler loop; held as in LBJF._loop (ConditionalMidPointTauL): both stages move the listed rows only, so x' = x
         on the held rows."""
@@ -387,14 +436,11 @@ class MidPointTauL(_GridSampler):
         key = self._key()
         with torch.no_grad(), self._borrow(model):
             x = self._initial(model, N, key, self.cfg.model.Q_sigma)
+            rows = None
             if held is not None:
                 xk, m, rows = held
                 x = torch.where(m, xk, x)
-            h = (self.max_t - self.min_t) / self.num_steps
-            full, half, t = [], [], self.max_t
-            while t - 0.5 * h > self.min_t:
-                full.append(t)
-                t = t - h
+            h, full = self._times()
             # t_05 = float32(t)*ones - 0.5*h evaluated in float32, as in the reference
             t32 = torch.tensor(full, dtype=torch.float64).to(torch.float32)
             t32_half = t32 - 0.5 * h
@@ -416,34 +462,12 @@ class MidPointTauL(_GridSampler):
                 t_ones = torch.full((N,), float(t32[i]), device=dev)
                 t_05 = torch.full((N,), float(t32_half[i]), device=dev)
                 logits = self._net_logits(model, x, t_ones, fast_full)
-                if held is not None:                # the same two stages on the free rows
-                    if fast_full is not None:
-                        native.tauleap_step_s256_rows(logits, x, fast_full, i, b_full[i], hf, 0, key, 0, rows, want_rates=True,
-                                                      rates=rates, want_x=False)
-                        x_prime = native.midpoint_from_rates_rows(rates, x, h, rows)
-                    else:
-                        x_prime = native.midpoint_predict_rows(self.branch, self.logit_type, logits, x,
-                                                               q_full[i] if need_q else None, pr.base_rate, b_full[i],
-                                                               self.eps_ratio, h, rows)
-                    logits_p = self._net_logits(model, x_prime, t_05, fast_half)
-                    # (x_base = x' also on the held rows, where x' = x: _leap_rows' x_base is only read at the listed rows)
-                    x_new = self._leap_rows(model, logits_p, x, q_half[i] if need_q else None, fast_half, i, b_half[i], hf,
-                                            flags, key, i, rows, changed=cnt[i, 0:3], x_base=x_prime)
-                    cnt[i, 3] = (x != x_prime).sum()
-                    cnt[i, 4] = (x_prime != x_new).sum()
-                    x = x_new
-                    continue
-                if fast_full is not None:           # S = 256: rates from the matrix-core kernel, drift on them
-                    _, rates = native.tauleap_step_s256(logits, x, fast_full, i, b_full[i], hf, 0, key, 0, want_rates=True,
-                                                        want_x=False)
-                    x_prime = native.midpoint_from_rates(rates, x, h)
-                else:
-                    x_prime = native.midpoint_predict(self.branch, self.logit_type, logits, x,
-                                                      q_full[i] if need_q else None, pr.base_rate, b_full[i],
-                                                      self.eps_ratio, h)
+                x_prime = self._midpoint_predict(model, logits, x, q_full[i] if need_q else None, fast_full, i, b_full[i], h, key,
+                                                 rows=rows, rates=rates)
                 logits_p = self._net_logits(model, x_prime, t_05, fast_half)
+                # (x_base = x' also on the held rows, where x' = x: it is only read at the listed rows)
                 x_new = self._leap(model, logits_p, x, q_half[i] if need_q else None, fast_half, i, b_half[i], hf,
-                                   flags, key, i, x_base=x_prime, changed=cnt[i, 0:3])
+                                   flags, key, i, x_base=x_prime, changed=cnt[i, 0:3], rows=rows)
                 cnt[i, 3] = (x != x_prime).sum()
                 cnt[i, 4] = (x_prime != x_new).sum()
                 x = x_new
@@ -470,34 +494,7 @@ class PCTauL(_GridSampler):
         self.branch, self.logit_type = native.BRANCH_CTELBO, "direct"
 
     def sample(self, model, N):
-        s = self.cfg.sampler
-        dev = torch.device(model.device)
-        key = self._key()
-        with torch.no_grad(), self._borrow(model):
-            x = self._initial(model, N, key, 200)
-            h0 = 1.0 / s.num_steps
-            ts = np.linspace(1.0, s.min_t + h0, s.num_steps)
-            pr = model.process
-            t32, qt0, betas = self._tables(model, ts)
-            fast = self._fast_tables(model, qt0)
-            sub = 1 + max(int(s.num_corrector_steps), 0)
-            for i, t in enumerate(ts[:-1]):
-                h = ts[i] - ts[i + 1]
-                logits = self._net_logits(model, x, self._t_ones(t32, i, N, dev), fast)
-                x = self._leap(model, logits, x, qt0[i], fast, i, betas[i], float(np.float32(h)), native.STEP_ORDINAL,
-                               key, i * sub)
-                if t <= s.corrector_entry_time:
-                    tc = torch.tensor([t - h], dtype=torch.float64).to(torch.float32)
-                    qc = pr.tables(tc, want_qt0=True)[0][0]
-                    bc = float(pr.beta(tc)[0])
-                    t_c = torch.full((N,), float(tc[0]), device=dev)
-                    fast_c = self._fast_tables(model, qc.unsqueeze(0)) if fast is not None else None
-                    for c in range(s.num_corrector_steps):
-                        logits = self._net_logits(model, x, t_c, fast_c)
-                        x = self._leap(model, logits, x, qc, fast_c, 0, bc, float(np.float32(s.corrector_step_size_multiplier * h)),
-                                       native.STEP_ORDINAL | native.STEP_CORRECTOR, key, i * sub + 1 + c)
-            x = self._final_argmax(model, x, N)
-            return x.cpu().numpy().astype(int)
+        return self._pc_loop(model, N, 200, native.STEP_ORDINAL)
 
 
 class _Conditioned:
@@ -505,11 +502,15 @@ class _Conditioned:
 
     `inpaint(model, x_known, mask)`: x_known (N, D) integer states, mask (D,) or (N, D) bool, True = held at x_known.  The
     state is always the full (N, D): held entries are scattered in once after the initial draw, so the network sees them at
-    every step, and every step launch moves only the free rows (the `_rows` step entry points: a held row costs no softmax,
+    every step, and every step launch moves only the free rows (the step helpers' `rows` list: a held row costs no softmax,
     no S x S contraction and no draw).  The final argmax is taken at min_t and the held entries are restored in the result.
     `sample(model, N, conditioner)` (the reference's call) is `inpaint` with the first cfg.sampler.condition_dim columns
     held.  D is cfg.model.concat_dim (the reference reads cfg.data.shape[0], which is D only for 1-D data); for image data
     the flattened order is the row-major (C, H, W) one, so a prefix of the dimensions is the top rows of the image."""
+
+    def sample(self, model, N, conditioner):
+        x_known, mask = self._prefix(N, conditioner)
+        return self.inpaint(model, x_known, mask)
 
     def _prefix(self, N, conditioner):
         cd = getattr(self.cfg.sampler, "condition_dim", None)
@@ -569,11 +570,6 @@ class ConditionalTauLeaping(_Conditioned, TauL):
         self.max_t = 1.0
         self.num_corrector_steps = 0
         self.is_ordinal = True
-        self._held_now = None
-
-    def sample(self, model, N, conditioner):
-        x_known, mask = self._prefix(N, conditioner)
-        return self.inpaint(model, x_known, mask)
 
     def inpaint(self, model, x_known, mask):
         N, xk, m = self._held(x_known, mask)
@@ -582,30 +578,13 @@ class ConditionalTauLeaping(_Conditioned, TauL):
         dev = torch.device(model.device)
         parts = self._pipeline_parts(model, N)
         rows = self._free_rows(m, parts, dev)
-        self._held_now = (xk.to(dev), m.to(dev))
-        try:
-            with torch.no_grad(), self._borrow(model):
-                st = self.begin(model, N, pipeline=parts)
-                st.rows = rows
-                for i in range(self.num_steps):
-                    self.advance(st, i)
-                x = self._final_argmax(model, self.state_x(st), N)
-                return torch.where(self._held_now[1], self._held_now[0], x).cpu().numpy().astype(int)
-        finally:
-            self._held_now = None
-
-    def _initial(self, model, N, key, std):
-        x = super()._initial(model, N, key, std)
-        return x if self._held_now is None else torch.where(self._held_now[1], self._held_now[0], x)
-
-    def _advance_one(self, st, i, x, N, key, changed, part=0):
-        model = st.model
-        h = float(np.float32(st.ts[i] - st.ts[i + 1]))
-        t_ones = st.t_dev[i].expand(N) if st.temb is not None else self._t_ones(st.t32, i, N, st.dev)
-        q_i = st.qt0[i] if st.qt0 is not None else None
-        logits = self._net_logits(model, x, t_ones, st.fast)
-        return self._leap_rows(model, logits, x, q_i, st.fast, i, st.betas[i], h, st.flags, key, i * st.sub, st.rows[part],
-                               changed=changed)
+        xk, m = xk.to(dev), m.to(dev)
+        with torch.no_grad(), self._borrow(model):
+            st = self.begin(model, N, pipeline=parts, held=(xk, m, rows))
+            for i in range(self.num_steps):
+                self.advance(st, i)
+            x = self._final_argmax(model, self.state_x(st), N)
+            return torch.where(m, xk, x).cpu().numpy().astype(int)
 
 
 @sampling_utils.register_sampler
@@ -620,44 +599,14 @@ class ConditionalPCTauLeaping(_Conditioned, _GridSampler):
         super().__init__(cfg)
         self.branch, self.logit_type = native.BRANCH_CTELBO, "direct"
 
-    def sample(self, model, N, conditioner):
-        x_known, mask = self._prefix(N, conditioner)
-        return self.inpaint(model, x_known, mask)
-
     def inpaint(self, model, x_known, mask):
         N, xk, m = self._held(x_known, mask)
         if bool(m.all()):
             return xk.numpy().astype(int)
-        s = self.cfg.sampler
         dev = torch.device(model.device)
         rows = self._free_rows(m, 1, dev)[0]
-        xk, m = xk.to(dev), m.to(dev)
-        flags = 0 if bool(getattr(s, "reject_multiple_jumps", False)) else native.STEP_ORDINAL
-        key = self._key()
-        with torch.no_grad(), self._borrow(model):
-            x = torch.where(m, xk, self._initial(model, N, key, self.cfg.model.Q_sigma))
-            h0 = 1.0 / s.num_steps
-            ts = np.linspace(1.0, s.min_t + h0, s.num_steps)
-            pr = model.process
-            t32, qt0, betas = self._tables(model, ts)
-            fast = self._fast_tables(model, qt0)
-            sub = 1 + max(int(s.num_corrector_steps), 0)
-            for i, t in enumerate(ts[:-1]):
-                h = ts[i] - ts[i + 1]
-                logits = self._net_logits(model, x, self._t_ones(t32, i, N, dev), fast)
-                x = self._leap_rows(model, logits, x, qt0[i], fast, i, betas[i], float(np.float32(h)), flags, key, i * sub, rows)
-                if t <= s.corrector_entry_time:
-                    tc = torch.tensor([t - h], dtype=torch.float64).to(torch.float32)
-                    qc = pr.tables(tc, want_qt0=True)[0][0]
-                    bc = float(pr.beta(tc)[0])
-                    t_c = torch.full((N,), float(tc[0]), device=dev)
-                    fast_c = self._fast_tables(model, qc.unsqueeze(0)) if fast is not None else None
-                    for c in range(s.num_corrector_steps):
-                        logits = self._net_logits(model, x, t_c, fast_c)
-                        x = self._leap_rows(model, logits, x, qc, fast_c, 0, bc, float(np.float32(s.corrector_step_size_multiplier * h)),
-                                            flags | native.STEP_CORRECTOR, key, i * sub + 1 + c, rows)
-            x = self._final_argmax(model, x, N)
-            return torch.where(m, xk, x).cpu().numpy().astype(int)
+        flags = 0 if bool(getattr(self.cfg.sampler, "reject_multiple_jumps", False)) else native.STEP_ORDINAL
+        return self._pc_loop(model, N, self.cfg.model.Q_sigma, flags, held=(xk.to(dev), m.to(dev), rows))
 
 
 @sampling_utils.register_sampler
@@ -681,10 +630,11 @@ class ExactSampling(_GridSampler):
         key = self._key()
         with torch.no_grad(), borrow_engine_output(model, uniform_time=True):
             x = self._initial(model, N, key, self.cfg.model.Q_sigma).long()
+            rows = None
             if held is not None:
                 xk, m, rows = held
                 x = torch.where(m, xk.long(), x)
-            ts = np.concatenate((np.linspace(self.max_t, self.min_t, self.num_steps), np.array([0])))
+            ts = self._grid()
             pr = model.process
             t_hi = torch.from_numpy(ts[:-1]).to(torch.float32)
             t_lo = torch.from_numpy(ts[:-1] - (ts[:-1] - ts[1:])).to(torch.float32)
@@ -698,10 +648,7 @@ class ExactSampling(_GridSampler):
                 logits = model(x.long(), t_ones).float().contiguous()
                 # softmax, the S x S contraction with q_{t-h|0}, the column x_t of q_{t|t-h}, normalisation and the categorical
                 # draw (exponential race on Philox(key, i, row, s)) in ONE launch: ctdd_exact_step
-                if held is not None:
-                    x = native.exact_step_rows(logits, x, q_lo[i], q_step[i], rows, None, key, i, changed=moved[i:i + 1])
-                else:
-                    x = native.exact_step(logits, x, q_lo[i], q_step[i], None, key, i, changed=moved[i:i + 1])
+                x = native._exact(logits, x, q_lo[i], q_step[i], rows, None, key, i, changed=moved[i:i + 1])
             change = moved.float() / float(N * self.D)
             return x.cpu().numpy().astype(int), change.cpu().tolist()
 
@@ -713,10 +660,6 @@ class _ConditionedLoop(_Conditioned):
     the final argmax exactly when the parent takes it, the parent's return tuple, and per-step counters with the parent's
     normalisation that count free rows only.  The Philox counter is keyed by the row of the N*D space, so an all-free mask
     returns the parent's samples bit for bit under the same seed on a deterministic model."""
-
-    def sample(self, model, N, conditioner):
-        x_known, mask = self._prefix(N, conditioner)
-        return self.inpaint(model, x_known, mask)
 
     def inpaint(self, model, x_known, mask):
         N, xk, m = self._held(x_known, mask)
@@ -746,11 +689,7 @@ class ConditionalMidPointTauL(_ConditionedLoop, MidPointTauL):
     pair with `ctdd_midpoint_from_rates_rows`), held rows of x' equal x; stage 2 the row-list tau-leap step with x_base = x'."""
 
     def _grid_len(self):
-        h = (self.max_t - self.min_t) / self.num_steps
-        n, t = 0, self.max_t
-        while t - 0.5 * h > self.min_t:
-            n, t = n + 1, t - h
-        return n
+        return len(self._times()[1])
 
     def _all_held(self, x):
         z = [0.0] * self._grid_len()

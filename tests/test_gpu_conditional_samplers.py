@@ -6,7 +6,8 @@
    tests/test_gpu_conditional.py);
 2. ConditionalLBJF / ConditionalMidPointTauL / ConditionalExactSampling in law against the oracle's own loops
    (oracle.samplers.lbjf_sample / midpoint_sample / exact_sample) run on the free part of a score that couples the dimensions;
-3. identities on a deterministic model: all free = the parent sampler bit for bit, all held = x_known and no launch;
+3. identities on a deterministic model: all free = the parent sampler bit for bit, all held = x_known and no launch (also for
+   ConditionalTauLeaping / ConditionalPCTauLeaping against TauL / PCTauL, whose loops they share);
 4. the samplers on the HIP engines (maze hollow transformer, masked synthetic transformer)."""
 import copy
 
@@ -433,9 +434,19 @@ class DeterministicToy:
 def _id_cfg(name, S, D=23):
     c = _law_cfg(name, S, D, 5, initial_dist="uniform" if S == 3 else "gaussian")
     c.sampler.num_steps = 6
-    if name.endswith("LBJF"):
+    pc = name in ("PCTauL", "ConditionalPCTauLeaping")
+    if name.endswith("LBJF") or pc:
         c.sampler.corrector_entry_time, c.sampler.num_corrector_steps = 0.6, 1
+    if name in ("TauL", "ConditionalTauLeaping"):                # TauL set to what ConditionalTauLeaping fixes (no corrector: _law_cfg)
+        c.training.max_t, c.sampler.is_ordinal = 1.0, True
+    if pc and S == 256:
+        c.model.Q_sigma = 200                                    # the initial std PCTauL hard-codes (S = 3 starts uniform)
     return c
+
+
+# parent -> (its conditional sampler, length of the return tuple; 0: a bare array from the conditional sampler)
+ID_PAIRS = {"LBJF": ("ConditionalLBJF", 2), "MidPointTauL": ("ConditionalMidPointTauL", 5), "ExactSampling": ("ConditionalExactSampling", 2),
+            "TauL": ("ConditionalTauLeaping", 0), "PCTauL": ("ConditionalPCTauLeaping", 0)}
 
 
 def _same(a, b):
@@ -445,38 +456,44 @@ def _same(a, b):
 
 
 @pytest.mark.parametrize("S", [3, 256])
-@pytest.mark.parametrize("parent", ["LBJF", "MidPointTauL", "ExactSampling"])
+@pytest.mark.parametrize("parent", list(ID_PAIRS))
 def test_all_free_mask_is_the_parent_sampler(parent, S):
     import lib.sampling.sampling  # noqa: F401
     import lib.sampling.sampling_utils as su
     from ctdd import native
     N, D = 37, 23
     model = DeterministicToy(S)
+    child, n_out = ID_PAIRS[parent]
     ps = su.get_sampler(_id_cfg(parent, S))
-    cs = su.get_sampler(_id_cfg("Conditional" + parent, S))
+    cs = su.get_sampler(_id_cfg(child, S))
     ps.seed = cs.seed = 99
     want = ps.sample(model, N)
     before = dict(native.LAUNCH_COUNTS)
     got = cs.inpaint(model, torch.zeros((N, D), dtype=torch.int64), torch.zeros(D, dtype=torch.bool))
     assert sum(_delta(before).values()) > 0
-    assert len(got) == len(want) == (5 if parent == "MidPointTauL" else 2)
+    if n_out == 0:                                               # (x, changed) from TauL, a bare array from PCTauL and both children
+        want, got, n_out = (want[0] if parent == "TauL" else want,), (got,), 1
+    assert len(got) == len(want) == n_out
     for k, (a, b) in enumerate(zip(got, want)):
         assert _same(a, b), (parent, S, k)
     assert (want[0] != want[0][:1]).any()                        # (the run does move: not a constant state)
 
 
 @pytest.mark.parametrize("S", [3, 256])
-@pytest.mark.parametrize("parent", ["LBJF", "MidPointTauL", "ExactSampling"])
+@pytest.mark.parametrize("parent", list(ID_PAIRS))
 def test_all_held_mask_returns_known_and_launches_nothing(parent, S):
     import lib.sampling.sampling  # noqa: F401
     import lib.sampling.sampling_utils as su
     from ctdd import native
     N, D = 9, 23
-    cs = su.get_sampler(_id_cfg("Conditional" + parent, S))
+    child, n_out = ID_PAIRS[parent]
+    cs = su.get_sampler(_id_cfg(child, S))
     xk = torch.randint(0, S, (N, D), generator=torch.Generator().manual_seed(1))
     before = dict(native.LAUNCH_COUNTS)
     out = cs.inpaint(DeterministicToy(S), xk, torch.ones((N, D), dtype=torch.bool))
-    assert (out[0] == xk.numpy()).all() and len(out) == (5 if parent == "MidPointTauL" else 2)
+    if n_out == 0:
+        out, n_out = (out,), 1
+    assert (out[0] == xk.numpy()).all() and len(out) == n_out
     assert all(native.LAUNCH_COUNTS.get(k, 0) == before.get(k, 0) for k in native.LAUNCH_COUNTS)
 
 
