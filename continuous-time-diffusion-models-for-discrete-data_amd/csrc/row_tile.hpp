@@ -1,7 +1,8 @@
 // row_tile.hpp -- the row-tile K loops that k_resblock_mid (unet_resblock_kernels.hip) and k_conv_rows (unet_rows_kernels.hip)
 // share, with their weight loads: a pixel tile is one output row of a zero-bordered LDS slab, a wave owns three 16-channel weight
 // tiles (v_mfma_f32_16x16x32_bf16, weights as the A operand) and streams its weights global -> registers through a ring of two units
-// (ctdd/unet_engine.py: pack_row_tile_weights).
+// (ctdd/unet_engine.py: pack_row_tile_weights).  rt_gemm_rows is the loop of the kernels with one wave per SIMD (two fragment sets),
+// rt_gemm_rows_1buf that of k_conv_rows' eight-wave split (one set).
 //
 // Deliberately NOT here, because lifting them changes the register allocation of the kernels they are inlined into (compare the
 // device assembly before and after when trying again): the 8-channel GroupNorm + Swish conversion, the group sums -> scale / shift
@@ -111,6 +112,63 @@ __device__ __attribute__((always_inline)) inline void rt_gemm_rows(f32x4 (&acc)[
   for (; u0 < nunits; u0 += 2) {
     step(wr[0], F[0], F[1], u0, std::true_type{});
     step(wr[1], F[1], F[0], u0 + 1, std::true_type{});
+  }
+}
+
+// The same K loop (FULL) on ONE set of NPT + 2 fragments, for a wave that has a partner on its SIMD to issue under its LDS waits
+// and no registers for a second set: the fragment of padded row y is dead once output row y has taken its nine matrix
+// instructions, and is requested again there for unit u + 1 (rows NPT and NPT + 1 behind the last output row), so every fragment
+// is requested at least NPT - 2 output rows before its first use.  Per output pixel the order of units, dy and tiles is
+// rt_gemm_rows': the same bits.
+template <int RS, int PITCH, int NPT>
+__device__ __attribute__((always_inline)) inline void rt_gemm_rows_1buf(f32x4 (&acc)[3][NPT], u32x4 (&wr)[2][3][3], const unsigned short* __restrict__ wrow,
+                                                                       int nunits, const unsigned char* sm, int fb) {
+  int un = 0, dxn = 0, cbn = 0;                                 // the unit whose fragments are requested next
+  auto xaddr = [&]() {                                         // (selects, not branches)
+    const int o = fb + (dxn - 1) * RS + cbn * 64;
+    const bool more = un + 1 < nunits, wrap = dxn == 2;
+    un += more ? 1 : 0;
+    cbn += more && wrap ? 1 : 0;
+    dxn = more ? (wrap ? 0 : dxn + 1) : dxn;
+    return o;
+  };
+  auto fload = [&](bf16x8& f, int o, int r) { f = *(const bf16x8*)(sm + o + r * (PITCH * RS)); };
+  bf16x8 F[NPT + 2];
+  auto step = [&](u32x4 (&slot)[3][3], int u, auto guard) {
+    constexpr bool GUARD = decltype(guard)::value;
+    if (GUARD && u >= nunits) return;
+    const int o = xaddr();
+#pragma unroll
+    for (int y = 0; y < NPT; ++y) {
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+          acc[t][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[dy][t]), F[y + dy], acc[t][y], 0, 0, 0);
+      fload(F[y], o, y);
+      if (y == NPT - 1) {
+        fload(F[NPT], o, NPT);
+        fload(F[NPT + 1], o, NPT + 1);
+      }
+      __builtin_amdgcn_sched_barrier(0);                        // (pins the requests to their rows, as in rt_gemm_rows)
+    }
+    if (!GUARD || u + 2 < nunits) rt_wload9(slot, wrow, u + 2);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  {
+    const int o = xaddr();
+#pragma unroll
+    for (int r = 0; r < NPT + 2; ++r) fload(F[r], o, r);
+  }
+  __builtin_amdgcn_s_waitcnt(0x0F70);                           // vmcnt(0), as in rt_gemm_rows
+  int u0 = 0;
+  for (; u0 + 4 <= nunits; u0 += 2) {
+    step(wr[0], u0, std::false_type{});
+    step(wr[1], u0 + 1, std::false_type{});
+  }
+  for (; u0 < nunits; u0 += 2) {
+    step(wr[0], u0, std::true_type{});
+    step(wr[1], u0 + 1, std::true_type{});
   }
 }
 

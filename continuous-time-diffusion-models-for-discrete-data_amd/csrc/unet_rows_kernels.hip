@@ -10,11 +10,12 @@
 // bf16, accumulation is fp32 on the matrix cores, acc + bias + time bias + residual is rounded once; the output's own statistics
 // are taken on the fp32 value before that rounding, as conv_epilogue_rows takes them.
 //
-// Work split: one workgroup of four waves per (sample, band of 14 output rows); wave (cg, h) owns output channels
-// [48 cg, 48 cg + 48) x column half h: lane j of half h is padded column 16 h + j (pixel x = 16 h + j - 1; lanes off the image
-// compute values that are never stored).  A pixel tile is one output row of one column half: 14 row tiles x 3 channel tiles of
-// v_mfma_f32_16x16x32_bf16 (weights as the A operand: a lane's four results are four consecutive channels of one pixel), 168
-// accumulator registers, the shape of k_resblock_mid.
+// Work split: one workgroup per (sample, band of 14 output rows), of eight waves (ctdd_unet_conv_rows) or four
+// (ctdd_unet_conv_rows_w4); wave ([rh,] cg, h) owns output channels [48 cg, 48 cg + 48) x column half h [x rows 7 rh .. 7 rh + 6 of
+// the band]: lane j of half h is padded column 16 h + j (pixel x = 16 h + j - 1; lanes off the image compute values that are
+// never stored).  A pixel tile is one output row of one column half: 14 (7) row tiles x 3 channel tiles of
+// v_mfma_f32_16x16x32_bf16 (weights as the A operand: a lane's four results are four consecutive channels of one pixel), 168 (84)
+// accumulator registers; four waves are the shape of k_resblock_mid, one wave per SIMD, eight put two on every SIMD.
 //
 // LDS: one zero-bordered slab of at most 96 channels: (14 + 2) padded rows x 32 positions, a guard position at either end, 224 bytes
 // per position (192 + 32: sixteen consecutive positions at 224 bytes are conflict-free under the lane groups of ds_read_b128 for
@@ -32,20 +33,22 @@
 namespace ctdd {
 namespace {
 
-constexpr int CR_THREADS = 256, CR_N = 96, CR_BAND = 14, CR_PITCH = 32, CR_RS = 224, CR_MAXW = 28, CR_MAXC = 384, CR_PIECE = 96;
+constexpr int CR_N = 96, CR_BAND = 14, CR_PITCH = 32, CR_RS = 224, CR_MAXW = 28, CR_MAXC = 384, CR_PIECE = 96;
 constexpr int CR_SLAB = ((CR_BAND + 2) * CR_PITCH + 2) * CR_RS;  // 115 136
 constexpr int CR_SCALE = CR_SLAB;                                // float scale[CR_MAXC], shift[CR_MAXC]
 constexpr int CR_RED = CR_SCALE + 2 * CR_MAXC * 4;               // double [column half][channel][moment]
 constexpr int CR_TOTAL = CR_RED + 2 * CR_N * 2 * 8;
-constexpr int CR_FB = 12;                                        // pixels per thread in flight in the fill
-static_assert(CR_BAND * CR_MAXW * CR_RS <= CR_SLAB, "the output image reuses the slab");
+constexpr int CR_FB = 12;                                        // pixels per thread in flight in the fill (half of them with eight waves)
+constexpr int CR_CARRY = CR_BAND * CR_MAXW * CR_RS;               // eight waves: float4 [wave & 3][channel tile][s | q][lane] past the output image
+static_assert(CR_CARRY + 4 * 3 * 2 * 64 * 16 <= CR_SLAB, "the output image and the upper waves' partial sums reuse the slab");
 
 // bf16(swish(x * scale + shift)) of one piece (`pc` channels from `src`, the sample's first pixel at the piece's first channel,
 // pixel stride `cs` channels; channels [coff, coff + pc) of the concatenation) into columns [0, pc) of the slab: padded rows
 // rlo .. rhi of the band (image rows y0 - 1 + r), which are consecutive pixels in memory.  No barrier of its own.
+template <int THREADS, int FB>
 __device__ __attribute__((always_inline)) inline void cr_fill(unsigned char* sm, const unsigned short* __restrict__ src, int cs, int pc, int coff,
                                                              int y0, int H, int W) {
-  const int t = threadIdx.x, noct = pc >> 3, npl = CR_THREADS / noct;
+  const int t = threadIdx.x, noct = pc >> 3, npl = THREADS / noct;
   if (t >= noct * npl) return;
   const int oct = t % noct, pl = t / noct;
   const float* scale = (const float*)(sm + CR_SCALE) + coff + oct * 8;
@@ -58,17 +61,18 @@ __device__ __attribute__((always_inline)) inline void cr_fill(unsigned char* sm,
   const unsigned npix = (unsigned)((rhi - rlo + 1) * W), uW = (unsigned)W;
   const unsigned short* sp = src + (size_t)((y0 - 1 + rlo) * W) * cs + oct * 8;
   unsigned char* dst = sm + (1 + rlo * CR_PITCH + 1) * CR_RS + oct * 16;
-  // CR_FB pixels per thread in flight (a 96-channel piece of a 16-row band is 22 pixels per thread: two round trips to memory, not
-  // six); the loads are unconditional on a clamped pixel, only the LDS stores are predicated
-  for (unsigned p0 = (unsigned)pl; p0 < npix; p0 += (unsigned)(CR_FB * npl)) {
-    u32x4 u[CR_FB];
+  // FB pixels per thread in flight (a 96-channel piece of a 16-row band is 22 pixels per thread of 256 at 12 in flight, 11 per
+  // thread of 512 at 6, where 12 spill: two round trips to memory, not six); the loads are unconditional on a clamped pixel, only
+  // the LDS stores are predicated
+  for (unsigned p0 = (unsigned)pl; p0 < npix; p0 += (unsigned)(FB * npl)) {
+    u32x4 u[FB];
 #pragma unroll
-    for (int k = 0; k < CR_FB; ++k) {
+    for (int k = 0; k < FB; ++k) {
       const unsigned p = p0 + (unsigned)(k * npl);
       u[k] = *(const u32x4*)(sp + (size_t)(p < npix ? p : npix - 1) * cs);
     }
 #pragma unroll
-    for (int k = 0; k < CR_FB; ++k) {
+    for (int k = 0; k < FB; ++k) {
       const unsigned p = p0 + (unsigned)(k * npl);
       unsigned ow[4];
 #pragma unroll
@@ -87,35 +91,37 @@ __device__ __attribute__((always_inline)) inline void cr_fill(unsigned char* sm,
 }
 
 // The 1x1 segments: nsk 32-channel units of the raw sources, B fragments straight from global memory (lane j of tile y: pixel
-// (y0 + y, xc), rows and columns off the image clamped into it: computed, never stored), weight ring ws holding units 0 and 1.
-__device__ __attribute__((always_inline)) inline void cr_gemm_skip(f32x4 (&acc)[3][CR_BAND], u32x4 (&ws)[2][3], const unsigned short* __restrict__ wrow, int nsk,
+// (y0 + y, xc), y0 the wave's first row, rows and columns off the image clamped into it: computed, never stored), weight ring ws
+// holding units 0 and 1.
+template <int NPT>
+__device__ __attribute__((always_inline)) inline void cr_gemm_skip(f32x4 (&acc)[3][NPT], u32x4 (&ws)[2][3], const unsigned short* __restrict__ wrow, int nsk,
                                                                   const unsigned short* __restrict__ r1, const unsigned short* __restrict__ r2,
                                                                   int C1, int C2, int xc, int lq, int y0, int H, int W) {
   const int nc1 = C1 >> 5;
-  auto gload = [&](bf16x8 (&g)[CR_BAND], int u) {
+  auto gload = [&](bf16x8 (&g)[NPT], int u) {
     const int ue = u < nsk ? u : nsk - 1;                       // past the last unit: the last unit again
     const bool two = ue >= nc1;
     const unsigned char* base = (const unsigned char*)(two ? r2 : r1);
     const int cs = two ? C2 : C1, cb = (ue - (two ? nc1 : 0)) * 32 + lq * 8;
 #pragma unroll
-    for (int y = 0; y < CR_BAND; ++y) {
+    for (int y = 0; y < NPT; ++y) {
       const int ye = y0 + y < H ? y0 + y : H - 1;
       g[y] = *(const bf16x8*)(base + (unsigned)(((ye * W + xc) * cs + cb) * 2));
     }
   };
-  auto step = [&](u32x4 (&slot)[3], bf16x8 (&gc)[CR_BAND], bf16x8 (&gn)[CR_BAND], int u, auto guard) {
+  auto step = [&](u32x4 (&slot)[3], bf16x8 (&gc)[NPT], bf16x8 (&gn)[NPT], int u, auto guard) {
     constexpr bool GUARD = decltype(guard)::value;
     if (GUARD && u >= nsk) return;
     gload(gn, u + 1);
 #pragma unroll
-    for (int y = 0; y < CR_BAND; ++y)
+    for (int y = 0; y < NPT; ++y)
 #pragma unroll
       for (int t = 0; t < 3; ++t)
         acc[t][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, slot[t]), gc[y], acc[t][y], 0, 0, 0);
     if (!GUARD || u + 2 < nsk) rt_wload3(slot, wrow, u + 2);
     __builtin_amdgcn_sched_barrier(0);
   };
-  bf16x8 G[2][CR_BAND];
+  bf16x8 G[2][NPT];
   gload(G[0], 0);
   __builtin_amdgcn_s_waitcnt(0x0F70);                           // vmcnt(0): unit 0's fragments are needed at once
   int u0 = 0;
@@ -144,14 +150,23 @@ __device__ __attribute__((always_inline)) inline void cr_gemm_skip(f32x4 (&acc)[
 
 // SKIP: with 1x1 segments and no residual; otherwise a residual (or neither) and no 1x1 segments -- a ResBlock has one or the
 // other, and one instantiation holding both loses its register allocation (189 spilled registers in the K loops)
-template <bool SKIP>
-__global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_rows_args a) {
+//
+// WAVES: 4 -- wave (cg, hh) owns the band's 14 rows; 8 -- wave (rh, cg, hh) owns rows [7 rh, 7 rh + 7) of the band, 84 accumulator
+// registers, two waves per SIMD: waves wv and wv + 4 share a SIMD and a weight stream, and 512 threads carry the fill, the zero
+// fill and the store.  Per output pixel the order of units, dy and tiles is the same, and the statistics keep the 4-wave chain
+// (fp32 down a lane's column in row order, then fp64): the upper wave leaves its running fp32 sums in LDS and the lower wave
+// continues from them, so both give the same bits.
+template <bool SKIP, int WAVES>
+__global__ __launch_bounds__(WAVES * 64, 1) void k_conv_rows(const ctdd_conv_rows_args a) {
+  static_assert(WAVES == 4 || WAVES == 8, "one or two row halves");
+  constexpr int CR_THREADS = WAVES * 64, NPT = CR_BAND * 4 / WAVES;   // rows of a wave
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   const int t = threadIdx.x;
   const int H = a.H, W = a.W, HW = H * W, C1 = a.C1, C2 = a.C2, C = C1 + C2;
   const int nbands = (H + CR_BAND - 1) / CR_BAND;
   const int b = blockIdx.x / nbands, y0 = (blockIdx.x - b * nbands) * CR_BAND;
-  const int lane = t & 63, wv = t >> 6, lj = lane & 15, lq = lane >> 4, cg = wv >> 1, hh = wv & 1;
+  const int lane = t & 63, wv = t >> 6, lj = lane & 15, lq = lane >> 4, cg = WAVES == 8 ? (wv >> 1) & 1 : wv >> 1, hh = wv & 1;
+  const int rh = WAVES == 8 ? __builtin_amdgcn_readfirstlane(wv >> 2) : 0, yw = y0 + NPT * rh;  // the wave's row half, its first image row
   const int nu3 = 3 * (C >> 5), nsk = SKIP ? (a.RC1 + a.RC2) >> 5 : 0;
   const unsigned short* wrow = (const unsigned short*)a.w + (size_t)cg * ((size_t)nu3 * RT_UNIT + (size_t)nsk * 1536) + lane * 8;
   u32x4 wr[2][3][3];                                          // the weight ring (rt_gemm_rows)
@@ -184,12 +199,13 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
   __syncthreads();
   CR_STAMP(1);
 
-  const int fb = (1 + 16 * hh + lj) * CR_RS + lq * 16;        // this lane's position of padded row 0 + its k quarter
-  f32x4 acc[3][CR_BAND];
+  // this lane's position of the wave's padded row 0 + its k quarter
+  const int fb = (1 + 16 * hh + lj) * CR_RS + lq * 16 + rh * (NPT * CR_PITCH * CR_RS);
+  f32x4 acc[3][NPT];
 #pragma unroll
   for (int tt = 0; tt < 3; ++tt)
 #pragma unroll
-    for (int y = 0; y < CR_BAND; ++y) acc[tt][y] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+    for (int y = 0; y < NPT; ++y) acc[tt][y] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 
   // ---- the 3x3 segment, piece by piece (the slab never holds more than 96 channels)
   int ub = 0;                                                 // the piece's first unit in the stream
@@ -198,10 +214,13 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
     const unsigned short* src = (const unsigned short*)(s ? a.s2_bf16 : a.s1_bf16) + (size_t)b * HW * cs;
     for (int c0 = 0; c0 < cs; c0 += CR_PIECE) {
       const int pc = cs - c0 < CR_PIECE ? cs - c0 : CR_PIECE, nun = 3 * (pc >> 5);
-      cr_fill(sm, src + c0, cs, pc, coff + c0, y0, H, W);
+      cr_fill<CR_THREADS, CR_FB * 4 / WAVES>(sm, src + c0, cs, pc, coff + c0, y0, H, W);
       __syncthreads();
-      // (all 14 row tiles whatever H: rows past the image read zeros and are never stored)
-      rt_gemm_rows<true, CR_RS, CR_PITCH>(acc, wr, wrow + (size_t)ub * RT_UNIT, nun, sm, fb, CR_BAND);
+      // (all the wave's row tiles whatever H: rows past the image read zeros and are never stored)
+      if constexpr (WAVES == 8)                               // (a second fragment set does not fit 256 registers)
+        rt_gemm_rows_1buf<CR_RS, CR_PITCH>(acc, wr, wrow + (size_t)ub * RT_UNIT, nun, sm, fb);
+      else
+        rt_gemm_rows<true, CR_RS, CR_PITCH>(acc, wr, wrow + (size_t)ub * RT_UNIT, nun, sm, fb, NPT);
       __syncthreads();                                        // every wave has read its last fragment of this piece
       ub += nun;
       if (ub < nu3) {                                         // the next piece's first two units travel behind its fill (a piece has >= 3)
@@ -220,26 +239,29 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
     if (nsk > 1) rt_wload3(ws[1], wsk, 1);
     const int cs_ = 16 * hh + rt_again(lj), xc = cs_ < 1 ? 0 : (cs_ > W ? W - 1 : cs_ - 1);
     cr_gemm_skip(acc, ws, wsk, nsk, (const unsigned short*)a.r1_bf16 + (size_t)b * HW * a.RC1,
-                 (const unsigned short*)a.r2_bf16 + (size_t)b * HW * a.RC2, a.RC1, a.RC2, xc, lq, y0, H, W);
+                 (const unsigned short*)a.r2_bf16 + (size_t)b * HW * a.RC2, a.RC1, a.RC2, xc, lq, yw, H, W);
   }
   CR_STAMP(3);
 
   // ---- epilogue: acc + bias + time bias + residual in the accumulator layout, one rounding, into the [pixels][N] output image
   // (the slab is dead: every wave passed the barrier after the last piece); statistics on the fp32 value: fp32 over a lane's <= 14
-  // rows, fp64 across the 16 lanes of a column half, the two halves meet in LDS
+  // rows, fp64 across the 16 lanes of a column half, the two halves meet in LDS.  Eight waves: the upper wave leaves its fp32
+  // sums at CR_CARRY, the lower wave keeps its fp32 values (before the rounding) in acc and goes on from those sums after the barrier
   const int col = 16 * hh + rt_again(lj);
   const bool own = col >= 1 && col <= W;                       // this lane's column is a pixel
   const int x2 = own ? col - 1 : 0;
-  const int nrows = H - y0 < CR_BAND ? H - y0 : CR_BAND;
+  const int nrows = H - y0 < CR_BAND ? H - y0 : CR_BAND;       // of the band
+  const int nr = WAVES == 8 ? (nrows - NPT * rh < 0 ? 0 : (nrows - NPT * rh < NPT ? nrows - NPT * rh : NPT)) : nrows;   // of the wave
   double* red = (double*)(sm + CR_RED);
+  float4* carry = (float4*)(sm + CR_CARRY) + (wv & 3) * (3 * 2 * 64) + lane;
   // the residual of all three channel tiles, requested at once (one round trip to memory, not three)
-  uint2 rr[3][CR_BAND] = {};
+  uint2 rr[3][NPT] = {};
   const bool res = !SKIP && a.res_bf16;
   if (res) {
     const unsigned short* rp = (const unsigned short*)a.res_bf16 + (size_t)b * HW * CR_N + cg * 48 + lq * 4;
 #pragma unroll
-    for (int y = 0; y < CR_BAND; ++y) {
-      const unsigned short* rpy = rp + (size_t)(((y < nrows ? y0 + y : H - 1)) * W + x2) * CR_N;
+    for (int y = 0; y < NPT; ++y) {
+      const unsigned short* rpy = rp + (size_t)(((y < nr ? yw + y : H - 1)) * W + x2) * CR_N;
 #pragma unroll
       for (int tt = 0; tt < 3; ++tt) rr[tt][y] = *(const uint2*)(rpy + tt * 16);
     }
@@ -250,24 +272,60 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
     const float4 bv = *(const float4*)(a.bias + n);
     const float4 tb = a.tbias ? *(const float4*)(a.tbias + (size_t)b * a.tb_stride + n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const float add[4] = {bv.x + tb.x, bv.y + tb.y, bv.z + tb.z, bv.w + tb.w};
-    const uint2 (&r)[CR_BAND] = rr[tt];
+    const uint2 (&r)[NPT] = rr[tt];
     float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int y = 0; y < CR_BAND; ++y) {
-      if (y < nrows && own) {
+    for (int y = 0; y < NPT; ++y) {
+      if (y < nr && own) {
         const f32x4 v = acc[tt][y];
         float o[4] = {v[0] + add[0], v[1] + add[1], v[2] + add[2], v[3] + add[3]};
         if (res) {
           o[0] += __uint_as_float(r[y].x << 16); o[1] += __uint_as_float(r[y].x & 0xFFFF0000u);
           o[2] += __uint_as_float(r[y].y << 16); o[3] += __uint_as_float(r[y].y & 0xFFFF0000u);
         }
+        if (WAVES == 8 && rh) {
+          acc[tt][y] = (f32x4){o[0], o[1], o[2], o[3]};          // summed after the barrier, behind the upper wave's rows
+        } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { s[i] += o[i]; q[i] = fmaf(o[i], o[i], q[i]); }
-        *(uint2*)(sm + (y * W + x2) * CR_RS + n * 2) = make_uint2(rt_pack2(o[0], o[1]), rt_pack2(o[2], o[3]));
+          for (int i = 0; i < 4; ++i) { s[i] += o[i]; q[i] = fmaf(o[i], o[i], q[i]); }
+        }
+        *(uint2*)(sm + ((NPT * rh + y) * W + x2) * CR_RS + n * 2) = make_uint2(rt_pack2(o[0], o[1]), rt_pack2(o[2], o[3]));
       }
     }
 #ifndef CTDD_ROWS_STAMPS
     if (a.out_stats) {
+      if constexpr (WAVES == 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          double ds = (double)s[i], dq = (double)q[i];
+#pragma unroll
+          for (int m = 1; m < 16; m <<= 1) { ds += __shfl_xor(ds, m, WAVE); dq += __shfl_xor(dq, m, WAVE); }
+          if (lj == 0) { red[(hh * CR_N + n + i) * 2] = ds; red[(hh * CR_N + n + i) * 2 + 1] = dq; }
+        }
+      } else if (!rh) {
+        carry[(tt * 2) * 64] = make_float4(s[0], s[1], s[2], s[3]);
+        carry[(tt * 2 + 1) * 64] = make_float4(q[0], q[1], q[2], q[3]);
+      }
+    }
+#endif
+  }
+  __syncthreads();
+  CR_STAMP(4);
+#ifndef CTDD_ROWS_STAMPS
+  if (WAVES == 8 && rh && a.out_stats) {
+#pragma unroll
+    for (int tt = 0; tt < 3; ++tt) {
+      const float4 cs_ = carry[(tt * 2) * 64], cq = carry[(tt * 2 + 1) * 64];
+      float s[4] = {cs_.x, cs_.y, cs_.z, cs_.w}, q[4] = {cq.x, cq.y, cq.z, cq.w};
+#pragma unroll
+      for (int y = 0; y < NPT; ++y) {
+        if (y < nr && own) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { s[i] += acc[tt][y][i]; q[i] = fmaf(acc[tt][y][i], acc[tt][y][i], q[i]); }
+        }
+      }
+      // (the reduction above, again: shared through a lambda it moves the 4-wave kernels off their code)
+      const int n = cg * 48 + tt * 16 + lq * 4;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         double ds = (double)s[i], dq = (double)q[i];
@@ -276,10 +334,8 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
         if (lj == 0) { red[(hh * CR_N + n + i) * 2] = ds; red[(hh * CR_N + n + i) * 2 + 1] = dq; }
       }
     }
-#endif
   }
-  __syncthreads();
-  CR_STAMP(4);
+#endif
   {
     constexpr int npc = CR_N / 8;
     unsigned short* out = (unsigned short*)a.out_bf16 + ((size_t)b * HW + (size_t)y0 * W) * CR_N;   // the band's pixels are consecutive
@@ -288,7 +344,8 @@ __global__ __launch_bounds__(CR_THREADS, 1) void k_conv_rows(const ctdd_conv_row
       *(uint4*)(out + (size_t)p * CR_N + c0) = *(const uint4*)(sm + p * CR_RS + c0 * 2);
     }
 #ifndef CTDD_ROWS_STAMPS
-    // one fp64 atomic per (sample, channel, moment) and workgroup
+    // one fp64 atomic per (sample, channel, moment) and workgroup (eight waves: red was written after the barrier above)
+    if (WAVES == 8) __syncthreads();
     if (a.out_stats && t < 2 * CR_N) atomicAdd(a.out_stats + (size_t)b * CR_N * 2 + t, red[t] + red[2 * CR_N + t]);
 #endif
   }
@@ -303,7 +360,8 @@ using namespace ctdd;
 // Refuses (non-zero, ctdd_last_error set, nothing launched) what the kernel does not take: fp32 mode, W > 28 (the slab's pitch of
 // 32 positions), N != 96, channel counts that are not multiples of 32 or exceed 384 in all, groups that do not divide the
 // channels, a GroupNorm source without statistics, 1x1 segments together with a residual, tensors that are not 16-byte aligned.
-extern "C" int ctdd_unet_conv_rows(const void* args_, int f32, void* stream) {
+template <int WAVES>
+static int launch_conv_rows(const void* args_, int f32, void* stream) {
   CTDD_REQUIRE(args_, CTDD_EINVAL, "ctdd_unet_conv_rows: null arguments");
   const ctdd_conv_rows_args& a = *(const ctdd_conv_rows_args*)args_;
   CTDD_REQUIRE(f32 == 0, CTDD_ERANGE, "ctdd_unet_conv_rows: bf16 inference only (the fp32 mode keeps GroupNorm and convolution apart)");
@@ -327,11 +385,16 @@ extern "C" int ctdd_unet_conv_rows(const void* args_, int f32, void* stream) {
   CTDD_REQUIRE(!(a.RC1 > 0 && a.res_bf16), CTDD_EINVAL, "ctdd_unet_conv_rows: 1x1 segments and a residual in one call");
   static bool attr_done[2][16] = {};
   if (a.RC1 > 0) {
-    ensure_lds_ceiling((const void*)k_conv_rows<true>, attr_done[1]);
-    hipLaunchKernelGGL(k_conv_rows<true>, dim3(a.B * nbands), dim3(CR_THREADS), (size_t)CR_TOTAL, (hipStream_t)stream, a);
+    ensure_lds_ceiling((const void*)k_conv_rows<true, WAVES>, attr_done[1]);
+    hipLaunchKernelGGL((k_conv_rows<true, WAVES>), dim3(a.B * nbands), dim3(WAVES * 64), (size_t)CR_TOTAL, (hipStream_t)stream, a);
   } else {
-    ensure_lds_ceiling((const void*)k_conv_rows<false>, attr_done[0]);
-    hipLaunchKernelGGL(k_conv_rows<false>, dim3(a.B * nbands), dim3(CR_THREADS), (size_t)CR_TOTAL, (hipStream_t)stream, a);
+    ensure_lds_ceiling((const void*)k_conv_rows<false, WAVES>, attr_done[0]);
+    hipLaunchKernelGGL((k_conv_rows<false, WAVES>), dim3(a.B * nbands), dim3(WAVES * 64), (size_t)CR_TOTAL, (hipStream_t)stream, a);
   }
   return finish_launch("k_conv_rows");
 }
+
+// eight waves per workgroup
+extern "C" int ctdd_unet_conv_rows(const void* args_, int f32, void* stream) { return launch_conv_rows<8>(args_, f32, stream); }
+// the same launch on four waves, each owning the band's 14 rows: bit-identical results
+extern "C" int ctdd_unet_conv_rows_w4(const void* args_, int f32, void* stream) { return launch_conv_rows<4>(args_, f32, stream); }

@@ -90,7 +90,7 @@ def _lib():
                            ("ctdd_unet_time", [_P, _P, _P, _I, _P, _P]), ("ctdd_unet_time_uniform", [_P, _P, _P, _I, _P, _P]),
                            ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_attention_block", [_P, _I, _P]),
                            ("ctdd_unet_resblock_small", [_P, _I, _P]),
-                           ("ctdd_unet_resblock_mid", [_P, _I, _P]), ("ctdd_unet_conv_rows", [_P, _I, _P]),
+                           ("ctdd_unet_resblock_mid", [_P, _I, _P]), ("ctdd_unet_conv_rows", [_P, _I, _P]), ("ctdd_unet_conv_rows_w4", [_P, _I, _P]),
                            ("ctdd_unet_conv_rows_head", [_P, _I, _P]),
                            ("ctdd_unet_logistic_head", [_P, _P])):
             fn = getattr(lib, name)
@@ -206,7 +206,9 @@ def pack_conv_rows_weights(w, cs, rcs):
 # default of cfg.model.conv_rows_min_wgs (UNetEngine._runs_conv_rows).  Graph replay of one MNIST plan, pairs | ctdd_unet_conv_rows:
 # batch 16 (32 workgroups) 1157 | 1302 us, batch 32 (64) 1219 | 1305 us, batch 40 (80) 1264-1288 | 1303-1305 us, batch 48 (96)
 # 1471-1485 | 1329-1331 us, batch 56 (112) 1519-1523 | 1344-1346 us, batch 64 (128) 1538 | 1381 us, batch 128 (256) 1710 | 1549 us
-# (tools/conv_table.py): the smallest measured grid at which the one launch wins
+# (tools/conv_table.py): the smallest measured grid at which the one launch wins.  Taken with four waves per
+# workgroup; with eight (cfg.model.conv_rows_waves, the default) 1247 | 1248 | 1251 | 1276 | 1306 | 1313 us at batch 16 | 32 | 40 | 48 | 56 | 64
+# against the pairs' 1146 | 1206 | 1255 | 1476 | 1507 | 1529 us: 80 workgroups are a tie within the repeats, the threshold stays
 CONV_ROWS_MIN_WGS = 96
 
 
@@ -540,7 +542,11 @@ class _PlanBuilder:
         a.B, a.H, a.W, a.N = B, Hc, Wc, N
         self.keep.extend([g, b_, w, bias, a])
         Ktot = w.shape[1]
-        self.launch(lib.ctdd_unet_conv_rows, C.byref(a), 0, label=f"{Hc}x{Wc} K={Ktot} N={N} gn+conv rows C={cs} raw={rcs}",
+        # cfg.model.conv_rows_waves: 8 (default) waves per workgroup, or 4: the same bits from the kernel's 4-wave work split
+        waves = int(getattr(eng.cfg.model, "conv_rows_waves", 8))
+        if waves not in (4, 8):
+            raise ValueError(f"cfg.model.conv_rows_waves = {waves}: 4 or 8")
+        self.launch(lib.ctdd_unet_conv_rows if waves == 8 else lib.ctdd_unet_conv_rows_w4, C.byref(a), 0, label=f"{Hc}x{Wc} K={Ktot} N={N} gn+conv rows C={cs} raw={rcs}",
                     flops=2 * B * Hc * Wc * N * Ktot)
 
     def conv_rows_head(self, src, norm, oc, logits):

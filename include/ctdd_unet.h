@@ -136,7 +136,7 @@ typedef struct {
  * the ctdd_unet_gn_apply + ctdd_unet_conv_ring / ctdd_unet_conv_patch pair without the activated tensor in memory; scale / shift come
  * from st1 / st2 as in ctdd_unet_gn_apply, the output's sums (taken before the bf16 rounding) are added into out_stats
  * by one fp64 atomic per band (bit-reproducible from a zeroed buffer for H <= 28, two bands; beyond that up to the order of the adds).  One
- * workgroup per (sample, band of 14 output rows).  1 <= W <= 28, any H, N = 96, C1, C2, RC1, RC2 multiples of 32 (C2, RC1, RC2 may
+ * workgroup of eight waves per (sample, band of 14 output rows): a wave owns 7 rows x 48 channels x a column half.  1 <= W <= 28, any H, N = 96, C1, C2, RC1, RC2 multiples of 32 (C2, RC1, RC2 may
  * be 0; RC2 > 0 needs RC1 > 0; <= 384 channels per concatenation), G divides C1 + C2, every GroupNorm source with statistics,
  * 1x1 segments or a residual but not both (a ResBlock has one of them), 16-byte aligned tensors, f32 must be 0.  Anything else: CTDD_ERANGE / CTDD_EINVAL, nothing launched.
  * Weights (ctdd/unet_engine.py: pack_conv_rows_weights = pack_row_tile_weights, the same order in two streams): two streams (output channels [48 s, 48 s + 48)), one after the other, each a
@@ -145,6 +145,10 @@ typedef struct {
  * for tile = 0, 1, 2: the fragment of tap (dy, dx) on that block (27 (C1 + C2) / 32 fragments); then for each raw source, for each
  * 32-channel block of it, for tile = 0, 1, 2: the fragment of the 1x1 segment (3 (RC1 + RC2) / 32 fragments).  Nothing is padded. */
 int ctdd_unet_conv_rows(const void* conv_rows_args, int f32, void* stream);
+/* The same launch, same arguments, weights and refusals, on four waves per workgroup (a wave owns the band's 14 rows x 48 channels x
+ * a column half): output and out_stats are bit-identical to ctdd_unet_conv_rows' (the sums keep one order: fp32 down a lane's
+ * column in row order, then fp64), so either stands in for the other (cfg.model.conv_rows_waves = 4 | 8). */
+int ctdd_unet_conv_rows_w4(const void* conv_rows_args, int f32, void* stream);
 /* The output head of such a level on the same argument struct (csrc/unet_head_kernels.hip): GroupNorm + Swish + 3x3 convolution
  * into N output channels in one launch,
  *   out[b][y][x][0..N) = bf16(conv3x3(bf16(swish(GN(s1)))) + bias)
