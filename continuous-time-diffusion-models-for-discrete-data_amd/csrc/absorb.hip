@@ -1,6 +1,7 @@
 // absorb.hip -- absorbing-state ("masked") diffusion: forward noising (ctdd_absorb_noise), the negative ELBO with its logit
-// gradient (ctdd_absorb_elbo_loss) and one reverse step (ctdd_absorb_step).  include/ctdd_absorb.h states the formulas and the
-// Philox counter layouts.
+// gradient (ctdd_absorb_elbo_loss), one reverse step (ctdd_absorb_step) and the two halves of a confidence-ordered step: a candidate
+// and a score per masked row (ctdd_absorb_propose, the step's layout and pick), then a per-sample top-k of the scores by radix select
+// (ctdd_absorb_commit).  include/ctdd_absorb.h states the formulas, the Philox counter layouts and the key that orders the scores.
 //
 // Loss and step are row softmaxes over a row that fits in registers.  A row is owned by a group of LPR lanes of one wave, lane j of
 // the group holding the PER consecutive states PER j .. PER j + PER - 1 (float4 loads when S % 4 == 0); 64 / LPR rows per wave,
@@ -180,23 +181,12 @@ struct AbsorbStepArgs {
   int32_t* changed;
 };
 
+// The new state of a row from the registers of its group (lane j holds v, the states PER j ..): argmax_{s != m} with the lowest
+// index on ties if `greedy`, else the first s whose running sum of e[s] = exp(l[s] - mx) exceeds u1 z.  The step and the proposal
+// share it, so the two take the same state from the same u1.  mx: the row maximum; z: the sum of the weights (draw mode only).
 template <int LPR, int PER>
-__global__ __launch_bounds__(64 * AWV) void k_absorb_step(const AbsorbStepArgs a) {
-  __shared__ int red[AWV];
-  constexpr int RPW = WAVE / LPR;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane % LPR, s0 = j * PER, S = a.S, m = a.mask_state;
-  const int64_t row = ((int64_t)blockIdx.x * AWV + wave) * RPW + lane / LPR;
-  const bool in = row < a.rows, greedy = (a.flags & CTDD_ABSORB_ARGMAX) != 0;
-  const int xo = in ? a.x[row] : 0;
-  bool need = in && xo == m;
-  float u1 = 0.0f;
-  if (need && !greedy) {
-    const u4 r = philox_row(a.seed, a.offset, (uint64_t)row, 0u);
-    need = u01(r.x) < a.p;
-    u1 = u01(r.y);
-  }
-  float v[PER];
-  absorb_load<PER>(a.logits + (size_t)(in ? row : 0) * S, S, s0, m, a.vec, need, v);
+__device__ inline int absorb_pick(const float (&v)[PER], int S, int m, int j, bool greedy, float u1, float& mx_out, float& z_out) {
+  const int s0 = j * PER;
   float mx = -INFINITY;
   int bi = S;                                                   // the lane's first index of its maximum
 #pragma unroll
@@ -211,6 +201,7 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_step(const AbsorbStepArgs a
       if (oi < S && (bi >= S || ov > mx || (ov == mx && oi < bi))) { mx = ov; bi = oi; }
     }
     pick = bi;
+    z_out = 0.0f;
   } else {
     mx = grp_max<LPR>(mx);
     if (!(mx > -INFINITY)) mx = 0.0f;
@@ -231,8 +222,32 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_step(const AbsorbStepArgs a
     for (int k = 0; k < PER; ++k)
       if (s0 + k < S && before + c[k] <= target) ++cnt;
     pick = grp_sum_i<LPR>(cnt);
+    z_out = total;
   }
+  mx_out = mx;
   if (pick >= S || pick == m || pick < 0) pick = (m == S - 1) ? S - 2 : S - 1;   // target == total after rounding: the last real state
+  return pick;
+}
+
+template <int LPR, int PER>
+__global__ __launch_bounds__(64 * AWV) void k_absorb_step(const AbsorbStepArgs a) {
+  __shared__ int red[AWV];
+  constexpr int RPW = WAVE / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane % LPR, s0 = j * PER, S = a.S, m = a.mask_state;
+  const int64_t row = ((int64_t)blockIdx.x * AWV + wave) * RPW + lane / LPR;
+  const bool in = row < a.rows, greedy = (a.flags & CTDD_ABSORB_ARGMAX) != 0;
+  const int xo = in ? a.x[row] : 0;
+  bool need = in && xo == m;
+  float u1 = 0.0f;
+  if (need && !greedy) {
+    const u4 r = philox_row(a.seed, a.offset, (uint64_t)row, 0u);
+    need = u01(r.x) < a.p;
+    u1 = u01(r.y);
+  }
+  float v[PER];
+  absorb_load<PER>(a.logits + (size_t)(in ? row : 0) * S, S, s0, m, a.vec, need, v);
+  float mx, z;
+  const int pick = absorb_pick<LPR, PER>(v, S, m, j, greedy, u1, mx, z);
   const bool left = need;
   if (in && j == 0) a.out_x[row] = left ? pick : xo;
   if (a.changed) {
@@ -248,6 +263,159 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_step(const AbsorbStepArgs a
       if (tot) atomicAdd(a.changed, tot);
     }
   }
+}
+
+// ---------------------------------------------------------------- confidence-ordered unmasking: candidate + score of every masked row
+struct AbsorbProposeArgs {
+  const float* logits;
+  const int32_t* x;
+  int64_t rows;
+  int S, mask_state;
+  int vec;
+  float noise;
+  uint32_t flags;
+  uint64_t seed, offset;
+  int32_t* out_cand;
+  float* out_score;
+};
+
+template <int LPR, int PER>
+__global__ __launch_bounds__(64 * AWV) void k_absorb_propose(const AbsorbProposeArgs a) {
+  constexpr int RPW = WAVE / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane % LPR, s0 = j * PER, S = a.S, m = a.mask_state;
+  const int64_t row = ((int64_t)blockIdx.x * AWV + wave) * RPW + lane / LPR;
+  const bool in = row < a.rows, greedy = (a.flags & CTDD_ABSORB_ARGMAX) != 0;
+  const bool need = in && a.x[in ? row : 0] == m;
+  float u1 = 0.0f, u2 = 0.5f;
+  if (need && (!greedy || a.noise != 0.0f)) {
+    const u4 r = philox_row(a.seed, a.offset, (uint64_t)row, 0u);  // (r.x is the step's unmasking coin: unused here)
+    u1 = u01(r.y);
+    u2 = u01(r.z);
+  }
+  float v[PER];
+  absorb_load<PER>(a.logits + (size_t)(in ? row : 0) * S, S, s0, m, a.vec, need, v);
+  float mx, z;
+  const int pick = absorb_pick<LPR, PER>(v, S, m, j, greedy, u1, mx, z);
+  if (greedy) {                                                 // the draw's scan has summed the weights already
+    z = 0.0f;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) z += expf(v[k] - mx);
+    z = grp_sum<LPR>(z);
+  }
+  float lc = 0.0f;                                              // l[cand] - mx: one lane of the group holds it
+#pragma unroll
+  for (int k = 0; k < PER; ++k)
+    if (s0 + k == pick) lc = v[k] - mx;
+  lc = grp_sum<LPR>(lc);
+  float score = lc - logf(z);
+  if (a.noise != 0.0f) score += a.noise * (-logf(-logf(u2)));
+  if (need && j == 0) {
+    a.out_cand[row] = pick;
+    a.out_score[row] = score;
+  }
+}
+
+// ---------------------------------------------------------------- confidence-ordered unmasking: per-sample top-k of the scores
+// order-preserving key of a score (include/ctdd_absorb.h): NaN 0, -0 as +0, b | 0x80000000 for b >= 0, ~b for b < 0
+__device__ inline uint32_t score_key(float s) {
+  uint32_t b = __float_as_uint(s);
+  if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0u;
+  if (b == 0x80000000u) b = 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+struct AbsorbCommitArgs {
+  const int32_t *x, *cand;
+  const float* score;
+  int D, mask_state;
+  float p;
+  const int32_t* counts;
+  int32_t* out_x;
+  int32_t* changed;
+};
+
+// One workgroup (256 threads) per sample.  Radix select, most significant digit first: a pass histograms the digit of the masked
+// rows whose key agrees with the digits found so far; wave 0 scans the 256 bins from the top (lane L owns the bins 255 - 4 L ..
+// 252 - 4 L) for the bin that holds the need-th largest key.  After four passes `prefix` is that key and `need` the number of rows at
+// it that are still wanted.  The last pass walks d in ascending chunks of 256: a ballot per wave, the waves' counts through LDS
+// (two buffers, so one barrier a chunk) and a running base put every row at the threshold key in its ascending-d position.
+__global__ __launch_bounds__(64 * AWV) void k_absorb_commit(const AbsorbCommitArgs a) {
+  static_assert(AWV == 4, "256 threads: one per histogram bin");
+  __shared__ int hist[256];
+  __shared__ int sel[3];                                        // digit, rows still wanted inside it, k_n
+  __shared__ int wcnt[2][AWV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, D = a.D, m = a.mask_state;
+  const size_t base = (size_t)blockIdx.x * D;
+  const int32_t* __restrict__ x = a.x + base;
+  const float* __restrict__ sc = a.score + base;
+  uint32_t prefix = 0u;
+  int need = 0, kn = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    hist[tid] = 0;
+    __syncthreads();
+    for (int d = tid; d < D; d += 64 * AWV)
+      if (x[d] == m) {
+        const uint32_t key = score_key(sc[d]);
+        if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
+      }
+    __syncthreads();
+    if (wave == 0) {
+      int h[4], s4 = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) { h[c] = hist[255 - 4 * lane - c]; s4 += h[c]; }
+      int incl = s4;                                            // inclusive scan from the top bin down
+#pragma unroll
+      for (int o = 1; o < WAVE; o <<= 1) {
+        const int up = __shfl_up(incl, o, WAVE);
+        if (lane >= o) incl += up;
+      }
+      if (pass == 0) {                                          // the histogram's total is M_n
+        const int M = __shfl(incl, WAVE - 1, WAVE);
+        need = a.counts ? min(M, max(0, a.counts[blockIdx.x])) : min(M, (int)ceil((double)a.p * (double)M));
+        if (lane == 0) sel[2] = need;
+      }
+      int cum = incl - s4, digit = -1, rest = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (digit < 0 && cum < need && need <= cum + h[c]) { digit = 255 - 4 * lane - c; rest = need - cum; }
+        cum += h[c];
+      }
+      if (digit >= 0) { sel[0] = digit; sel[1] = rest; }         // one lane: the bins' running count passes `need` once
+    }
+    __syncthreads();
+    kn = sel[2];
+    if (kn == 0) break;                                         // (uniform) nothing to commit: every masked row stays masked
+    prefix = (prefix << 8) | (uint32_t)sel[0];
+    need = sel[1];
+  }
+  if (kn == 0) { prefix = 0xFFFFFFFFu; need = 0; }              // above every key
+  int seen = 0;                                                 // rows at the threshold key in the chunks before this one
+  for (int c0 = 0, buf = 0; c0 < D; c0 += 64 * AWV, buf ^= 1) {
+    const int d = c0 + tid;
+    int xo = 0;
+    uint32_t key = 0u;
+    bool masked = false;
+    if (d < D) {
+      xo = x[d];
+      masked = xo == m;
+      if (masked) key = score_key(sc[d]);
+    }
+    const bool tie = masked && key == prefix;
+    const unsigned long long bal = __ballot(tie);
+    if (lane == 0) wcnt[buf][wave] = __popcll(bal);
+    __syncthreads();
+    int before = seen + __popcll(bal & ((1ull << lane) - 1ull)), all = 0;
+#pragma unroll
+    for (int w = 0; w < AWV; ++w) {
+      const int c = wcnt[buf][w];
+      if (w < wave) before += c;
+      all += c;
+    }
+    seen += all;
+    if (d < D) a.out_x[base + d] = (masked && (key > prefix || (tie && before < need))) ? a.cand[base + d] : xo;
+  }
+  if (tid == 0 && a.changed && kn > 0) atomicAdd(a.changed, kn);
 }
 
 // (LPR, PER) of a row width; rows per workgroup = AWV * 64 / LPR
@@ -309,4 +477,32 @@ extern "C" int ctdd_absorb_step(const float* logits, const int32_t* x, int N, in
   AbsorbStepArgs a = {logits, x, rows, S, mask_state, S % 4 == 0 && aligned16(logits), p_unmask, flags, seed, offset, out_x, out_changed};
   ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_step<LPR, PER>), dim3((unsigned)blocks), dim3(64 * AWV), 0, (hipStream_t)stream, a));
   return finish_launch("k_absorb_step");
+}
+
+extern "C" int ctdd_absorb_propose(const float* logits, const int32_t* x, int N, int D, int S, int mask_state, float noise, uint32_t flags,
+                                   uint64_t seed, uint64_t offset, int32_t* out_cand, float* out_score, void* stream) {
+  CTDD_REQUIRE(logits && x && out_cand && out_score, CTDD_EINVAL, "absorb propose: null buffer");
+  CTDD_REQUIRE(N > 0 && D > 0 && S >= 2 && S <= CTDD_MAX_S && mask_state >= 0 && mask_state < S, CTDD_ERANGE,
+               "absorb propose: N=%d D=%d S=%d mask_state=%d (2 <= S <= %d, 0 <= mask_state < S)", N, D, S, mask_state, CTDD_MAX_S);
+  CTDD_REQUIRE((flags & ~CTDD_ABSORB_ARGMAX) == 0, CTDD_EINVAL, "absorb propose: unknown flags %u", flags);
+  CTDD_REQUIRE(noise == noise && noise - noise == 0.0f, CTDD_ERANGE, "absorb propose: noise=%g is not finite", (double)noise);
+  const int64_t rows = (int64_t)N * D;
+  const int rpb = AWV * WAVE / absorb_lpr(S);
+  const int64_t blocks = (rows + rpb - 1) / rpb;
+  CTDD_REQUIRE(blocks <= INT32_MAX, CTDD_ERANGE, "absorb propose: N D = %lld rows", (long long)rows);
+  AbsorbProposeArgs a = {logits, x, rows, S, mask_state, S % 4 == 0 && aligned16(logits), noise, flags, seed, offset, out_cand, out_score};
+  ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_propose<LPR, PER>), dim3((unsigned)blocks), dim3(64 * AWV), 0, (hipStream_t)stream, a));
+  return finish_launch("k_absorb_propose");
+}
+
+extern "C" int ctdd_absorb_commit(const int32_t* x, const int32_t* cand, const float* score, int N, int D, int mask_state, float p_unmask,
+                                  const int32_t* counts, int32_t* out_x, int32_t* out_changed, void* stream) {
+  CTDD_REQUIRE(x && cand && score && out_x, CTDD_EINVAL, "absorb commit: null buffer");
+  CTDD_REQUIRE(out_x != x, CTDD_EINVAL, "absorb commit: out_x aliases x");
+  CTDD_REQUIRE(N > 0 && D > 0 && D <= (1 << 30) && mask_state >= 0, CTDD_ERANGE, "absorb commit: N=%d D=%d mask_state=%d (1 <= D <= 2^30)", N, D,
+               mask_state);
+  CTDD_REQUIRE(counts || (p_unmask >= 0.0f && p_unmask <= 1.0f), CTDD_ERANGE, "absorb commit: p_unmask=%g outside [0, 1]", (double)p_unmask);
+  AbsorbCommitArgs a = {x, cand, score, D, mask_state, p_unmask, counts, out_x, out_changed};
+  hipLaunchKernelGGL(k_absorb_commit, dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, a);
+  return finish_launch("k_absorb_commit");
 }

@@ -87,6 +87,8 @@ _SIGS = {
     "ctdd_absorb_scratch_bytes": ([], _I64),
     "ctdd_absorb_elbo_loss": ([_P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P], _I),
     "ctdd_absorb_step": ([_P, _P, _I, _I, _I, _I, _F, _U32, _U64, _U64, _P, _P, _P], _I),
+    "ctdd_absorb_propose": ([_P, _P, _I, _I, _I, _I, _F, _U32, _U64, _U64, _P, _P, _P], _I),
+    "ctdd_absorb_commit": ([_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P], _I),
 }
 UNET_EXPORTS = ("ctdd_unet_conv", "ctdd_unet_conv_patch", "ctdd_unet_conv_res", "ctdd_unet_conv_ring", "ctdd_unet_conv_up_phases", "ctdd_unet_upsample2x", "ctdd_unet_first_conv", "ctdd_unet_gn_apply", "ctdd_unet_gn_onepass", "ctdd_unet_channel_stats",
                 "ctdd_unet_time", "ctdd_unet_time_uniform", "ctdd_unet_attention", "ctdd_unet_logistic_head", "ctdd_unet_resblock_small",
@@ -615,6 +617,44 @@ def absorb_step(logits, x, mask_state, p_unmask, flags=0, seed=0, offset=0, out=
     _count("ctdd_absorb_step")
     _check(load().ctdd_absorb_step(*ptrs, N, D, S, int(mask_state), float(p_unmask), int(flags), int(seed), int(offset), _ptr(out, i32, "out"),
                                    _ptr(changed, i32, "changed"), _stream()), "ctdd_absorb_step")
+    return out
+
+
+def absorb_propose(logits, x, mask_state, noise=0.0, flags=0, seed=0, offset=0):
+    """(cand int32 (N, D), score fp32 (N, D)) of the rows of x at mask_state (ctdd_absorb_propose): the state ctdd_absorb_step
+    would draw for the same (seed, offset) (flags = ABSORB_ARGMAX: the argmax) and its log-probability under the softmax over
+    s != mask_state, plus noise times a standard Gumbel variate when noise != 0.  Entries of the other rows are not written."""
+    N, D, S = _absorb_shapes("absorb_propose", logits, (("x", x),))
+    ptrs = (_ptr(logits, f32, "logits"), _ptr(x, i32, "x"))
+    cand, score = torch.empty_like(x), torch.empty(x.shape, dtype=f32, device=x.device)
+    _count("ctdd_absorb_propose")
+    _check(load().ctdd_absorb_propose(*ptrs, N, D, S, int(mask_state), float(noise), int(flags), int(seed), int(offset), _ptr(cand),
+                                      _ptr(score), _stream()), "ctdd_absorb_propose")
+    return cand, score
+
+
+def absorb_commit(x, cand, score, mask_state, p_unmask=None, counts=None, out=None, changed=None):
+    """x with, per sample n, the k_n rows at mask_state that have the largest score set to cand (ctdd_absorb_commit; ties in
+    ascending d, NaN below -inf).  Exactly one of p_unmask (k_n = ceil(p_unmask M_n) over the sample's M_n masked rows) and counts
+    (int32 (N,) on the device, k_n = counts[n] clamped to [0, M_n]).  changed: int32[1] device counter, incremented by sum k_n."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise CtddError(f"absorb_commit: x {tuple(getattr(x, 'shape', ()))}, expected (N, D)")
+    N, D = (int(v) for v in x.shape)
+    for name, t in (("cand", cand), ("score", score)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (N, D):
+            raise CtddError(f"absorb_commit: {name} {tuple(getattr(t, 'shape', ()))} against x {(N, D)}")
+    if (p_unmask is None) == (counts is None):
+        raise CtddError("absorb_commit: exactly one of p_unmask and counts")
+    if counts is not None and (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (N,)):
+        raise CtddError(f"absorb_commit: counts {tuple(getattr(counts, 'shape', ()))}, expected {(N,)}")
+    ptrs = (_ptr(x, i32, "x"), _ptr(cand, i32, "cand"), _ptr(score, f32, "score"))
+    if out is None:
+        out = torch.empty_like(x)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (N, D):
+        raise CtddError(f"absorb_commit: out {tuple(getattr(out, 'shape', ()))} against x {(N, D)}")
+    _count("ctdd_absorb_commit")
+    _check(load().ctdd_absorb_commit(*ptrs, N, D, int(mask_state), 0.0 if p_unmask is None else float(p_unmask), _ptr(counts, i32, "counts"),
+                                     _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream()), "ctdd_absorb_commit")
     return out
 
 

@@ -806,6 +806,10 @@ class AbsorbingLeap(_Conditioned):
         x = torch.where(held.to(dev), xk.to(dev), torch.full((), m, dtype=torch.int32, device=dev))
         return self._loop(model, x.contiguous())[0]
 
+    def _advance(self, logits, x, m, p, key, i, changed):
+        """Step i of the grid on the network's logits: every masked entry unmasks with probability p."""
+        return native.absorb_step(logits, x, m, p, 0, key, i, changed=changed)
+
     def _loop(self, model, x):
         pr = self._process(model)
         m, N, dev, key = pr.mask_state, x.shape[0], x.device, self._key()
@@ -818,7 +822,36 @@ class AbsorbingLeap(_Conditioned):
         with torch.no_grad(), borrow_engine_output(model, bf16_logits=False, uniform_time=True):
             for i in range(self.num_steps):
                 logits = _GridSampler._net_logits(model, x, _GridSampler._t_ones(t32, i, N, dev))
-                x = native.absorb_step(logits, x, m, p[i], 0, key, i, changed=changed[i:i + 1])
+                x = self._advance(logits, x, m, p[i], key, i, changed[i:i + 1])
             logits = _GridSampler._net_logits(model, x, torch.full((N,), float(np.float32(self.min_t)), device=dev))
             x = native.absorb_step(logits, x, m, 1.0, native.ABSORB_ARGMAX, key, self.num_steps, changed=changed[self.num_steps:])
         return x.cpu().numpy().astype(int), (changed[:self.num_steps].cpu().numpy() / N).tolist()
+
+
+@sampling_utils.register_sampler
+class AbsorbingConfidence(AbsorbingLeap):
+    """Confidence-ordered unmasking for the absorbing-state process (MaskGIT-style decoding; not in the reference).  Grid, rules,
+    seed, rank_stream, `sample` and `inpaint` are AbsorbingLeap's, and so is the host-side fp64 p of every step -- but p is spent as a
+    count, not as a coin per row: a step proposes a candidate for every masked entry (ctdd_absorb_propose: the state the plain step
+    would draw, or the argmax, with its log-probability as the score) and commits, per sample, the ceil(p M_n) candidates with the
+    largest score among the sample's own M_n masked entries (ctdd_absorb_commit).  One network forward and two launches per step,
+    no host sync inside the loop.  Held entries of `inpaint` are not masked: they are neither counted nor moved.
+
+    cfg.sampler.conf_temp (default 1.0): step i of num_steps adds conf_temp (1 - (i + 1) / num_steps) times a standard Gumbel variate
+    to the scores, an annealed randomisation of the ranking (0 ranks by the log-probability alone).  cfg.sampler.candidate: "sample"
+    (default) or "argmax".  The closing forward at min_t with its argmax step is the parent's."""
+
+    CANDIDATES = ("sample", "argmax")
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        self.conf_temp = float(getattr(cfg.sampler, "conf_temp", 1.0))
+        self.candidate = getattr(cfg.sampler, "candidate", "sample")
+        if self.candidate not in self.CANDIDATES:
+            raise ValueError(f"sampler.candidate must be one of {self.CANDIDATES}, got {self.candidate!r}")
+
+    def _advance(self, logits, x, m, p, key, i, changed):
+        """Step i of the grid: a candidate and a score for every masked entry, then per sample the ceil(p M_n) best-scored commit."""
+        flags = native.ABSORB_ARGMAX if self.candidate == "argmax" else 0
+        cand, score = native.absorb_propose(logits, x, m, self.conf_temp * (1.0 - (i + 1) / self.num_steps), flags, key, i)
+        return native.absorb_commit(x, cand, score, m, p_unmask=p, changed=changed)

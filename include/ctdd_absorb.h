@@ -1,10 +1,11 @@
 /* ctdd_absorb.h -- C ABI of the absorbing-state ("masked") diffusion kernels (csrc/absorb.hip): forward noising, the negative
- * ELBO with its logit gradient, and one reverse (unmasking) step.  Conventions as in ctdd.h: device pointers, row-major, int status
+ * ELBO with its logit gradient, one reverse (unmasking) step, and the two halves of a confidence-ordered unmasking step
+ * (ctdd_absorb_propose, ctdd_absorb_commit).  Conventions as in ctdd.h: device pointers, row-major, int status
  * (CTDD_OK == 0, message through ctdd_last_error), `stream` a hipStream_t.  Logits fp32 (B, D, S) contiguous, states int32,
  * 2 <= S <= CTDD_MAX_S (S counts the mask state: S = 2 is one real state plus the mask), 0 <= mask_state < S.
  *
  * The process: with alpha_t = exp(-c(t)) the probability that an entry is still unmasked at t, an entry of x_t is mask_state with
- * probability 1 - alpha_t and x0 otherwise, independently.  No S x S table enters any of the three kernels.
+ * probability 1 - alpha_t and x0 otherwise, independently.  No S x S table enters any of the kernels.
  *
  * Softmax excluding the mask state (every softmax below): over the states s != m = mask_state only.  l[m] takes no part in the
  * row maximum, its weight is exactly 0 and its gradient entry is exactly 0:
@@ -20,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CTDD_ABSORB_ARGMAX 1u   /* ctdd_absorb_step: every masked row takes argmax_{s != m} l[s] (lowest index on ties), no draw */
+#define CTDD_ABSORB_ARGMAX 1u   /* ctdd_absorb_step / _propose: every masked row takes argmax_{s != m} l[s] (lowest index on ties), no draw */
 
 /* x_t[b][d] = mask_state iff u >= alpha[b], else x0[b][d].   x0, out_xt (B, D); alpha (B,) on the device.
  * u: one Philox uniform per entry.  Entry e = b D + d reads component (e & 3) of the block Philox(key = seed,
@@ -51,6 +52,42 @@ int ctdd_absorb_elbo_loss(const float* logits, const int32_t* x0, const int32_t*
  * out_changed (int32[1] or NULL) += the number of rows that left the mask state (one atomic per workgroup). */
 int ctdd_absorb_step(const float* logits, const int32_t* x, int N, int D, int S, int mask_state, float p_unmask, uint32_t flags,
                      uint64_t seed, uint64_t offset, int32_t* out_x, int32_t* out_changed, void* stream);
+
+/* Confidence-ordered unmasking, first half: a candidate state and a confidence score for every masked row.
+ *   logits (N, D, S), x (N, D); out_cand int32 (N, D), out_score fp32 (N, D).
+ *   x != m: the row's logits are not read and nothing is written for it (out_cand / out_score keep what they held).
+ *   x == m: the row r = n D + d reads ONE block Philox(key = seed, counter = (row = r, offset, draw = 0)), laid out as the step's:
+ *     component 0: unused (the step's unmasking coin), so that component 1 is the step's;
+ *     component 1: u1 -- the candidate, by the inverse-CDF rule of ctdd_absorb_step (the same device code): for the same
+ *                  (seed, offset) the candidate IS the state ctdd_absorb_step would draw for the row.  Never m.
+ *     component 2: u2 -- the ranking noise, read only when noise != 0.
+ *   flags & CTDD_ABSORB_ARGMAX: the candidate is argmax_{s != m} l[s], lowest index on ties (u1 unused).
+ *   score = lp[cand] = (l[cand] - mx) - log z   (the softmax excluding the mask state, above),
+ *           + noise * (-log(-log u2))             when noise != 0 (a standard Gumbel variate scaled by `noise`). */
+int ctdd_absorb_propose(const float* logits, const int32_t* x, int N, int D, int S, int mask_state, float noise, uint32_t flags,
+                        uint64_t seed, uint64_t offset, int32_t* out_cand, float* out_score, void* stream);
+
+/* Confidence-ordered unmasking, second half: per sample, the k_n masked rows with the largest score take their candidate.
+ *   x, cand, out_x int32 (N, D); score fp32 (N, D); out_x does not alias x.  One workgroup per sample, 1 <= D <= 2^30.
+ *   M_n = the number of rows d of sample n with x[n][d] == m.  The number of rows to commit:
+ *     counts != NULL (int32 (N,) on the device): k_n = min(M_n, max(0, counts[n]));
+ *     counts == NULL: k_n = min(M_n, (int)ceil((double)p_unmask * M_n)), 0 <= p_unmask <= 1 (CTDD_ERANGE otherwise; p_unmask is
+ *                     unused when counts is given).  The fp64 product of an fp32 and an int below 2^29 is exact: the host can restate k_n.
+ *   x != m: out_x = x, bit for bit; cand and score are not read there.
+ *   x == m: out_x = cand for the k_n rows first in the order below, m for the others.
+ *   Order: descending by the 32-bit key of the score, equal keys in ascending d.  With b the score's bits:
+ *     NaN (either sign)            key = 0            (below -inf)
+ *     -0                           counts as +0       (b = 0)
+ *     sign bit clear (+0 .. +inf)  key = b | 0x80000000
+ *     sign bit set   (-inf .. <0)  key = ~b
+ *   so key(a) < key(b) iff a < b for all non-NaN a, b, and -inf has the key 0x007FFFFF.
+ *   Selection is a radix select over the key: four passes of 8-bit digit histograms (256 LDS bins), most significant digit first,
+ *   find the key T of the k_n-th row and how many rows at T are still wanted; one pass over d in ascending chunks of 256 (ballots
+ *   and prefix counts) then takes every key > T and exactly that many of the rows at T.  Keys are recomputed from `score` in each
+ *   pass (4 bytes a row, from L2); nothing but the histogram is kept in LDS, so D has no bound set by it.
+ * out_changed (int32[1] or NULL) += sum_n k_n (one atomic per workgroup). */
+int ctdd_absorb_commit(const int32_t* x, const int32_t* cand, const float* score, int N, int D, int mask_state, float p_unmask,
+                       const int32_t* counts, int32_t* out_x, int32_t* out_changed, void* stream);
 
 #ifdef __cplusplus
 }
