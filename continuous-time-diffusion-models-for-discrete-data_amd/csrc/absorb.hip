@@ -1,7 +1,9 @@
 // absorb.hip -- absorbing-state ("masked") diffusion: forward noising (ctdd_absorb_noise), the negative ELBO with its logit
 // gradient (ctdd_absorb_elbo_loss), one reverse step (ctdd_absorb_step) and the two halves of a confidence-ordered step: a candidate
 // and a score per masked row (ctdd_absorb_propose, the step's layout and pick), then a per-sample top-k of the scores by radix select
-// (ctdd_absorb_commit).  include/ctdd_absorb.h states the formulas, the Philox counter layouts and the key that orders the scores.
+// (ctdd_absorb_commit); and the terms of the held-out likelihood bounds, a row pass and a deterministic per-sample fp64 sum
+// (ctdd_absorb_nll).  include/ctdd_absorb.h states the formulas, the Philox counter layouts, the key that orders the scores and the
+// order of that sum.
 //
 // Loss and step are row softmaxes over a row that fits in registers.  A row is owned by a group of LPR lanes of one wave, lane j of
 // the group holding the PER consecutive states PER j .. PER j + PER - 1 (float4 loads when S % 4 == 0); 64 / LPR rows per wave,
@@ -418,6 +420,105 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_commit(const AbsorbCommitAr
   if (tid == 0 && a.changed && kn > 0) atomicAdd(a.changed, kn);
 }
 
+// ---------------------------------------------------------------- held-out bound: per-row -log p(x0), then per-sample fp64 sums
+struct AbsorbNllArgs {
+  const float* logits;
+  const int32_t *x0, *xt;
+  int D, S, mask_state;
+  int vec;
+  int chunks, iters;          // workgroups per sample; row groups (of AWV * 64 / LPR rows) a workgroup walks
+  float* row_nll;
+  int32_t* masked;
+  int32_t* hit;
+};
+
+// The row pass: k_absorb_propose's layout in argmax mode (the pick is absorb_pick's, so a hit is judged by the step's own rule).
+// A row without a term is not read and stores 0.0f.  A workgroup stays inside one sample -- chunk c of sample n walks `iters`
+// consecutive groups of AWV * 64 / LPR rows -- so the two counters take one integer atomic per workgroup each (integers: exact in any
+// order), not one per wave or row: the counters of all samples share a few cache lines.
+template <int LPR, int PER>
+__global__ __launch_bounds__(64 * AWV) void k_absorb_nll_rows(const AbsorbNllArgs a) {
+  __shared__ int red[2][AWV];
+  constexpr int RPW = WAVE / LPR, RPB = AWV * RPW;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane % LPR, s0 = j * PER, S = a.S, m = a.mask_state;
+  const int n = blockIdx.x / a.chunks, c = blockIdx.x % a.chunks;
+  const int64_t base = (int64_t)n * a.D;
+  int nt = 0, nh = 0;                                           // the lane's rows with a term, and the hits among them
+  for (int it = 0; it < a.iters; ++it) {
+    const int64_t d = ((int64_t)c * a.iters + it) * RPB + wave * RPW + lane / LPR;
+    const bool in = d < a.D;
+    const int64_t row = base + d;
+    int x0 = -1;
+    bool need = false;                                          // uniform over the row's group
+    if (in) {
+      x0 = a.x0[row];
+      need = a.xt[row] == m && x0 != m && x0 >= 0 && x0 < S;
+    }
+    float v[PER];
+    absorb_load<PER>(a.logits + (size_t)(in ? row : 0) * S, S, s0, m, a.vec, need, v);
+    float mx, z;
+    const int pick = absorb_pick<LPR, PER>(v, S, m, j, true, 0.0f, mx, z);
+    if (!(mx > -INFINITY)) mx = 0.0f;                           // rows that were not read
+    float lx = 0.0f;
+    z = 0.0f;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      z += expf(v[k] - mx);                                     // exp(-inf) = 0: the mask state and the states past S
+      if (s0 + k == x0) lx = v[k] - mx;
+    }
+    z = grp_sum<LPR>(z);
+    lx = grp_sum<LPR>(lx);
+    if (in && j == 0) a.row_nll[row] = need ? logf(z) - lx : 0.0f;
+    if (need && j == 0) {
+      ++nt;
+      nh += pick == x0;
+    }
+  }
+  if (a.masked || a.hit) {                                      // (uniform)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      nt += __shfl_xor(nt, o, WAVE);
+      nh += __shfl_xor(nh, o, WAVE);
+    }
+    if (lane == 0) { red[0][wave] = nt; red[1][wave] = nh; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int t = 0, h = 0;
+#pragma unroll
+      for (int i = 0; i < AWV; ++i) { t += red[0][i]; h += red[1][i]; }
+      if (a.masked && t) atomicAdd(a.masked + n, t);
+      if (a.hit && h) atomicAdd(a.hit + n, h);
+    }
+  }
+}
+
+struct AbsorbNllSumArgs {
+  const float* row_nll;
+  const float* w;
+  int D;
+  double* out;
+};
+
+// One workgroup (256 threads) per sample, no atomics, the order of include/ctdd_absorb.h: thread i adds the rows d = i, i + 256, ..
+// in ascending d; the 64 lanes of a wave combine by the xor butterfly 32, 16, .. 1; thread 0 adds the four waves' sums in wave order.
+__global__ __launch_bounds__(64 * AWV) void k_absorb_nll_sum(const AbsorbNllSumArgs a) {
+  __shared__ double red[AWV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, D = a.D;
+  const float* __restrict__ r = a.row_nll + (size_t)blockIdx.x * D;
+  double t = 0.0;
+  for (int d = tid; d < D; d += 64 * AWV) t += (double)r[d];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o, WAVE);
+  if (lane == 0) red[wave] = t;
+  __syncthreads();
+  if (tid == 0) {
+    double tot = red[0];
+#pragma unroll
+    for (int i = 1; i < AWV; ++i) tot += red[i];
+    a.out[blockIdx.x] += (a.w ? (double)a.w[blockIdx.x] : 1.0) * tot;
+  }
+}
+
 // (LPR, PER) of a row width; rows per workgroup = AWV * 64 / LPR
 #define ABSORB_SHAPE(S, CALL)                                                       \
   if ((S) <= 4) { constexpr int LPR = 1, PER = 4; CALL; }                           \
@@ -505,4 +606,22 @@ extern "C" int ctdd_absorb_commit(const int32_t* x, const int32_t* cand, const f
   AbsorbCommitArgs a = {x, cand, score, D, mask_state, p_unmask, counts, out_x, out_changed};
   hipLaunchKernelGGL(k_absorb_commit, dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, a);
   return finish_launch("k_absorb_commit");
+}
+
+extern "C" int ctdd_absorb_nll(const float* logits, const int32_t* x0, const int32_t* xt, const float* w, int N, int D, int S, int mask_state,
+                               float* row_nll, double* out_nll, int32_t* out_masked, int32_t* out_hit, void* stream) {
+  CTDD_REQUIRE(logits && x0 && xt && row_nll && out_nll, CTDD_EINVAL, "absorb nll: null buffer");
+  CTDD_REQUIRE(N > 0 && D > 0 && D <= (1 << 30) && S >= 2 && S <= CTDD_MAX_S && mask_state >= 0 && mask_state < S, CTDD_ERANGE,
+               "absorb nll: N=%d D=%d S=%d mask_state=%d (1 <= D <= 2^30, 2 <= S <= %d, 0 <= mask_state < S)", N, D, S, mask_state, CTDD_MAX_S);
+  const int rpb = AWV * WAVE / absorb_lpr(S);
+  const int groups = (D + rpb - 1) / rpb, iters = groups < 8 ? groups : 8;      // up to eight row groups a workgroup
+  const int chunks = (int)(((int64_t)D + (int64_t)rpb * iters - 1) / ((int64_t)rpb * iters));
+  const int64_t blocks = (int64_t)N * chunks;
+  CTDD_REQUIRE(blocks <= INT32_MAX, CTDD_ERANGE, "absorb nll: N = %d samples of %d workgroups", N, chunks);
+  AbsorbNllArgs a = {logits, x0, xt, D, S, mask_state, S % 4 == 0 && aligned16(logits), chunks, iters, row_nll, out_masked, out_hit};
+  ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_nll_rows<LPR, PER>), dim3((unsigned)blocks), dim3(64 * AWV), 0, (hipStream_t)stream, a));
+  if (int rc = finish_launch("k_absorb_nll_rows")) return rc;
+  AbsorbNllSumArgs b = {row_nll, w, D, out_nll};
+  hipLaunchKernelGGL(k_absorb_nll_sum, dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, b);
+  return finish_launch("k_absorb_nll_sum");
 }

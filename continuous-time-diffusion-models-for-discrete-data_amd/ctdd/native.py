@@ -89,6 +89,7 @@ _SIGS = {
     "ctdd_absorb_step": ([_P, _P, _I, _I, _I, _I, _F, _U32, _U64, _U64, _P, _P, _P], _I),
     "ctdd_absorb_propose": ([_P, _P, _I, _I, _I, _I, _F, _U32, _U64, _U64, _P, _P, _P], _I),
     "ctdd_absorb_commit": ([_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P], _I),
+    "ctdd_absorb_nll": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
 }
 UNET_EXPORTS = ("ctdd_unet_conv", "ctdd_unet_conv_patch", "ctdd_unet_conv_res", "ctdd_unet_conv_ring", "ctdd_unet_conv_up_phases", "ctdd_unet_upsample2x", "ctdd_unet_first_conv", "ctdd_unet_gn_apply", "ctdd_unet_gn_onepass", "ctdd_unet_channel_stats",
                 "ctdd_unet_time", "ctdd_unet_time_uniform", "ctdd_unet_attention", "ctdd_unet_logistic_head", "ctdd_unet_resblock_small",
@@ -656,6 +657,26 @@ def absorb_commit(x, cand, score, mask_state, p_unmask=None, counts=None, out=No
     _check(load().ctdd_absorb_commit(*ptrs, N, D, int(mask_state), 0.0 if p_unmask is None else float(p_unmask), _ptr(counts, i32, "counts"),
                                      _ptr(out, i32, "out"), _ptr(changed, i32, "changed"), _stream()), "ctdd_absorb_commit")
     return out
+
+
+def absorb_nll(logits, x0, xt, mask_state, w=None, out=None, masked=None, hit=None):
+    """(row_nll fp32 (N, D), out fp64 (N,)): -log p(x0) under the softmax over s != mask_state at every row with xt == mask_state
+    (and x0 a real state), exact 0 at the others, which are not read; out[n] += w[n] * sum_d row_nll[n][d] in fp64, in a fixed order
+    (ctdd_absorb_nll: repeated calls give the same bits).  w: fp32 (N,) or None (1).  out: fp64 (N,), e.g. a row of a (K, N) buffer, is
+    accumulated into (None: a fresh zeroed one).  masked / hit: int32 (N,) device counters, incremented by the sample's rows with a
+    term / by those of them whose argmax over s != mask_state (lowest index on ties) is x0."""
+    N, D, S = _absorb_shapes("absorb_nll", logits, (("x0", x0), ("xt", xt)))
+    for name, t in (("w", w), ("out", out), ("masked", masked), ("hit", hit)):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (N,)):
+            raise CtddError(f"absorb_nll: {name} {tuple(getattr(t, 'shape', ()))}, expected {(N,)}")
+    ptrs = (_ptr(logits, f32, "logits"), _ptr(x0, i32, "x0"), _ptr(xt, i32, "xt"), _ptr(w, f32, "w"))
+    if out is None:
+        out = torch.zeros((N,), dtype=torch.float64, device=logits.device)
+    row = torch.empty((N, D), dtype=f32, device=logits.device)
+    tail = (_ptr(row), _ptr(out, torch.float64, "out"), _ptr(masked, i32, "masked"), _ptr(hit, i32, "hit"))
+    _count("ctdd_absorb_nll")
+    _check(load().ctdd_absorb_nll(*ptrs, N, D, S, int(mask_state), *tail, _stream()), "ctdd_absorb_nll")
+    return row, out
 
 
 # ---------------------------------------------------------------- the fused training objectives (csrc/losses.hip)

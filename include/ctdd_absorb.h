@@ -1,7 +1,8 @@
 /* ctdd_absorb.h -- C ABI of the absorbing-state ("masked") diffusion kernels (csrc/absorb.hip): forward noising, the negative
- * ELBO with its logit gradient, one reverse (unmasking) step, and the two halves of a confidence-ordered unmasking step
- * (ctdd_absorb_propose, ctdd_absorb_commit).  Conventions as in ctdd.h: device pointers, row-major, int status
- * (CTDD_OK == 0, message through ctdd_last_error), `stream` a hipStream_t.  Logits fp32 (B, D, S) contiguous, states int32,
+ * ELBO with its logit gradient, one reverse (unmasking) step, the two halves of a confidence-ordered unmasking step
+ * (ctdd_absorb_propose, ctdd_absorb_commit), and the per-sample terms of the held-out likelihood bounds (ctdd_absorb_nll).
+ * Conventions as in ctdd.h: device pointers, row-major, int status (CTDD_OK == 0, message through ctdd_last_error), `stream` a
+ * hipStream_t.  Logits fp32 (B, D, S) contiguous, states int32,
  * 2 <= S <= CTDD_MAX_S (S counts the mask state: S = 2 is one real state plus the mask), 0 <= mask_state < S.
  *
  * The process: with alpha_t = exp(-c(t)) the probability that an entry is still unmasked at t, an entry of x_t is mask_state with
@@ -88,6 +89,24 @@ int ctdd_absorb_propose(const float* logits, const int32_t* x, int N, int D, int
  * out_changed (int32[1] or NULL) += sum_n k_n (one atomic per workgroup). */
 int ctdd_absorb_commit(const int32_t* x, const int32_t* cand, const float* score, int N, int D, int mask_state, float p_unmask,
                        const int32_t* counts, int32_t* out_x, int32_t* out_changed, void* stream);
+
+/* Per-row and per-sample negative log-likelihood of x0 at the masked rows of x_t: the terms of the held-out likelihood bounds.
+ *   logits (N, D, S), x0, xt (N, D); w (N,) on the device or NULL (every weight 1).
+ *   Row (n, d) carries a term iff xt == m, x0 != m and 0 <= x0 < S:
+ *     row_nll[n][d] = log z - (l[x0] - mx)   (the softmax excluding the mask state, above; fp32)
+ *   Every other row's logits are not read and its row_nll is stored as exact 0.0f.  row_nll (N, D) is written in full.
+ *   out_nll[n]    += (double)w[n] * sum_d row_nll[n][d]                                    (fp64 (N,))
+ *   out_masked[n] += the number of rows of sample n that carry a term                      (int32 (N,) or NULL)
+ *   out_hit[n]    += the number of those whose argmax_{s != m} l[s], lowest index on ties (ctdd_absorb_step's rule), is x0  (or NULL)
+ * The sum is deterministic: no floating-point atomic enters it, and repeated calls on the same inputs add the same bits.  Two
+ * launches: the row pass (rows packed as above inside one sample: a workgroup walks up to eight groups of 256 / LPR rows of its sample
+ * and sends one integer atomic per counter -- integers are exact in any order), then one
+ * workgroup of 256 threads per sample in this order: thread i adds row_nll[n][d] for d = i, i + 256, i + 512, .. in ascending d,
+ * in fp64; the 64 lanes of a wave combine by the xor butterfly with the offsets 32, 16, 8, 4, 2, 1; the four waves' sums are added in
+ * wave order 0, 1, 2, 3; the total is multiplied by w[n] and added to out_nll[n] by that workgroup's one thread.  Nothing of a sample
+ * is kept in LDS but the four wave sums: 1 <= D <= 2^30. */
+int ctdd_absorb_nll(const float* logits, const int32_t* x0, const int32_t* xt, const float* w, int N, int D, int S, int mask_state,
+                    float* row_nll, double* out_nll, int32_t* out_masked, int32_t* out_hit, void* stream);
 
 #ifdef __cplusplus
 }
