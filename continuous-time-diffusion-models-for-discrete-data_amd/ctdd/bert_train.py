@@ -6,8 +6,8 @@ residual readout)).
 the hollow transformer's: every operation a libctdd launch, autograd as the tape only, one Function per block.
 
   embedding     `ctdd_bert_embed` in plain mode ([temb | x_0..x_{D-1}] + pe, T = D + 1 tokens) / `ctdd_bert_embed_bwd`
-  encoder       per layer `AttnBlockFn` and `MlpBlockFn` of hollow_train with Tq = Tk = T, packed qkv rows and attention mode 3
-                (unmasked: `ctdd_hollow_attention_train(_bf16)` / `_bwd(_bf16)`)
+  encoder       hollow_train.Forward.encoder: per layer `AttnBlockFn` and `MlpBlockFn` with Tq = Tk = T, packed qkv rows and
+                attention mode 3 (unmasked: `ctdd_hollow_attention_train(_bf16)` / `_bwd(_bf16)`)
   readout       `ctdd_bert_gather` (rows 1..D of every sequence) / `ctdd_bert_gather_bwd`, then hollow_train.film_readout
 
 Precisions as there: "fp32" (parity mode) and "bf16" (default; head dimensions 16 and 32 run the matrix-core attention, 4 and 8
@@ -21,8 +21,8 @@ import torch
 
 from . import bert_engine, native
 from .bert_engine import _BertEmbedArgs
-from .hollow_train import AttnBlockFn, DropoutFn, MlpBlockFn, WeightPacks, _ck, _st, film_readout, lib as _train_lib
-from .unet_engine import _unwrap
+from .hollow_train import Forward, Trainer, _ck, _st, film_readout, lib as _train_lib
+from .plan_launch import set_state_ptr, unwrap
 
 _P, _I = C.c_void_p, C.c_int
 
@@ -47,12 +47,7 @@ def lib():
 
 
 def _state_ptrs(a, x):
-    if x.dtype == torch.int64:
-        a.x64 = x.data_ptr()
-    elif x.dtype == torch.int32:
-        a.x32 = x.data_ptr()
-    else:
-        raise native.CtddError(f"BertTrainer expects integer states, got {x.dtype}")
+    set_state_ptr(a, x, "BertTrainer")
 
 
 class BertEmbedFn(torch.autograd.Function):
@@ -117,66 +112,28 @@ class BertGatherFn(torch.autograd.Function):
 def training_supported(model):
     """The x0-prediction net inside the inference engine's coverage and the training kernels' shape limits (those of
     hollow_train.training_supported)."""
-    net = _unwrap(getattr(model, "net", None))
+    net = unwrap(getattr(model, "net", None))
     if net is None or net.__class__.__name__ != "BertEnumTransformer" or not bert_engine.supports(model):
         return False
     m = net.config.model
     return (m.embed_dim // m.num_heads) in (4, 8, 16, 32) and m.embed_dim <= 256 and m.embed_dim % 16 == 0 and m.mlp_dim % 16 == 0
 
 
-class BertTrainer:
+class BertTrainer(Trainer):
     def __init__(self, model, precision=None):
-        self.model, self.net = model, _unwrap(model.net)
         if not training_supported(model):
             raise native.CtddError("BertTrainer: network outside the training kernels' coverage (see bert_train.training_supported)")
-        m = self.net.config.model
-        self.precision = precision or getattr(m, "engine_train_precision", "bf16")
-        if self.precision not in ("fp32", "bf16"):
-            raise ValueError(f"unknown training precision {self.precision}")
-        self.dev = next(self.net.parameters()).device
-        if self.dev.type != "cuda":
-            raise native.CtddError("BertTrainer needs the model on a GPU")
+        super().__init__(model, precision)
         lib()
-        self.rng = torch.zeros(2, dtype=torch.int64, device=self.dev)
-        self.rng[0] = native.dropout_seed()
-        self.pe = None
-        self.pk = WeightPacks(self.net, self.precision == "bf16", self.dev)
 
     def __call__(self, x, times):
         net = self.net
-        m = net.config.model
-        bf = self.precision == "bf16"
-        E, H, S = m.embed_dim, m.num_heads, net.S
-        hd = E // H
         x = x.view(x.shape[0], -1)
         B, D = x.shape
         T = D + 1
-        training = bool(self.model.training)
-        p_drop = float(m.dropout_rate) if training else 0.0
-        p_att = float(m.attention_dropout_rate) if training else 0.0
-        self.pk.refresh(self.rng if training else None)       # (+ one dropout stream per training forward)
-        # every forward keeps its OWN {seed, step} (see HollowTrainer.__call__): two forwards before one backward keep their masks
-        rng, pk = (self.rng.clone() if training else self.rng), self.pk
-        layer = [0]
-
-        def nxt():
-            layer[0] += 1
-            return layer[0]
-
-        def drop(t, p):
-            return DropoutFn.apply(t, p, rng, nxt()) if p > 0.0 else t
-
+        fw = Forward(self)
         enc = net.trans_encoder
-        if self.pe is None or self.pe.shape[0] != T:
-            self.pe = enc.pos_embed.pe[0, :T].to(self.dev).float().contiguous()
-        h, temb = BertEmbedFn.apply(x, times, net.input_embedding.weight, net.input_embedding.bias, self.pe, S, float(net.temb_scale))
-        h = drop(drop(h, p_drop), p_drop)                     # PositionalEncoding's dropout, then the encoder's (TransformerEncoder.forward)
-        for blk in enc.trans_block_layers:
-            sa, ff = blk.self_attention_block, blk.feed_forward_block
-            mha = sa.self_attention
-            h = AttnBlockFn.apply(h, sa.norm.weight, sa.norm.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                                  mha.out_proj.bias, rng,
-                                  (B, T, H, hd, 3, p_att, p_drop, nxt(), nxt(), bf, sa.norm.eps, pk(mha.in_proj_weight), pk(mha.out_proj.weight)))
-            h = MlpBlockFn.apply(h, ff.norm.weight, ff.norm.bias, ff.mlp.fc1.weight, ff.mlp.fc1.bias, ff.mlp.fc2.weight, rng,
-                                 (B, T, E, p_drop, nxt(), nxt(), bf, ff.norm.eps, pk(ff.mlp.fc1.weight), pk(ff.mlp.fc2.weight)))
-        return film_readout(net.model, BertGatherFn.apply(h), temb, B, D, bf, pk)
+        pe = self.pos_table(enc.pos_embed, T)
+        h, temb = BertEmbedFn.apply(x, times, net.input_embedding.weight, net.input_embedding.bias, pe, net.S, float(net.temb_scale))
+        h = fw.encoder(h, enc.trans_block_layers, B, T, 3)    # (the generic attention kernels: short is MaskedTrainer's)
+        return film_readout(net.model, BertGatherFn.apply(h), temb, B, D, fw.bf, fw.pk)

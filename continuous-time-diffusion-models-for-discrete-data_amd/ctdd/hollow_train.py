@@ -4,7 +4,10 @@ TAUnSDDM/lib/networks/hollow_networks.py:668-755 and the blocks it is built from
 `HollowTrainer(model)(x, t)` computes the logits of a `BidirectionalTransformer2` with every operation a libctdd launch and
 autograd as the tape only: each node is a `torch.autograd.Function` whose forward and backward call the C ABI
 (include/ctdd_hollow.h, ctdd_hollow_train.h, ctdd_unet.h, ctdd_unet_train.h) -- one Function per prenorm attention block and
-per feed-forward block (`AttnBlockFn`, `MlpBlockFn`: hand-scheduled backward), per-op Functions for the once-per-network readout:
+per feed-forward block (`AttnBlockFn`, `MlpBlockFn`: hand-scheduled backward), per-op Functions for the once-per-network readout.
+What the single-stream trainers (ctdd/bert_train.py, ctdd/masked_train.py) share with this one lives here too: `Trainer` (the
+constructor and the positional-table cache), `Forward` (one per forward: its dropout streams and `encoder`, the one place the block
+loop is written), `WeightPacks` and `film_readout`.  The launches:
 
   linear layers      forward / data gradient (the same GEMM with the packed transposed weight): `ctdd_gemm_bf16` (bf16 operands),
                      `ctdd_unet_conv` (exact fp32);  weight gradient `ctdd_unet_wgrad` (kind 1x1: tokens are the contraction index);
@@ -28,9 +31,10 @@ import math
 import torch
 
 from . import native
-from .plan_launch import patch_gemm_tiles, ptr as _p
-from .unet_engine import SEG_1x1, _ConvArgs, _unwrap
-from .hollow_engine import _AttnArgs as _InfAttnArgs, _EmbedArgs, _GemmArgs, _LnArgs, _lib as _hollow_lib, supports  # noqa: F401
+from .plan_launch import patch_gemm_tiles, ptr as _p, unwrap
+from .unet_engine import SEG_1x1, _ConvArgs
+from .plan_common import _EmbedArgs, _GemmArgs, _LnArgs, _lib as _hollow_lib
+from .hollow_engine import supports
 from . import unet_train
 
 _P, _I, _F, _I64, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
@@ -660,7 +664,7 @@ class EmbedFn(torch.autograd.Function):
 
 # ---------------------------------------------------------------------- the network
 def training_supported(model):
-    net = _unwrap(getattr(model, "net", None))
+    net = unwrap(getattr(model, "net", None))
     if net is None or getattr(net.config.model, "engine_train", "hip") != "hip" or not supports(model):
         return False
     m = net.config.model
@@ -732,63 +736,96 @@ def film_readout(rr, xr, temb, B, D, bf, pk):
     return logits.view(B, D, rr.out_dim)
 
 
-class HollowTrainer:
+class Trainer:
+    """What the transformer trainers (HollowTrainer, bert_train.BertTrainer, masked_train.MaskedTrainer) are built on: the
+    precision ("fp32" parity mode / "bf16"), the device, the {seed, step} tensor `rng` of the dropout streams, the packed weights
+    `pk` and the cached positional table `pe`.  A subclass checks its own training_supported before, and registers its own
+    entry points after, this constructor."""
+
     def __init__(self, model, precision=None):
-        self.model, self.net = model, _unwrap(model.net)
-        m = self.net.config.model
-        self.precision = precision or getattr(m, "engine_train_precision", "bf16")
+        self.model, self.net = model, unwrap(model.net)
+        self.precision = precision or getattr(self.net.config.model, "engine_train_precision", "bf16")
         if self.precision not in ("fp32", "bf16"):
             raise ValueError(f"unknown training precision {self.precision}")
         self.dev = next(self.net.parameters()).device
         if self.dev.type != "cuda":
-            raise native.CtddError("HollowTrainer needs the model on a GPU")
+            raise native.CtddError(f"{type(self).__name__} needs the model on a GPU")
         lib()
         self.rng = torch.zeros(2, dtype=torch.int64, device=self.dev)
         self.rng[0] = native.dropout_seed()
         self.pe = None
         self.pk = WeightPacks(self.net, self.precision == "bf16", self.dev)
 
-    def __call__(self, x, times):
-        net = self.net
-        m = net.config.model
-        bf = self.precision == "bf16"
-        E, H, S = m.embed_dim, m.num_heads, net.S
-        hd = E // H
-        B, D = x.shape
-        training = bool(self.model.training)
-        p_drop = float(m.dropout_rate) if training else 0.0
-        p_att = float(m.attention_dropout_rate) if training else 0.0
-        self.pk.refresh(self.rng if training else None)       # (+ one dropout stream per training forward)
+    def pos_table(self, pos_embed, T, exact=True):
+        """The first T rows of the positional table on the device, cached (exact: rebuilt unless it has exactly T rows;
+        otherwise any table of at least T rows serves)."""
+        if self.pe is None or (self.pe.shape[0] != T if exact else self.pe.shape[0] < T):
+            self.pe = pos_embed.pe[0, :T].to(self.dev).float().contiguous()
+        return self.pe
+
+
+class Forward:
+    """One forward of a Trainer: the rates and operand type it runs with, its {seed, step} tensor and its dropout layer counter.
+    The constructor repacks the weights, which in training mode also moves the trainer's step: one dropout stream per forward.
+    The layer numbers are the dropout streams, so the order of the nxt() calls below is part of the format: a mask is
+    Philox(seed, step, layer, element), and the backward of a block regenerates the forward's from the numbers in its meta."""
+
+    def __init__(self, tr, clone=True):
+        m = tr.net.config.model
+        self.training = bool(tr.model.training)
+        self.p_drop = float(m.dropout_rate) if self.training else 0.0
+        self.p_att = float(m.attention_dropout_rate) if self.training else 0.0
+        self.bf, self.pk = tr.precision == "bf16", tr.pk
+        self.E, self.H = m.embed_dim, m.num_heads
+        self.hd = self.E // self.H
+        self.pk.refresh(tr.rng if self.training else None)
         # every forward keeps its OWN {seed, step}: the Functions save this tensor and their backward kernels read the step
         # from it, so a second training forward before the first one's backward (two-forward-pass CT-ELBO, gradient
-        # accumulation over micro-batches) must not move the first one's masks
-        rng, pk = (self.rng.clone() if training else self.rng), self.pk
-        layer = [0]
+        # accumulation over micro-batches) must not move the first one's masks.  (clone = False: the caller hands every
+        # chunk its own through restart)
+        self.rng = tr.rng.clone() if (self.training and clone) else tr.rng
+        self.layer = 0
 
-        def nxt():
-            layer[0] += 1
-            return layer[0]
+    def restart(self, rng):
+        """The next chunk of the same forward: its own {seed, step}, layers numbered from 1 again."""
+        self.rng, self.layer = rng, 0
 
-        def drop(t, p):
-            return DropoutFn.apply(t, p, rng, nxt()) if p > 0.0 else t
+    def nxt(self):
+        self.layer += 1
+        return self.layer
 
-        if self.pe is None or self.pe.shape[0] < D:
-            self.pe = net.module_l2r.pos_embed.pe[0, :D].to(self.dev).float().contiguous()
-        l2r, r2l, temb = EmbedFn.apply(x, times, net.input_embedding.weight, net.input_embedding.bias, self.pe, S, float(net.temb_scale))
+    def drop(self, t, p):
+        return DropoutFn.apply(t, p, self.rng, self.nxt()) if p > 0.0 else t
+
+    def encoder(self, h, layers, n, T, mode, short=False):
+        """The prenorm blocks `layers` over h (n, T, E) after PositionalEncoding's dropout and the stack's
+        (hollow_networks.py:562-563, TransformerEncoder.forward).  short: the short-sequence attention kernels
+        (short_attention_applies).  Per block the counter advances: attention dropout, output dropout, then the MLP's two."""
+        E, H, hd, p_att, p_drop, bf, pk, rng, nxt = self.E, self.H, self.hd, self.p_att, self.p_drop, self.bf, self.pk, self.rng, self.nxt
+        h = self.drop(self.drop(h, p_drop), p_drop)
+        for blk in layers:
+            sa, ff = blk.self_attention_block, blk.feed_forward_block
+            mha = sa.self_attention
+            h = AttnBlockFn.apply(h, sa.norm.weight, sa.norm.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
+                                  mha.out_proj.bias, rng,
+                                  (n, T, H, hd, mode, p_att, p_drop, nxt(), nxt(), bf, sa.norm.eps, pk(mha.in_proj_weight), pk(mha.out_proj.weight))
+                                  + ((True,) if short else ()))
+            h = MlpBlockFn.apply(h, ff.norm.weight, ff.norm.bias, ff.mlp.fc1.weight, ff.mlp.fc1.bias, ff.mlp.fc2.weight, rng,
+                                 (n, T, E, p_drop, nxt(), nxt(), bf, ff.norm.eps, pk(ff.mlp.fc1.weight), pk(ff.mlp.fc2.weight)))
+        return h
+
+
+class HollowTrainer(Trainer):
+    def __call__(self, x, times):
+        net = self.net
+        B, D = x.shape
+        fw = Forward(self)
+        bf, pk, E, H, hd = fw.bf, fw.pk, fw.E, fw.H, fw.hd
+        pe = self.pos_table(net.module_l2r.pos_embed, D, exact=False)
+        l2r, r2l, temb = EmbedFn.apply(x, times, net.input_embedding.weight, net.input_embedding.bias, pe, net.S, float(net.temb_scale))
         R = B * D
-        streams = []
-        for seq, stack, mode in ((l2r, net.module_l2r, 0), (r2l, net.module_r2l, 1)):
-            h = drop(drop(seq, p_drop), p_drop)               # PositionalEncoding's dropout, then the stack's (hollow_networks.py:562-563)
-            for blk in stack.trans_block_layers:
-                sa, ff = blk.self_attention_block, blk.feed_forward_block
-                mha = sa.self_attention
-                h = AttnBlockFn.apply(h, sa.norm.weight, sa.norm.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                                      mha.out_proj.bias, rng,
-                                      (B, D, H, hd, mode, p_att, p_drop, nxt(), nxt(), bf, sa.norm.eps, pk(mha.in_proj_weight), pk(mha.out_proj.weight)))
-                h = MlpBlockFn.apply(h, ff.norm.weight, ff.norm.bias, ff.mlp.fc1.weight, ff.mlp.fc1.bias, ff.mlp.fc2.weight, rng,
-                                     (B, D, E, p_drop, nxt(), nxt(), bf, ff.norm.eps, pk(ff.mlp.fc1.weight), pk(ff.mlp.fc2.weight)))
-            streams.append(h)
-        l2r, r2l = streams
+        l2r = fw.encoder(l2r, net.module_l2r.trans_block_layers, B, D, 0)
+        r2l = fw.encoder(r2l, net.module_r2l.trans_block_layers, B, D, 1)
         dense = pk.linear
         # ---- attention readout (prenorm): cross attention over [temb | ln1(l2r) | ln2(r2l)] + (l2r + r2l)
         ro = net.readout_module
@@ -802,6 +839,6 @@ class HollowTrainer:
         qb = dense(qin, ca.dense_query.weight, None, bf)
         kb = dense(allk, ca.dense_key.weight, ca.dense_key.bias, bf)
         vb = dense(allk, ca.dense_val.weight, ca.dense_val.bias, bf)
-        ctxv = AttentionFn.apply(qb, kb, vb, B, D, Tk, H, hd, 2, 0.0, None, nxt(), bf)
+        ctxv = AttentionFn.apply(qb, kb, vb, B, D, Tk, H, hd, 2, 0.0, None, fw.nxt(), bf)
         xr = dense(ctxv, ca.out_linear.weight, ca.out_linear.bias, bf, res=raw)
         return film_readout(ro.model, xr, temb, B, D, bf, pk)

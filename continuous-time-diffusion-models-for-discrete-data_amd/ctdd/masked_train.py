@@ -8,7 +8,7 @@ computes the x0-prediction transformer's.  logits[b, p] = readout(encoder(x_b wi
 hollow_networks.enum_chunk_size() sequences, the last chunk with its true row count.
 
   per chunk     `ctdd_bert_embed` in enumerate mode over the window [r0, r0 + n) / `ctdd_bert_embed_enum_bwd`; the two dropouts;
-                per layer `AttnBlockFn` and `MlpBlockFn` of hollow_train with Tq = Tk = T = D + 1 and attention mode 3 -- on
+                hollow_train.Forward.encoder: per layer `AttnBlockFn` and `MlpBlockFn` with Tq = Tk = T = D + 1 and attention mode 3 -- on
                 `ctdd_bert_attention_short_train` / `_bwd` where T <= 64 and the head dimension is 4 or 8 (both shipped masked
                 configs at D = 32; the maze config's T = 226 runs the generic kernels); `ctdd_bert_gather` in enumerate mode
                 into the chunk's rows of ONE (B D', E) readout input / `ctdd_bert_gather_enum_bwd`
@@ -29,9 +29,9 @@ import torch
 
 from . import bert_engine, native
 from .bert_engine import _BertEmbedArgs
-from .bert_train import _state_ptrs, lib as _bert_lib
-from .hollow_train import AttnBlockFn, DropoutFn, MlpBlockFn, WeightPacks, _ck, _st, film_readout, short_attention_applies
-from .unet_engine import _unwrap
+from .bert_train import lib as _bert_lib
+from .hollow_train import Forward, Trainer, _ck, _st, film_readout, short_attention_applies
+from .plan_launch import set_state_ptr, unwrap
 
 _P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
 MAX_CHUNK = 65535              # sequences per launch (a grid dimension of the embed and attention kernels)
@@ -73,7 +73,7 @@ class EnumEmbedFn(torch.autograd.Function):
         E = w_in.numel()
         out = torch.empty((n, D + 1, E), dtype=torch.float32, device=x.device)
         a = _BertEmbedArgs()
-        _state_ptrs(a, x)
+        set_state_ptr(a, x, "MaskedTrainer")
         wv, bv = w_in.detach().reshape(-1).contiguous(), b_in.detach().contiguous()
         a.t, a.w_in, a.b_in, a.pe = t.data_ptr(), wv.data_ptr(), bv.data_ptr(), pe.data_ptr()
         a.B, a.D, a.E, a.S, a.temb_scale = B, D, E, S, float(temb_scale)
@@ -92,7 +92,7 @@ class EnumEmbedFn(torch.autograd.Function):
         dout = dout.contiguous()
         dwb = torch.zeros((2, E), dtype=torch.float32, device=x.device)
         a = _BertEmbedEnumBwdArgs()
-        _state_ptrs(a, x)
+        set_state_ptr(a, x, "MaskedTrainer")
         a.g, a.B, a.D, a.E, a.S, a.cond, a.rows, a.r0 = dout.data_ptr(), B, D, E, S, cond, n, r0
         a.dw, a.db = dwb[0].data_ptr(), dwb[1].data_ptr()
         _ck(lib().ctdd_bert_embed_enum_bwd(C.byref(a), _st()), "ctdd_bert_embed_enum_bwd")
@@ -126,7 +126,7 @@ class EnumGatherFn(torch.autograd.Function):
 def training_supported(model):
     """The masked net with the FiLM residual readout, inside the inference engine's coverage and the training kernels' shape limits
     (those of hollow_train.training_supported)."""
-    net = _unwrap(getattr(model, "net", None))
+    net = unwrap(getattr(model, "net", None))
     if net is None or net.__class__.__name__ != "EnumerativeTransformer":
         return False
     m = net.config.model
@@ -135,35 +135,21 @@ def training_supported(model):
     return (m.embed_dim // m.num_heads) in (4, 8, 16, 32) and m.embed_dim <= 256 and m.embed_dim % 16 == 0 and m.mlp_dim % 16 == 0
 
 
-class MaskedTrainer:
+class MaskedTrainer(Trainer):
     def __init__(self, model, precision=None):
-        self.model, self.net = model, _unwrap(model.net)
         if not training_supported(model):
             raise native.CtddError("MaskedTrainer: network outside the training kernels' coverage (see masked_train.training_supported)")
-        m = self.net.config.model
-        self.precision = precision or getattr(m, "engine_train_precision", "bf16")
-        if self.precision not in ("fp32", "bf16"):
-            raise ValueError(f"unknown training precision {self.precision}")
-        self.dev = next(self.net.parameters()).device
-        if self.dev.type != "cuda":
-            raise native.CtddError("MaskedTrainer needs the model on a GPU")
+        super().__init__(model, precision)
         lib()
-        self.rng = torch.zeros(2, dtype=torch.int64, device=self.dev)
-        self.rng[0] = native.dropout_seed()
-        self.pe, self._walk, self.chunk_rngs = None, None, None
-        self.pk = WeightPacks(self.net, self.precision == "bf16", self.dev)
+        self._walk, self.chunk_rngs = None, None
 
     def __call__(self, x, times):
         from lib.networks.hollow_networks import enum_chunk_size
         net, tf = self.net, self.net.transformer
         m = net.config.model
-        bf = self.precision == "bf16"
-        E, H, S = m.embed_dim, m.num_heads, net.S
-        hd = E // H
+        E, S = m.embed_dim, net.S
         shape = tuple(x.shape)
         x = x.view(x.shape[0], -1).contiguous()
-        if x.dtype not in (torch.int64, torch.int32):
-            raise native.CtddError(f"MaskedTrainer expects integer states, got {x.dtype}")
         B, D = x.shape
         T = D + 1
         c = int(getattr(m, "conditional_dim", 0) or 0)
@@ -173,50 +159,27 @@ class MaskedTrainer:
         if self._walk is None or self._walk[0] != walk:
             self._walk = (walk, torch.tensor([r0 for r0, _ in walk], dtype=torch.int32, device=self.dev))
         r0s = self._walk[1]
-        training = bool(self.model.training)
-        p_drop = float(m.dropout_rate) if training else 0.0
-        p_att = float(m.attention_dropout_rate) if training else 0.0
-        self.pk.refresh(self.rng if training else None)       # (+ one dropout stream per training forward)
-        pk = self.pk
-        if training:
+        fw = Forward(self, clone=False)
+        if fw.training:
             # one {seed, step} per chunk, cloned: this forward's masks stay put whatever runs before its backward, and the
             # trainer's own step moves past the chunks' so the next forward shares none of them
             rngs = self.rng.repeat(len(walk), 1)
             rngs[:, 1] += torch.arange(len(walk), dtype=torch.int64, device=self.dev)
             self.rng[1] += len(walk) - 1
             self.chunk_rngs = rngs                            # (the last training forward's table: the tests read it)
-        short = short_attention_applies(T, T, hd, 3)
+        short = short_attention_applies(T, T, fw.hd, 3)
         enc = tf.trans_encoder
-        if self.pe is None or self.pe.shape[0] != T:
-            self.pe = enc.pos_embed.pe[0, :T].to(self.dev).float().contiguous()
+        pe = self.pos_table(enc.pos_embed, T)
         tv = times.float().contiguous()
         temb = torch.empty((B, E), dtype=torch.float32, device=self.dev)       # complete after the last chunk (module docstring)
         rows = torch.empty((total, E), dtype=torch.float32, device=self.dev)
         w_emb, b_emb = tf.input_embedding.weight, tf.input_embedding.bias
         for i, (r0, n) in enumerate(walk):
-            rng = rngs[i] if training else self.rng
-            layer = [0]
-
-            def nxt():
-                layer[0] += 1
-                return layer[0]
-
-            def drop(t_, p):
-                return DropoutFn.apply(t_, p, rng, nxt()) if p > 0.0 else t_
-
-            h = EnumEmbedFn.apply(x, tv, w_emb, b_emb, self.pe, temb, r0s[i:i + 1], (S, float(net.temb_scale), c, r0, n))
-            h = drop(drop(h, p_drop), p_drop)                 # PositionalEncoding's dropout, then the encoder's (TransformerEncoder.forward)
-            for blk in enc.trans_block_layers:
-                sa, ff = blk.self_attention_block, blk.feed_forward_block
-                mha = sa.self_attention
-                h = AttnBlockFn.apply(h, sa.norm.weight, sa.norm.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                                      mha.out_proj.bias, rng,
-                                      (n, T, H, hd, 3, p_att, p_drop, nxt(), nxt(), bf, sa.norm.eps, pk(mha.in_proj_weight), pk(mha.out_proj.weight),
-                                       short))
-                h = MlpBlockFn.apply(h, ff.norm.weight, ff.norm.bias, ff.mlp.fc1.weight, ff.mlp.fc1.bias, ff.mlp.fc2.weight, rng,
-                                     (n, T, E, p_drop, nxt(), nxt(), bf, ff.norm.eps, pk(ff.mlp.fc1.weight), pk(ff.mlp.fc2.weight)))
+            fw.restart(rngs[i] if fw.training else self.rng)
+            h = EnumEmbedFn.apply(x, tv, w_emb, b_emb, pe, temb, r0s[i:i + 1], (S, float(net.temb_scale), c, r0, n))
+            h = fw.encoder(h, enc.trans_block_layers, n, T, 3, short=short)
             rows = EnumGatherFn.apply(rows, h, r0s[i:i + 1], (B, D, c, r0, n))
-        logits = film_readout(tf.model, rows, temb, B, Dp, bf, pk)
+        logits = film_readout(tf.model, rows, temb, B, Dp, fw.bf, fw.pk)
         if c:                                                 # the never-masked prefix: all-zero logits, no gradient
             logits = torch.cat([torch.zeros((B, c, logits.shape[-1]), dtype=logits.dtype, device=self.dev), logits], dim=1)
         return logits.view(shape + (S,))

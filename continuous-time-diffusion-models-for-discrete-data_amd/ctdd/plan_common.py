@@ -1,12 +1,16 @@
 """What the transformer inference engines (ctdd/hollow_engine.py, ctdd/bert_engine.py) share: the ctypes argument blocks of the
-hollow-transformer entry points (include/ctdd_hollow.h) and PlanBuilder, which records a forward as a flat list of pre-bound
-libctdd launches -- linear layers on the GEMM kernels per engine precision, LayerNorm (+ FiLM), attention."""
+hollow-transformer entry points (include/ctdd_hollow.h); PlanBuilder, which records a forward as a flat list of pre-bound
+libctdd launches -- linear layers on the GEMM kernels per engine precision, LayerNorm (+ FiLM), attention, and out of those the
+prenorm encoder block (encoder_blocks) and the FiLM residual readout (film_readout) that both networks are made of; and
+PlanEngine, the wrapper that caches one plan per (batch, state dtype), warms it, captures it and replays it."""
 import ctypes as C
 import math
+import types
 
 import torch
 
-from .plan_launch import bound_launch, patch_gemm_tiles, ptr
+from . import native
+from .plan_launch import bound_launch, graph_capture, patch_gemm_tiles, ptr, unwrap
 from .unet_engine import _ConvArgs, _lib as _unet_lib, SEG_1x1
 
 _P, _I, _F, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
@@ -180,3 +184,127 @@ class PlanBuilder:
         if fn is None:                                  # (fn: another entry point with the same argument block)
             fn = lib.ctdd_hollow_attention_bf16 if (fast and hd in (16, 32) and getattr(m, "engine_attention", "mfma") == "mfma") else lib.ctdd_hollow_attention
         self.launch(fn, C.byref(a), label=f"attention mode {mode} {Tq}x{Tk}")
+
+    def encoder_buffers(self, R):
+        """The work buffers of encoder_blocks over R token rows (kept alive): LayerNorm output, packed qkv, attention context
+        and MLP hidden rows in fp32, and the hi / lo bf16 operand twins of all but qkv."""
+        E, mlp, fast, f32, hi, lo = self.E, self.m.mlp_dim, self.fast, self.f32, self.hi, self.lo
+        b = types.SimpleNamespace(ln=None if fast else f32(R, E), qkv=f32(R, 3 * E), ctx=None if fast else f32(R, E),
+                                  hid=None if fast else f32(R, mlp))
+        b.ln_hi, b.ctx_hi, b.hid_hi = hi(R, E), hi(R, E), hi(R, mlp)
+        b.ln_lo, b.ctx_lo, b.hid_lo = lo(R, E), lo(R, E), lo(R, mlp)
+        self.keep.extend(vars(b).values())
+        return b
+
+    def encoder_blocks(self, x, layers, seqs, T, mode, bufs, attention_fn=None):
+        """The prenorm transformer blocks `layers` over the residual stream x (seqs, T, E), in place: LayerNorm -> qkv linear ->
+        attention `mode` over the T tokens of every sequence -> out-proj + x -> LayerNorm -> fc1 (ReLU) -> fc2 + x.
+        bufs: encoder_buffers(seqs * T); attention_fn: another attention entry point (PlanBuilder.attention's fn)."""
+        E, mlp, P, b, linear, layernorm = self.E, self.m.mlp_dim, self.P, bufs, self.linear, self.layernorm
+        R = seqs * T
+        for blk in layers:
+            sa, ff = blk.self_attention_block, blk.feed_forward_block
+            mha = sa.self_attention
+            layernorm(x, T * E, T, E, sa.norm, b.ln, T * E, out_hi=b.ln_hi, out_hi_bs=T * E, out_lo=b.ln_lo, B=seqs)
+            linear(b.ln, R, E, mha.in_proj_weight, mha.in_proj_bias, b.qkv, label="qkv", x_hi=b.ln_hi, x_lo=b.ln_lo)
+            self.attention(P(b.qkv), T * 3 * E, 3 * E, P(b.qkv) + 4 * E, T * 3 * E, 3 * E, P(b.qkv) + 8 * E, T * 3 * E, 3 * E, T, T, mode, b.ctx,
+                           out_hi=b.ctx_hi, out_lo=b.ctx_lo, B=seqs, fn=attention_fn)
+            linear(b.ctx, R, E, mha.out_proj.weight, mha.out_proj.bias, x, res=x, label="attn out", x_hi=b.ctx_hi, x_lo=b.ctx_lo)   # in place: + inputs
+            layernorm(x, T * E, T, E, ff.norm, b.ln, T * E, out_hi=b.ln_hi, out_hi_bs=T * E, out_lo=b.ln_lo, B=seqs)
+            linear(b.ln, R, E, ff.mlp.fc1.weight, ff.mlp.fc1.bias, b.hid, act=1, label="fc1", x_hi=b.ln_hi, x_lo=b.ln_lo, out_hi=b.hid_hi,
+                   out_lo=b.hid_lo)
+            linear(b.hid, R, mlp, ff.mlp.fc2.weight, None, x, res=x, label="fc2", x_hi=b.hid_hi, x_lo=b.hid_lo)
+
+    def film_readout(self, rr, xr, xr_hi, xr_lo, temb, B, Dp):
+        """The FiLM residual readout `rr` (hollow_networks.py: ResidualReadout) over the B * Dp rows xr (fp32 and / or hi, lo) with
+        the per-sample time embedding temb (B, E) -> the logits buffer (B, Dp, out_dim)."""
+        E, mlp, fast, f32, hi, lo, keep, linear = self.E, self.m.mlp_dim, self.fast, self.f32, self.hi, self.lo, self.keep, self.linear
+        R, E2 = B * Dp, 2 * E
+        tm_h, tm = f32(B, mlp), f32(B, 4 * E)
+        lin = [l for l in rr.mlp.layers if isinstance(l, torch.nn.Linear)]
+        linear(temb, B, E, lin[0].weight, lin[0].bias, tm_h, act=2, label="temb mlp 1")
+        linear(tm_h, B, mlp, lin[1].weight, lin[1].bias, tm, label="temb mlp 2")
+        h, r, rh = f32(R, E2), f32(R, E2), (None if fast else f32(R, mlp))
+        h_hi, rh_hi, h_lo, rh_lo = hi(R, E2), hi(R, mlp), lo(R, E2), lo(R, mlp)
+        keep.extend([tm_h, tm, h, r, rh, h_hi, rh_hi, h_lo, rh_lo])
+        linear(xr, R, E, rr.input_layer.weight, rr.input_layer.bias, h, label="readout in", x_hi=xr_hi, x_lo=xr_lo, out_hi=h_hi, out_lo=h_lo)
+        for i in range(rr.n_res):
+            mlp_i, ln_i = rr.resid_layers[2 * i], rr.resid_layers[2 * i + 1]
+            li = [l for l in mlp_i.layers if isinstance(l, torch.nn.Linear)]
+            linear(h, R, E2, li[0].weight, li[0].bias, rh, act=2, label="resid 1", x_hi=h_hi, x_lo=h_lo, out_hi=rh_hi, out_lo=rh_lo)
+            linear(rh, R, mlp, li[1].weight, li[1].bias, r, label="resid 2", x_hi=rh_hi, x_lo=rh_lo)
+            fl = f32(B, 4 * E)                          # one per iteration: the plan keeps them alive across graph replay
+            keep.append(fl)
+            linear(tm, B, 4 * E, rr.film_layer[i].weight, rr.film_layer[i].bias, fl, label="film")          # per-sample path: fp32
+            self.layernorm(h, Dp * E2, Dp, E2, ln_i, h, Dp * E2, y=r, y_bs=Dp * E2, film=fl, film_stride=4 * E, out_hi=h_hi, out_hi_bs=Dp * E2,
+                           out_lo=h_lo, B=B)
+        logits = f32(B, Dp, rr.out_dim)
+        linear(h, R, E2, rr.logits_layer.weight, rr.logits_layer.bias, logits, label="logits", x_hi=h_hi, x_lo=h_lo)
+        return logits
+
+
+class PlanEngine:
+    """The inference engine around a plan: subclasses give `_build(B, x_dtype)`, which returns a plan object with the input
+    buffers x_in, t_in, the output buffer logits and -- for the default `_run` / `_capture` -- one launch list `plan` and
+    `graph = None`.  One plan per (batch, state dtype), dropped when the weights move.
+
+    precision "fp32": exact-fp32 matrix instructions and fp32 FMA attention; "bf16": bf16 operands (~1e-3 absolute on the logits);
+    "bf16x3" (default): every GEMM / attention operand as a hi + lo bf16 pair, three bf16 products per contraction with fp32
+    accumulation (x w ~ xh wh + xl wh + xh wl, dropped terms ~2^-17 relative): fp32-grade logits at bf16 matrix rates.
+    model.engine_bf16_linears: names of linear layers (the labels given to PlanBuilder.linear: "qkv", "attn out", "fc1", "fc2", ...) that take ONE bf16 product
+    in the bf16x3 mode (their inputs' hi parts against the weights' hi parts): a third of their matrix work for a measured logit
+    error between the two pure modes (tests/test_gpu_hollow.py states it per setting)."""
+
+    def __init__(self, model, precision=None):
+        self.model, self.net = model, unwrap(model.net)
+        self.precision = precision or getattr(self.net.config.model, "engine_precision", "bf16x3")
+        if self.precision not in ("fp32", "bf16", "bf16x3"):
+            raise ValueError(f"unknown engine precision {self.precision}")
+        self.fast = self.precision in ("bf16", "bf16x3")
+        self.split = self.precision == "bf16x3"
+        self.single = set(getattr(self.net.config.model, "engine_bf16_linears", ()) or ())
+        self.dev = next(self.net.parameters()).device
+        if self.dev.type != "cuda":
+            raise native.CtddError(f"{type(self).__name__} needs the model on a GPU")
+        self._plans, self._wver = {}, None
+
+    def _weights_version(self):
+        return sum(p._version for p in self.net.parameters()) + 7919 * getattr(self.model, "_weights_version", 0)
+
+    @staticmethod
+    def _run(st):
+        if st.graph is not None:
+            st.graph.replay()
+        else:
+            for step in st.plan:
+                step()
+
+    @staticmethod
+    def _capture(st):
+        g = torch.cuda.CUDAGraph()
+        with graph_capture(g):
+            for step in st.plan:
+                step()
+        st.graph = g
+
+    def __call__(self, x, times):
+        key = (x.shape[0], x.dtype)
+        ver = self._weights_version()
+        if ver != self._wver:
+            self._plans.clear()
+            self._wver = ver
+        st = self._plans.get(key)
+        if st is None:
+            # build (which refuses other than integer states) -> inputs -> eager warm run -> synchronize -> capture: in this
+            # order, so that nothing of the warm run is in flight when the capture begins (plan_launch.graph_capture)
+            st = self._plans[key] = self._build(*key)
+            st.x_in.copy_(x.reshape(st.x_in.shape))
+            st.t_in.copy_(times.float())
+            self._run(st)
+            torch.cuda.synchronize()
+            if getattr(self.net.config.model, "engine_graph", True):
+                self._capture(st)
+        st.x_in.copy_(x.reshape(st.x_in.shape))
+        st.t_in.copy_(times.float())
+        self._run(st)
+        return st.logits

@@ -1,5 +1,6 @@
-"""What every plan builder shares (ctdd/unet_engine.py, ctdd/plan_common.py, ctdd/hollow_train.py): the pointer helper, the
-pre-bound launch a plan is a list of, and the tile pick of the patch kernel run as a plain GEMM."""
+"""What every engine and trainer shares (ctdd/unet_engine.py, ctdd/plan_common.py, ctdd/hollow_train.py and the modules built on
+them): the pointer helpers, the network behind a DistributedDataParallel wrapper, the pre-bound launch a plan is a list of, graph
+capture, and the tile pick of the patch kernel run as a plain GEMM."""
 import contextlib
 import gc
 
@@ -10,6 +11,21 @@ from . import native
 
 def ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def unwrap(net):
+    """cfg.distributed wraps the network in DistributedDataParallel (models.py:104-107); the engines read the module behind it."""
+    return net.module if hasattr(net, "module") and net.__class__.__name__ == "DistributedDataParallel" else net
+
+
+def set_state_ptr(args, x, who):
+    """Point the x64 / x32 pair of an argument block at the integer states x; `who` names the caller in the error."""
+    if x.dtype == torch.int64:
+        args.x64 = x.data_ptr()
+    elif x.dtype == torch.int32:
+        args.x32 = x.data_ptr()
+    else:
+        raise native.CtddError(f"{who} expects integer states, got {x.dtype}")
 
 
 def bound_launch(fn, *args, label=None, flops=0):

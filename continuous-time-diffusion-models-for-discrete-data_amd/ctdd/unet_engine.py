@@ -19,7 +19,7 @@ import ctypes as C
 import torch
 
 from . import native
-from .plan_launch import bound_launch, graph_capture, ptr
+from .plan_launch import bound_launch, graph_capture, ptr, unwrap as _unwrap
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SEG_3x3, SEG_1x1, SEG_3x3_S2, SEG_3x3_UP = 0, 1, 2, 3
@@ -97,11 +97,6 @@ def _lib():
             fn.argtypes, fn.restype = argt, _I
         _sigs_done = True
     return lib
-
-
-def _unwrap(net):
-    """cfg.distributed wraps the network in DistributedDataParallel (models.py:104-107); the engine reads the module behind it."""
-    return net.module if hasattr(net, "module") and net.__class__.__name__ == "DistributedDataParallel" else net
 
 
 def supports(model):

@@ -239,7 +239,7 @@ def test_masked_train_dropout_streams_are_consistent(golden, monkeypatch):
     regenerates the forward's Philox masks (analytic directional derivative against a central finite difference with the SAME step
     counter), the same step gives the same loss, the next step another, two chunks of one forward do not carry the same
     residual-dropout mask, and eval mode equals the golden logits."""
-    from ctdd import masked_train as mt
+    from ctdd import hollow_train as ht, masked_train as mt
     cfg, model, x, t, ref = tiny_model(golden, "mask_a", "cuda")
     _set_dropout(cfg, model, 0.2, 0.2)
     cfg.model.enum_chunk = 7
@@ -259,8 +259,8 @@ def test_masked_train_dropout_streams_are_consistent(golden, monkeypatch):
                 first.append((t_.detach(), out.detach()))
             return out
 
-    mt_DropoutFn = mt.DropoutFn
-    monkeypatch.setattr(mt, "DropoutFn", Recording)
+    mt_DropoutFn = ht.DropoutFn                           # (the trainers' dropout sites live in hollow_train.Forward)
+    monkeypatch.setattr(ht, "DropoutFn", Recording)
 
     def loss_at(step):
         tr.rng[1] = step                                  # the forward bumps it: chunk i draws the masks of step + 1 + i
