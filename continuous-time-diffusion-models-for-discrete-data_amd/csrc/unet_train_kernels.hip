@@ -1265,14 +1265,22 @@ extern "C" int ctdd_unet_wgrad(const void* table_dev, const void* table_host, in
   return finish_launch("k_wgrad");
 }
 
-extern "C" int ctdd_unet_gn_bwd(const void* args_, void* stream) {
-  const GnBwdArgs& a = *(const GnBwdArgs*)args_;
+// Which kernel a GroupNorm backward call runs, and on what geometry: the argument checks and the selection rule of
+// ctdd_unet_gn_bwd as pure host code, so that ctdd_unet_gn_bwd_plan answers without a device.
+struct GnBwdPlan {
+  int variant;   // 0: k_gn_bwd_sums + k_gn_bwd_dx;  2 / 4 / 8: k_gn_bwd_onepass<MAXV>
+  int slabC;     // channels per workgroup (two-pass: all of them)
+  int noct;      // 8-channel vectors per workgroup
+  int npl;       // pixel lanes
+  int gx;        // pixel slices per sample (one-pass: 1)
+};
+static int gn_bwd_plan(const GnBwdArgs& a, GnBwdPlan& p) {
   const int C = a.C1 + a.C2;
-  CTDD_REQUIRE(C % 8 == 0 && a.C1 % 8 == 0 && C % a.G == 0 && C <= 2048 && a.sums, CTDD_EINVAL, "gn bwd: C=%d C1=%d G=%d", C, a.C1, a.G);
+  CTDD_REQUIRE(a.G > 0 && C > 0 && C % 8 == 0 && a.C1 % 8 == 0 && C % a.G == 0 && C <= 2048 && a.sums, CTDD_EINVAL, "gn bwd: C=%d C1=%d G=%d", C, a.C1,
+               a.G);
   CTDD_REQUIRE((a.s1_f32 || a.s1_bf16) && (a.da_f32 || a.da_bf16) && (a.d1_f32 || a.d1_bf16), CTDD_EINVAL, "gn bwd: null tensor");
   CTDD_REQUIRE(!(a.dsum_bn || a.dsum_n) || a.C2 == 0, CTDD_EINVAL, "gn bwd: per-sample sums of dX are for a single source");
   CTDD_REQUIRE(a.drop_p >= 0.0f && a.drop_p < 1.0f && (a.drop_p == 0.0f || a.rng), CTDD_EINVAL, "gn bwd: dropout p=%g", (double)a.drop_p);
-  hipStream_t st = (hipStream_t)stream;
   // bf16 tensors: one launch, a workgroup per (sample, slab of whole groups) when such a slab fits the registers
   // (<= 8 vectors of 8 channels per thread at <= 512 threads); CTDD_GN_BWD_TWO_PASS=1 keeps the two launches (A/B runs)
   static const bool two_pass = [] { const char* e = getenv("CTDD_GN_BWD_TWO_PASS"); return e && e[0] == '1'; }();
@@ -1293,26 +1301,52 @@ extern "C" int ctdd_unet_gn_bwd(const void* args_, void* stream) {
       if (wgs < 256) break;
     }
     if (best > 0) {
-      const int threads = max(64, ((bo * bp + 63) / 64) * 64);
-      const size_t lds = (size_t)bo * bp * 80 + (size_t)8 * best * sizeof(float);      // (80-byte thread records: PST)
-      const dim3 g((unsigned)a.B, (unsigned)(C / best));
-      static bool attr_done[3][16] = {};
-      auto go = [&](auto kernel, int slot) {
-        ensure_lds_ceiling((const void*)kernel, attr_done[slot]);
-        hipLaunchKernelGGL(kernel, g, dim3(threads), lds, st, a, best, bo, bp);
-      };
-      if (bv <= 2) go(k_gn_bwd_onepass<2>, 0);
-      else if (bv <= 4) go(k_gn_bwd_onepass<4>, 1);
-      else go(k_gn_bwd_onepass<8>, 2);
-      return finish_launch("k_gn_bwd_onepass");
+      p.variant = bv <= 2 ? 2 : bv <= 4 ? 4 : 8;
+      p.slabC = best; p.noct = bo; p.npl = bp; p.gx = 1;
+      return CTDD_OK;
     }
   }
   const int vpp = C / 8, lanes = 256 / vpp;
   // ~8 pixels per thread and pass: slices of 8 * lanes pixels, at most ~1024 workgroups
-  const int gx = max(1, min((a.HW + 8 * lanes - 1) / (8 * lanes), max(1, 1024 / max(a.B, 1))));
-  hipLaunchKernelGGL(k_gn_bwd_sums, dim3(gx, a.B), dim3(256), (size_t)(8 * C + 256 * 16) * sizeof(float), st, a);
+  p.variant = 0; p.slabC = C; p.noct = vpp; p.npl = lanes;
+  p.gx = max(1, min((a.HW + 8 * lanes - 1) / (8 * lanes), max(1, 1024 / max(a.B, 1))));
+  return CTDD_OK;
+}
+extern "C" int ctdd_unet_gn_bwd_plan(const void* args_, int* out5) {
+  CTDD_REQUIRE(args_ && out5, CTDD_EINVAL, "gn bwd plan: null argument");
+  GnBwdPlan p;
+  if (int rc = gn_bwd_plan(*(const GnBwdArgs*)args_, p)) return rc;
+  out5[0] = p.variant; out5[1] = p.slabC; out5[2] = p.noct; out5[3] = p.npl; out5[4] = p.gx;
+  return CTDD_OK;
+}
+
+extern "C" int ctdd_unet_gn_bwd(const void* args_, void* stream) {
+  const GnBwdArgs& a = *(const GnBwdArgs*)args_;
+  GnBwdPlan p;
+  if (int rc = gn_bwd_plan(a, p)) return rc;
+  const int C = a.C1 + a.C2;
+  hipStream_t st = (hipStream_t)stream;
+  if (p.variant) {
+    const int threads = max(64, ((p.noct * p.npl + 63) / 64) * 64);
+    const size_t lds = (size_t)p.noct * p.npl * 80 + (size_t)8 * p.slabC * sizeof(float);      // (80-byte thread records: PST)
+    const dim3 g((unsigned)a.B, (unsigned)(C / p.slabC));
+    static bool attr_done[3][16] = {};
+    auto go = [&](auto kernel, int slot) {
+      ensure_lds_ceiling((const void*)kernel, attr_done[slot]);
+      hipLaunchKernelGGL(kernel, g, dim3(threads), lds, st, a, p.slabC, p.noct, p.npl);
+    };
+    if (p.variant == 2) go(k_gn_bwd_onepass<2>, 0);
+    else if (p.variant == 4) go(k_gn_bwd_onepass<4>, 1);
+    else go(k_gn_bwd_onepass<8>, 2);
+    return finish_launch("k_gn_bwd_onepass");
+  }
+  // (above C = 1365 / 1536 the two kernels' tables pass the 64 KiB a launch gets without asking)
+  static bool sums_done[16] = {}, dx_done[16] = {};
+  ensure_lds_ceiling((const void*)k_gn_bwd_sums, sums_done);
+  hipLaunchKernelGGL(k_gn_bwd_sums, dim3(p.gx, a.B), dim3(256), (size_t)(8 * C + 256 * 16) * sizeof(float), st, a);
   if (int rc = finish_launch("k_gn_bwd_sums")) return rc;
-  hipLaunchKernelGGL(k_gn_bwd_dx, dim3(gx, a.B), dim3(256), (size_t)(8 * C + 4 * C) * sizeof(float), st, a);
+  ensure_lds_ceiling((const void*)k_gn_bwd_dx, dx_done);
+  hipLaunchKernelGGL(k_gn_bwd_dx, dim3(p.gx, a.B), dim3(256), (size_t)(8 * C + 4 * C) * sizeof(float), st, a);
   return finish_launch("k_gn_bwd_dx");
 }
 
@@ -1372,23 +1406,43 @@ extern "C" int ctdd_unet_cast_rows(const float* in, int64_t rows, int n, int ld_
   return finish_launch("k_cast_rows");
 }
 
+// Which attention backward kernel a call runs (t4: the 4 x 4 register-tile kernel) and its dynamic LDS bytes: the checks and the
+// rule of ctdd_unet_attention_bwd as pure host code (ctdd_unet_attention_bwd_plan answers without a device).
+static int attn_bwd_plan(const AttnBwdArgs& a, int& t4, size_t& lds) {
+  CTDD_REQUIRE(a.qkv && (a.d_out_f32 || a.d_out_bf16) && (a.d_qkv || a.d_qkv_bf16) && a.heads > 0 && a.T > 0 && a.C > 0 && a.C % a.heads == 0,
+               CTDD_EINVAL, "attention bwd: bad arguments");
+  const int ch = a.C / a.heads, Tp = (a.T + 3) & ~3;
+  const size_t lds4 = ((size_t)4 * ch * Tp + (size_t)3 * a.T * ch + (size_t)3 * a.T * Tp) * sizeof(float);
+  static const bool old_attn = [] { const char* e = getenv("CTDD_ATTN_SMALL_OLD"); return e && e[0] == '1'; }();    // (A/B)
+  if (!old_attn && ch % 4 == 0 && a.C % 4 == 0 && lds4 <= 160 * 1024) {
+    t4 = 1; lds = lds4;
+    return CTDD_OK;
+  }
+  t4 = 0;
+  lds = ((size_t)4 * a.T * ch + (size_t)2 * a.T * a.T) * sizeof(float);
+  CTDD_REQUIRE(lds <= 160 * 1024, CTDD_ERANGE, "attention bwd tile too large (T=%d)", a.T);
+  return CTDD_OK;
+}
+extern "C" int ctdd_unet_attention_bwd_plan(const void* args_, int* out2) {
+  CTDD_REQUIRE(args_ && out2, CTDD_EINVAL, "attention bwd plan: null argument");
+  int t4 = 0;
+  size_t lds = 0;
+  if (int rc = attn_bwd_plan(*(const AttnBwdArgs*)args_, t4, lds)) return rc;
+  out2[0] = t4; out2[1] = (int)lds;
+  return CTDD_OK;
+}
+
 extern "C" int ctdd_unet_attention_bwd(const void* args_, void* stream) {
   const AttnBwdArgs& a = *(const AttnBwdArgs*)args_;
-  CTDD_REQUIRE(a.qkv && (a.d_out_f32 || a.d_out_bf16) && (a.d_qkv || a.d_qkv_bf16) && a.C % a.heads == 0, CTDD_EINVAL, "attention bwd: bad arguments");
-  const int ch = a.C / a.heads;
-  {
-    const int Tp = (a.T + 3) & ~3;
-    const size_t lds4 = (size_t)(4 * ch * Tp + 3 * a.T * ch + 3 * a.T * Tp) * sizeof(float);
-    static const bool old_attn = [] { const char* e = getenv("CTDD_ATTN_SMALL_OLD"); return e && e[0] == '1'; }();    // (A/B)
-    if (!old_attn && ch % 4 == 0 && a.C % 4 == 0 && lds4 <= 160 * 1024) {
-      static bool done4[16] = {};
-      ensure_lds_ceiling((const void*)k_attn_small_bwd_t4, done4);
-      hipLaunchKernelGGL(k_attn_small_bwd_t4, dim3(a.B * a.heads), dim3(256), lds4, (hipStream_t)stream, a);
-      return finish_launch("k_attn_small_bwd_t4");
-    }
+  int t4 = 0;
+  size_t lds = 0;
+  if (int rc = attn_bwd_plan(a, t4, lds)) return rc;
+  if (t4) {
+    static bool done4[16] = {};
+    ensure_lds_ceiling((const void*)k_attn_small_bwd_t4, done4);
+    hipLaunchKernelGGL(k_attn_small_bwd_t4, dim3(a.B * a.heads), dim3(256), lds, (hipStream_t)stream, a);
+    return finish_launch("k_attn_small_bwd_t4");
   }
-  const size_t lds = (size_t)(4 * a.T * ch + 2 * a.T * a.T) * sizeof(float);
-  CTDD_REQUIRE(lds <= 160 * 1024, CTDD_ERANGE, "attention bwd tile too large (T=%d)", a.T);
   static bool done[16] = {};
   ensure_lds_ceiling((const void*)k_attn_small_bwd, done);
   hipLaunchKernelGGL(k_attn_small_bwd, dim3(a.B * a.heads), dim3(256), lds, (hipStream_t)stream, a);

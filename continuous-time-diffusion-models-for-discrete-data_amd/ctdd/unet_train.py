@@ -62,7 +62,8 @@ class _PackEntry(C.Structure):
 
 TRAIN_EXPORTS = ("ctdd_unet_wgrad", "ctdd_unet_gn_bwd", "ctdd_unet_dropout", "ctdd_unet_colsum", "ctdd_unet_sum_batch", "ctdd_unet_sum_jobs", "ctdd_unet_accumulate",
                  "ctdd_unet_downsum2x", "ctdd_unet_upsample2x_f32", "ctdd_unet_cast_rows", "ctdd_unet_attention_bwd",
-                 "ctdd_unet_first_conv_wgrad", "ctdd_unet_first_conv_wgrad_scratch", "ctdd_unet_pack_weights", "ctdd_unet_unpack_grads")
+                 "ctdd_unet_first_conv_wgrad", "ctdd_unet_first_conv_wgrad_scratch", "ctdd_unet_pack_weights", "ctdd_unet_unpack_grads",
+                 "ctdd_unet_gn_bwd_plan", "ctdd_unet_attention_bwd_plan")
 _sigs_done = False
 
 
@@ -71,6 +72,7 @@ def lib():
     l = _lib()
     if not _sigs_done:
         for name, argt in (("ctdd_unet_wgrad", [_P, _P, _I, _I, _P]), ("ctdd_unet_gn_bwd", [_P, _P]),
+                           ("ctdd_unet_gn_bwd_plan", [_P, _P]), ("ctdd_unet_attention_bwd_plan", [_P, _P]),
                            ("ctdd_unet_dropout", [_P, _P, _I64, _F, _P, _U64, _P]),
                            ("ctdd_unet_colsum", [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P]),
                            ("ctdd_unet_sum_batch", [_P, _I, _I64, _I, _I, _P, _I, _P]),

@@ -62,6 +62,11 @@ typedef struct {
                                                                              += into dsum_n[c]: the time-projection / conv1-bias gradients (unet.py:110,131) */
 } ctdd_gn_bwd_args;
 int ctdd_unet_gn_bwd(const void* gn_bwd_args, void* stream);
+/* Which kernel that call runs, from host code alone (no device is touched; same argument checks and status codes):
+ * out5 = {variant: 0 the two launches, 2 / 4 / 8 the one-launch kernel with that many pixel vectors per thread,
+ *         channels per workgroup, 8-channel vectors per workgroup, pixel lanes, pixel slices per sample (one launch: 1)}.
+ * bf16 tensors take the one-launch kernel when a slab of whole groups fits it; CTDD_GN_BWD_TWO_PASS=1 keeps the two launches. */
+int ctdd_unet_gn_bwd_plan(const void* gn_bwd_args, int* out5);
 /* the forward side of that dropout, in place on the activated tensor: a *= keep / (1 - p); same mask rule */
 int ctdd_unet_dropout(float* a_f32, void* a_bf16, int64_t n, float p, const uint64_t* rng, uint64_t layer, void* stream);
 
@@ -85,6 +90,10 @@ int ctdd_unet_cast_rows(const float* in, int64_t rows, int n, int ld_in, int ld_
 /* mid-block attention backward (unet.py:176-200): d_out [B][T][C] -> d_qkv [B][T][3C] (fp32 and/or bf16) */
 typedef struct { const float* qkv; const float* d_out_f32; const void* d_out_bf16; int B, T, C, heads; float* d_qkv; void* d_qkv_bf16; } ctdd_attn_bwd_args;
 int ctdd_unet_attention_bwd(const void* attn_bwd_args, void* stream);
+/* Which kernel that call runs, from host code alone: out2 = {1: 4 x 4 register tiles (head width a multiple of 4, tables within
+ * 160 KiB of LDS) | 0: a thread per score, dynamic LDS bytes}; CTDD_ERANGE where the call refuses (neither kernel's tables fit).
+ * CTDD_ATTN_SMALL_OLD=1 keeps the thread-per-score kernel. */
+int ctdd_unet_attention_bwd_plan(const void* attn_bwd_args, int* out2);
 
 /* weight (torch layout [Cout][Cin][3][3]) and bias gradient of the first conv on the centred integer state (unet.py:343) */
 typedef struct { const int64_t* x64; const int32_t* x32; float lo, hi; const float* dy_f32; const void* dy_bf16;

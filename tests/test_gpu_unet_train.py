@@ -211,8 +211,9 @@ def test_dropout_mask_is_shared_by_forward_and_backward():
 
 @pytest.mark.parametrize("B,T,Cc,heads", [(3, 49, 64, 4), (2, 49, 192, 8), (2, 50, 48, 2), (2, 16, 192, 1)])
 def test_attention_backward(B, T, Cc, heads):
-    """ctdd_unet_attention_bwd (k_attn_small_bwd_t4 where its tables fit the LDS, the thread-per-score kernel otherwise) against autograd
-    through the reference's attention; token counts off the 4 x 4 tile size included."""
+    """ctdd_unet_attention_bwd against fp32 autograd through the reference's attention; token counts off the 4 x 4 tile size
+    included.  All four shapes take k_attn_small_bwd_t4 with fp32 d_out and d_qkv: the thread-per-score kernel, the bf16 input and
+    output and the refusal are in test_gpu_unet_bwd_fp64.py (against fp64, the kernel asserted through the plan query)."""
     from ctdd import unet_train as ut
     lib = ut.lib()
     g = torch.Generator(device="cuda").manual_seed(0)
