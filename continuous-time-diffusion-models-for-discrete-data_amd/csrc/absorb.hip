@@ -2,8 +2,9 @@
 // gradient (ctdd_absorb_elbo_loss), one reverse step (ctdd_absorb_step) and the two halves of a confidence-ordered step: a candidate
 // and a score per masked row (ctdd_absorb_propose, the step's layout and pick), then a per-sample top-k of the scores by radix select
 // (ctdd_absorb_commit); and the terms of the held-out likelihood bounds, a row pass and a deterministic per-sample fp64 sum
-// (ctdd_absorb_nll).  include/ctdd_absorb.h states the formulas, the Philox counter layouts, the key that orders the scores and the
-// order of that sum.
+// (ctdd_absorb_nll); and the step with remasking (ctdd_absorb_remask_step: the step's layout and pick, held rows, a remask coin for
+// committed rows, the confidence a row committed at) with its per-sample normaliser (ctdd_absorb_remask_norm).
+// include/ctdd_absorb.h states the formulas, the Philox counter layouts, the key that orders the scores and the order of the sums.
 //
 // Loss and step are row softmaxes over a row that fits in registers.  A row is owned by a group of LPR lanes of one wave, lane j of
 // the group holding the PER consecutive states PER j .. PER j + PER - 1 (float4 loads when S % 4 == 0); 64 / LPR rows per wave,
@@ -519,6 +520,132 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_nll_sum(const AbsorbNllSumA
   }
 }
 
+// ---------------------------------------------------------------- one reverse step with remasking
+struct AbsorbRemaskArgs {
+  const float* logits;
+  const int32_t* x;
+  const uint8_t* held;        // or nullptr
+  const float* conf_in;       // or nullptr (with conf_out)
+  const float* norm;          // (N, 2) or nullptr
+  int64_t rows;
+  int D, S, mask_state;
+  int vec;
+  float p, sigma, temp;
+  uint32_t flags;
+  uint64_t seed, offset;
+  int32_t* out_x;
+  float* conf_out;
+  int32_t* counts;
+};
+
+// k_absorb_step's grid, row ownership, Philox block and pick, so a masked row ends where the plain step puts it.  A held row and a
+// free unmasked row read no logits; an unmasked row computes its Philox block (for component 3) only when sigma > 0.  Every lane of
+// a row's group reads x / held / conf_in of the row before lane 0 of the group writes the row's outputs (one wave, in program
+// order): out_x == x and conf_out == conf_in are fine.
+template <int LPR, int PER>
+__global__ __launch_bounds__(64 * AWV) void k_absorb_remask_step(const AbsorbRemaskArgs a) {
+  __shared__ int red[2][AWV];
+  constexpr int RPW = WAVE / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane % LPR, s0 = j * PER, S = a.S, m = a.mask_state;
+  const int64_t row = ((int64_t)blockIdx.x * AWV + wave) * RPW + lane / LPR;
+  const bool in = row < a.rows, by_conf = (a.flags & CTDD_ABSORB_REMASK_CONF) != 0;
+  const int xo = in ? a.x[row] : 0;
+  const bool hd = in && a.held && a.held[row] != 0;
+  const float ci = (in && a.conf_in) ? a.conf_in[row] : 0.0f;
+  const bool masked = in && !hd && xo == m, placed = in && !hd && xo != m;   // (uniform over the row's group)
+  bool need = masked, remask = false;
+  float u1 = 0.0f;
+  if (masked || (placed && a.sigma > 0.0f)) {
+    const u4 r = philox_row(a.seed, a.offset, (uint64_t)row, 0u);
+    if (masked) {
+      need = u01(r.x) < a.p;
+      u1 = u01(r.y);
+    } else {
+      float sg = a.sigma;
+      if (by_conf) {
+        const float U = a.norm[2 * (row / a.D)], Z = a.norm[2 * (row / a.D) + 1];
+        sg = Z > 0.0f ? fminf(1.0f, ((a.sigma * U) * expf(-ci / a.temp)) / Z) : 0.0f;
+      }
+      remask = u01(r.w) < sg;
+    }
+  }
+  float v[PER];
+  absorb_load<PER>(a.logits + (size_t)(in ? row : 0) * S, S, s0, m, a.vec, need, v);
+  float mx, z;
+  const int pick = absorb_pick<LPR, PER>(v, S, m, j, false, u1, mx, z);
+  float co = ci;                                                // held and kept rows: the bits that came in
+  if (a.conf_out) {                                             // (uniform)
+    float lc = 0.0f;                                            // l[pick] - mx: one lane of the group holds it
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if (s0 + k == pick) lc = v[k] - mx;
+    lc = grp_sum<LPR>(lc);
+    if (masked) co = need ? expf(lc) / z : 0.0f;
+    else if (remask) co = 0.0f;
+  }
+  if (in && j == 0) {
+    a.out_x[row] = need ? pick : (remask ? m : xo);
+    if (a.conf_out) a.conf_out[row] = co;
+  }
+  if (a.counts) {                                               // (uniform)
+    int nu = (need && j == 0) ? 1 : 0, nr = (remask && j == 0) ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      nu += __shfl_xor(nu, o, WAVE);
+      nr += __shfl_xor(nr, o, WAVE);
+    }
+    if (lane == 0) { red[0][wave] = nu; red[1][wave] = nr; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int tu = 0, tr = 0;
+#pragma unroll
+      for (int i = 0; i < AWV; ++i) { tu += red[0][i]; tr += red[1][i]; }
+      if (tu) atomicAdd(a.counts, tu);
+      if (tr) atomicAdd(a.counts + 1, tr);
+    }
+  }
+}
+
+struct AbsorbRemaskNormArgs {
+  const int32_t* x;
+  const uint8_t* held;
+  const float* conf;
+  int D, mask_state;
+  float temp;
+  float* out;
+};
+
+// One workgroup (256 threads) per sample, no atomics, k_absorb_nll_sum's order: thread i adds its rows d = i, i + 256, .. in
+// ascending d (the weights in fp64, the count as an integer), the xor butterfly over the wave, thread 0 adds the waves in wave order.
+__global__ __launch_bounds__(64 * AWV) void k_absorb_remask_norm(const AbsorbRemaskNormArgs a) {
+  __shared__ double red[AWV];
+  __shared__ int cnt[AWV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, D = a.D;
+  const size_t base = (size_t)blockIdx.x * D;
+  double t = 0.0;
+  int u = 0;
+  for (int d = tid; d < D; d += 64 * AWV)
+    if (a.x[base + d] != a.mask_state && !(a.held && a.held[base + d] != 0)) {
+      t += (double)expf(-a.conf[base + d] / a.temp);
+      ++u;
+    }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    t += __shfl_xor(t, o, WAVE);
+    u += __shfl_xor(u, o, WAVE);
+  }
+  if (lane == 0) { red[wave] = t; cnt[wave] = u; }
+  __syncthreads();
+  if (tid == 0) {
+    double tot = red[0];
+    int n = cnt[0];
+#pragma unroll
+    for (int i = 1; i < AWV; ++i) { tot += red[i]; n += cnt[i]; }
+    a.out[2 * (size_t)blockIdx.x] = (float)n;
+    a.out[2 * (size_t)blockIdx.x + 1] = (float)tot;
+  }
+}
+
 // (LPR, PER) of a row width; rows per workgroup = AWV * 64 / LPR
 #define ABSORB_SHAPE(S, CALL)                                                       \
   if ((S) <= 4) { constexpr int LPR = 1, PER = 4; CALL; }                           \
@@ -624,4 +751,38 @@ extern "C" int ctdd_absorb_nll(const float* logits, const int32_t* x0, const int
   AbsorbNllSumArgs b = {row_nll, w, D, out_nll};
   hipLaunchKernelGGL(k_absorb_nll_sum, dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, b);
   return finish_launch("k_absorb_nll_sum");
+}
+
+extern "C" int ctdd_absorb_remask_step(const float* logits, const int32_t* x, const uint8_t* held, const float* conf_in, const float* norm, int N,
+                                       int D, int S, int mask_state, float p_unmask, float sigma, float temp, uint32_t flags, uint64_t seed,
+                                       uint64_t offset, int32_t* out_x, float* conf_out, int32_t* out_counts, void* stream) {
+  CTDD_REQUIRE(logits && x && out_x, CTDD_EINVAL, "absorb remask step: null buffer");
+  CTDD_REQUIRE(N > 0 && D > 0 && S >= 2 && S <= CTDD_MAX_S && mask_state >= 0 && mask_state < S, CTDD_ERANGE,
+               "absorb remask step: N=%d D=%d S=%d mask_state=%d (2 <= S <= %d, 0 <= mask_state < S)", N, D, S, mask_state, CTDD_MAX_S);
+  CTDD_REQUIRE((flags & ~CTDD_ABSORB_REMASK_CONF) == 0, CTDD_EINVAL, "absorb remask step: flags %u (CTDD_ABSORB_REMASK_CONF or 0)", flags);
+  CTDD_REQUIRE(p_unmask >= 0.0f && p_unmask <= 1.0f, CTDD_ERANGE, "absorb remask step: p_unmask=%g outside [0, 1]", (double)p_unmask);
+  CTDD_REQUIRE(sigma >= 0.0f && sigma <= 1.0f, CTDD_ERANGE, "absorb remask step: sigma=%g outside [0, 1]", (double)sigma);
+  CTDD_REQUIRE(temp >= 0.02f, CTDD_ERANGE, "absorb remask step: temp=%g below 0.02", (double)temp);
+  CTDD_REQUIRE((conf_in != nullptr) == (conf_out != nullptr), CTDD_EINVAL, "absorb remask step: conf_in and conf_out go together");
+  CTDD_REQUIRE(!(flags & CTDD_ABSORB_REMASK_CONF) || (conf_in && conf_out && norm), CTDD_EINVAL,
+               "absorb remask step: CTDD_ABSORB_REMASK_CONF needs conf_in, conf_out and norm");
+  const int64_t rows = (int64_t)N * D;
+  const int rpb = AWV * WAVE / absorb_lpr(S);
+  const int64_t blocks = (rows + rpb - 1) / rpb;
+  CTDD_REQUIRE(blocks <= INT32_MAX, CTDD_ERANGE, "absorb remask step: N D = %lld rows", (long long)rows);
+  AbsorbRemaskArgs a = {logits, x, held, conf_in, norm, rows, D, S, mask_state, S % 4 == 0 && aligned16(logits), p_unmask, sigma, temp, flags,
+                        seed, offset, out_x, conf_out, out_counts};
+  ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_remask_step<LPR, PER>), dim3((unsigned)blocks), dim3(64 * AWV), 0, (hipStream_t)stream, a));
+  return finish_launch("k_absorb_remask_step");
+}
+
+extern "C" int ctdd_absorb_remask_norm(const int32_t* x, const uint8_t* held, const float* conf, int N, int D, int mask_state, float temp,
+                                       float* out_norm, void* stream) {
+  CTDD_REQUIRE(x && conf && out_norm, CTDD_EINVAL, "absorb remask norm: null buffer");
+  CTDD_REQUIRE(N > 0 && D > 0 && D <= (1 << 24) && mask_state >= 0, CTDD_ERANGE, "absorb remask norm: N=%d D=%d mask_state=%d (1 <= D <= 2^24)", N, D,
+               mask_state);
+  CTDD_REQUIRE(temp >= 0.02f, CTDD_ERANGE, "absorb remask norm: temp=%g below 0.02", (double)temp);
+  AbsorbRemaskNormArgs a = {x, held, conf, D, mask_state, temp, out_norm};
+  hipLaunchKernelGGL(k_absorb_remask_norm, dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, a);
+  return finish_launch("k_absorb_remask_norm");
 }

@@ -90,6 +90,8 @@ _SIGS = {
     "ctdd_absorb_propose": ([_P, _P, _I, _I, _I, _I, _F, _U32, _U64, _U64, _P, _P, _P], _I),
     "ctdd_absorb_commit": ([_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P], _I),
     "ctdd_absorb_nll": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "ctdd_absorb_remask_step": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _U32, _U64, _U64, _P, _P, _P, _P], _I),
+    "ctdd_absorb_remask_norm": ([_P, _P, _P, _I, _I, _I, _F, _P, _P], _I),
 }
 UNET_EXPORTS = ("ctdd_unet_conv", "ctdd_unet_conv_patch", "ctdd_unet_conv_res", "ctdd_unet_conv_ring", "ctdd_unet_conv_up_phases", "ctdd_unet_upsample2x", "ctdd_unet_first_conv", "ctdd_unet_gn_apply", "ctdd_unet_gn_onepass", "ctdd_unet_channel_stats",
                 "ctdd_unet_time", "ctdd_unet_time_uniform", "ctdd_unet_attention", "ctdd_unet_logistic_head", "ctdd_unet_resblock_small",
@@ -677,6 +679,72 @@ def absorb_nll(logits, x0, xt, mask_state, w=None, out=None, masked=None, hit=No
     _count("ctdd_absorb_nll")
     _check(load().ctdd_absorb_nll(*ptrs, N, D, S, int(mask_state), *tail, _stream()), "ctdd_absorb_nll")
     return row, out
+
+
+ABSORB_REMASK_CONF = 2
+
+
+def _held_mask(held, N, D, what):
+    """The (N, D) mask of held entries as the kernels read it: uint8 (a bool tensor is reinterpreted, not copied), or None."""
+    if held is None:
+        return None
+    if not isinstance(held, torch.Tensor) or held.dtype not in (torch.bool, torch.uint8):
+        raise CtddError(f"{what}: held must be a bool or uint8 tensor, got {getattr(held, 'dtype', type(held))}")
+    if tuple(held.shape) != (N, D):
+        raise CtddError(f"{what}: held {tuple(held.shape)} against states {(N, D)}")
+    return _ptr(held.view(torch.uint8) if held.dtype == torch.bool else held, torch.uint8, "held")
+
+
+def absorb_remask_step(logits, x, mask_state, p_unmask, sigma, held=None, conf=None, norm=None, temp=1.0, flags=0, seed=0, offset=0, out=None,
+                       conf_out=None, counts=None):
+    """(out_x, conf_out or None): one reverse step with remasking (ctdd_absorb_remask_step).  A masked free row follows absorb_step's
+    rule with p_unmask (the same state under the same seed and offset); a free unmasked row returns to mask_state with probability
+    sigma (flags = ABSORB_REMASK_CONF: sigma U_n exp(-conf / temp) / Z_n, clamped at 1, (U_n, Z_n) = norm[n] from absorb_remask_norm);
+    a held row (held (N, D) bool / uint8) is copied through.  conf: fp32 (N, D), the probability at which each entry committed; given,
+    conf_out (default a fresh tensor; conf itself for an in-place call) takes that probability for a row that unmasks, 0 for a row
+    that is or becomes masked, conf's bits otherwise.  out may be x.  counts: int32[2] device counters, incremented by the rows that
+    left the mask state and by the rows remasked."""
+    N, D, S = _absorb_shapes("absorb_remask_step", logits, (("x", x),))
+    hp = _held_mask(held, N, D, "absorb_remask_step")
+    for name, t in (("conf", conf), ("conf_out", conf_out), ("out", out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (N, D)):
+            raise CtddError(f"absorb_remask_step: {name} {tuple(getattr(t, 'shape', ()))} against x {(N, D)}")
+    if norm is not None and (not isinstance(norm, torch.Tensor) or tuple(norm.shape) != (N, 2)):
+        raise CtddError(f"absorb_remask_step: norm {tuple(getattr(norm, 'shape', ()))}, expected {(N, 2)}")
+    if counts is not None and (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (2,)):
+        raise CtddError(f"absorb_remask_step: counts {tuple(getattr(counts, 'shape', ()))}, expected (2,)")
+    if conf is None and conf_out is not None:
+        raise CtddError("absorb_remask_step: conf_out without conf")
+    ptrs = (_ptr(logits, f32, "logits"), _ptr(x, i32, "x"), hp, _ptr(conf, f32, "conf"), _ptr(norm, f32, "norm"))
+    if out is None:
+        out = torch.empty_like(x)
+    if conf is not None and conf_out is None:
+        conf_out = torch.empty_like(conf)
+    _count("ctdd_absorb_remask_step")
+    _check(load().ctdd_absorb_remask_step(*ptrs, N, D, S, int(mask_state), float(p_unmask), float(sigma), float(temp), int(flags), int(seed),
+                                          int(offset), _ptr(out, i32, "out"), _ptr(conf_out, f32, "conf_out"), _ptr(counts, i32, "counts"),
+                                          _stream()), "ctdd_absorb_remask_step")
+    return out, conf_out
+
+
+def absorb_remask_norm(x, mask_state, conf, held=None, temp=1.0, out=None):
+    """norm fp32 (N, 2) = (U_n, Z_n) per sample (ctdd_absorb_remask_norm): the number of free unmasked entries of x (N, D) -- not at
+    mask_state, not held -- and the sum of exp(-conf / temp) over them, in a fixed order (repeated calls give the same bits); (0, 0)
+    for a sample without one."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise CtddError(f"absorb_remask_norm: x {tuple(getattr(x, 'shape', ()))}, expected (N, D)")
+    N, D = (int(v) for v in x.shape)
+    if not isinstance(conf, torch.Tensor) or tuple(conf.shape) != (N, D):
+        raise CtddError(f"absorb_remask_norm: conf {tuple(getattr(conf, 'shape', ()))} against x {(N, D)}")
+    hp = _held_mask(held, N, D, "absorb_remask_norm")
+    ptrs = (_ptr(x, i32, "x"), hp, _ptr(conf, f32, "conf"))
+    if out is None:
+        out = torch.empty((N, 2), dtype=f32, device=x.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (N, 2):
+        raise CtddError(f"absorb_remask_norm: out {tuple(getattr(out, 'shape', ()))}, expected {(N, 2)}")
+    _count("ctdd_absorb_remask_norm")
+    _check(load().ctdd_absorb_remask_norm(*ptrs, N, D, int(mask_state), float(temp), _ptr(out, f32, "out"), _stream()), "ctdd_absorb_remask_norm")
+    return out
 
 
 # ---------------------------------------------------------------- the fused training objectives (csrc/losses.hip)

@@ -2,7 +2,7 @@
 LBJF 238-356, MidPointTauL 360-526, PCTauL 530-646, ConditionalTauLeaping 649-758,
 ConditionalPCTauLeaping 761-905, ExactSampling 975-1061; ConditionalLBJF, ConditionalMidPointTauL and
 ConditionalExactSampling (not in the reference) hold entries the way its two conditional samplers do; AbsorbingLeap (not in the
-reference either) is the absorbing-state process's sampler, on its own step kernel.
+reference either) is the absorbing-state process's sampler, on its own step kernel; AbsorbingConfidence and AbsorbingRemask build on it.
 
 Same constructor `(cfg)`, same `sample(model, N)` return shapes; the per-step work is one fused
 libctdd launch (reverse rates -> jump draw -> state update) on int32 device state.  Differences
@@ -855,3 +855,128 @@ class AbsorbingConfidence(AbsorbingLeap):
         flags = native.ABSORB_ARGMAX if self.candidate == "argmax" else 0
         cand, score = native.absorb_propose(logits, x, m, self.conf_temp * (1.0 - (i + 1) / self.num_steps), flags, key, i)
         return native.absorb_commit(x, cand, score, m, p_unmask=p, changed=changed)
+
+
+REMASK_STRATEGIES = ("cap", "rescale", "conf")
+
+
+def remask_schedule(p, strategy, eta, active=None):
+    """(sigma, p_prime), two lists of fp64: the per-step remask probability of a committed entry and the raised unmasking probability
+    that keeps the expected masked share of AbsorbingLeap's chain.  p: AbsorbingLeap's per-step unmasking probabilities in [0, 1];
+    active: per-step booleans (None: every step), sigma_k = 0 where false.  Host arithmetic only.
+
+    With surv_0 = 1 and surv_{k+1} = surv_k (1 - p_k) the masked share AbsorbingLeap has before step k, a step that unmasks with p'_k
+    and remasks the unmasked share with sigma_k leaves surv_k (1 - p'_k) + (1 - surv_k) sigma_k masked; equating that to surv_{k+1} gives
+        p'_k = p_k + sigma_k (1 - surv_k) / surv_k                (p'_k = p_k where surv_k == 0: nothing is masked),
+    and p'_k <= 1 iff sigma_k <= sigma_max_k = min(1, surv_{k+1} / (1 - surv_k)) (sigma_k = 0 at surv_k == 1: nothing is unmasked).
+    "cap" and "conf": sigma_k = min(eta, sigma_max_k); "rescale": sigma_k = eta sigma_max_k.  eta = 0 returns p itself."""
+    if strategy not in REMASK_STRATEGIES:
+        raise ValueError(f"remask strategy must be one of {REMASK_STRATEGIES}, got {strategy!r}")
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"remask eta must lie in [0, 1], got {eta!r}")
+    p = [float(v) for v in p]
+    if any(not 0.0 <= v <= 1.0 for v in p):
+        raise ValueError("remask_schedule: every p must lie in [0, 1]")
+    active = [True] * len(p) if active is None else [bool(v) for v in active]
+    if len(active) != len(p):
+        raise ValueError(f"remask_schedule: {len(active)} active flags for {len(p)} steps")
+    sigma, p_prime, surv = [], [], 1.0
+    for pk, on in zip(p, active):
+        nxt = surv * (1.0 - pk)
+        sk = 0.0
+        if on and surv < 1.0:
+            smax = min(1.0, nxt / (1.0 - surv))
+            sk = eta * smax if strategy == "rescale" else min(eta, smax)
+        sigma.append(sk)
+        p_prime.append(min(1.0, pk + sk * (1.0 - surv) / surv) if surv > 0.0 and sk > 0.0 else pk)
+        surv = nxt
+    return sigma, p_prime
+
+
+@sampling_utils.register_sampler
+class AbsorbingRemask(AbsorbingLeap):
+    """AbsorbingLeap with remasking (after ReMDM, Wang et al.; not in the reference): at every step each committed free entry returns to
+    the mask state with a small probability sigma_k, and the unmasking probability is raised to p'_k so that the expected masked share
+    after every step stays AbsorbingLeap's (remask_schedule; derived for this chain, which starts all-masked at max_t).  The trained
+    network is used as is; a remasked entry is drawn again at a later step, from the logits of that step.  Grid, rules, seed,
+    rank_stream, `sample`, `inpaint` and the closing argmax forward are the parent's; sigma and p' of every step are computed on the
+    host before the loop; one network forward and one ctdd_absorb_remask_step launch per step, no host sync inside the loop.
+
+    cfg.sampler.remask: "cap" (default; sigma_k = min(eta, sigma_max_k)), "rescale" (eta sigma_max_k) or "conf" (cap's sigma_k as the
+    per-sample mean, spread over the committed entries in proportion to exp(-conf / remask_temp), conf the probability at which the
+    entry committed: a second launch per step, ctdd_absorb_remask_norm, and a conf buffer carried across the steps, 1 at the start so
+    that held entries weigh least).  cfg.sampler.remask_eta in [0, 1] (default 0.02, untuned; 0: AbsorbingLeap bit for bit under the same seed);
+    cfg.sampler.remask_temp (default 1.0, at least 0.02); cfg.sampler.remask_window = (t_on, t_off) (default: the whole grid): step k
+    remasks iff t_off <= t_k <= t_on.  `inpaint` hands the held mask to the kernel: a held entry is never remasked.  After a run
+    `remasked` holds the per-step number of remasked entries over N, as `changed` holds the entries that left the mask state."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        s = cfg.sampler
+        self.remask = getattr(s, "remask", "cap")
+        if self.remask not in REMASK_STRATEGIES:
+            raise ValueError(f"sampler.remask must be one of {REMASK_STRATEGIES}, got {self.remask!r}")
+        self.remask_eta = float(getattr(s, "remask_eta", 0.02))
+        if not 0.0 <= self.remask_eta <= 1.0:
+            raise ValueError(f"sampler.remask_eta must lie in [0, 1], got {self.remask_eta!r}")
+        self.remask_temp = float(getattr(s, "remask_temp", 1.0))
+        if not self.remask_temp >= 0.02:
+            raise ValueError(f"sampler.remask_temp must be at least 0.02, got {self.remask_temp!r}")
+        window = getattr(s, "remask_window", None)
+        if window is None:
+            window = (float("inf"), float("-inf"))
+        try:
+            t_on, t_off = (float(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError(f"sampler.remask_window must be a pair (t_on, t_off), got {window!r}") from None
+        if not t_on >= t_off:
+            raise ValueError(f"sampler.remask_window = (t_on, t_off) needs t_on >= t_off, got {window!r}")
+        self.remask_window = (t_on, t_off)
+        self.remasked = []
+
+    def inpaint(self, model, x_known, mask):
+        m = self._process(model).mask_state
+        N, xk, held = self._held(x_known, mask)
+        if bool((xk[held] == m).any()):
+            raise ValueError(f"x_known: a held entry is the mask state {m}")
+        if bool(held.all()):
+            return xk.numpy().astype(int)
+        dev = torch.device(model.device)
+        held = held.to(dev)
+        x = torch.where(held, xk.to(dev), torch.full((), m, dtype=torch.int32, device=dev))
+        return self._loop(model, x.contiguous(), held.contiguous())[0]
+
+    def schedule(self, pr):
+        """(t64 of the grid with its closing 0, sigma, p') of a run on the process pr: the host side of the loop."""
+        ts = np.concatenate((np.linspace(self.max_t, self.min_t, self.num_steps), np.array([0])))
+        t64 = torch.from_numpy(ts)
+        p = torch.clamp(pr.unmask_prob(t64[:-1], t64[:-1] - t64[1:], self.rule), 0.0, 1.0).tolist()
+        t_on, t_off = self.remask_window
+        sigma, p_prime = remask_schedule(p, self.remask, self.remask_eta, [t_off <= t <= t_on for t in ts[:-1].tolist()])
+        return t64, sigma, p_prime
+
+    def _loop(self, model, x, held=None):
+        pr = self._process(model)
+        m, N, dev, key, K = pr.mask_state, x.shape[0], x.device, self._key(), self.num_steps
+        t64, sigma, p = self.schedule(pr)
+        t32 = t64[:-1].to(torch.float32)
+        counts = torch.zeros((K, 2), dtype=torch.int32, device=dev)
+        closing = torch.zeros(1, dtype=torch.int32, device=dev)
+        by_conf = self.remask == "conf"
+        conf = torch.ones(x.shape, dtype=torch.float32, device=dev) if by_conf else None
+        norm = torch.empty((N, 2), dtype=torch.float32, device=dev) if by_conf else None
+        with torch.no_grad(), borrow_engine_output(model, bf16_logits=False, uniform_time=True):
+            for i in range(K):
+                logits = _GridSampler._net_logits(model, x, _GridSampler._t_ones(t32, i, N, dev))
+                if by_conf:
+                    native.absorb_remask_norm(x, m, conf, held, self.remask_temp, out=norm)
+                    native.absorb_remask_step(logits, x, m, p[i], sigma[i], held, conf, norm, self.remask_temp, native.ABSORB_REMASK_CONF, key, i,
+                                              out=x, conf_out=conf, counts=counts[i])
+                else:
+                    native.absorb_remask_step(logits, x, m, p[i], sigma[i], held, seed=key, offset=i, out=x, counts=counts[i])
+            logits = _GridSampler._net_logits(model, x, torch.full((N,), float(np.float32(self.min_t)), device=dev))
+            x = native.absorb_step(logits, x, m, 1.0, native.ABSORB_ARGMAX, key, K, changed=closing)
+        counts = counts.cpu().numpy()
+        self.remasked = (counts[:, 1] / N).tolist()
+        return x.cpu().numpy().astype(int), (counts[:, 0] / N).tolist()

@@ -1,6 +1,7 @@
 /* ctdd_absorb.h -- C ABI of the absorbing-state ("masked") diffusion kernels (csrc/absorb.hip): forward noising, the negative
  * ELBO with its logit gradient, one reverse (unmasking) step, the two halves of a confidence-ordered unmasking step
- * (ctdd_absorb_propose, ctdd_absorb_commit), and the per-sample terms of the held-out likelihood bounds (ctdd_absorb_nll).
+ * (ctdd_absorb_propose, ctdd_absorb_commit), the per-sample terms of the held-out likelihood bounds (ctdd_absorb_nll), and the
+ * reverse step with remasking and its per-sample normaliser (ctdd_absorb_remask_step, ctdd_absorb_remask_norm).
  * Conventions as in ctdd.h: device pointers, row-major, int status (CTDD_OK == 0, message through ctdd_last_error), `stream` a
  * hipStream_t.  Logits fp32 (B, D, S) contiguous, states int32,
  * 2 <= S <= CTDD_MAX_S (S counts the mask state: S = 2 is one real state plus the mask), 0 <= mask_state < S.
@@ -107,6 +108,46 @@ int ctdd_absorb_commit(const int32_t* x, const int32_t* cand, const float* score
  * is kept in LDS but the four wave sums: 1 <= D <= 2^30. */
 int ctdd_absorb_nll(const float* logits, const int32_t* x0, const int32_t* xt, const float* w, int N, int D, int S, int mask_state,
                     float* row_nll, double* out_nll, int32_t* out_masked, int32_t* out_hit, void* stream);
+
+/* One reverse step with remasking (ReMDM-style) for N D rows: ctdd_absorb_step's grid and row ownership, plus held rows, a remask
+ * coin for the committed rows and an optional record of the confidence at which a row committed.
+ *   logits (N, D, S), x, out_x int32 (N, D); held uint8 (N, D) or NULL (non-zero = held; NULL: nothing is held);
+ *   conf_in, conf_out fp32 (N, D), both given or both NULL; norm fp32 (N, 2) or NULL (ctdd_absorb_remask_norm's output).
+ *   0 <= p_unmask, sigma <= 1; temp >= 0.02; flags: CTDD_ABSORB_REMASK_CONF or 0 (CTDD_ABSORB_ARGMAX is refused: CTDD_EINVAL).
+ * The row r = n D + d reads ONE block Philox(key = seed, counter = (row = r, offset, draw = 0)), laid out as ctdd_absorb_step's:
+ *     component 0: u0 -- the unmask coin of a masked row            (ctdd_absorb_step's)
+ *     component 1: u1 -- the state draw of a row that unmasks        (ctdd_absorb_step's, the same device code)
+ *     component 2: unused here (ctdd_absorb_propose's ranking noise)
+ *     component 3: u3 -- the remask coin of a free unmasked row
+ *   held row (held[r] != 0, whatever x is): out_x = x and conf_out = conf_in, bit for bit; no draw, the logits are not read.
+ *   masked row (x == m, not held): ctdd_absorb_step's rule with p_unmask -- for the same (seed, offset, p_unmask) out_x IS what
+ *     ctdd_absorb_step writes.  If it unmasks, conf_out = exp(l[out_x] - mx) / z, the probability of the state written under the
+ *     softmax excluding the mask state (above), in (0, 1]; if it stays masked, conf_out = 0 and the logits are not read.
+ *   free unmasked row (x != m, not held): remasked iff u3 < sigma_row; the logits are never read.
+ *     flags == 0:                       sigma_row = sigma
+ *     flags & CTDD_ABSORB_REMASK_CONF:  sigma_row = min(1, ((sigma U_n) exp(-conf_in / temp)) / Z_n) in fp32, (U_n, Z_n) = norm[n]
+ *                                       (0 where Z_n is not positive); needs conf_in, conf_out and norm (CTDD_EINVAL otherwise).
+ *       The weights exp(-conf / temp) lie in [exp(-1 / temp), 1] for conf in [0, 1] (a normal fp32 for temp >= 0.02), so the mean
+ *       sigma_row over the free unmasked rows of a sample is sigma whenever no row clamps at 1, e.g. for sigma <= exp(-1 / temp).
+ *     remasked: out_x = m, conf_out = 0.   kept: out_x = x, conf_out = conf_in, bit for bit.
+ *   sigma == 0: no Philox block is computed for an unmasked row; the call costs what ctdd_absorb_step costs.
+ * out_x may be x and conf_out may be conf_in (in place): a row reads and writes its own entries only.
+ * out_counts (int32[2] or NULL): [0] += the rows that left the mask state, [1] += the rows remasked (one atomic per workgroup each). */
+#define CTDD_ABSORB_REMASK_CONF 2u   /* ctdd_absorb_remask_step: the remask probability of a row follows the confidence it committed at */
+int ctdd_absorb_remask_step(const float* logits, const int32_t* x, const uint8_t* held, const float* conf_in, const float* norm, int N, int D,
+                            int S, int mask_state, float p_unmask, float sigma, float temp, uint32_t flags, uint64_t seed, uint64_t offset,
+                            int32_t* out_x, float* conf_out, int32_t* out_counts, void* stream);
+
+/* The per-sample normaliser of the confidence-weighted remask probability.   x int32, conf fp32 (N, D); held uint8 (N, D) or NULL;
+ * out_norm fp32 (N, 2), written in full; temp >= 0.02; 1 <= D <= 2^24 (U_n is exact in fp32).
+ *   out_norm[n] = (U_n, Z_n):  U_n = the number of free unmasked rows d of sample n (x != m, not held),
+ *                              Z_n = the sum over those rows of exp(-conf[n][d] / temp)   (expf of the fp32 quotient, summed in fp64).
+ * A sample without a free unmasked row gets (0, 0): ctdd_absorb_remask_step then remasks nothing in it.
+ * Deterministic, no floating-point atomic (the order of ctdd_absorb_nll's sum): one workgroup of 256 threads per sample; thread i adds
+ * its rows d = i, i + 256, .. in ascending d in fp64; the 64 lanes of a wave combine by the xor butterfly 32, 16, 8, 4, 2, 1; the four
+ * waves' sums are added in wave order; the total is rounded to fp32 once.  Repeated calls write the same bits. */
+int ctdd_absorb_remask_norm(const int32_t* x, const uint8_t* held, const float* conf, int N, int D, int mask_state, float temp,
+                            float* out_norm, void* stream);
 
 #ifdef __cplusplus
 }
