@@ -3,7 +3,12 @@
 // and a score per masked row (ctdd_absorb_propose, the step's layout and pick), then a per-sample top-k of the scores by radix select
 // (ctdd_absorb_commit); and the terms of the held-out likelihood bounds, a row pass and a deterministic per-sample fp64 sum
 // (ctdd_absorb_nll); and the step with remasking (ctdd_absorb_remask_step: the step's layout and pick, held rows, a remask coin for
-// committed rows, the confidence a row committed at) with its per-sample normaliser (ctdd_absorb_remask_norm).
+// committed rows, the confidence a row committed at) with its per-sample normaliser (ctdd_absorb_remask_norm); and the two halves of
+// a first-hitting step, which simulates the reverse chain event by event instead of on a time grid: with M entries masked at level
+// c = 1 - alpha_t their masking levels are i.i.d. uniform on (0, c), so the next entry to unmask is uniform among them and unmasks
+// at level c u^(1/M).  ctdd_absorb_hit_time counts a sample's masked rows and walks that recursion in fp64 logs (up to kmax events,
+// none below the closing level) to a per-sample event count and network time; ctdd_absorb_hit_step selects that many masked rows
+// uniformly (the commit's radix select, on Philox keys) and gives each the state the plain step would draw for it.
 // include/ctdd_absorb.h states the formulas, the Philox counter layouts, the key that orders the scores and the order of the sums.
 //
 // Loss and step are row softmaxes over a row that fits in registers.  A row is owned by a group of LPR lanes of one wave, lane j of
@@ -337,29 +342,27 @@ struct AbsorbCommitArgs {
   int32_t* changed;
 };
 
-// One workgroup (256 threads) per sample.  Radix select, most significant digit first: a pass histograms the digit of the masked
-// rows whose key agrees with the digits found so far; wave 0 scans the 256 bins from the top (lane L owns the bins 255 - 4 L ..
-// 252 - 4 L) for the bin that holds the need-th largest key.  After four passes `prefix` is that key and `need` the number of rows at
-// it that are still wanted.  The last pass walks d in ascending chunks of 256: a ballot per wave, the waves' counts through LDS
-// (two buffers, so one barrier a chunk) and a running base put every row at the threshold key in its ascending-d position.
-__global__ __launch_bounds__(64 * AWV) void k_absorb_commit(const AbsorbCommitArgs a) {
+// Radix select over the 32-bit keys of one sample's masked rows, by a workgroup of 256 threads, most significant digit first: a pass
+// histograms the digit of the masked rows whose key agrees with the digits found so far; wave 0 scans the 256 bins from the top
+// (lane L owns the bins 255 - 4 L .. 252 - 4 L) for the bin that holds the need-th largest key.  After four passes `prefix` is that
+// key and `need` the number of rows at it that are still wanted.  key_of(d): the key of the masked row d (recomputed in every pass);
+// want_of(M): k_n from the number of masked rows, which is the first pass's total.  k_n == 0 ends after that pass, with `prefix`
+// above every key.  hist: 256 bins; sel: digit, rows still wanted inside it, k_n.  Shared by k_absorb_commit and k_absorb_hit_step.
+template <class KeyOf, class WantOf>
+__device__ inline void radix_select(const int32_t* __restrict__ x, int D, int m, KeyOf key_of, WantOf want_of, int* hist, int* sel,
+                                    uint32_t& prefix, int& need, int& kn) {
   static_assert(AWV == 4, "256 threads: one per histogram bin");
-  __shared__ int hist[256];
-  __shared__ int sel[3];                                        // digit, rows still wanted inside it, k_n
-  __shared__ int wcnt[2][AWV];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, D = a.D, m = a.mask_state;
-  const size_t base = (size_t)blockIdx.x * D;
-  const int32_t* __restrict__ x = a.x + base;
-  const float* __restrict__ sc = a.score + base;
-  uint32_t prefix = 0u;
-  int need = 0, kn = 0;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  prefix = 0u;
+  need = 0;
+  kn = 0;
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = 24 - 8 * pass;
     hist[tid] = 0;
     __syncthreads();
     for (int d = tid; d < D; d += 64 * AWV)
       if (x[d] == m) {
-        const uint32_t key = score_key(sc[d]);
+        const uint32_t key = key_of(d);
         if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
       }
     __syncthreads();
@@ -374,8 +377,7 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_commit(const AbsorbCommitAr
         if (lane >= o) incl += up;
       }
       if (pass == 0) {                                          // the histogram's total is M_n
-        const int M = __shfl(incl, WAVE - 1, WAVE);
-        need = a.counts ? min(M, max(0, a.counts[blockIdx.x])) : min(M, (int)ceil((double)a.p * (double)M));
+        need = want_of(__shfl(incl, WAVE - 1, WAVE));
         if (lane == 0) sel[2] = need;
       }
       int cum = incl - s4, digit = -1, rest = 0;
@@ -388,11 +390,30 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_commit(const AbsorbCommitAr
     }
     __syncthreads();
     kn = sel[2];
-    if (kn == 0) break;                                         // (uniform) nothing to commit: every masked row stays masked
+    if (kn == 0) break;                                         // (uniform) nothing to select: every masked row stays masked
     prefix = (prefix << 8) | (uint32_t)sel[0];
     need = sel[1];
   }
   if (kn == 0) { prefix = 0xFFFFFFFFu; need = 0; }              // above every key
+}
+
+// One workgroup (256 threads) per sample: the radix select above on the scores' keys.  The last pass walks d in ascending chunks
+// of 256: a ballot per wave, the waves' counts through LDS (two buffers, so one barrier a chunk) and a running base put every row
+// at the threshold key in its ascending-d position.
+__global__ __launch_bounds__(64 * AWV) void k_absorb_commit(const AbsorbCommitArgs a) {
+  __shared__ int hist[256];
+  __shared__ int sel[3];                                        // digit, rows still wanted inside it, k_n
+  __shared__ int wcnt[2][AWV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, D = a.D, m = a.mask_state;
+  const size_t base = (size_t)blockIdx.x * D;
+  const int32_t* __restrict__ x = a.x + base;
+  const float* __restrict__ sc = a.score + base;
+  uint32_t prefix;
+  int need, kn;
+  radix_select(
+      x, D, m, [&](int d) { return score_key(sc[d]); },
+      [&](int M) { return a.counts ? min(M, max(0, a.counts[blockIdx.x])) : min(M, (int)ceil((double)a.p * (double)M)); }, hist, sel, prefix,
+      need, kn);
   int seen = 0;                                                 // rows at the threshold key in the chunks before this one
   for (int c0 = 0, buf = 0; c0 < D; c0 += 64 * AWV, buf ^= 1) {
     const int d = c0 + tid;
@@ -646,6 +667,165 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_remask_norm(const AbsorbRem
   }
 }
 
+// ---------------------------------------------------------------- first-hitting sampling: per-sample event levels
+struct AbsorbHitTimeArgs {
+  const int32_t* x;
+  const double* logc_in;
+  int N, D, mask_state, kmax;
+  double log_cmin;
+  int t_func;
+  double rate_const, alpha_eps, time_base, time_exp, t_min, t_max;
+  uint64_t seed, offset;
+  int32_t* counts;
+  float* t_eval;
+  double* logc_out;
+};
+
+// the inverse of alpha_t in fp64 (include/ctdd_absorb.h; DeviceForwardProcess.time_of_alpha states the same forms)
+__device__ inline double absorb_time_of_alpha(const AbsorbHitTimeArgs& a, double al) {
+  switch (a.t_func) {
+    case CTDD_ABSORB_T_LOGLINEAR: return (1.0 - al) / (1.0 - a.alpha_eps);
+    case CTDD_ABSORB_T_LOG_SQR: return sqrt(pow(al, -1.0 / a.rate_const) - 1.0);
+    case CTDD_ABSORB_T_SQRT_COS: {
+      const double r = fmin(fmax(1.0 + log(al) / a.rate_const, 0.0), 1.0);
+      return (2.0 / 3.14159265358979323846) * acos(r * r);
+    }
+    default: return log(1.0 - log(al) / (a.rate_const * a.time_base)) / log(a.time_exp);
+  }
+}
+
+// One workgroup (256 threads) per sample: the masked rows are counted by all (integers: exact in any order), then thread 0 walks the
+// level recursion in fp64 -- at most kmax steps of one log and one division each, a Philox block every fourth.  M_n and the level
+// never leave the device.  logc_out may be logc_in: thread 0 reads its sample's entry before it writes it.
+__global__ __launch_bounds__(64 * AWV) void k_absorb_hit_time(const AbsorbHitTimeArgs a) {
+  __shared__ int red[AWV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, D = a.D, n = blockIdx.x;
+  const int32_t* __restrict__ x = a.x + (size_t)n * D;
+  int c = 0;
+  for (int d = tid; d < D; d += 64 * AWV) c += x[d] == a.mask_state;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, WAVE);
+  if (lane == 0) red[wave] = c;
+  __syncthreads();
+  if (tid != 0) return;
+  int M = 0;
+#pragma unroll
+  for (int i = 0; i < AWV; ++i) M += red[i];
+  double L = a.logc_in[n], L1 = L;
+  const int K = min(a.kmax, M);
+  int acc = 0;
+  u4 r = {0u, 0u, 0u, 0u};
+  for (int i = 0; i < K; ++i) {
+    if ((i & 3) == 0) r = philox_row(a.seed, a.offset, (uint64_t)a.N * (uint64_t)D + (uint64_t)n, (uint32_t)(i >> 2));
+    const uint32_t w = (i & 3) == 0 ? r.x : (i & 3) == 1 ? r.y : (i & 3) == 2 ? r.z : r.w;
+    const double Ln = L + log((double)u01(w)) / (double)(M - i);
+    if (!(Ln >= a.log_cmin)) {                                  // the first refusal ends the sample
+      L = a.log_cmin;
+      break;
+    }
+    L = Ln;
+    if (i == 0) L1 = Ln;
+    ++acc;
+  }
+  a.counts[n] = acc;
+  a.logc_out[n] = L;                                            // (M_n == 0: the bits that came in)
+  double t = a.t_min;
+  if (acc > 0) t = fmin(fmax(absorb_time_of_alpha(a, 1.0 - exp(L1)), a.t_min), a.t_max);   // (fmax / fmin drop a NaN)
+  a.t_eval[n] = (float)t;
+}
+
+// ---------------------------------------------------------------- first-hitting sampling: k_n uniform rows per sample take a state
+struct AbsorbHitStepArgs {
+  const float* logits;
+  const int32_t* x;
+  const int32_t* counts;
+  int D, S, mask_state;
+  int vec;
+  uint32_t flags;
+  uint64_t seed, offset;
+  int32_t* out_x;
+  int32_t* changed;
+};
+
+// One workgroup (256 threads) per sample.  k_absorb_commit's radix select on the rows' Philox keys (draw 1), then its last pass
+// with a second ballot: per chunk of 256 rows the rows above the threshold key and the rows at it that are still wanted are
+// compacted, in ascending d, into an LDS list, and the four waves' row groups -- k_absorb_step's packing, load and pick (draw 0,
+// component 1) -- walk that list.  Logits are read for the selected rows only.  out_x may be x (no __restrict__ on either): the
+// select reads x before anything is written, and in the last pass a row is read by its chunk's thread before the chunk's barrier and
+// written after it, by that thread (copied) or by one row group (selected), never both.
+template <int LPR, int PER>
+__global__ __launch_bounds__(64 * AWV) void k_absorb_hit_step(const AbsorbHitStepArgs a) {
+  __shared__ int hist[256];
+  __shared__ int sel[3];                                        // digit, rows still wanted inside it, k_n
+  __shared__ int wcnt[2][2][AWV];                               // [buffer][above / at the threshold key][wave]
+  __shared__ int list[64 * AWV];                                // the selected rows of one chunk
+  constexpr int RPW = WAVE / LPR, RPB = AWV * RPW;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane % LPR, D = a.D, S = a.S, m = a.mask_state;
+  const bool greedy = (a.flags & CTDD_ABSORB_ARGMAX) != 0;
+  const size_t base = (size_t)blockIdx.x * D;
+  const int32_t* x = a.x + base;
+  int32_t* out = a.out_x + base;
+  const auto key_of = [&](int d) { return philox_row(a.seed, a.offset, (uint64_t)(base + d), 1u).x; };
+  uint32_t prefix;
+  int need, kn;
+  radix_select(x, D, m, key_of, [&](int M) { return min(M, max(0, a.counts[blockIdx.x])); }, hist, sel, prefix, need, kn);
+  if (kn == 0) {                                                // (uniform) nothing moves in this sample
+    if (out != x)
+      for (int d = tid; d < D; d += 64 * AWV) out[d] = x[d];
+    return;
+  }
+  int seen = 0, done = 0;                                       // rows at the threshold key / rows selected in the chunks before this one
+  for (int c0 = 0, buf = 0; c0 < D; c0 += 64 * AWV, buf ^= 1) {
+    if (done == kn && out == x) break;                          // (uniform) in place: the rest stays as it is
+    const int d = c0 + tid;
+    int xo = 0;
+    uint32_t key = 0u;
+    bool masked = false;
+    if (d < D) {
+      xo = x[d];
+      masked = xo == m;
+      if (masked) key = key_of(d);
+    }
+    const bool above = masked && key > prefix, tie = masked && key == prefix;
+    const unsigned long long ba = __ballot(above), bt = __ballot(tie);
+    if (lane == 0) { wcnt[buf][0][wave] = __popcll(ba); wcnt[buf][1][wave] = __popcll(bt); }
+    __syncthreads();
+    const unsigned long long lower = (1ull << lane) - 1ull;
+    int ab = __popcll(ba & lower), tb = seen + __popcll(bt & lower), aall = 0, tall = 0;
+#pragma unroll
+    for (int w = 0; w < AWV; ++w) {
+      const int ca = wcnt[buf][0][w], ct = wcnt[buf][1][w];
+      if (w < wave) { ab += ca; tb += ct; }
+      aall += ca;
+      tall += ct;
+    }
+    const int t0 = min(seen, need);                             // rows at the threshold key taken in earlier chunks
+    const bool take = above || (tie && tb < need);
+    const int nsel = aall + min(seen + tall, need) - t0;        // (uniform) the chunk's selected rows
+    if (d < D && !take && out != x) out[d] = xo;
+    if (nsel > 0) {
+      if (take) list[ab + min(tb, need) - t0] = d;              // ascending d: the selected rows before this one in the chunk
+      __syncthreads();
+      for (int i0 = 0; i0 < nsel; i0 += RPB) {
+        const int idx = i0 + wave * RPW + lane / LPR;
+        const bool have = idx < nsel;                           // (uniform over the row's group)
+        const int ds = have ? list[idx] : 0;
+        const size_t row = base + ds;
+        float u1 = 0.0f;
+        if (have && !greedy) u1 = u01(philox_row(a.seed, a.offset, (uint64_t)row, 0u).y);
+        float v[PER];
+        absorb_load<PER>(a.logits + row * S, S, j * PER, m, a.vec, have, v);
+        float mx, z;
+        const int pick = absorb_pick<LPR, PER>(v, S, m, j, greedy, u1, mx, z);
+        if (have && j == 0) out[ds] = pick;
+      }
+    }
+    seen += tall;
+    done += nsel;
+  }
+  if (tid == 0 && a.changed) atomicAdd(a.changed, kn);
+}
+
 // (LPR, PER) of a row width; rows per workgroup = AWV * 64 / LPR
 #define ABSORB_SHAPE(S, CALL)                                                       \
   if ((S) <= 4) { constexpr int LPR = 1, PER = 4; CALL; }                           \
@@ -785,4 +965,37 @@ extern "C" int ctdd_absorb_remask_norm(const int32_t* x, const uint8_t* held, co
   AbsorbRemaskNormArgs a = {x, held, conf, D, mask_state, temp, out_norm};
   hipLaunchKernelGGL(k_absorb_remask_norm, dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, a);
   return finish_launch("k_absorb_remask_norm");
+}
+
+extern "C" int ctdd_absorb_hit_time(const int32_t* x, const double* logc_in, int N, int D, int mask_state, int kmax, double log_cmin, int t_func,
+                                    double rate_const, double alpha_eps, double time_base, double time_exp, double t_min, double t_max,
+                                    uint64_t seed, uint64_t offset, int32_t* out_counts, float* out_t_eval, double* logc_out, void* stream) {
+  CTDD_REQUIRE(x && logc_in && out_counts && out_t_eval && logc_out, CTDD_EINVAL, "absorb hit time: null buffer");
+  CTDD_REQUIRE(N > 0 && D > 0 && D <= (1 << 30) && mask_state >= 0 && kmax >= 1, CTDD_ERANGE,
+               "absorb hit time: N=%d D=%d mask_state=%d kmax=%d (1 <= D <= 2^30, kmax >= 1)", N, D, mask_state, kmax);
+  CTDD_REQUIRE(t_func >= CTDD_ABSORB_T_LOGLINEAR && t_func <= CTDD_ABSORB_T_LOG, CTDD_EINVAL, "absorb hit time: unknown t_func %d", t_func);
+  CTDD_REQUIRE(log_cmin == log_cmin, CTDD_ERANGE, "absorb hit time: log_cmin is NaN");
+  CTDD_REQUIRE(t_min <= t_max, CTDD_ERANGE, "absorb hit time: t_min=%g t_max=%g (t_min <= t_max)", t_min, t_max);
+  if (t_func == CTDD_ABSORB_T_LOGLINEAR)
+    CTDD_REQUIRE(alpha_eps < 1.0, CTDD_ERANGE, "absorb hit time: loglinear alpha_eps=%g (below 1)", alpha_eps);
+  else
+    CTDD_REQUIRE(rate_const > 0.0, CTDD_ERANGE, "absorb hit time: rate_const=%g (positive)", rate_const);
+  if (t_func == CTDD_ABSORB_T_LOG)
+    CTDD_REQUIRE(time_base > 0.0 && time_exp > 1.0, CTDD_ERANGE, "absorb hit time: log schedule time_base=%g time_exp=%g (positive, above 1)",
+                 time_base, time_exp);
+  AbsorbHitTimeArgs a = {x, logc_in, N, D, mask_state, kmax, log_cmin, t_func, rate_const, alpha_eps, time_base, time_exp, t_min, t_max,
+                         seed, offset, out_counts, out_t_eval, logc_out};
+  hipLaunchKernelGGL(k_absorb_hit_time, dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, a);
+  return finish_launch("k_absorb_hit_time");
+}
+
+extern "C" int ctdd_absorb_hit_step(const float* logits, const int32_t* x, const int32_t* counts, int N, int D, int S, int mask_state,
+                                    uint32_t flags, uint64_t seed, uint64_t offset, int32_t* out_x, int32_t* out_changed, void* stream) {
+  CTDD_REQUIRE(logits && x && counts && out_x, CTDD_EINVAL, "absorb hit step: null buffer");
+  CTDD_REQUIRE(N > 0 && D > 0 && D <= (1 << 30) && S >= 2 && S <= CTDD_MAX_S && mask_state >= 0 && mask_state < S, CTDD_ERANGE,
+               "absorb hit step: N=%d D=%d S=%d mask_state=%d (1 <= D <= 2^30, 2 <= S <= %d, 0 <= mask_state < S)", N, D, S, mask_state, CTDD_MAX_S);
+  CTDD_REQUIRE((flags & ~CTDD_ABSORB_ARGMAX) == 0, CTDD_EINVAL, "absorb hit step: unknown flags %u", flags);
+  AbsorbHitStepArgs a = {logits, x, counts, D, S, mask_state, S % 4 == 0 && aligned16(logits), flags, seed, offset, out_x, out_changed};
+  ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_hit_step<LPR, PER>), dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, a));
+  return finish_launch("k_absorb_hit_step");
 }

@@ -28,7 +28,7 @@ def lib_path():
     return os.environ.get("CTDD_LIBRARY") or os.path.join(_HERE, "libctdd.so")
 
 
-_P, _I, _F, _U64, _U32, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_int64
+_P, _I, _F, _U64, _U32, _I64, _D = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_int64, C.c_double
 _SIGS = {
     "ctdd_abi_version": ([], _I),
     "ctdd_last_error": ([], C.c_char_p),
@@ -92,6 +92,8 @@ _SIGS = {
     "ctdd_absorb_nll": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
     "ctdd_absorb_remask_step": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _U32, _U64, _U64, _P, _P, _P, _P], _I),
     "ctdd_absorb_remask_norm": ([_P, _P, _P, _I, _I, _I, _F, _P, _P], _I),
+    "ctdd_absorb_hit_time": ([_P, _P, _I, _I, _I, _I, _D, _I, _D, _D, _D, _D, _D, _D, _U64, _U64, _P, _P, _P, _P], _I),
+    "ctdd_absorb_hit_step": ([_P, _P, _P, _I, _I, _I, _I, _U32, _U64, _U64, _P, _P, _P], _I),
 }
 UNET_EXPORTS = ("ctdd_unet_conv", "ctdd_unet_conv_patch", "ctdd_unet_conv_res", "ctdd_unet_conv_ring", "ctdd_unet_conv_up_phases", "ctdd_unet_upsample2x", "ctdd_unet_first_conv", "ctdd_unet_gn_apply", "ctdd_unet_gn_onepass", "ctdd_unet_channel_stats",
                 "ctdd_unet_time", "ctdd_unet_time_uniform", "ctdd_unet_attention", "ctdd_unet_logistic_head", "ctdd_unet_resblock_small",
@@ -744,6 +746,59 @@ def absorb_remask_norm(x, mask_state, conf, held=None, temp=1.0, out=None):
         raise CtddError(f"absorb_remask_norm: out {tuple(getattr(out, 'shape', ()))}, expected {(N, 2)}")
     _count("ctdd_absorb_remask_norm")
     _check(load().ctdd_absorb_remask_norm(*ptrs, N, D, int(mask_state), float(temp), _ptr(out, f32, "out"), _stream()), "ctdd_absorb_remask_norm")
+    return out
+
+
+ABSORB_T_FUNCS = {"loglinear": 0, "log_sqr": 1, "sqrt_cos": 2, "log": 3}      # CTDD_ABSORB_T_*
+
+
+def absorb_hit_time(x, logc, mask_state, kmax, log_cmin, schedule, t_min, t_max, seed=0, offset=0, counts=None, t_eval=None, out=None):
+    """(counts int32 (N,), t_eval fp32 (N,), logc_out fp64 (N,)): the first-hitting events of one step, per sample
+    (ctdd_absorb_hit_time).  With M_n entries of x[n] (x (N, D) int32) at mask_state and the log level logc[n] (fp64 (N,)), up to
+    min(kmax, M_n) events L <- L + log(u) / (M_n - i) are taken while L stays at or above log_cmin (a float, -inf allowed); counts:
+    how many; logc_out: the level after them (log_cmin once an event was refused); t_eval: the time of the first event's level,
+    clamped to [t_min, t_max] (t_min without an event).  schedule: the absorbing process's parameters (DeviceForwardProcess.p:
+    t_func, rate_const and alpha_eps or time_base / time_exp as the t_func needs).  out: logc itself for an in-place call."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise CtddError(f"absorb_hit_time: x {tuple(getattr(x, 'shape', ()))}, expected (N, D)")
+    N, D = (int(v) for v in x.shape)
+    for name, t in (("logc", logc), ("counts", counts), ("t_eval", t_eval), ("out", out)):
+        if (t is not None or name == "logc") and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (N,)):
+            raise CtddError(f"absorb_hit_time: {name} {tuple(getattr(t, 'shape', ()))}, expected {(N,)}")
+    f = schedule.get("t_func")
+    if f not in ABSORB_T_FUNCS:
+        raise CtddError(f"absorb_hit_time: t_func {f!r}, expected one of {tuple(ABSORB_T_FUNCS)}")
+    par = [float(schedule.get(k, 0.0)) for k in ("rate_const", "alpha_eps", "time_base", "time_exp")]
+    ptrs = (_ptr(x, i32, "x"), _ptr(logc, torch.float64, "logc"))
+    if counts is None:
+        counts = torch.empty((N,), dtype=i32, device=x.device)
+    if t_eval is None:
+        t_eval = torch.empty((N,), dtype=f32, device=x.device)
+    if out is None:
+        out = torch.empty_like(logc)
+    _count("ctdd_absorb_hit_time")
+    _check(load().ctdd_absorb_hit_time(*ptrs, N, D, int(mask_state), int(kmax), float(log_cmin), ABSORB_T_FUNCS[f], *par, float(t_min),
+                                       float(t_max), int(seed), int(offset), _ptr(counts, i32, "counts"), _ptr(t_eval, f32, "t_eval"),
+                                       _ptr(out, torch.float64, "out"), _stream()), "ctdd_absorb_hit_time")
+    return counts, t_eval, out
+
+
+def absorb_hit_step(logits, x, counts, mask_state, flags=0, seed=0, offset=0, out=None, changed=None):
+    """x with, per sample n, k_n = counts[n] (int32 (N,) on the device, clamped to [0, M_n]) of its M_n rows at mask_state, drawn
+    uniformly without replacement from Philox keys, set to the state absorb_step draws for the row at p_unmask = 1 under the same
+    seed and offset (flags = ABSORB_ARGMAX: its argmax); every other row is copied and its logits are not read
+    (ctdd_absorb_hit_step).  out may be x.  changed: int32[1] device counter, incremented by sum k_n."""
+    N, D, S = _absorb_shapes("absorb_hit_step", logits, (("x", x),))
+    if not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (N,):
+        raise CtddError(f"absorb_hit_step: counts {tuple(getattr(counts, 'shape', ()))}, expected {(N,)}")
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (N, D)):
+        raise CtddError(f"absorb_hit_step: out {tuple(getattr(out, 'shape', ()))} against x {(N, D)}")
+    ptrs = (_ptr(logits, f32, "logits"), _ptr(x, i32, "x"), _ptr(counts, i32, "counts"))
+    if out is None:
+        out = torch.empty_like(x)
+    _count("ctdd_absorb_hit_step")
+    _check(load().ctdd_absorb_hit_step(*ptrs, N, D, S, int(mask_state), int(flags), int(seed), int(offset), _ptr(out, i32, "out"),
+                                       _ptr(changed, i32, "changed"), _stream()), "ctdd_absorb_hit_step")
     return out
 
 

@@ -2,7 +2,7 @@
 float64, exactly as lib/models/forward_model.py does), per-t tables by the K1 HIP kernel.
 
 One object serves the four reference processes and the absorbing-state one (closed-form eigensystem, plus the scalars
-alpha / elbo_weight / unmask_prob that its own objective and sampler run on); `lib.models.forward_model` wraps it with the
+alpha / time_of_alpha / elbo_weight / unmask_prob that its own objective and samplers run on); `lib.models.forward_model` wraps it with the
 reference's class / attribute names."""
 import math
 
@@ -203,6 +203,23 @@ class DeviceForwardProcess:
         if self.p["t_func"] == "loglinear":
             return 1 - (1 - self.p["alpha_eps"]) * t
         return torch.exp(-self.p["rate_const"] * self.exponent(t))
+
+    def time_of_alpha(self, a):
+        """The inverse of alpha: the t with alpha(t) = a, in closed form for each of ABSORBING_T_FUNCS; a a float tensor, the dtype
+        follows it (fp64 in: the reference of ctdd_absorb_hit_time, which states the same forms).
+        loglinear (1 - a) / (1 - alpha_eps); log_sqr sqrt(a^(-1/rc) - 1); sqrt_cos (2 / pi) acos(r^2) with r = 1 + ln a / rc clamped
+        to [0, 1] (a below alpha(1) = exp(-rc) has no preimage: t = 1); log log_{time_exp}(1 - ln a / (rc time_base))."""
+        self._absorbing("time_of_alpha")
+        p, a = self.p, torch.as_tensor(a)
+        f, rc = p["t_func"], p["rate_const"]
+        if f == "loglinear":
+            return (1 - a) / (1 - p["alpha_eps"])
+        if f == "log_sqr":
+            return torch.sqrt(a ** (-1.0 / rc) - 1)
+        if f == "sqrt_cos":
+            r = torch.clamp(1 + torch.log(a) / rc, 0.0, 1.0)
+            return (2 / math.pi) * torch.acos(r * r)
+        return torch.log(1 - torch.log(a) / (rc * p["time_base"])) / math.log(p["time_exp"])
 
     def elbo_weight(self, t):
         """c'(t) alpha_t / (1 - alpha_t) with c' = rate_const beta(t): the weight of the masked cross entropy in the negative ELBO

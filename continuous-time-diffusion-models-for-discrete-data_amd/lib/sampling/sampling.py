@@ -2,7 +2,7 @@
 LBJF 238-356, MidPointTauL 360-526, PCTauL 530-646, ConditionalTauLeaping 649-758,
 ConditionalPCTauLeaping 761-905, ExactSampling 975-1061; ConditionalLBJF, ConditionalMidPointTauL and
 ConditionalExactSampling (not in the reference) hold entries the way its two conditional samplers do; AbsorbingLeap (not in the
-reference either) is the absorbing-state process's sampler, on its own step kernel; AbsorbingConfidence and AbsorbingRemask build on it.
+reference either) is the absorbing-state process's sampler, on its own step kernel; AbsorbingConfidence, AbsorbingRemask and AbsorbingFirstHit build on it.
 
 Same constructor `(cfg)`, same `sample(model, N)` return shapes; the per-step work is one fused
 libctdd launch (reverse rates -> jump draw -> state update) on int32 device state.  Differences
@@ -980,3 +980,79 @@ class AbsorbingRemask(AbsorbingLeap):
         counts = counts.cpu().numpy()
         self.remasked = (counts[:, 1] / N).tolist()
         return x.cpu().numpy().astype(int), (counts[:, 0] / N).tolist()
+
+
+@sampling_utils.register_sampler
+class AbsorbingFirstHit(AbsorbingLeap):
+    """First-hitting sampler for the absorbing-state process (Zheng et al., "Masked diffusion models are secretly time-agnostic masked
+    models and exploit inaccurate categorical sampling"; not in the reference): the reverse chain of the fixed network simulated event
+    by event, with no time grid and so no time-discretisation error.  Write c(t) = 1 - alpha(t).  Given that an entry is masked at
+    level c, the level at which it was masked is uniform on (0, c), independently over the entries; with M entries masked at level c
+    the next one to unmask is therefore uniform among the M, and it unmasks at the largest of M uniforms on (0, c), c u^(1/M).  In
+    logs: L <- L + log(u) / M, then M - 1 entries are masked.  The network is evaluated at the time of that level,
+    DeviceForwardProcess.time_of_alpha(1 - exp(L)), per sample: this is the continuous-time sampler whose likelihood
+    lib/likelihood.py's spacing = "alpha" bound describes.
+
+    Seed, rank_stream, `sample`, `inpaint` and the closing argmax forward at min_t are AbsorbingLeap's.  Mmax, the largest masked count
+    at the start (D for `sample`, from the held mask for `inpaint`), sets k = ceil(Mmax / num_steps) events per forward and
+    ceil(Mmax / k) iterations: num_steps >= D is the exact sampler, one event and one forward each; a smaller num_steps buys fewer
+    forwards by drawing k events from the logits at the first event's time, which is an approximation (the later events of an
+    iteration see neither the earlier ones' states nor their own, later, times).  Per iteration: ctdd_absorb_hit_time (each sample's
+    masked count, event levels, event count and network time, all kept on the device), model(x, t_eval) with per-sample times, then
+    ctdd_absorb_hit_step in place (that many masked entries, uniformly, each with the state AbsorbingLeap's step would draw for it).
+    Two launches per iteration, no host sync inside the loop.  Events that would fall below the level of min_t are not taken: their
+    entries are left to the closing step, as the grid samplers leave theirs.  A sample with fewer masked entries than Mmax runs out
+    of events early and is left alone from then on.
+
+    cfg.sampler.candidate: "sample" (default) or "argmax".  cfg.sampler.rule has no meaning here: anything but the default is refused.
+    `sample` returns (x, changed per iteration / N); after a run `times` holds the (iterations, N) fp32 evaluation times (min_t where
+    a sample had no event)."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        if self.rule != "ancestral":
+            raise ValueError(f"sampler.rule does not apply to AbsorbingFirstHit (it has no grid step to fill), got {self.rule!r}")
+        self.candidate = getattr(cfg.sampler, "candidate", "sample")
+        if self.candidate not in AbsorbingConfidence.CANDIDATES:
+            raise ValueError(f"sampler.candidate must be one of {AbsorbingConfidence.CANDIDATES}, got {self.candidate!r}")
+        if int(self.num_steps) < 1:
+            raise ValueError(f"sampler.num_steps must be at least 1, got {self.num_steps!r}")
+        self.times = np.zeros((0, 0), dtype=np.float32)
+
+    def inpaint(self, model, x_known, mask):
+        m = self._process(model).mask_state
+        N, xk, held = self._held(x_known, mask)
+        if bool((xk[held] == m).any()):
+            raise ValueError(f"x_known: a held entry is the mask state {m}")
+        if bool(held.all()):
+            return xk.numpy().astype(int)
+        mmax = int((~held).sum(dim=1).max())                     # on the host, before the loop
+        dev = torch.device(model.device)
+        x = torch.where(held.to(dev), xk.to(dev), torch.full((), m, dtype=torch.int32, device=dev))
+        return self._loop(model, x.contiguous(), mmax)[0]
+
+    def plan(self, mmax):
+        """(k, iterations): events per forward and forwards for a largest starting masked count of mmax."""
+        k = -(-int(mmax) // int(self.num_steps))
+        return k, -(-int(mmax) // k)
+
+    def _loop(self, model, x, mmax=None):
+        pr = self._process(model)
+        m, N, dev, key = pr.mask_state, x.shape[0], x.device, self._key()
+        k, iters = self.plan(x.shape[1] if mmax is None else mmax)
+        # the start and closing levels on the host in fp64, before the loop
+        logc0, log_cmin = torch.log(1 - pr.alpha(torch.tensor([self.max_t, self.min_t], dtype=torch.float64))).tolist()
+        logc = torch.full((N,), logc0, dtype=torch.float64, device=dev)
+        counts = torch.empty((N,), dtype=torch.int32, device=dev)
+        times = torch.empty((iters, N), dtype=torch.float32, device=dev)
+        changed = torch.zeros(iters + 1, dtype=torch.int32, device=dev)
+        flags = native.ABSORB_ARGMAX if self.candidate == "argmax" else 0
+        with torch.no_grad(), borrow_engine_output(model, bf16_logits=False, uniform_time=False):
+            for i in range(iters):
+                native.absorb_hit_time(x, logc, m, k, log_cmin, pr.p, self.min_t, self.max_t, key, i, counts=counts, t_eval=times[i], out=logc)
+                logits = _GridSampler._net_logits(model, x, times[i])
+                native.absorb_hit_step(logits, x, counts, m, flags, key, i, out=x, changed=changed[i:i + 1])
+            logits = _GridSampler._net_logits(model, x, torch.full((N,), float(np.float32(self.min_t)), device=dev))
+            x = native.absorb_step(logits, x, m, 1.0, native.ABSORB_ARGMAX, key, iters, changed=changed[iters:])
+        self.times = times.cpu().numpy()
+        return x.cpu().numpy().astype(int), (changed[:iters].cpu().numpy() / N).tolist()

@@ -1,7 +1,8 @@
 /* ctdd_absorb.h -- C ABI of the absorbing-state ("masked") diffusion kernels (csrc/absorb.hip): forward noising, the negative
  * ELBO with its logit gradient, one reverse (unmasking) step, the two halves of a confidence-ordered unmasking step
  * (ctdd_absorb_propose, ctdd_absorb_commit), the per-sample terms of the held-out likelihood bounds (ctdd_absorb_nll), and the
- * reverse step with remasking and its per-sample normaliser (ctdd_absorb_remask_step, ctdd_absorb_remask_norm).
+ * reverse step with remasking and its per-sample normaliser (ctdd_absorb_remask_step, ctdd_absorb_remask_norm), and the two halves
+ * of a first-hitting step (ctdd_absorb_hit_time, ctdd_absorb_hit_step).
  * Conventions as in ctdd.h: device pointers, row-major, int status (CTDD_OK == 0, message through ctdd_last_error), `stream` a
  * hipStream_t.  Logits fp32 (B, D, S) contiguous, states int32,
  * 2 <= S <= CTDD_MAX_S (S counts the mask state: S = 2 is one real state plus the mask), 0 <= mask_state < S.
@@ -148,6 +149,62 @@ int ctdd_absorb_remask_step(const float* logits, const int32_t* x, const uint8_t
  * waves' sums are added in wave order; the total is rounded to fp32 once.  Repeated calls write the same bits. */
 int ctdd_absorb_remask_norm(const int32_t* x, const uint8_t* held, const float* conf, int N, int D, int mask_state, float temp,
                             float* out_norm, void* stream);
+
+/* First-hitting sampling (Zheng et al., "Masked diffusion models are secretly time-agnostic masked models and exploit inaccurate
+ * categorical sampling"): the reverse chain of a fixed network simulated event by event, without a time grid.  Write the masking
+ * level of time t as c(t) = 1 - alpha_t.  Given that an entry is masked at level c, the level at which it was masked is uniform on
+ * (0, c), independently over the entries; so with M entries masked at level c the next one to unmask is uniform among the M, and it
+ * unmasks at the largest of M uniforms on (0, c), c u^(1/M) with u uniform on (0, 1).  In logs, L = log c:
+ *   L' = L + log(u) / M,   then M - 1 entries are masked at level exp(L').
+ * ctdd_absorb_hit_time walks that recursion per sample before the network runs; ctdd_absorb_hit_step, after it, picks which masked
+ * rows the events fall on and draws their states.
+ *
+ * ctdd_absorb_hit_time: per-sample event levels.   x int32 (N, D); logc_in, logc_out fp64 (N,), logc_out may be logc_in;
+ * counts int32 (N,), t_eval fp32 (N,), both written in full; kmax >= 1; 1 <= D <= 2^30.  One workgroup of 256 threads per sample.
+ *   M_n = the number of rows d with x[n][d] == m (ballots, then an integer sum over the four waves: exact).
+ *   In fp64, by one thread:  L_0 = logc_in[n];  L_{i+1} = L_i + log((double)u_i) / (double)(M_n - i),  i = 0 .. min(kmax, M_n) - 1.
+ *   Event i is accepted iff L_{i+1} >= log_cmin (log_cmin may be -inf: every event is accepted).  The first refusal ends the sample:
+ *   no later event is accepted and logc_out[n] = log_cmin.
+ *   counts[n]   = the number of accepted events, in [0, min(kmax, M_n)];
+ *   logc_out[n] = the level after the last accepted event if none was refused (logc_in[n], bit for bit, if M_n == 0);
+ *   t_eval[n]   = (float)min(max(T(1 - exp(L_1)), t_min), t_max) if at least one event is accepted, else (float)t_min, with
+ *                 T the inverse of alpha_t in fp64, by t_func:
+ *     CTDD_ABSORB_T_LOGLINEAR  T(a) = (1 - a) / (1 - alpha_eps)
+ *     CTDD_ABSORB_T_LOG_SQR    T(a) = sqrt(a^(-1 / rate_const) - 1)
+ *     CTDD_ABSORB_T_SQRT_COS   T(a) = (2 / pi) acos(r^2),  r = 1 + ln a / rate_const clamped to [0, 1]
+ *     CTDD_ABSORB_T_LOG        T(a) = ln(1 - ln a / (rate_const time_base)) / ln(time_exp)
+ *   (parameters a schedule does not name are unused; a = 0 gives +inf or the clamp: t_max).
+ *   u_i: component (i & 3) of the block Philox(key = seed, counter = (row = N D + n, offset, draw = i >> 2)), mapped to (0, 1) as
+ *   ctdd_philox_uniform does.  The rows N D .. N D + N - 1 lie past every entry row n D + d, so no block of
+ *   ctdd_absorb_hit_step (or of ctdd_absorb_step) under the same (seed, offset) is read twice. */
+#define CTDD_ABSORB_T_LOGLINEAR 0
+#define CTDD_ABSORB_T_LOG_SQR 1
+#define CTDD_ABSORB_T_SQRT_COS 2
+#define CTDD_ABSORB_T_LOG 3
+int ctdd_absorb_hit_time(const int32_t* x, const double* logc_in, int N, int D, int mask_state, int kmax, double log_cmin, int t_func,
+                         double rate_const, double alpha_eps, double time_base, double time_exp, double t_min, double t_max, uint64_t seed,
+                         uint64_t offset, int32_t* out_counts, float* out_t_eval, double* logc_out, void* stream);
+
+/* ctdd_absorb_hit_step: per sample, k_n masked rows drawn uniformly without replacement take a state from the network's logits.
+ *   logits (N, D, S); x, out_x int32 (N, D), out_x may be x; counts int32 (N,) on the device (ctdd_absorb_hit_time's);
+ *   flags: CTDD_ABSORB_ARGMAX or 0.  One workgroup of 256 threads per sample, 1 <= D <= 2^30, 2 <= S <= CTDD_MAX_S.
+ *   M_n = the number of rows d with x[n][d] == m;  k_n = min(M_n, max(0, counts[n])).
+ *   Selection: the key of a masked row d is the uint32 component 0 of the block Philox(key = seed, counter = (row = n D + d, offset,
+ *   draw = 1)); the k_n masked rows first in the order (key descending, equal keys in ascending d) are selected -- the keys are
+ *   i.i.d., so this is a uniform draw of k_n of the M_n rows.  It is ctdd_absorb_commit's radix select (the same device code) on
+ *   these keys: four passes of 8-bit digit histograms, then one pass over d in ascending chunks of 256.  The keys are recomputed in
+ *   every pass; nothing of a sample is kept in LDS but the histogram and one chunk's list of selected rows.
+ *   Draw: a selected row r = n D + d takes the state ctdd_absorb_step gives it at p_unmask = 1 under the same (seed, offset) (the
+ *   same device code in the same row packing): u1 = component 1 of the block (row = r, offset, draw = 0), the first s whose running
+ *   sum of e[s] exceeds u1 z; argmax_{s != m} l[s] with the lowest index on ties under CTDD_ABSORB_ARGMAX.  Never m.
+ *   Order of operations in the last pass, per chunk of 256 rows: two ballots per wave (keys above the threshold, keys at it), the
+ *   waves' counts through LDS, the selected rows of the chunk written to an LDS list in ascending d, then the four waves' row groups
+ *   (64, 16, 4 or 1 rows a wave, by S) walk the list: logits are read for the selected rows only.
+ *   Every other row: out_x = x, bit for bit; its logits are not read.  A sample with k_n == 0 is finished after the count (and
+ *   copied to out_x when out_x != x).
+ * out_changed (int32[1] or NULL) += sum_n k_n (one atomic per workgroup with k_n > 0). */
+int ctdd_absorb_hit_step(const float* logits, const int32_t* x, const int32_t* counts, int N, int D, int S, int mask_state, uint32_t flags,
+                         uint64_t seed, uint64_t offset, int32_t* out_x, int32_t* out_changed, void* stream);
 
 #ifdef __cplusplus
 }
