@@ -8,7 +8,8 @@
 // c = 1 - alpha_t their masking levels are i.i.d. uniform on (0, c), so the next entry to unmask is uniform among them and unmasks
 // at level c u^(1/M).  ctdd_absorb_hit_time counts a sample's masked rows and walks that recursion in fp64 logs (up to kmax events,
 // none below the closing level) to a per-sample event count and network time; ctdd_absorb_hit_step selects that many masked rows
-// uniformly (the commit's radix select, on Philox keys) and gives each the state the plain step would draw for it.
+// uniformly (the commit's radix select, on Philox keys) and gives each the state the plain step would draw for it; and
+// ctdd_absorb_filter, which tempers and truncates (top-k, top-p) the logits of the masked rows in place ahead of any of these steps.
 // include/ctdd_absorb.h states the formulas, the Philox counter layouts, the key that orders the scores and the order of the sums.
 //
 // Loss and step are row softmaxes over a row that fits in registers.  A row is owned by a group of LPR lanes of one wave, lane j of
@@ -826,6 +827,140 @@ __global__ __launch_bounds__(64 * AWV) void k_absorb_hit_step(const AbsorbHitSte
   if (tid == 0 && a.changed) atomicAdd(a.changed, kn);
 }
 
+// ---------------------------------------------------------------- temperature, top-k and top-p (nucleus) truncation of the masked rows
+struct AbsorbFilterArgs {
+  const float* logits;
+  const int32_t* x;
+  int64_t rows;
+  int S, mask_state;
+  int vec;
+  float temp;
+  int k;                      // 0: no top-k
+  float p;                    // 1: no top-p
+  float* out;                 // logits itself, or a buffer that does not overlap it
+};
+
+// the number of the group's held keys that are >= t.  One row a wave with few states a lane: a ballot and a scalar popcount per
+// held state; otherwise a lane count and the shuffle sum.
+template <int LPR, int PER>
+__device__ inline int grp_count_ge(const uint32_t (&key)[PER], uint32_t t) {
+  int c = 0;
+  if constexpr (LPR == WAVE && PER <= 8) {
+#pragma unroll
+    for (int k = 0; k < PER; ++k) c += __popcll(__ballot(key[k] >= t));
+    return c;
+  } else {
+#pragma unroll
+    for (int k = 0; k < PER; ++k) c += key[k] >= t;
+    return grp_sum_i<LPR>(c);
+  }
+}
+
+// the largest t with enough(t), for a predicate that holds at 0 and is monotone (true up to some key, false above it) and uniform
+// over the group: 32 rounds, most significant bit first
+template <class Enough>
+__device__ inline uint32_t key_search(Enough enough) {
+  uint32_t t = 0u;
+#pragma unroll 1
+  for (int b = 31; b >= 0; --b) {
+    const uint32_t c = t | (1u << b);
+    if (enough(c)) t = c;
+  }
+  return t;
+}
+
+// the number of the group's keys equal to t at lower states than the lane's first (an exclusive scan of the lanes' counts: lane j
+// holds the states PER j .., so lane order is state order)
+template <int LPR, int PER>
+__device__ inline int grp_ties_before(const uint32_t (&key)[PER], uint32_t t, int j) {
+  int n = 0;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) n += key[k] == t;
+  int inc = n;
+#pragma unroll
+  for (int o = 1; o < LPR; o <<= 1) {
+    const int up = __shfl_up(inc, o, LPR);
+    if (j >= o) inc += up;
+  }
+  return inc - n;
+}
+
+// k_absorb_step's grid and row ownership.  The row is held in full -- v = l / T, the key of v (score_key; 0 marks what is not or no
+// longer a candidate: the mask state, the states past S, the states dropped so far) and, for top-p, the weights -- before anything is
+// stored, so out may be logits.  Both selections are searches over the key's 32 bits (key_search) on a group count / a group sum, then
+// an index scan over the states at the threshold key; no LDS, no sort.  The sums of top-p all go through one function of the
+// threshold (mass_ge: the lane's states in ascending k, then the xor butterfly): it is monotone in the threshold, as every fp32 add
+// of non-negative terms is in each operand, which is what the search needs.  A wave none of whose rows is masked returns at once.
+template <int LPR, int PER>
+__global__ __launch_bounds__(64 * AWV) void k_absorb_filter(const AbsorbFilterArgs a) {
+  constexpr int RPW = WAVE / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane % LPR, s0 = j * PER, S = a.S, m = a.mask_state;
+  const int64_t row = ((int64_t)blockIdx.x * AWV + wave) * RPW + lane / LPR;
+  const bool in = row < a.rows;
+  const bool need = in && a.x[in ? row : 0] == m;              // uniform over the row's group
+  if (__ballot(need) == 0ull) return;                           // (uniform over the wave; the kernel has no barrier)
+  const size_t at = (size_t)(in ? row : 0) * S;
+  float v[PER];
+  uint32_t key[PER];
+  absorb_load<PER>(a.logits + at, S, s0, -1, a.vec, need, v);   // the raw row: no state is the mask state -1
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const int s = s0 + k;
+    const bool real = s < S && s != m;
+    float q = v[k] / a.temp;                                    // IEEE quotient (-fno-fast-math): T == 1 keeps the bits
+    if (!(q == q)) q = -INFINITY;                               // NaN counts as -inf
+    v[k] = real ? q : -INFINITY;
+    key[k] = real ? score_key(v[k]) : 0u;                       // a real state's key is at least that of -inf, 0x007FFFFF
+    mx = fmaxf(mx, v[k]);
+  }
+  mx = grp_max<LPR>(mx);
+  const bool finite = mx > -INFINITY;                           // (uniform over the row's group)
+  if (a.k > 0 && a.k < S - 1) {                                 // (uniform over the launch) top-k: thr is the k-th largest key
+    const uint32_t thr = key_search([&](uint32_t c) { return grp_count_ge<LPR, PER>(key, c) >= a.k; });
+    const int want = a.k - grp_count_ge<LPR, PER>(key, thr + 1u);      // states at thr that are kept: the lowest `want` of them
+    int before = grp_ties_before<LPR, PER>(key, thr, j);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const bool tie = key[k] == thr;
+      if (key[k] < thr || (tie && before >= want)) key[k] = 0u;
+      before += tie;
+    }
+  }
+  if (a.p < 1.0f) {                                             // (uniform over the launch) top-p over the states kept so far
+    const float base_mx = finite ? mx : 0.0f;
+    float w[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) w[k] = key[k] != 0u ? expf(v[k] - base_mx) : 0.0f;
+    const auto mass_ge = [&](uint32_t c) {
+      float t = 0.0f;
+#pragma unroll
+      for (int k = 0; k < PER; ++k) t += key[k] >= c ? w[k] : 0.0f;
+      return grp_sum<LPR>(t);
+    };
+    const float target = a.p * mass_ge(1u);                     // p z; fl(p z) <= z = mass_ge(0), so the search's predicate holds at 0
+    const uint32_t tau = key_search([&](uint32_t c) { return mass_ge(c) >= target; });
+    const float above = mass_ge(tau + 1u);                      // < target by the search: the first state at tau is always kept
+    int before = grp_ties_before<LPR, PER>(key, tau, j);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const bool tie = key[k] == tau;
+      if (key[k] < tau || (tie && !(above + (float)before * w[k] < target))) key[k] = 0u;
+      before += tie;
+    }
+  }
+  if (!need) return;
+  if (finite) {
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if (key[k] == 0u) v[k] = -INFINITY;
+    absorb_store<PER>(a.out + at, S, s0, a.vec, v);
+  } else if (a.out != a.logits) {                               // no finite real-state logit: the row as it came
+    absorb_load<PER>(a.logits + at, S, s0, -1, a.vec, true, v);
+    absorb_store<PER>(a.out + at, S, s0, a.vec, v);
+  }
+}
+
 // (LPR, PER) of a row width; rows per workgroup = AWV * 64 / LPR
 #define ABSORB_SHAPE(S, CALL)                                                       \
   if ((S) <= 4) { constexpr int LPR = 1, PER = 4; CALL; }                           \
@@ -998,4 +1133,22 @@ extern "C" int ctdd_absorb_hit_step(const float* logits, const int32_t* x, const
   AbsorbHitStepArgs a = {logits, x, counts, D, S, mask_state, S % 4 == 0 && aligned16(logits), flags, seed, offset, out_x, out_changed};
   ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_hit_step<LPR, PER>), dim3((unsigned)N), dim3(64 * AWV), 0, (hipStream_t)stream, a));
   return finish_launch("k_absorb_hit_step");
+}
+
+extern "C" int ctdd_absorb_filter(const float* logits, const int32_t* x, int N, int D, int S, int mask_state, float temperature, int top_k,
+                                  float top_p, float* out, void* stream) {
+  CTDD_REQUIRE(logits && x && out, CTDD_EINVAL, "absorb filter: null buffer");
+  CTDD_REQUIRE(N > 0 && D > 0 && S >= 2 && S <= CTDD_MAX_S && mask_state >= 0 && mask_state < S, CTDD_ERANGE,
+               "absorb filter: N=%d D=%d S=%d mask_state=%d (2 <= S <= %d, 0 <= mask_state < S)", N, D, S, mask_state, CTDD_MAX_S);
+  CTDD_REQUIRE(temperature > 0.0f && temperature - temperature == 0.0f, CTDD_ERANGE, "absorb filter: temperature=%g (positive, finite)",
+               (double)temperature);
+  CTDD_REQUIRE(top_k >= 0, CTDD_ERANGE, "absorb filter: top_k=%d (0 or a count)", top_k);
+  CTDD_REQUIRE(top_p > 0.0f && top_p <= 1.0f, CTDD_ERANGE, "absorb filter: top_p=%g outside (0, 1]", (double)top_p);
+  const int64_t rows = (int64_t)N * D;
+  const int rpb = AWV * WAVE / absorb_lpr(S);
+  const int64_t blocks = (rows + rpb - 1) / rpb;
+  CTDD_REQUIRE(blocks <= INT32_MAX, CTDD_ERANGE, "absorb filter: N D = %lld rows", (long long)rows);
+  AbsorbFilterArgs a = {logits, x, rows, S, mask_state, S % 4 == 0 && aligned16(logits) && aligned16(out), temperature, top_k, top_p, out};
+  ABSORB_SHAPE(S, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_absorb_filter<LPR, PER>), dim3((unsigned)blocks), dim3(64 * AWV), 0, (hipStream_t)stream, a));
+  return finish_launch("k_absorb_filter");
 }

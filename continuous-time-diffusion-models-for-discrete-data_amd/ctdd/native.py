@@ -94,6 +94,7 @@ _SIGS = {
     "ctdd_absorb_remask_norm": ([_P, _P, _P, _I, _I, _I, _F, _P, _P], _I),
     "ctdd_absorb_hit_time": ([_P, _P, _I, _I, _I, _I, _D, _I, _D, _D, _D, _D, _D, _D, _U64, _U64, _P, _P, _P, _P], _I),
     "ctdd_absorb_hit_step": ([_P, _P, _P, _I, _I, _I, _I, _U32, _U64, _U64, _P, _P, _P], _I),
+    "ctdd_absorb_filter": ([_P, _P, _I, _I, _I, _I, _F, _I, _F, _P, _P], _I),
 }
 UNET_EXPORTS = ("ctdd_unet_conv", "ctdd_unet_conv_patch", "ctdd_unet_conv_res", "ctdd_unet_conv_ring", "ctdd_unet_conv_up_phases", "ctdd_unet_upsample2x", "ctdd_unet_first_conv", "ctdd_unet_gn_apply", "ctdd_unet_gn_onepass", "ctdd_unet_channel_stats",
                 "ctdd_unet_time", "ctdd_unet_time_uniform", "ctdd_unet_attention", "ctdd_unet_logistic_head", "ctdd_unet_resblock_small",
@@ -799,6 +800,32 @@ def absorb_hit_step(logits, x, counts, mask_state, flags=0, seed=0, offset=0, ou
     _count("ctdd_absorb_hit_step")
     _check(load().ctdd_absorb_hit_step(*ptrs, N, D, S, int(mask_state), int(flags), int(seed), int(offset), _ptr(out, i32, "out"),
                                        _ptr(changed, i32, "changed"), _stream()), "ctdd_absorb_hit_step")
+    return out
+
+
+def absorb_filter_is_neutral(temperature=1.0, top_k=0, top_p=1.0):
+    """Whether (temperature, top_k, top_p) leave every distribution as it is: the samplers launch nothing then."""
+    return float(temperature) == 1.0 and int(top_k) == 0 and float(top_p) == 1.0
+
+
+def absorb_filter(logits, x, mask_state, temperature=1.0, top_k=0, top_p=1.0, out=None):
+    """logits (N, D, S) fp32 with the rows of x (N, D) int32 at mask_state tempered and truncated (ctdd_absorb_filter): over the
+    states s != mask_state, v = l / temperature; ordered by (v descending, s ascending), the first top_k stay (0: all), then the
+    shortest prefix whose softmax mass reaches top_p (1: all; one state at least); a state that stays gets v, every other one and the
+    mask state's column -inf, so the step kernels draw from the truncated, renormalised distribution.  A row without a finite real-state
+    logit comes back as it was.  The other rows are neither read nor written.  out: logits itself for the in-place call; None returns a
+    copy of logits with the masked rows rewritten."""
+    N, D, S = _absorb_shapes("absorb_filter", logits, (("x", x),))
+    ptrs = (_ptr(logits, f32, "logits"), _ptr(x, i32, "x"))
+    if out is None:
+        out = logits.clone()
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (N, D, S):
+        raise CtddError(f"absorb_filter: out {tuple(getattr(out, 'shape', ()))} against logits {(N, D, S)}")
+    elif out.data_ptr() != logits.data_ptr() and abs(out.data_ptr() - logits.data_ptr()) < 4 * N * D * S:
+        raise CtddError("absorb_filter: out overlaps logits without being it")
+    _count("ctdd_absorb_filter")
+    _check(load().ctdd_absorb_filter(*ptrs, N, D, S, int(mask_state), float(temperature), min(int(top_k), S), float(top_p), _ptr(out, f32, "out"),
+                                     _stream()), "ctdd_absorb_filter")
     return out
 
 

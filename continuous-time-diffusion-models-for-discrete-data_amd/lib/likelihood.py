@@ -29,6 +29,7 @@ ctdd_absorb_nll launch pair into the draw's row of an fp64 buffer (deterministic
 the loop and one read-back after it.  fused = False or a CPU model: the same terms in fp64 torch ops."""
 import dataclasses
 import math
+import warnings
 
 import numpy as np
 import torch
@@ -201,8 +202,14 @@ def eval_likelihood(cfg, model, dataloader, max_batches=None):
     cfg.sampler.{min_t, num_steps, rule ("ancestral")} and cfg.training.max_t; batch b draws with the key seed + b.  Returns
     {"bits_per_dim", "nats_per_dim", "perplexity" = exp(nats_per_dim), "stderr", "accuracy", "n"}: the bound summed over the samples
     over the number of their entries; stderr: the standard error of the mean across samples of the per-sample bits per dimension;
-    accuracy: the share of masked entries predicted by the argmax, over all draws; n: the number of samples."""
+    accuracy: the share of masked entries predicted by the argmax, over all draws; n: the number of samples.
+    The bound describes the unfiltered samplers: a cfg.sampler that sets temperature, top_k or top_p away from 1, 0 and 1 draws from a
+    truncated distribution, under which held-out data has no finite bound; one RuntimeWarning says so and the computation is unchanged."""
     ev, s = getattr(cfg, "eval", None), cfg.sampler
+    knobs = {k: getattr(s, k, d) for k, d in (("temperature", 1.0), ("top_k", 0), ("top_p", 1.0))}
+    if any(v != d for v, d in zip(knobs.values(), (1.0, 0, 1.0))):
+        warnings.warn(f"eval_likelihood: cfg.sampler sets {knobs}; the bound is that of the unfiltered sampler (a tempered, truncated "
+                      "distribution has no finite held-out bound)", RuntimeWarning, stacklevel=2)
     spacing, n_times, seed = (getattr(ev, k, d) for k, d in (("spacing", "alpha"), ("n_times", 16), ("seed", 0)))
     kw = dict(spacing=spacing, n_times=n_times, num_steps=getattr(s, "num_steps", None), rule=getattr(s, "rule", "ancestral"),
               min_t=s.min_t, max_t=cfg.training.max_t, fused=getattr(cfg.loss, "fused", True))

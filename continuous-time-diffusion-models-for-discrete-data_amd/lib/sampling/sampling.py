@@ -766,7 +766,15 @@ class AbsorbingLeap(_Conditioned):
     grid is linspace(max_t, min_t, num_steps) followed by 0; after the loop one forward at min_t assigns every entry that is
     still masked its argmax.  `sample(model, N)` starts from the all-mask state and returns (x int (N, D), changed per step / N);
     `inpaint(model, x_known, mask)` (mask True = held, as in the conditional samplers) starts the held entries at their known
-    value, which is all it takes: they are not masked, so no step touches them."""
+    value, which is all it takes: they are not masked, so no step touches them.
+
+    cfg.sampler.temperature (default 1.0, positive), cfg.sampler.top_k (default 0: off) and cfg.sampler.top_p (default 1.0, in (0, 1]),
+    here and in the three samplers built on this one: a masked entry's state is drawn from the softmax of logits / temperature,
+    truncated to its top_k most likely states and then to the shortest prefix of them whose mass reaches top_p, and renormalised.
+    Unless all three are at their defaults, every iteration launches ctdd_absorb_filter once, in place on the network's logits,
+    before its step kernel (one more read and write of the masked rows); the closing forward is not filtered, the argmax being the
+    same.  At the defaults nothing is launched and the sampler is bit for bit what it is without the keys.  Held entries of `inpaint`
+    are not masked, so their rows are skipped.  The likelihood bounds of lib/likelihood.py describe the unfiltered samplers only."""
 
     def __init__(self, cfg):
         self.cfg = cfg
@@ -778,10 +786,34 @@ class AbsorbingLeap(_Conditioned):
         from ctdd.process import UNMASK_RULES
         if self.rule not in UNMASK_RULES:
             raise ValueError(f"sampler.rule must be one of {UNMASK_RULES}, got {self.rule!r}")
+        temperature, top_k, top_p = getattr(s, "temperature", 1.0), getattr(s, "top_k", 0), getattr(s, "top_p", 1.0)
+        try:
+            self.temperature = float(temperature)
+        except (TypeError, ValueError):
+            self.temperature = float("nan")
+        if not 0.0 < self.temperature < float("inf"):
+            raise ValueError(f"sampler.temperature must be positive and finite, got {temperature!r}")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0:
+            raise ValueError(f"sampler.top_k must be a non-negative integer (0: off), got {top_k!r}")
+        self.top_k = int(top_k)
+        try:
+            self.top_p = float(top_p)
+        except (TypeError, ValueError):
+            self.top_p = float("nan")
+        if not 0.0 < self.top_p <= 1.0:
+            raise ValueError(f"sampler.top_p must lie in (0, 1], got {top_p!r}")
+        self.filtered = not native.absorb_filter_is_neutral(self.temperature, self.top_k, self.top_p)
         self.seed = None              # set to an int for a fixed Philox key
         self.rank_stream = 0          # added to the key by the multi-GPU driver (ctdd/distributed.py)
 
     _key = _GridSampler._key
+
+    def _filter(self, logits, x, m):
+        """The step's logits with the masked rows tempered and truncated, in place (the sampler owns them for the length of a step:
+        borrow_engine_output); nothing is launched at the neutral values."""
+        if self.filtered:
+            native.absorb_filter(logits, x, m, self.temperature, self.top_k, self.top_p, out=logits)
+        return logits
 
     @staticmethod
     def _process(model):
@@ -821,7 +853,7 @@ class AbsorbingLeap(_Conditioned):
         changed = torch.zeros(self.num_steps + 1, dtype=torch.int32, device=dev)
         with torch.no_grad(), borrow_engine_output(model, bf16_logits=False, uniform_time=True):
             for i in range(self.num_steps):
-                logits = _GridSampler._net_logits(model, x, _GridSampler._t_ones(t32, i, N, dev))
+                logits = self._filter(_GridSampler._net_logits(model, x, _GridSampler._t_ones(t32, i, N, dev)), x, m)
                 x = self._advance(logits, x, m, p[i], key, i, changed[i:i + 1])
             logits = _GridSampler._net_logits(model, x, torch.full((N,), float(np.float32(self.min_t)), device=dev))
             x = native.absorb_step(logits, x, m, 1.0, native.ABSORB_ARGMAX, key, self.num_steps, changed=changed[self.num_steps:])
@@ -839,7 +871,8 @@ class AbsorbingConfidence(AbsorbingLeap):
 
     cfg.sampler.conf_temp (default 1.0): step i of num_steps adds conf_temp (1 - (i + 1) / num_steps) times a standard Gumbel variate
     to the scores, an annealed randomisation of the ranking (0 ranks by the log-probability alone).  cfg.sampler.candidate: "sample"
-    (default) or "argmax".  The closing forward at min_t with its argmax step is the parent's."""
+    (default) or "argmax".  The closing forward at min_t with its argmax step is the parent's.  Under a temperature / top_k / top_p
+    filter (AbsorbingLeap) the score is the candidate's log-probability under the filtered distribution."""
 
     CANDIDATES = ("sample", "argmax")
 
@@ -909,7 +942,9 @@ class AbsorbingRemask(AbsorbingLeap):
     that held entries weigh least).  cfg.sampler.remask_eta in [0, 1] (default 0.02, untuned; 0: AbsorbingLeap bit for bit under the same seed);
     cfg.sampler.remask_temp (default 1.0, at least 0.02); cfg.sampler.remask_window = (t_on, t_off) (default: the whole grid): step k
     remasks iff t_off <= t_k <= t_on.  `inpaint` hands the held mask to the kernel: a held entry is never remasked.  After a run
-    `remasked` holds the per-step number of remasked entries over N, as `changed` holds the entries that left the mask state."""
+    `remasked` holds the per-step number of remasked entries over N, as `changed` holds the entries that left the mask state.  Under a
+    temperature / top_k / top_p filter (AbsorbingLeap) the "conf" weight is the probability the entry committed at under the filtered
+    distribution."""
 
     def __init__(self, cfg):
         super().__init__(cfg)
@@ -968,7 +1003,7 @@ class AbsorbingRemask(AbsorbingLeap):
         norm = torch.empty((N, 2), dtype=torch.float32, device=dev) if by_conf else None
         with torch.no_grad(), borrow_engine_output(model, bf16_logits=False, uniform_time=True):
             for i in range(K):
-                logits = _GridSampler._net_logits(model, x, _GridSampler._t_ones(t32, i, N, dev))
+                logits = self._filter(_GridSampler._net_logits(model, x, _GridSampler._t_ones(t32, i, N, dev)), x, m)
                 if by_conf:
                     native.absorb_remask_norm(x, m, conf, held, self.remask_temp, out=norm)
                     native.absorb_remask_step(logits, x, m, p[i], sigma[i], held, conf, norm, self.remask_temp, native.ABSORB_REMASK_CONF, key, i,
@@ -1006,7 +1041,8 @@ class AbsorbingFirstHit(AbsorbingLeap):
 
     cfg.sampler.candidate: "sample" (default) or "argmax".  cfg.sampler.rule has no meaning here: anything but the default is refused.
     `sample` returns (x, changed per iteration / N); after a run `times` holds the (iterations, N) fp32 evaluation times (min_t where
-    a sample had no event)."""
+    a sample had no event).  A temperature / top_k / top_p filter (AbsorbingLeap) is applied to every iteration's logits before
+    ctdd_absorb_hit_step: with top_k = 1 the "sample" candidate is the "argmax" candidate."""
 
     def __init__(self, cfg):
         super().__init__(cfg)
@@ -1050,7 +1086,7 @@ class AbsorbingFirstHit(AbsorbingLeap):
         with torch.no_grad(), borrow_engine_output(model, bf16_logits=False, uniform_time=False):
             for i in range(iters):
                 native.absorb_hit_time(x, logc, m, k, log_cmin, pr.p, self.min_t, self.max_t, key, i, counts=counts, t_eval=times[i], out=logc)
-                logits = _GridSampler._net_logits(model, x, times[i])
+                logits = self._filter(_GridSampler._net_logits(model, x, times[i]), x, m)
                 native.absorb_hit_step(logits, x, counts, m, flags, key, i, out=x, changed=changed[i:i + 1])
             logits = _GridSampler._net_logits(model, x, torch.full((N,), float(np.float32(self.min_t)), device=dev))
             x = native.absorb_step(logits, x, m, 1.0, native.ABSORB_ARGMAX, key, iters, changed=changed[iters:])

@@ -2,7 +2,8 @@
  * ELBO with its logit gradient, one reverse (unmasking) step, the two halves of a confidence-ordered unmasking step
  * (ctdd_absorb_propose, ctdd_absorb_commit), the per-sample terms of the held-out likelihood bounds (ctdd_absorb_nll), and the
  * reverse step with remasking and its per-sample normaliser (ctdd_absorb_remask_step, ctdd_absorb_remask_norm), and the two halves
- * of a first-hitting step (ctdd_absorb_hit_time, ctdd_absorb_hit_step).
+ * of a first-hitting step (ctdd_absorb_hit_time, ctdd_absorb_hit_step), and the temperature / top-k / top-p truncation of the
+ * masked rows' logits that any of the steps may be given (ctdd_absorb_filter).
  * Conventions as in ctdd.h: device pointers, row-major, int status (CTDD_OK == 0, message through ctdd_last_error), `stream` a
  * hipStream_t.  Logits fp32 (B, D, S) contiguous, states int32,
  * 2 <= S <= CTDD_MAX_S (S counts the mask state: S = 2 is one real state plus the mask), 0 <= mask_state < S.
@@ -205,6 +206,33 @@ int ctdd_absorb_hit_time(const int32_t* x, const double* logc_in, int N, int D, 
  * out_changed (int32[1] or NULL) += sum_n k_n (one atomic per workgroup with k_n > 0). */
 int ctdd_absorb_hit_step(const float* logits, const int32_t* x, const int32_t* counts, int N, int D, int S, int mask_state, uint32_t flags,
                          uint64_t seed, uint64_t offset, int32_t* out_x, int32_t* out_changed, void* stream);
+
+/* ctdd_absorb_filter: temperature, top-k and top-p (nucleus) truncation of the logits of the masked rows, ahead of any of the step
+ * kernels above (ctdd_absorb_step, _propose, _remask_step, _hit_step), which then draw from -- or take the argmax, the score, the
+ * confidence of -- the tempered, truncated and renormalised distribution without a change: a logit of -inf has the weight exactly 0.
+ *   logits, out fp32 (N, D, S); x int32 (N, D).  out may be logits (in place); otherwise the two do not overlap.
+ *   temperature T > 0 and finite; top_k >= 0; 0 < top_p <= 1 (CTDD_ERANGE otherwise).  ctdd_absorb_step's grid and row packing.
+ *   x != m: the row is neither read nor written (out keeps what it held).
+ *   x == m: over the real states s != m, in this order:
+ *     1. v[s] = l[s] / T, the IEEE fp32 quotient: T == 1 keeps the bits.  A NaN counts as -inf from here on.
+ *     2. The states are ordered by (v descending, s ascending); v is compared through the 32-bit key of ctdd_absorb_commit.
+ *     3. top_k = k with 1 <= k < S - 1: the first k states of the order stay candidates.  k = 0 or k >= S - 1: all of them do.
+ *     4. top_p = p < 1: with e[s] = exp(v[s] - mx) over the candidates (mx their maximum) and z their sum, the shortest prefix of the
+ *        order whose sum of e reaches p z stays: state i of the order stays iff the sum over the states before it is below p z, so
+ *        the first always does.  The sums are fp32 (over the states above the boundary value as one group sum, plus a multiple of
+ *        the common weight for states that tie at the boundary value): a prefix whose mass lies within about 1e-6 z of p z may be
+ *        judged either way.  p = 1: every candidate stays.
+ *     5. out[s] = v[s] for a state that stays, -inf for one that does not, -inf for s == m.
+ *     6. A row without a finite real-state logit (every v is -inf) is left as it came: out's row = the row of logits, bit for bit.
+ *   A quotient that overflows to +inf (or a logit of +inf) is outside the contract, as it is for the step kernels.
+ *   With T == 1, k off and p == 1 the call only sets the masked rows' mask column and NaNs to -inf; callers skip it.
+ * The row is held in registers in full before anything is stored.  Selection, per row group (64, 16, 4 or 1 rows a wave, by S):
+ * the k-th largest key by a search over the key's 32 bits, most significant first, one group count a round; the states at that key
+ * by an exclusive index scan; for top-p a second 32-round search for the largest key tau whose set {key >= tau} carries at least
+ * p z, on one summation function of the threshold (monotone in it), and the same index scan at tau.  No LDS, no sort; one read and
+ * one write of a masked row.  A wave without a masked row returns after reading x. */
+int ctdd_absorb_filter(const float* logits, const int32_t* x, int N, int D, int S, int mask_state, float temperature, int top_k,
+                       float top_p, float* out, void* stream);
 
 #ifdef __cplusplus
 }
