@@ -2,7 +2,7 @@
 // share, with their weight loads: a pixel tile is one output row of a zero-bordered LDS slab, a wave owns three 16-channel weight
 // tiles (v_mfma_f32_16x16x32_bf16, weights as the A operand) and streams its weights global -> registers through a ring of two units
 // (ctdd/unet_engine.py: pack_row_tile_weights).  rt_gemm_rows is the loop of the kernels with one wave per SIMD (two fragment sets),
-// rt_gemm_rows_1buf that of k_conv_rows' eight-wave split (one set).
+// rt_gemm_rows_1buf that of the eight-wave splits of k_conv_rows and k_conv_rows_head (one set).
 //
 // Deliberately NOT here, because lifting them changes the register allocation of the kernels they are inlined into (compare the
 // device assembly before and after when trying again): the 8-channel GroupNorm + Swish conversion, the group sums -> scale / shift

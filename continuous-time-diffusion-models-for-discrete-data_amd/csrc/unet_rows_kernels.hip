@@ -36,7 +36,7 @@ namespace {
 constexpr int CR_N = 96, CR_BAND = 14, CR_PITCH = 32, CR_RS = 224, CR_MAXW = 28, CR_MAXC = 384, CR_PIECE = 96;
 constexpr int CR_SLAB = ((CR_BAND + 2) * CR_PITCH + 2) * CR_RS;  // 115 136
 constexpr int CR_SCALE = CR_SLAB;                                // float scale[CR_MAXC], shift[CR_MAXC]
-constexpr int CR_RED = CR_SCALE + 2 * CR_MAXC * 4;               // double [column half][channel][moment]
+constexpr int CR_RED = CR_SCALE + 2 * CR_MAXC * 4;               // double [column half][channel][moment] (four waves)
 constexpr int CR_TOTAL = CR_RED + 2 * CR_N * 2 * 8;
 constexpr int CR_FB = 12;                                        // pixels per thread in flight in the fill (half of them with eight waves)
 constexpr int CR_CARRY = CR_BAND * CR_MAXW * CR_RS;               // eight waves: float4 [wave & 3][channel tile][s | q][lane] past the output image
@@ -155,7 +155,8 @@ __device__ __attribute__((always_inline)) inline void cr_gemm_skip(f32x4 (&acc)[
 // registers, two waves per SIMD: waves wv and wv + 4 share a SIMD and a weight stream, and 512 threads carry the fill, the zero
 // fill and the store.  Per output pixel the order of units, dy and tiles is the same, and the statistics keep the 4-wave chain
 // (fp32 down a lane's column in row order, then fp64): the upper wave leaves its running fp32 sums in LDS and the lower wave
-// continues from them, so both give the same bits.
+// continues from them, and the 16 lanes of a column half are added in fp64 from LDS in the order of the 4-wave kernel's lane
+// butterfly, so both give the same bits.
 template <bool SKIP, int WAVES>
 __global__ __launch_bounds__(WAVES * 64, 1) void k_conv_rows(const ctdd_conv_rows_args a) {
   static_assert(WAVES == 4 || WAVES == 8, "one or two row halves");
@@ -324,15 +325,10 @@ __global__ __launch_bounds__(WAVES * 64, 1) void k_conv_rows(const ctdd_conv_row
           for (int i = 0; i < 4; ++i) { s[i] += acc[tt][y][i]; q[i] = fmaf(acc[tt][y][i], acc[tt][y][i], q[i]); }
         }
       }
-      // (the reduction above, again: shared through a lambda it moves the 4-wave kernels off their code)
-      const int n = cg * 48 + tt * 16 + lq * 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        double ds = (double)s[i], dq = (double)q[i];
-#pragma unroll
-        for (int m = 1; m < 16; m <<= 1) { ds += __shfl_xor(ds, m, WAVE); dq += __shfl_xor(dq, m, WAVE); }
-        if (lj == 0) { red[(hh * CR_N + n + i) * 2] = ds; red[(hh * CR_N + n + i) * 2 + 1] = dq; }
-      }
+      // the finished per-lane sums back into this wave's own slots (it is their only reader and has read them; the LDS
+      // operations of one wave complete in order): the 16 lanes of a column half meet behind the next barrier
+      carry[(tt * 2) * 64] = make_float4(s[0], s[1], s[2], s[3]);
+      carry[(tt * 2 + 1) * 64] = make_float4(q[0], q[1], q[2], q[3]);
     }
   }
 #endif
@@ -344,9 +340,33 @@ __global__ __launch_bounds__(WAVES * 64, 1) void k_conv_rows(const ctdd_conv_row
       *(uint4*)(out + (size_t)p * CR_N + c0) = *(const uint4*)(sm + p * CR_RS + c0 * 2);
     }
 #ifndef CTDD_ROWS_STAMPS
-    // one fp64 atomic per (sample, channel, moment) and workgroup (eight waves: red was written after the barrier above)
-    if (WAVES == 8) __syncthreads();
-    if (a.out_stats && t < 2 * CR_N) atomicAdd(a.out_stats + (size_t)b * CR_N * 2 + t, red[t] + red[2 * CR_N + t]);
+    // one fp64 atomic per (sample, channel, moment) and workgroup
+    if constexpr (WAVES == 8) {
+      // the lower waves' per-lane fp32 sums were written after the barrier above.  Thread (channel, moment) adds the 16 lanes of
+      // either column half in fp64 in the tree of the 4-wave kernel's xor butterfly, ((v0 + v1) + (v2 + v3)) + ((v4 + v5) +
+      // (v6 + v7)) and the same of v8 .. v15 on top, then half 0 + half 1: the same bits without its 96 fp64 shuffles per wave
+      // (lanes whose column is no pixel hold 0.0 there as they did in the butterfly)
+      __syncthreads();
+      if (a.out_stats && t < 2 * CR_N) {
+        const int n = t >> 1, ncg = n / 48, ntt = (n - ncg * 48) >> 4, nlq = (n >> 2) & 3;
+        const float* tab = (const float*)(sm + CR_CARRY) + ((ncg * 2 * 3 + ntt) * 2 + (t & 1)) * 256 + nlq * 64 + (n & 3);
+        double h[2];
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          double v[16];
+#pragma unroll
+          for (int j = 0; j < 16; ++j) v[j] = (double)tab[hf * (3 * 2 * 256) + j * 4];
+#pragma unroll
+          for (int m = 1; m < 16; m <<= 1)
+#pragma unroll
+            for (int j = 0; j < 16; j += 2 * m) v[j] += v[j + m];
+          h[hf] = v[0];
+        }
+        atomicAdd(a.out_stats + (size_t)b * CR_N * 2 + t, h[0] + h[1]);
+      }
+    } else {
+      if (a.out_stats && t < 2 * CR_N) atomicAdd(a.out_stats + (size_t)b * CR_N * 2 + t, red[t] + red[2 * CR_N + t]);
+    }
 #endif
   }
   CR_STAMP(5);

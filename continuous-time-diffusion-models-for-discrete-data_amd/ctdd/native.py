@@ -98,7 +98,7 @@ _SIGS = {
 }
 UNET_EXPORTS = ("ctdd_unet_conv", "ctdd_unet_conv_patch", "ctdd_unet_conv_res", "ctdd_unet_conv_ring", "ctdd_unet_conv_up_phases", "ctdd_unet_upsample2x", "ctdd_unet_first_conv", "ctdd_unet_gn_apply", "ctdd_unet_gn_onepass", "ctdd_unet_channel_stats",
                 "ctdd_unet_time", "ctdd_unet_time_uniform", "ctdd_unet_attention", "ctdd_unet_logistic_head", "ctdd_unet_resblock_small",
-                "ctdd_unet_resblock_mid", "ctdd_unet_conv_rows", "ctdd_unet_conv_rows_w4", "ctdd_unet_conv_rows_head", "ctdd_unet_attention_block")    # bound in ctdd/unet_engine.py
+                "ctdd_unet_resblock_mid", "ctdd_unet_conv_rows", "ctdd_unet_conv_rows_w4", "ctdd_unet_conv_rows_head", "ctdd_unet_conv_rows_head_w4", "ctdd_unet_attention_block")    # bound in ctdd/unet_engine.py
 HOLLOW_EXPORTS = ("ctdd_gemm_bf16", "ctdd_hollow_small_linear", "ctdd_hollow_embed", "ctdd_hollow_layernorm", "ctdd_hollow_add", "ctdd_hollow_put_rows", "ctdd_hollow_attention", "ctdd_hollow_attention_bf16")
 UNET_TRAIN_EXPORTS = ("ctdd_unet_wgrad", "ctdd_unet_gn_bwd", "ctdd_unet_dropout", "ctdd_unet_colsum", "ctdd_unet_sum_batch", "ctdd_unet_sum_jobs", "ctdd_unet_accumulate",
                       "ctdd_unet_downsum2x", "ctdd_unet_upsample2x_f32", "ctdd_unet_cast_rows", "ctdd_unet_attention_bwd",

@@ -91,7 +91,7 @@ def _lib():
                            ("ctdd_unet_attention", [_P, _P]), ("ctdd_unet_attention_block", [_P, _I, _P]),
                            ("ctdd_unet_resblock_small", [_P, _I, _P]),
                            ("ctdd_unet_resblock_mid", [_P, _I, _P]), ("ctdd_unet_conv_rows", [_P, _I, _P]), ("ctdd_unet_conv_rows_w4", [_P, _I, _P]),
-                           ("ctdd_unet_conv_rows_head", [_P, _I, _P]),
+                           ("ctdd_unet_conv_rows_head", [_P, _I, _P]), ("ctdd_unet_conv_rows_head_w4", [_P, _I, _P]),
                            ("ctdd_unet_logistic_head", [_P, _P])):
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argt, _I
@@ -559,8 +559,12 @@ class _PlanBuilder:
         a.w, a.bias, a.out_bf16 = ptr(w), ptr(bias), ptr(logits)
         a.B, a.H, a.W, a.N = B, src.H, src.W, N
         self.keep.extend([g, b_, w, bias, a])
+        # cfg.model.head_rows_waves: 8 (default) waves per workgroup, or 4: the same bits from the kernel's 4-wave work split
+        waves = int(getattr(eng.cfg.model, "head_rows_waves", 8))
+        if waves not in (4, 8):
+            raise ValueError(f"cfg.model.head_rows_waves = {waves}: 4 or 8")
         # (flops: the unpadded N; the channels past N that the last pass computes are not the network's)
-        self.launch(self.lib.ctdd_unet_conv_rows_head, C.byref(a), 0, label=f"{src.H}x{src.W} K={9 * C1} N={N} gn+conv rows head C={[C1]}",
+        self.launch(self.lib.ctdd_unet_conv_rows_head if waves == 8 else self.lib.ctdd_unet_conv_rows_head_w4, C.byref(a), 0, label=f"{src.H}x{src.W} K={9 * C1} N={N} gn+conv rows head C={[C1]}",
                     flops=2 * B * src.H * src.W * N * 9 * C1)
 
     def conv2_operands(self, rb, a2, srcs):

@@ -160,8 +160,13 @@ int ctdd_unet_conv_rows_w4(const void* conv_rows_args, int f32, void* stream);
  * CTDD_ERANGE / CTDD_EINVAL, nothing launched.
  * Weights (ctdd/unet_engine.py: pack_conv_rows_head_weights): the [N][9 C1] matrix zero-padded to 96 ceil(N / 96) rows, in
  * 2 ceil(N / 96) streams of ctdd_unet_conv_rows' order (stream s: output channels [48 s, 48 s + 48), 27 C1 / 32 fragments), one after
- * the other: pass p reads streams 2 p and 2 p + 1.  Channels >= N are computed and never stored. */
+ * the other: pass p reads streams 2 p and 2 p + 1.  Channels >= N are computed and never stored.  The workgroup has eight waves: a
+ * wave owns 7 rows x 48 channels x a column half of the current pass. */
 int ctdd_unet_conv_rows_head(const void* conv_rows_args, int f32, void* stream);
+/* The same launch, same arguments, weights and refusals, on four waves per workgroup (a wave owns the band's 14 rows x 48 channels x
+ * a column half): the output is bit-identical to ctdd_unet_conv_rows_head's (per output pixel the order of the sums is the same),
+ * so either stands in for the other (cfg.model.head_rows_waves = 4 | 8). */
+int ctdd_unet_conv_rows_head_w4(const void* conv_rows_args, int f32, void* stream);
 
 typedef struct {
   const float* t; int B, ch, tdim;

@@ -6,7 +6,7 @@ launch runs alone (HIP events, 5 repetitions), matrix TFLOP/s, share of the summ
 --model-opt sets integer cfg.model knobs: head_rows=0 keeps the output head's ctdd_unet_gn_apply + ctdd_unet_conv_ring pair instead
 of the ctdd_unet_conv_rows_head step, head_rows_min_wgs=1 / conv_rows_min_wgs=1 take the grid-size rules out of the way below their
 default thresholds, conv_rows=0 keeps every 28x28 pair, conv_rows_waves=4 runs the 28x28 row launches on four waves per workgroup
-(ctdd_unet_conv_rows_w4), attention_fused=0 keeps the mid attention block's qkv convolution +
+(ctdd_unet_conv_rows_w4), head_rows_waves=4 the output head's on four (ctdd_unet_conv_rows_head_w4), attention_fused=0 keeps the mid attention block's qkv convolution +
 ctdd_unet_attention + proj convolution instead of the ctdd_unet_attention_block step.
 """
 import argparse

@@ -3,10 +3,11 @@
 passed as out_stats; the statistics are off in that build).  Printed as raw s_memtime ticks (shader cycles), mean / min / max over
 the workgroups of the third launch.
 
-    bash tools/build_conv_stamps.sh && python tools/stamp_conv_rows.py [--batch 128] [--waves 8 4]
+    bash tools/build_conv_stamps.sh && python tools/stamp_conv_rows.py [--batch 128] [--waves 8 4] [--head-waves 8 4]
 
 --waves: the work splits of k_conv_rows to stamp (8: ctdd_unet_conv_rows, 4: ctdd_unet_conv_rows_w4; default both).  The stamps are
-those of wave 0, which owns the band's upper 7 rows in the eight-wave kernel.
+those of wave 0, which owns the band's upper 7 rows in the eight-wave kernel.  --head-waves: the same for k_conv_rows_head
+(8: ctdd_unet_conv_rows_head, 4: ctdd_unet_conv_rows_head_w4; default both).
 """
 import argparse
 import ctypes as C
@@ -20,6 +21,7 @@ import torch  # noqa: E402
 from ctdd import unet_engine as ue  # noqa: E402
 
 ENTRY = {8: "ctdd_unet_conv_rows", 4: "ctdd_unet_conv_rows_w4"}
+HEAD_ENTRY = {8: "ctdd_unet_conv_rows_head", 4: "ctdd_unet_conv_rows_head_w4"}
 PHASES = ["prologue (zero fill, scale/shift)", "3x3 pieces (fill + K loop)", "1x1 segments", "epilogue to LDS", "store"]
 
 
@@ -59,7 +61,7 @@ def run(lib, waves, B, cs, rcs, res):
         print(f"   {nm:36s} mean {float(dur[:, i].mean()):8.0f}  min {float(dur[:, i].min()):8.0f}  max {float(dur[:, i].max()):8.0f}")
 
 
-def run_head(lib, B, C1, N):
+def run_head(lib, waves, B, C1, N):
     """k_conv_rows_head at 28x28: [workgroups][16] stamps: entry, prologue, fill, then per pass its K loop and its epilogue / store."""
     H = W = 28
     M, K, npass = B * H * W, 9 * C1, -(-N // 96)
@@ -78,13 +80,13 @@ def run_head(lib, B, C1, N):
     a.out_bf16, a.out_stats, a.B, a.H, a.W, a.N = out.data_ptr(), buf.data_ptr(), B, H, W, N
     st_ = torch.cuda.current_stream().cuda_stream
     for _ in range(3):
-        assert lib.ctdd_unet_conv_rows_head(C.byref(a), 0, st_) == 0, lib.ctdd_last_error().decode()
+        assert getattr(lib, HEAD_ENTRY[waves])(C.byref(a), 0, st_) == 0, lib.ctdd_last_error().decode()
     torch.cuda.synchronize()
     d = buf.cpu().double()
     nst = 3 + 2 * npass
     dur = d[:, 1:nst] - d[:, 0:nst - 1]
     names = ["prologue (zero fill, scale/shift)", "fill"] + [f"pass {p} {what}" for p in range(npass) for what in ("K loop", "epilogue + store")]
-    print(f"head B={B} 28x28 C1={C1} N={N}: {nwg} workgroups, per workgroup {float((d[:, nst - 1] - d[:, 0]).mean()):.0f} cycles")
+    print(f"head {waves} waves B={B} 28x28 C1={C1} N={N}: {nwg} workgroups, per workgroup {float((d[:, nst - 1] - d[:, 0]).mean()):.0f} cycles")
     for i, nm in enumerate(names):
         print(f"   {nm:36s} mean {float(dur[:, i].mean()):8.0f}  min {float(dur[:, i].min()):8.0f}  max {float(dur[:, i].max()):8.0f}")
 
@@ -93,16 +95,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--waves", type=int, nargs="+", choices=(4, 8), default=[8, 4])
+    ap.add_argument("--head-waves", type=int, nargs="+", choices=(4, 8), default=[8, 4])
     a = ap.parse_args()
     lib = C.CDLL(os.path.join(_R, "continuous-time-diffusion-models-for-discrete-data_amd", "librows_stamps.so"))
-    for fn in (lib.ctdd_unet_conv_rows, lib.ctdd_unet_conv_rows_w4, lib.ctdd_unet_conv_rows_head):
+    for fn in (lib.ctdd_unet_conv_rows, lib.ctdd_unet_conv_rows_w4, lib.ctdd_unet_conv_rows_head, lib.ctdd_unet_conv_rows_head_w4):
         fn.argtypes, fn.restype = [C.c_void_p, C.c_int, C.c_void_p], C.c_int
     lib.ctdd_last_error.restype = C.c_char_p
     for cs, rcs, res in (([96], [], False), ([96], [], True), ([96, 96], [], False), ([192, 96], [], False), ([96], [96, 96], False)):
         for waves in a.waves:
             run(lib, waves, a.batch, cs, rcs, res)
     for C1, N in ((96, 256), (96, 96)):
-        run_head(lib, a.batch, C1, N)
+        for waves in a.head_waves:
+            run_head(lib, waves, a.batch, C1, N)
 
 
 if __name__ == "__main__":
